@@ -77,6 +77,9 @@ def parse_args(argv=None):
     ap.add_argument("--variant", type=int, default=-1, help="stencil kernel variant (-1 = default)")
     ap.add_argument("--preheat", type=int, default=300,
                     help="untimed set-up steps before the warm-up, to bring the clocks up from idle (the state is reset afterwards)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state they left (phi's work cells: all of them, or a fixed seeded "
+                         "sample of a larger grid) as DIR/*.npy, so that two builds can be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -283,6 +286,50 @@ def pmc_traffic(kernel_instance: str):
     return None, None, None
 
 
+DUMP_MAX_CELLS = 1 << 21     # 16 MB of float64: a grid with more work cells is sampled
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, ctx, shape, z_begin, z_count, dist, rank):
+    """What the timed steps left for a caller of wafer_evolve: phi's work cells (the frame is zero by construction), as float64.
+    A grid of at most DUMP_MAX_CELLS cells is written whole (phi.npy, shape NX x NY x NZ); a larger one as the cells at a fixed,
+    seeded sample of global positions (phi_sample.npy, ascending C-order index), the same positions for every run of the same
+    grid and for every slab decomposition of it.  Collective over the ranks; rank 0 writes."""
+    import numpy as np
+    owned = ctx.download_phi_owned()                 # (nx, ny, z_count): this rank's planes, or the whole grid
+    zb = z_begin if z_count else 0
+    total = shape[0] * shape[1] * shape[2]
+    if total <= DUMP_MAX_CELLS:
+        name, idx = "phi", None
+    else:
+        name = "phi_sample"
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=DUMP_MAX_CELLS, replace=False))
+    if dist is None:
+        out = owned if idx is None else owned.reshape(-1)[idx]
+    else:
+        if idx is None:
+            idx = np.arange(total)
+        i, j, k = np.unravel_index(idx, shape)
+        mine = np.nonzero((k >= zb) & (k < zb + owned.shape[2]))[0]
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (mine, owned[i[mine], j[mine], k[mine] - zb]))
+        out = np.full(idx.shape, np.nan)
+        for pos, vals in parts:
+            out[pos] = vals
+        if name == "phi":
+            out = out.reshape(shape)
+    del owned
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    np.save(os.path.join(out_dir, name + ".npy"), out)
+    return {"dir": out_dir, "files": {name + ".npy": {"shape": list(out.shape), "dtype": "float64"}},
+            "what": "phi's work cells after the timed steps" + ("" if name == "phi" else
+                    f" at {DUMP_MAX_CELLS} positions drawn without replacement (numpy default_rng({DUMP_SEED})) from the "
+                    "C-order flat index of the NX x NY x NZ work area, ascending")}
+
+
 # ---------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------
@@ -295,13 +342,6 @@ def run_rank(args) -> int:
     # 20 s / 80 s, which are sized for hosts that write files between calls.  A schedule whose wait gives up in the set-up trial is
     # dropped on every rank; the shorter bound keeps a fabric that cannot serve one of them from eating the run's time budget.
     os.environ.setdefault("WAFER_HV_WAIT_MS", "5000")
-    # N > 1: a rank's process runs the engine's two streams beside RCCL's and torch's.  The overlap schedules keep kernels resident
-    # that wait for a word another stream's kernel (or copy) writes -- a gate kernel for a count, a workgroup for a flag -- and the
-    # runtime folds a process's streams onto FOUR hardware queues by default, in order within a queue: two such streams on one
-    # queue serialise at best and, where the waited-for work sits behind the waiter, stall until the bounded wait gives up (seen
-    # with 30 streams in one process, tools/hv_sweep.py, round 6).  Read by the HIP runtime when it initialises (nothing has yet).
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     # stdout carries exactly ONE line, the JSON result: native libraries that write to the C stdout
     # (RCCL prints a version banner there, flushed at exit) are sent to stderr instead
     sys.stdout.flush()
@@ -558,6 +598,7 @@ def run_rank(args) -> int:
         dist.all_reduce(one, op=dist.ReduceOp.SUM)
         ranks_seen = int(one[0])
     total_steps = args.warmup + args.steps    # what phi has been through since the initial condition
+    dumped = dump_outputs(args.dump_outputs, ctx, shape, z_begin, z_count, dist, rank) if args.dump_outputs else None
 
     pts_total = shape[0] * shape[1] * shape[2]
     value = pts_total * args.steps / elapsed
@@ -635,6 +676,8 @@ def run_rank(args) -> int:
     }
     if comm_info:
         result["comm"] = comm_info
+    if dumped:
+        result["dump_outputs"] = dumped
     rc = 0
 
     # ---- N > 1: the same grid undecomposed on rank 0's GPU: T1, and the slabs' bits -----------------

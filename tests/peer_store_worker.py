@@ -1,7 +1,6 @@
-"""Overlap mode 3 (peer stores) on WORLD slabs of one grid, all contexts in this process, against one context: prints which planes
-differ after every evolve call (tests/test_gpu_slab.py runs it as a subprocess for four slabs: more contexts than the runtime's
-default hardware queues make two ranks' kernels share a queue on ONE GPU, and a kernel that polls for a neighbour's stores must not
-sit in front of that neighbour's kernel -- GPU_MAX_HW_QUEUES lifts the limit; with one process per GPU the situation cannot arise).
+"""Overlap mode 3 (peer stores) on WORLD slabs of one grid against one context: prints which planes
+differ after every evolve call (tests/test_gpu_slab.py runs it for four slabs with WAFER_TEST_RANK_PROCESSES=1: run_slabs then
+runs each slab as a process of its own, so that no kernel polling for a neighbour's stores shares a hardware queue with it).
 
     python tests/peer_store_worker.py WORLD NX,NY,NZ STEPS[,STEPS...] [MODE [WAFER_HV_LAYOUT]]"""
 import os, sys

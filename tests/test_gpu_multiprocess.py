@@ -94,26 +94,27 @@ def test_bench_multi_rank_path(peers):
     _check_bench_two_rank_line(json.loads(lines[0]), peers)
 
 
-def test_bench_eight_rank_path():
-    """the driver's N = 8 call shape on the one GPU (host-staged transport): eight slabs of 32 planes, the set-up
-    trial over all exchange schedules -- the peer-store one included (WAFER_BENCH_PEERS=force: eight processes mapping
-    their z-neighbours' buffers through HIP IPC; the grid is kept at 16 workgroups per rank so that all eight ranks'
-    kernels are resident together and a polling workgroup cannot keep its neighbour's kernel off the CUs) -- three-step
-    passes with a two-step remainder, every slab's bits against the undecomposed run"""
+def test_bench_four_rank_path():
+    """the driver's multi-rank call shape on the one GPU (host-staged transport), at the most ranks the GPU may serve at once
+    beside this process and the bare call's launcher: four slabs of 32 planes (two middle ranks, so a middle-to-middle link),
+    the set-up trial over all exchange schedules -- the peer-store one included (WAFER_BENCH_PEERS=force: four processes
+    mapping their z-neighbours' buffers through HIP IPC; the grid is kept at 16 workgroups per rank so that all ranks' kernels
+    are resident together and a polling workgroup cannot keep its neighbour's kernel off the CUs) -- three-step passes with a
+    two-step remainder, every slab's bits against the undecomposed run"""
     import json
     import subprocess
     import sys
     env = dict(os.environ, WAFER_BENCH_TRANSPORT="host", WAFER_BENCH_PEERS="force", WAFER_HV_WAIT_MS="5000")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "11", "--warmup", "3",
-                        "--grid", "128,128,256"], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "11", "--warmup", "3",
+                        "--grid", "128,128,128"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert d["n_gpus"] == 8 and d["ranks"] == 8 and d["config"]["parallelism"] == "zslab8"
+    assert d["n_gpus"] == 4 and d["ranks"] == 4 and d["config"]["parallelism"] == "zslab4"
     ms = d["config"]["halo_overlap"]["ms_per_step"]
     assert d["config"]["points_per_gpu"] == 128 * 128 * 32 and len(ms) in (7, 9, 11) and "3_single_launch_peer_stores" in ms and "4_single_launch_peer_copies" in ms and "6_no_overlap_peer_copies" in ms
     assert d["config"]["halo_overlap"]["peer_store_check"]["identical"] is True and d["config"]["halo_overlap"]["peer_copy_check"]["identical"] is True
-    assert d["parity"]["identical"] is True and d["parity"]["slabs"] == 8 and d["parity"]["differing_slabs"] == []
-    assert d["single_gpu_ref"]["grid"] == [128, 128, 256] and d["comm"]["process_group_ranks"] == 8
+    assert d["parity"]["identical"] is True and d["parity"]["slabs"] == 4 and d["parity"]["differing_slabs"] == []
+    assert d["single_gpu_ref"]["grid"] == [128, 128, 128] and d["comm"]["process_group_ranks"] == 4
 
 
 def test_bench_bare_call_starts_its_own_ranks():

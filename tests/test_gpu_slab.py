@@ -7,6 +7,7 @@ import ctypes as C
 import functools
 import os
 import re
+import signal
 import subprocess
 import sys
 import threading
@@ -21,30 +22,29 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # context on its own device unless told that this is on purpose (read once per context).
 os.environ.setdefault("WAFER_PEER_SAME_DEVICE", "1")
 
-_CHILD_RESULTS = {}
-
-
 def peer_store_process(fn):
-    """Runs the decorated test -- all of its parameter sets, once -- in a pytest process of its own with more hardware queues
-    than the runtime hands a process by default.  In overlap mode 3 a rank's kernel polls for stores of its neighbour's kernel;
-    with the ranks as contexts of ONE process on ONE GPU (2 streams each) and the default of four hardware queues two such
-    kernels can share a queue, and the poller then sits in front of the kernel it waits for until its bounded wait gives up.
-    GPU_MAX_HW_QUEUES is read when the runtime initialises, so it cannot be raised for one test of a running process -- and
-    raising it for the whole suite would test everything else under a configuration no user has.  With one process per GPU
-    (every real run) the situation cannot arise."""
+    """Runs each parameter set of the decorated test in a pytest process of its own, where run_slabs runs connected
+    slabs as one process per rank (run_slabs_as_processes).  In overlap mode 3 a rank's kernel polls for
+    stores of its neighbour's kernel (modes 4 - 6: copies ordered by a credit rendezvous); with the ranks as contexts of ONE
+    process the runtime folds their streams onto the process's few hardware queues, and where two such kernels share one the
+    waiter sits in front of the kernel it waits for until its bounded wait gives up."""
     @functools.wraps(fn)
     def wrapper(*args, request, **kwargs):
         if os.environ.get("WAFER_TEST_CHILD") == "1":
             return fn(*args, **kwargs)
-        name = request.node.originalname or request.node.name
-        if name not in _CHILD_RESULTS:
-            env = dict(os.environ, WAFER_TEST_CHILD="1", GPU_MAX_HW_QUEUES="16")
-            r = subprocess.run([sys.executable, "-m", "pytest", f"{os.path.join(ROOT, 'tests', 'test_gpu_slab.py')}::{name}", "-q", "-rA", "-m", "gpu",
-                                "-p", "no:cacheprovider"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
-            verdicts = dict((m.group(2), m.group(1)) for m in re.finditer(r"^(PASSED|FAILED|ERROR) \S*::(\S+)", r.stdout, re.M))
-            _CHILD_RESULTS[name] = (verdicts, r.stdout[-6000:] + r.stderr[-2000:])
-        verdicts, log = _CHILD_RESULTS[name]
-        assert verdicts.get(request.node.name) == "PASSED", f"{request.node.name}: {verdicts.get(request.node.name)}\n{log}"
+        env = dict(os.environ, WAFER_TEST_CHILD="1", WAFER_TEST_RANK_PROCESSES="1")
+        # (a session of its own: on a time-out the child's rank processes go with it)
+        p = subprocess.Popen([sys.executable, "-m", "pytest", request.node.nodeid, "-q", "-rA", "-m", "gpu", "-p", "no:cacheprovider"],
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=request.config.rootpath,
+                             start_new_session=True)
+        try:
+            out, err = p.communicate(timeout=280)
+        except subprocess.TimeoutExpired:
+            os.killpg(p.pid, signal.SIGKILL)
+            out, err = p.communicate()
+            raise AssertionError(f"{request.node.name}: no verdict within 280 s\n{out[-6000:]}{err[-2000:]}")
+        verdicts = dict((m.group(2), m.group(1)) for m in re.finditer(r"^(PASSED|FAILED|ERROR) \S*::(\S+)", out, re.M))
+        assert verdicts.get(request.node.name) == "PASSED", f"{request.node.name}: {verdicts.get(request.node.name)}\n{out[-6000:]}{err[-2000:]}"
     # pytest must see `request` among the arguments it fills in
     import inspect
     sig = inspect.signature(fn)
@@ -131,9 +131,13 @@ class FakeFabric:
 
 def run_slabs(wa, base, world, body, connect=None):
     """body(ctx, rank) runs in one thread per slab; returns the list of results.  connect: wafer_peer_connect between the slabs
-    (None: where overlap mode 3 could apply -- ThreePoint with three ghost planes)"""
+    (None: where overlap mode 3 could apply -- ThreePoint with three ghost planes).  Under WAFER_TEST_RANK_PROCESSES=1 connected
+    slabs run as processes instead (run_slabs_as_processes)."""
     from wafer_amd.slab import partition
     import dataclasses
+    peers = connect or (connect is None and base.ext == 1 and base.halo_depth >= 3)
+    if world >= 2 and peers and os.environ.get("WAFER_TEST_RANK_PROCESSES") == "1":
+        return run_slabs_as_processes(base, world, body, connect)
     fabric = FakeFabric(world)
     results, errors = [None] * world, []
 
@@ -162,6 +166,59 @@ def run_slabs(wa, base, world, body, connect=None):
     if errors:
         raise errors[0]
     return results, fabric
+
+
+def run_slabs_as_processes(base, world, body, connect=None, timeout=240):
+    """run_slabs with one process per slab (tests/slab_rank_worker.py): the same body, results and halo hook counts.  Kernels
+    that wait for a neighbour's stores or copies must all be resident at once; contexts of ONE process share its few hardware
+    queues, and two such kernels can land on one queue, the waiter in front of the kernel it waits for.  A
+    process per rank has queues of its own, as every real run does.  The fabric is gloo with host staging instead of in-process
+    copies (bytes move differently, the engine's arithmetic is the same)."""
+    import pickle
+    import socket
+    import tempfile
+    import types
+    import cloudpickle
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    with tempfile.TemporaryDirectory() as tmp:
+        job = os.path.join(tmp, "job.pkl")
+        with open(job, "wb") as f:
+            cloudpickle.dump((base, body, connect), f)
+        procs, logs = [], []
+        try:
+            for r in range(world):
+                logs.append(open(os.path.join(tmp, f"rank{r}.log"), "w+"))
+                env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                           MASTER_PORT=str(port), WAFER_PEER_SAME_DEVICE="1", PYTHONUNBUFFERED="1")
+                procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "slab_rank_worker.py"), job,
+                                               os.path.join(tmp, f"out{r}.pkl")], env=env, cwd=ROOT, stdout=logs[-1],
+                                              stderr=subprocess.STDOUT))
+            codes = []
+            for p in procs:
+                try:
+                    codes.append(p.wait(timeout=timeout))
+                except subprocess.TimeoutExpired:
+                    codes.append(None)
+                    break
+        finally:
+            for p in procs:
+                if p.poll() is None:
+                    p.kill()
+                    p.wait()
+            text = []
+            for r, f in enumerate(logs):
+                f.seek(0)
+                text.append(f"--- rank {r} ---\n" + f.read()[-3000:])
+                f.close()
+        if codes != [0] * world:
+            raise AssertionError(f"slab rank processes exited with {codes}\n" + "\n".join(text))
+        outs = []
+        for r in range(world):
+            with open(os.path.join(tmp, f"out{r}.pkl"), "rb") as f:
+                outs.append(pickle.load(f))
+    return [o[0] for o in outs], types.SimpleNamespace(halo_calls=[o[1] for o in outs])
 
 
 def assemble(base, world, pieces):
@@ -298,7 +355,7 @@ F3_SLAB_CASES = [(2, (40, 24, 32), 12), (3, (140, 17, 37), 7), (4, (130, 33, 48)
 # exchanges (four contexts on ONE GPU share hardware queues: that case runs in test_peer_store_four_slabs_in_a_subprocess)
 @pytest.mark.parametrize("world,shape,steps,cycle,overlap",
                          [(w, sh, st, cy, ov) for (w, sh, st) in F3_SLAB_CASES for cy in (1, 2) for ov in (True, False, 2, 3) if not (ov == 3 and w > 3)])
-@peer_store_process   # (mode 3 among the parameters: in a long-lived process two of the 3 x 2 streams can land on one of the four default hardware queues -- round 6)
+@peer_store_process   # (mode 3 among the parameters: three slabs run as processes)
 def test_three_step_kernel_on_slabs_bit_exact(wa, world, shape, steps, cycle, overlap, monkeypatch):
     """three fused ThreePoint steps per pass on z-slabs (3 ghost planes per pass and side; 6 with one exchange
     per two passes): boundary-first overlap, the mixed long / short interior launch, two-step and single-step
@@ -582,15 +639,15 @@ def test_peer_connect_refuses_another_context_on_the_same_device(wa, monkeypatch
 
 
 def test_peer_store_four_slabs_in_a_subprocess():
-    """four slabs (two middle ranks) need more hardware queues than the runtime hands one process by default: a kernel polling
-    for its neighbour's stores would otherwise sit in the same queue in front of that neighbour's kernel"""
+    """four slabs (two middle ranks), each a process of its own (run_slabs_as_processes): a kernel polling for its neighbour's
+    stores never shares a hardware queue with that neighbour's kernel"""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for layout in ("3", "4"):
         r = subprocess.run([sys.executable, os.path.join(root, "tests", "peer_store_worker.py"), "4", "130,33,48", "10,5,9", "3", layout],
-                           capture_output=True, text=True, timeout=600, env=dict(os.environ, GPU_MAX_HW_QUEUES="16", WAFER_PEER_SAME_DEVICE="1"), cwd=root)
+                           capture_output=True, text=True, timeout=600, env=dict(os.environ, WAFER_PEER_SAME_DEVICE="1", WAFER_TEST_RANK_PROCESSES="1"), cwd=root)
         assert r.returncode == 0 and "PEER-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
@@ -598,9 +655,9 @@ def test_peer_store_four_slabs_in_a_subprocess():
 def test_randomised_slab_sweep_against_the_oracle(seed):
     """tests/fuzz_slabs.py: random grids, stencil orders, storage types, 2 - 4 uneven slabs, every overlap mode (peer stores in both
     pass layouts), deep halos, several evolve calls, potentials incl. the z-special ones -- the assembled slabs against the ORACLE
-    bit for bit (fp32 storage: against one context), all-reduced observables to 1e-11; in a process of its own (hardware queues)"""
+    bit for bit (fp32 storage: against one context), all-reduced observables to 1e-11; connected slabs as processes (run_slabs_as_processes)"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_slabs.py")], capture_output=True, text=True,
-                       env=dict(os.environ, N="40", SEED=str(seed), GPU_MAX_HW_QUEUES="16", WAFER_PEER_SAME_DEVICE="1"), timeout=900, cwd=ROOT)
+                       env=dict(os.environ, N="40", SEED=str(seed), WAFER_PEER_SAME_DEVICE="1", WAFER_TEST_RANK_PROCESSES="1"), timeout=900, cwd=ROOT)
     assert r.returncode == 0 and "bad = 0" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
