@@ -131,6 +131,7 @@ pub struct wafer_device_info {
 }
 
 pub enum wafer_ctx {}
+pub enum wafer_batch {}
 
 pub type wafer_halo_fn = extern "C" fn(*mut c_void, *mut c_void, *mut c_void, *mut c_void, *mut c_void, usize, *mut c_void) -> c_int;
 pub type wafer_allreduce_fn = extern "C" fn(*mut c_void, *mut c_void, usize, *mut c_void) -> c_int;
@@ -199,6 +200,25 @@ extern "C" {
     pub fn wafer_diag_div_planned_f32(ctx: *mut wafer_ctx, plan: *const wafer_div_plan_f32_t, lo_exp: c_int, hi_exp: c_int, mismatches: *mut u64) -> c_int;
     pub fn wafer_diag_div_planned(ctx: *mut wafer_ctx, plan: *const wafer_div_plan_t, seed: u64, n_random: u64, lo_exp: c_int, hi_exp: c_int,
                                   operands: *const f64, n_operands: usize, mismatches_random: *mut u64, mismatches_operands: *mut u64) -> c_int;
+    // batched ensembles: B ground-state problems of one shape, one launch per step (include/wafer_hip.h)
+    pub fn wafer_batch_create(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
+    pub fn wafer_batch_destroy(b: *mut wafer_batch) -> c_int;
+    pub fn wafer_batch_size(b: *mut wafer_batch, n_members: *mut u32) -> c_int;
+    pub fn wafer_batch_set_potential_builtin(b: *mut wafer_batch, member: u32, potential: c_int) -> c_int;
+    pub fn wafer_batch_set_potential_host(b: *mut wafer_batch, member: u32, v: *const f64, potsub_kind: c_int, potsub_scalar: f64,
+                                          potsub: *const f64) -> c_int;
+    pub fn wafer_batch_set_initial_condition(b: *mut wafer_batch, member: u32, ic: c_int, seed: u64) -> c_int;
+    pub fn wafer_batch_upload_phi(b: *mut wafer_batch, member: u32, phi: *const f64) -> c_int;
+    pub fn wafer_batch_download_phi(b: *mut wafer_batch, member: u32, phi: *mut f64) -> c_int;
+    pub fn wafer_batch_evolve(b: *mut wafer_batch, active: *const u8, n_steps: u64) -> c_int;
+    pub fn wafer_batch_observables(b: *mut wafer_batch, out: *mut wafer_observables_t) -> c_int;
+    pub fn wafer_batch_normalise(b: *mut wafer_batch, active: *const u8, norm2: *const f64) -> c_int;
+    pub fn wafer_batch_solve(
+        b: *mut wafer_batch, tolerance: f64, screen_update: u64, has_max_steps: c_int, max_steps: u64, records: *mut wafer_block_record,
+        max_records_per_member: usize, n_records: *mut usize, finals: *mut wafer_observables_output, status: *mut c_int,
+    ) -> c_int;
+    pub fn wafer_batch_last_evolve_ms(b: *mut wafer_batch, ms: *mut f32, steps: *mut u64) -> c_int;
+    pub fn wafer_batch_kernel_name(b: *mut wafer_batch) -> *const c_char;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

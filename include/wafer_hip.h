@@ -426,6 +426,45 @@ typedef struct wafer_device_info {
 } wafer_device_info;
 int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
 
+/* ---- batched ensembles ------------------------------------------------------
+ * A batch holds B independent ground-state problems ("members") on one device, all with the same work-area shape, the same
+ * central_difference and dtype WAFER_F64, each with its own dn, dt, mass, sig, flags, potential, pot_sub and wavefunction.  One
+ * launch per step advances every ACTIVE member (a workgroup table built from the active members only: a member that is not
+ * active costs nothing); observables are one launch, one reduce launch and one small download for all members.  Every member
+ * computes bit for bit what a single wafer_ctx with its wafer_params computes: phi after evolve, the observables (the single
+ * context's partition and reduction order), normalisation and solve.  No z-slabs (z_count must be 0), no excited states.
+ * Member arrays live in one allocation per array kind (phi ping-pong, V, pot_sub) with a member stride.
+ * wafer_batch_create validates every member before any HIP call (WAFER_ERR_INVALID names the member and the field). */
+typedef struct wafer_batch wafer_batch;
+int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out);
+int wafer_batch_destroy(wafer_batch *b);
+int wafer_batch_size(wafer_batch *b, uint32_t *n_members);
+/* per member, as wafer_set_potential_builtin / wafer_set_potential_host / wafer_set_initial_condition / wafer_upload_phi /
+ * wafer_download_phi do for a context (same array layouts) */
+int wafer_batch_set_potential_builtin(wafer_batch *b, uint32_t member, int potential);
+int wafer_batch_set_potential_host(wafer_batch *b, uint32_t member, const double *v, int potsub_kind, double potsub_scalar,
+                                   const double *potsub);
+int wafer_batch_set_initial_condition(wafer_batch *b, uint32_t member, int ic, uint64_t seed);
+int wafer_batch_upload_phi(wafer_batch *b, uint32_t member, const double *phi);
+int wafer_batch_download_phi(wafer_batch *b, uint32_t member, double *phi);
+/* n_steps ground-state steps (0 takes one, as wafer_evolve) of the members with active[m] != 0 (active NULL: all) */
+int wafer_batch_evolve(wafer_batch *b, const uint8_t *active, uint64_t n_steps);
+/* compute_observables of every member: out has n_members entries */
+int wafer_batch_observables(wafer_batch *b, wafer_observables_t *out);
+/* normalise_wavefunction of the active members, member m by norm2[m] (n_members entries) */
+int wafer_batch_normalise(wafer_batch *b, const uint8_t *active, const double *norm2);
+/* wafer_solve_state(ctx, 0, ...) for every member at once.  records: n_members * max_records_per_member rows, member m's at
+ * m * max_records_per_member; n_records, finals, status: n_members entries.  status[m]: WAFER_OK (converged),
+ * WAFER_ERR_MAX_STEP, or WAFER_ERR_STATE (non-finite energy; wafer_last_error names the first such member).  A member that
+ * has finished is frozen: it is not normalised or advanced again.  Returns WAFER_OK unless the call itself failed. */
+int wafer_batch_solve(wafer_batch *b, double tolerance, uint64_t screen_update, int has_max_steps, uint64_t max_steps,
+                      wafer_block_record *records, size_t max_records_per_member, size_t *n_records,
+                      wafer_observables_output *finals, int *status);
+/* HIP-event time of the step launches of the last wafer_batch_evolve and its step count (blocks until they finish) */
+int wafer_batch_last_evolve_ms(wafer_batch *b, float *ms, uint64_t *steps);
+/* the kernel a batched step launches: wafer_k_batch_step */
+const char *wafer_batch_kernel_name(wafer_batch *b);
+
 #ifdef __cplusplus
 }
 #endif

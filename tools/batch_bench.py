@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Batched ensembles against what a user does today: B members of one shape (Harmonic, ThreePoint fp64, members differing in
+dt) advanced by one wafer_batch_evolve, by B Contexts one after another from one thread, and by B Contexts on B Python threads
+(ctypes releases the GIL).  One JSON line per (shape, B):
+  batch_us_per_step / batch_gups  HIP events around the batch's step launches, after warm-up
+  batch_host_us_per_step / _gups  host clock around the batch's evolve call until its last step has finished (host work, launches
+                                  and the wait included: timed like the two baselines; the speedups are taken from these)
+  seq_us_per_step / seq_gups      host clock around B x (evolve + synchronise), one context after another
+  thr_us_per_step / thr_gups      host clock around B threads, each evolve + synchronise on its own context
+  parity                          member 0 of the batch bit-identical to a single context after the same steps
+gups: grid-point updates per second (members x work cells x steps / time), 1e9."""
+import argparse, json, os, sys, threading, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import wafer_amd
+
+
+def members(n, B):
+    return [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0) for k in range(B)]
+
+
+def row(n, B, steps, warmup, only_batch=False):
+    pars = members(n, B)
+    cells = n ** 3
+    out = {"shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "stencil": "ThreePoint", "dtype": "f64",
+           "potential": "Harmonic"}
+    with wafer_amd.Batch(pars) as b:
+        for k in range(B):
+            b.set_potential(k, "Harmonic")
+            b.set_initial_condition(k, "Gaussian")
+        b.evolve(warmup)
+        b.last_evolve_ms()   # (waits for the warm-up)
+        t0 = time.perf_counter()
+        b.evolve(steps)
+        ms, st = b.last_evolve_ms()   # blocks until the last step has finished
+        t = time.perf_counter() - t0
+        out["batch_host_us_per_step"] = 1e6 * t / steps
+        out["batch_host_gups"] = B * cells * steps / t / 1e9
+        out["kernel"] = b.kernel_name()
+        out["batch_us_per_step"] = 1e3 * ms / st
+        out["batch_gups"] = B * cells * st / (ms * 1e-3) / 1e9
+        if only_batch:
+            return out
+        with wafer_amd.Context(pars[0]) as ctx:   # parity of member 0 in the same run
+            ctx.set_potential("Harmonic")
+            ctx.set_initial_condition("Gaussian")
+            ctx.evolve(0, warmup)
+            ctx.evolve(0, steps)
+            out["parity"] = bool(np.array_equal(ctx.download_phi().view(np.int64), b.download_phi(0).view(np.int64)))
+    ctxs = [wafer_amd.Context(p) for p in pars]
+    try:
+        for c in ctxs:
+            c.set_potential("Harmonic")
+            c.set_initial_condition("Gaussian")
+            c.evolve(0, warmup)
+            c.synchronize()
+        out["single_kernel"] = ctxs[0].stencil_kernel_name()
+        t0 = time.perf_counter()
+        for c in ctxs:
+            c.evolve(0, steps)
+            c.synchronize()
+        t = time.perf_counter() - t0
+        out["seq_us_per_step"] = 1e6 * t / steps
+        out["seq_gups"] = B * cells * steps / t / 1e9
+
+        def work(c):
+            c.evolve(0, steps)
+            c.synchronize()
+        ths = [threading.Thread(target=work, args=(c,)) for c in ctxs]
+        t0 = time.perf_counter()
+        for th in ths:
+            th.start()
+        for th in ths:
+            th.join()
+        t = time.perf_counter() - t0
+        out["thr_us_per_step"] = 1e6 * t / steps
+        out["thr_gups"] = B * cells * steps / t / 1e9
+    finally:
+        for c in ctxs:
+            c.close()
+    out["speedup_vs_seq"] = out["batch_host_gups"] / out["seq_gups"]
+    out["speedup_vs_thr"] = out["batch_host_gups"] / out["thr_gups"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[50, 64])
+    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8, 32, 64])
+    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--warmup", type=int, default=40)
+    ap.add_argument("--out", help="also append the lines to this file")
+    ap.add_argument("--only-batch", action="store_true", help="the batch alone, no contexts (counter runs)")
+    a = ap.parse_args()
+    for n in a.sizes:
+        for B in a.batch:
+            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch).items()})
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

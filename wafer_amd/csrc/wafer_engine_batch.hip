@@ -1,0 +1,523 @@
+// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B ground-state problems of one shape on one
+// device, one launch per step over the active members (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip).
+//
+// Each member is also a context VIEW: a wafer_ctx whose arrays are the member's slices of the batch's allocations and whose
+// stream is the batch's.  Potentials, initial conditions, uploads and downloads go through the context entry points on that
+// view, so a member is set up by the very code that sets up a single context.  The views own nothing.
+#include "wafer_engine.h"
+#include "wafer_stencil_lds.hip.h"
+#include "wafer_stencil_batch.hip.h"
+
+struct wafer_batch {
+    uint32_t n = 0;
+    std::vector<wafer_params> P;
+    WaferGeom g;
+    int device = 0, num_cus = 256;
+    WaferTuning tune;
+    hipStream_t s = nullptr;
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    size_t stride = 0;                        // elements per member in each array allocation
+    void *alloc[4] = {nullptr, nullptr, nullptr, nullptr};   // phi[0], phi[1], V, pot_sub
+    std::vector<wafer_ctx *> views;
+    double *view_scal = nullptr, *view_scal_host = nullptr;  // SCAL_SLOTS per view
+    // device tables
+    std::vector<WaferBatchMember> mem;
+    WaferBatchMember *mem_dev = nullptr;
+    std::vector<WaferBatchBlock> blk;
+    WaferBatchBlock *blk_dev = nullptr;
+    size_t blk_cap = 0;
+    std::vector<uint8_t> blk_key;             // the active set the device block table was built for
+    int *act_dev = nullptr, *act_host = nullptr;
+    // observables: the single context's partition
+    int obs_ntx = 0, obs_nty = 0, obs_zchunk = 0, obs_nb = 0, swz = 0;
+    double *partials = nullptr;               // [member][4][obs_nb]
+    double *sums = nullptr, *sums_host = nullptr;   // [member][4]
+    double *n2 = nullptr, *n2_host = nullptr;        // [member]
+    uint64_t last_steps = 0;
+    bool timing_valid = false;
+};
+
+namespace {
+
+int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0)
+{
+    if (m->struct_size != sizeof(wafer_params))
+        return fail(WAFER_ERR_INVALID, "member %u: wafer_params.struct_size %u != %zu (ABI mismatch)", i, m->struct_size, sizeof(wafer_params));
+    if (m->nx < 1 || m->ny < 1 || m->nz < 1) return fail(WAFER_ERR_INVALID, "member %u: grid size must be >= 1", i);
+    if (m->central_difference < 1 || m->central_difference > 3)
+        return fail(WAFER_ERR_INVALID, "member %u: central_difference must be 1 (Three), 2 (Five) or 3 (SevenPoint)", i);
+    if (m->dtype != WAFER_F64) return fail(WAFER_ERR_INVALID, "member %u: dtype must be f64 (WAFER_F64) in a batch", i);
+    if (m->z_count != 0) return fail(WAFER_ERR_INVALID, "member %u: z_count must be 0 (a batch holds no z-slabs)", i);
+    if (!(m->dn > 0) || !(m->dt > 0) || !(m->mass > 0)) return fail(WAFER_ERR_INVALID, "member %u: dn, dt, mass must be > 0", i);
+    const double den = wafer_stencil_den(m->central_difference, m->dn, m->mass);
+    if (!std::isnormal(den) || !std::isnormal(1.0 / den))
+        return fail(WAFER_ERR_INVALID, "member %u: dn^2 * mass = %g is outside the range of normal doubles (or its reciprocal is)", i,
+                    m->dn * m->dn * m->mass);
+    if (!(m->flags & WAFER_FLAG_SKIP_DT_CHECK) && m->dt > m->dn * m->dn / 3.)   // config.rs:362-365
+        return fail(WAFER_ERR_INVALID, "member %u: LargeDt: dt must be <= dn^2/3 (config.rs:363)", i);
+    if (m->halo_depth != 0 && (int)m->halo_depth < m->central_difference)
+        return fail(WAFER_ERR_INVALID, "member %u: halo_depth must be >= ext", i);
+    if (m0) {
+        if (m->nx != m0->nx) return fail(WAFER_ERR_INVALID, "member %u: nx = %u differs from member 0's %u", i, m->nx, m0->nx);
+        if (m->ny != m0->ny) return fail(WAFER_ERR_INVALID, "member %u: ny = %u differs from member 0's %u", i, m->ny, m0->ny);
+        if (m->nz != m0->nz) return fail(WAFER_ERR_INVALID, "member %u: nz = %u differs from member 0's %u", i, m->nz, m0->nz);
+        if (m->central_difference != m0->central_difference)
+            return fail(WAFER_ERR_INVALID, "member %u: central_difference = %d differs from member 0's %d", i, m->central_difference,
+                        m0->central_difference);
+        if (m->device != m0->device) return fail(WAFER_ERR_INVALID, "member %u: device = %d differs from member 0's %d", i, m->device, m0->device);
+        if (m->halo_depth != m0->halo_depth)   // (the batch's one geometry is built with it)
+            return fail(WAFER_ERR_INVALID, "member %u: halo_depth = %u differs from member 0's %u", i, m->halo_depth, m0->halo_depth);
+    }
+    return WAFER_OK;
+}
+
+void destroy(wafer_batch *b)
+{
+    (void)hipSetDevice(b->device);
+    if (b->s) (void)hipStreamSynchronize(b->s);
+    for (wafer_ctx *v : b->views) delete v;   // views borrow every array and the stream
+    for (void *p : b->alloc)
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
+                    (void *)b->n2})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host})
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : {b->ev_start, b->ev_stop})
+        if (e) (void)hipEventDestroy(e);
+    if (b->s) (void)hipStreamDestroy(b->s);
+    delete b;
+}
+
+int check_member_index(const wafer_batch *b, uint32_t m)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    if (m >= b->n) return fail(WAFER_ERR_INVALID, "member %u out of range (the batch has %u)", m, b->n);
+    return WAFER_OK;
+}
+
+// the member table as the views stand now (potential range, pot_sub, current buffer), to the device if it changed
+int sync_members(wafer_batch *b)
+{
+    bool changed = false;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        const wafer_ctx *c = b->views[m];
+        WaferBatchMember e = b->mem[m];
+        e.short_forms = short_forms(c) ? 1 : 0;
+        e.potsub_kind = c->potsub_kind;
+        e.potsub_scalar = c->potsub_scalar;
+        e.cur = c->cur;
+        if (memcmp(&e, &b->mem[m], sizeof e) != 0) {
+            b->mem[m] = e;
+            changed = true;
+        }
+    }
+    if (!changed) return WAFER_OK;
+    HIP_TRY(hipStreamSynchronize(b->s));   // no launch in flight reads the table
+    HIP_TRY(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * b->n, hipMemcpyHostToDevice));
+    return WAFER_OK;
+}
+
+// the active members' slots into act_dev; returns their number
+int upload_active(wafer_batch *b, const uint8_t *active, int *nact)
+{
+    HIP_TRY(hipStreamSynchronize(b->s));   // act_host is read by a copy of an earlier call
+    int k = 0;
+    for (uint32_t m = 0; m < b->n; ++m)
+        if (!active || active[m]) b->act_host[k++] = (int)m;
+    *nact = k;
+    if (k) HIP_TRY(hipMemcpyAsync(b->act_dev, b->act_host, sizeof(int) * k, hipMemcpyHostToDevice, b->s));
+    return WAFER_OK;
+}
+
+// The step's workgroup table: 64 x 4 tiles of the work area, z cut into chunks so that the active members together give
+// ~8 workgroups per CU (a CU holds 8 of these 256-thread workgroups), no chunk shorter than 8 planes.
+int build_blocks(wafer_batch *b, const uint8_t *active)
+{
+    std::vector<uint8_t> key(b->n);
+    for (uint32_t m = 0; m < b->n; ++m) key[m] = (!active || active[m]) ? 1 : 0;
+    if (key == b->blk_key && b->blk_dev) return WAFER_OK;
+    const WaferGeom &g = b->g;
+    const int ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX, nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    long long nact = 0;
+    for (uint8_t a : key) nact += a;
+    const long long layer = nact * ntx * nty;
+    const long long target = 8LL * b->num_cus;
+    long long nch = layer > 0 ? (target + layer - 1) / layer : 1;
+    nch = std::max(1LL, std::min(nch, (long long)(g.nzl + 7) / 8));
+    const int zchunk = (int)((g.nzl + nch - 1) / nch);
+    b->blk.clear();
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (!key[m]) continue;
+        for (int z0 = g.G; z0 < g.G + g.nzl; z0 += zchunk)
+            for (int ty = 0; ty < nty; ++ty)
+                for (int tx = 0; tx < ntx; ++tx)
+                    b->blk.push_back(WaferBatchBlock{(int)m, tx * WAFER_BATCH_TX, ty * WAFER_BATCH_TY, z0, std::min(z0 + zchunk, g.G + g.nzl), 0});
+    }
+    HIP_TRY(hipStreamSynchronize(b->s));
+    if (b->blk.size() > b->blk_cap) {
+        if (b->blk_dev) HIP_TRY(hipFree(b->blk_dev));
+        b->blk_dev = nullptr;
+        HIP_TRY(hipMalloc((void **)&b->blk_dev, sizeof(WaferBatchBlock) * b->blk.size()));
+        b->blk_cap = b->blk.size();
+    }
+    if (!b->blk.empty()) HIP_TRY(hipMemcpy(b->blk_dev, b->blk.data(), sizeof(WaferBatchBlock) * b->blk.size(), hipMemcpyHostToDevice));
+    b->blk_key = key;
+    return WAFER_OK;
+}
+
+int evolve(wafer_batch *b, const uint8_t *active, uint64_t n_steps)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_pot || !b->views[m]->have_phi)
+            return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set before evolve", m);
+    }
+    const uint64_t steps = n_steps == 0 ? 1 : n_steps;   // grid.rs:682-685
+    TRY(sync_members(b));
+    TRY(build_blocks(b, active));
+    RoctxRange range_("wafer_batch_evolve");
+    HIP_TRY(hipEventRecord(b->ev_start, b->s));
+    if (!b->blk.empty()) {
+        for (uint64_t k = 0; k < steps; ++k) {
+            const hipError_t e = wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), (int)(k & 1), b->s);
+            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
+    b->last_steps = steps;
+    b->timing_valid = true;
+    if (steps & 1)
+        for (uint32_t m = 0; m < b->n; ++m)
+            if (!active || active[m]) b->views[m]->cur ^= 1;
+    return WAFER_OK;
+}
+
+// the four raw sums of the active members into sums_host[m * 4 ..]
+int observables(wafer_batch *b, const uint8_t *active)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_pot || !b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set", m);
+    }
+    TRY(sync_members(b));
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    if (!nact) return WAFER_OK;
+    RoctxRange range_("wafer_batch_observables");
+    const hipError_t e = wafer_entry_batch_observables(b->g.R, b->g, b->mem_dev, b->act_dev, nact, b->obs_ntx, b->obs_nty, b->obs_nb,
+                                                       b->obs_zchunk, b->swz, b->partials, b->sums, b->s);
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched observables launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(b->sums_host, b->sums, sizeof(double) * 4 * b->n, hipMemcpyDeviceToHost, b->s));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    return WAFER_OK;
+}
+
+void obs_of(const wafer_batch *b, uint32_t m, wafer_observables_t *o)
+{
+    const double *r = b->sums_host + (size_t)m * 4;
+    o->energy = r[0];
+    o->norm2 = r[1];
+    o->v_infinity = (b->views[m]->potsub_kind == WAFER_POTSUB_NONE) ? 0.0 : r[2];   // grid.rs:425
+    o->r2 = r[3];
+}
+
+// normalise the active members; norm2 on the device, member m's at norm2_dev[m * stride]
+int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, int stride)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+    }
+    TRY(sync_members(b));
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    if (!nact) return WAFER_OK;
+    const hipError_t e = wafer_entry_batch_normalise(b->g, b->mem_dev, b->act_dev, nact, norm2_dev, stride, b->s);
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
+    return WAFER_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out)
+{
+    if (!members || !out) return fail(WAFER_ERR_INVALID, "null argument");
+    if (n_members == 0) return fail(WAFER_ERR_INVALID, "a batch needs at least one member (n_members = 0)");
+    for (uint32_t i = 0; i < n_members; ++i) TRY(check_member(&members[i], i, i ? &members[0] : nullptr));
+    const wafer_params &p0 = members[0];
+    const int R = p0.central_difference;
+    const int G = p0.halo_depth ? (int)p0.halo_depth : R;
+    const WaferGeom g = wafer_make_geom((int)p0.nx, (int)p0.ny, (int)p0.nz, R, G, 0, (int)p0.nz, 8);
+    size_t bytes = 0;
+    if (__builtin_mul_overflow((size_t)g.total, (size_t)n_members, &bytes) || __builtin_mul_overflow(bytes, (size_t)8, &bytes))
+        return fail(WAFER_ERR_INVALID, "%u members of %lld padded cells overflow the size of one allocation", n_members, (long long)g.total);
+
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (ndev < 1) return fail(WAFER_ERR_HIP, "no HIP device visible: the engine has no CPU path");
+    if (p0.device < 0 || p0.device >= ndev) return fail(WAFER_ERR_INVALID, "member 0: device %d out of range", p0.device);
+    HIP_TRY(hipSetDevice(p0.device));
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p0.device));
+
+    wafer_batch *b = new wafer_batch();
+    b->n = n_members;
+    b->P.assign(members, members + n_members);
+    b->g = g;
+    b->device = p0.device;
+    b->num_cus = cus > 0 ? cus : 256;
+    b->tune = wafer_tuning_from_env();
+    b->stride = (size_t)g.total;
+#define HIP_TRYB(expr)                                                                               \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            const int rc_ = fail(WAFER_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
+            destroy(b);                                                                              \
+            return rc_;                                                                              \
+        }                                                                                            \
+    } while (0)
+    HIP_TRYB(hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
+    HIP_TRYB(hipEventCreate(&b->ev_start));
+    HIP_TRYB(hipEventCreate(&b->ev_stop));
+    for (void *&a : b->alloc) {   // one allocation per array kind, zeros: frames, pads and guard zones of every member
+        HIP_TRYB(hipMalloc(&a, bytes));
+        HIP_TRYB(hipMemsetAsync(a, 0, bytes, b->s));
+    }
+    HIP_TRYB(hipMalloc((void **)&b->view_scal, sizeof(double) * SCAL_SLOTS * n_members));
+    HIP_TRYB(hipMemsetAsync(b->view_scal, 0, sizeof(double) * SCAL_SLOTS * n_members, b->s));
+    HIP_TRYB(hipHostMalloc((void **)&b->view_scal_host, sizeof(double) * SCAL_SLOTS * n_members, hipHostMallocDefault));
+
+    // observables: the partition wafer_launch_observables_lds gives a single context of this shape
+    {
+        const int NW = R <= 2 ? 8 : 4;
+        const int TX = 128, TY = 2 * NW;
+        b->obs_zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, 2 * (NW / 4), b->num_cus)
+                        : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, 2 * (NW / 4), b->num_cus)
+                                 : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, 2 * (NW / 4), b->num_cus);
+        b->obs_ntx = (g.nx + TX - 1) / TX;
+        b->obs_nty = (g.ny + TY - 1) / TY;
+        b->obs_nb = b->obs_ntx * b->obs_nty * ((g.nzl + b->obs_zchunk - 1) / b->obs_zchunk);
+        b->swz = wafer_lds_opts(b->tune).swz;
+    }
+    HIP_TRYB(hipMalloc((void **)&b->partials, sizeof(double) * 4 * (size_t)b->obs_nb * n_members));
+    HIP_TRYB(hipMalloc((void **)&b->sums, sizeof(double) * 4 * n_members));
+    HIP_TRYB(hipHostMalloc((void **)&b->sums_host, sizeof(double) * 4 * n_members, hipHostMallocDefault));
+    HIP_TRYB(hipMalloc((void **)&b->n2, sizeof(double) * n_members));
+    HIP_TRYB(hipHostMalloc((void **)&b->n2_host, sizeof(double) * n_members, hipHostMallocDefault));
+    HIP_TRYB(hipMalloc((void **)&b->act_dev, sizeof(int) * n_members));
+    HIP_TRYB(hipHostMalloc((void **)&b->act_host, sizeof(int) * n_members, hipHostMallocDefault));
+    HIP_TRYB(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
+
+    b->views.reserve(n_members);
+    b->mem.resize(n_members);
+    for (uint32_t m = 0; m < n_members; ++m) {
+        wafer_ctx *c = new wafer_ctx();
+        b->views.push_back(c);
+        c->P = members[m];
+        c->g = g;
+        c->esz = 8;
+        c->num_cus = b->num_cus;
+        c->tune = b->tune;
+        c->bx = (g.px + 63) / 64;
+        c->by = (g.py + 3) / 4;
+        c->s_main = c->s_aux = b->s;
+        c->div_plan = wafer_divplan_make(wafer_stencil_den(R, members[m].dn, members[m].mass));
+        if (members[m].flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = 0;
+        void **arr[4] = {&c->phi[0], &c->phi[1], &c->v, &c->potsub};
+        for (int k = 0; k < 4; ++k)
+            *arr[k] = static_cast<char *>(b->alloc[k]) + ((size_t)m * b->stride + (size_t)g.base_off) * 8;
+        c->scal = b->view_scal + (size_t)m * SCAL_SLOTS;
+        c->scal_host = b->view_scal_host + (size_t)m * SCAL_SLOTS;
+        c->kernel_name = "wafer_k_batch_step";
+        WaferBatchMember &e = b->mem[m];
+        memset(&e, 0, sizeof e);
+        e.phi[0] = c->phi[0];
+        e.phi[1] = c->phi[1];
+        e.v = c->v;
+        e.potsub = c->potsub;
+        e.dt = members[m].dt;
+        e.den = c->div_plan.den;
+        e.zh = c->div_plan.zh;
+        e.zl = c->div_plan.zl;
+    }
+    HIP_TRYB(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * n_members, hipMemcpyHostToDevice));
+    HIP_TRYB(hipStreamSynchronize(b->s));
+#undef HIP_TRYB
+    *out = b;
+    return WAFER_OK;
+}
+
+int wafer_batch_destroy(wafer_batch *b)
+{
+    if (b) destroy(b);
+    return WAFER_OK;
+}
+
+int wafer_batch_size(wafer_batch *b, uint32_t *n_members)
+{
+    if (!b || !n_members) return fail(WAFER_ERR_INVALID, "null argument");
+    *n_members = b->n;
+    return WAFER_OK;
+}
+
+int wafer_batch_set_potential_builtin(wafer_batch *b, uint32_t member, int potential)
+{
+    TRY(check_member_index(b, member));
+    return wafer_set_potential_builtin(b->views[member], potential);
+}
+
+int wafer_batch_set_potential_host(wafer_batch *b, uint32_t member, const double *v, int potsub_kind, double potsub_scalar,
+                                   const double *potsub)
+{
+    TRY(check_member_index(b, member));
+    return wafer_set_potential_host(b->views[member], v, potsub_kind, potsub_scalar, potsub);
+}
+
+int wafer_batch_set_initial_condition(wafer_batch *b, uint32_t member, int ic, uint64_t seed)
+{
+    TRY(check_member_index(b, member));
+    return wafer_set_initial_condition(b->views[member], ic, seed);
+}
+
+int wafer_batch_upload_phi(wafer_batch *b, uint32_t member, const double *phi)
+{
+    TRY(check_member_index(b, member));
+    return wafer_upload_phi(b->views[member], phi);
+}
+
+int wafer_batch_download_phi(wafer_batch *b, uint32_t member, double *phi)
+{
+    TRY(check_member_index(b, member));
+    return wafer_download_phi(b->views[member], phi);
+}
+
+int wafer_batch_evolve(wafer_batch *b, const uint8_t *active, uint64_t n_steps)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    return evolve(b, active, n_steps);
+}
+
+int wafer_batch_observables(wafer_batch *b, wafer_observables_t *out)
+{
+    if (!b || !out) return fail(WAFER_ERR_INVALID, "null argument");
+    TRY(observables(b, nullptr));
+    for (uint32_t m = 0; m < b->n; ++m) obs_of(b, m, &out[m]);
+    return WAFER_OK;
+}
+
+int wafer_batch_normalise(wafer_batch *b, const uint8_t *active, const double *norm2)
+{
+    if (!b || !norm2) return fail(WAFER_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->s));   // n2_host is read by a copy of an earlier call
+    memcpy(b->n2_host, norm2, sizeof(double) * b->n);
+    HIP_TRY(hipMemcpyAsync(b->n2, b->n2_host, sizeof(double) * b->n, hipMemcpyHostToDevice, b->s));
+    return normalise(b, active, b->n2, 1);
+}
+
+// grid.rs:50-246 for every member, the loop of wafer_solve_state(ctx, 0, ...) with one launch per operation for all running members
+int wafer_batch_solve(wafer_batch *b, double tolerance, uint64_t screen_update, int has_max_steps, uint64_t max_steps,
+                      wafer_block_record *records, size_t max_records_per_member, size_t *n_records,
+                      wafer_observables_output *finals, int *status)
+{
+    if (!b || !status) return fail(WAFER_ERR_INVALID, "null argument");
+    const uint32_t n = b->n;
+    std::vector<uint8_t> run(n, 1);
+    std::vector<double> last_energy(n, DBL_MAX);   // grid.rs:124
+    std::vector<size_t> nrec(n, 0);
+    std::vector<wafer_observables_t> obs(n);
+    for (uint32_t m = 0; m < n; ++m) {
+        status[m] = WAFER_OK;
+        if (n_records) n_records[m] = 0;
+        if (finals) memset(&finals[m], 0, sizeof finals[m]);
+    }
+    std::string first_state_error;
+    uint64_t step = 0;
+    auto finish = [&](uint32_t m) { // output.rs:540-547
+        run[m] = 0;
+        if (!finals) return;
+        const wafer_observables_t &o = obs[m];
+        const double r_norm = std::sqrt(o.r2 / o.norm2);
+        finals[m].state = 0;
+        finals[m].energy = o.energy / o.norm2;
+        finals[m].binding_energy = (o.energy - o.v_infinity) / o.norm2;
+        finals[m].r = r_norm;
+        finals[m].l_r = (double)b->P[m].nx / r_norm;
+    };
+    for (;;) {
+        TRY(observables(b, run.data()));                          // :127
+        std::vector<uint8_t> norm(run);
+        for (uint32_t m = 0; m < n; ++m) {
+            if (!run[m]) continue;
+            obs_of(b, m, &obs[m]);
+            const double norm_energy = obs[m].energy / obs[m].norm2;   // :128
+            if (!std::isfinite(norm_energy)) {
+                char msg[256];
+                snprintf(msg, sizeof msg, "member %u, state 0: energy is not finite at step %llu (norm2 = %g): "
+                         "the wavefunction vanished or diverged", m, (unsigned long long)step, obs[m].norm2);
+                if (first_state_error.empty()) first_state_error = msg;
+                status[m] = WAFER_ERR_STATE;
+                run[m] = norm[m] = 0;
+            }
+        }
+        // :130, the members' norm2 straight from the sums on the device (the same doubles the host holds)
+        TRY(normalise(b, norm.data(), b->sums + 1, 4));
+        for (uint32_t m = 0; m < n; ++m) {
+            if (!run[m]) continue;
+            const double norm_energy = obs[m].energy / obs[m].norm2;
+            const double tau = (double)step * b->P[m].dt;           // :129
+            const double diff = std::fabs(norm_energy - last_energy[m]); // :161
+            if (records && nrec[m] < max_records_per_member) {
+                wafer_block_record &r = records[(size_t)m * max_records_per_member + nrec[m]];
+                r.step = step;
+                r.tau = tau;
+                r.obs = obs[m];
+                r.diff = diff;
+            }
+            ++nrec[m];
+            if (n_records) n_records[m] = nrec[m];
+            if (diff < tolerance) { // :162-192
+                finish(m);
+                continue;
+            }
+            last_energy[m] = norm_energy;                           // :194
+            if (has_max_steps && step > max_steps) {                // :211-213
+                status[m] = WAFER_ERR_MAX_STEP;
+                finish(m);
+            }
+        }
+        bool any = false;
+        for (uint8_t r : run) any = any || r;
+        if (!any) break;
+        TRY(evolve(b, run.data(), screen_update));                  // :216
+        step += screen_update;                                      // :220
+    }
+    HIP_TRY(hipStreamSynchronize(b->s));
+    if (!first_state_error.empty()) fail(WAFER_ERR_STATE, "%s", first_state_error.c_str());
+    return WAFER_OK;
+}
+
+int wafer_batch_last_evolve_ms(wafer_batch *b, float *ms, uint64_t *steps)
+{
+    if (!b || !ms || !steps) return fail(WAFER_ERR_INVALID, "null argument");
+    if (!b->timing_valid) return fail(WAFER_ERR_STATE, "no wafer_batch_evolve has run");
+    HIP_TRY(hipEventSynchronize(b->ev_stop));
+    HIP_TRY(hipEventElapsedTime(ms, b->ev_start, b->ev_stop));
+    *steps = b->last_steps;
+    return WAFER_OK;
+}
+
+const char *wafer_batch_kernel_name(wafer_batch *b)
+{
+    (void)b;
+    return "wafer_k_batch_step";
+}
+
+} // extern "C"

@@ -28,6 +28,9 @@ INITIAL_CONDITIONS = ["FromFile", "Gaussian", "Coulomb", "Constant", "Boolean"] 
 CENTRAL_DIFFERENCE = {"ThreePoint": 1, "FivePoint": 2, "SevenPoint": 3}  # config.rs:224-238
 
 WAFER_OK = 0
+WAFER_ERR_INVALID = -1
+WAFER_ERR_HIP = -2
+WAFER_ERR_STATE = -4
 WAFER_ERR_MAX_STEP = -5
 FLAG_SKIP_DT_CHECK = 1
 FLAG_UNPLANNED_DIV = 2
@@ -44,6 +47,10 @@ EXPORTS = [
     "wafer_get_device_info", "wafer_set_potsub", "wafer_set_potsub_resampled", "wafer_symmetrise", "wafer_download_phi_owned", "wafer_diag_div_check", "wafer_div_plan", "wafer_get_div_plan", "wafer_diag_div_planned", "wafer_div_plan_f32", "wafer_diag_div_planned_f32",
     "wafer_diag_copy_bw", "wafer_diag_checksum", "wafer_diag_download_window", "wafer_diag_dispatch", "wafer_set_halo_cycle", "wafer_diag_x2_passes",
     "wafer_peer_export", "wafer_peer_connect", "wafer_peer_disconnect",
+    "wafer_batch_create", "wafer_batch_destroy", "wafer_batch_size", "wafer_batch_set_potential_builtin",
+    "wafer_batch_set_potential_host", "wafer_batch_set_initial_condition", "wafer_batch_upload_phi", "wafer_batch_download_phi",
+    "wafer_batch_evolve", "wafer_batch_observables", "wafer_batch_normalise", "wafer_batch_solve", "wafer_batch_last_evolve_ms",
+    "wafer_batch_kernel_name",
 ]
 
 
@@ -207,6 +214,23 @@ def load_library():
     L.wafer_set_stream.argtypes = [vp, vp]
     L.wafer_get_slab_info.argtypes = [vp, C.POINTER(_SlabInfo)]
     L.wafer_get_device_info.argtypes = [vp, C.POINTER(_DeviceInfo)]
+    u8p = C.POINTER(C.c_uint8)
+    L.wafer_batch_create.argtypes = [C.POINTER(_Params), C.c_uint32, C.POINTER(vp)]
+    L.wafer_batch_destroy.argtypes = [vp]
+    L.wafer_batch_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.wafer_batch_set_potential_builtin.argtypes = [vp, C.c_uint32, C.c_int]
+    L.wafer_batch_set_potential_host.argtypes = [vp, C.c_uint32, dp, C.c_int, C.c_double, dp]
+    L.wafer_batch_set_initial_condition.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint64]
+    L.wafer_batch_upload_phi.argtypes = [vp, C.c_uint32, dp]
+    L.wafer_batch_download_phi.argtypes = [vp, C.c_uint32, dp]
+    L.wafer_batch_evolve.argtypes = [vp, u8p, C.c_uint64]
+    L.wafer_batch_observables.argtypes = [vp, C.POINTER(_Obs)]
+    L.wafer_batch_normalise.argtypes = [vp, u8p, dp]
+    L.wafer_batch_solve.argtypes = [vp, C.c_double, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(_Record), C.c_size_t,
+                                    C.POINTER(C.c_size_t), C.POINTER(_ObsOut), C.POINTER(C.c_int)]
+    L.wafer_batch_last_evolve_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    L.wafer_batch_kernel_name.argtypes = [vp]
+    L.wafer_batch_kernel_name.restype = C.c_char_p
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -613,3 +637,129 @@ class Context:
         s = _SlabInfo()
         self._check(self._L.wafer_get_slab_info(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in _SlabInfo._fields_}
+
+
+class Batch:
+    """B independent ground-state problems of one shape on one device (wafer_batch_*): one launch per step advances every
+    active member, and each member computes bit for bit what a Context with its Params computes."""
+
+    def __init__(self, members: list):
+        self._L = load_library()
+        self.members = list(members)
+        self._h = C.c_void_p()
+        arr = (_Params * max(1, len(self.members)))(*[m.c() for m in self.members])
+        self._check(self._L.wafer_batch_create(arr, len(self.members), C.byref(self._h)))
+
+    def _check(self, rc: int) -> None:
+        if rc != WAFER_OK:
+            raise WaferError(rc, self._L.wafer_last_error().decode())
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.wafer_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self) -> int:
+        return len(self.members)
+
+    def _mask(self, active):
+        if active is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(active, dtype=np.uint8))
+        if a.shape != (len(self.members),):
+            raise ValueError("active must hold one entry per member")
+        return a
+
+    @staticmethod
+    def _u8(a):
+        return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    # -- set-up, per member --------------------------------------------------------------
+    def set_potential(self, i: int, name: str) -> None:
+        self._check(self._L.wafer_batch_set_potential_builtin(self._h, i, POTENTIALS.index(name)))
+
+    def set_potential_host(self, i: int, v: np.ndarray, potsub_kind: int = 0, potsub_scalar: float = 0.0,
+                           potsub: np.ndarray | None = None) -> None:
+        assert v.shape == self.members[i].padded_shape
+        self._check(self._L.wafer_batch_set_potential_host(
+            self._h, i, _dp(v), potsub_kind, potsub_scalar, _dp(potsub) if potsub is not None else None))
+
+    def set_initial_condition(self, i: int, name: str, seed: int = 0) -> None:
+        self._check(self._L.wafer_batch_set_initial_condition(self._h, i, INITIAL_CONDITIONS.index(name), seed))
+
+    def upload_phi(self, i: int, phi: np.ndarray) -> None:
+        assert phi.shape == self.members[i].padded_shape
+        self._check(self._L.wafer_batch_upload_phi(self._h, i, _dp(phi)))
+
+    def download_phi(self, i: int, out: np.ndarray | None = None) -> np.ndarray:
+        if out is None:
+            out = np.zeros(self.members[i].padded_shape)
+        self._check(self._L.wafer_batch_download_phi(self._h, i, _dp(out)))
+        return out
+
+    # -- hot path ----------------------------------------------------------------------
+    def evolve(self, steps: int, active=None) -> None:
+        """`steps` ground-state steps of the active members (None: all)"""
+        a = self._mask(active)
+        self._check(self._L.wafer_batch_evolve(self._h, self._u8(a), steps))
+
+    def observables(self) -> list:
+        """compute_observables (un-normalised) of every member"""
+        o = (_Obs * len(self.members))()
+        self._check(self._L.wafer_batch_observables(self._h, o))
+        return [dict(energy=x.energy, norm2=x.norm2, v_infinity=x.v_infinity, r2=x.r2) for x in o]
+
+    def normalise(self, norm2s, active=None) -> None:
+        n2 = np.ascontiguousarray(np.asarray(norm2s, dtype=np.float64))
+        if n2.shape != (len(self.members),):
+            raise ValueError("norm2s must hold one value per member")
+        a = self._mask(active)
+        self._check(self._L.wafer_batch_normalise(self._h, self._u8(a), _dp(n2)))
+
+    def solve(self, tolerance: float, screen_update: int, max_steps=None, max_records: int | None = None) -> list:
+        """-> per member (rows, final, converged, status) in Context.solve_state's format; status is WAFER_OK,
+        WAFER_ERR_MAX_STEP or WAFER_ERR_STATE.  max_records (rows kept per member; None: every row a run bounded by max_steps
+        can produce, else 100000 shared out over the members, at least 1000 each)"""
+        B = len(self.members)
+        if max_records is None:
+            if max_steps is not None:   # rows at steps 0, su, 2 su, ... up to the first step past max_steps
+                max_records = int(max_steps) // max(1, int(screen_update)) + 2
+            else:
+                max_records = max(1000, 100000 // max(1, B))
+        recs = (_Record * (B * max_records))()
+        n = (C.c_size_t * B)()
+        fin = (_ObsOut * B)()
+        st = (C.c_int * B)()
+        self._check(self._L.wafer_batch_solve(self._h, tolerance, screen_update, 0 if max_steps is None else 1,
+                                              0 if max_steps is None else int(max_steps), recs, max_records, n, fin, st))
+        out = []
+        for m in range(B):
+            rows = []
+            for k in range(min(n[m], max_records)):
+                r = recs[m * max_records + k]
+                rows.append(dict(step=r.step, tau=r.tau, energy=r.obs.energy, norm2=r.obs.norm2,
+                                 v_infinity=r.obs.v_infinity, r2=r.obs.r2, diff=r.diff))
+            f = fin[m]
+            final = dict(state=f.state, energy=f.energy, binding_energy=f.binding_energy, r=f.r, l_r=f.l_r)
+            out.append((rows, final, st[m] == WAFER_OK, st[m]))
+        return out
+
+    def last_evolve_ms(self):
+        ms, steps = C.c_float(0.0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_last_evolve_ms(self._h, C.byref(ms), C.byref(steps)))
+        return ms.value, steps.value
+
+    def kernel_name(self) -> str:
+        return self._L.wafer_batch_kernel_name(self._h).decode()
