@@ -219,6 +219,21 @@ extern "C" {
     ) -> c_int;
     pub fn wafer_batch_last_evolve_ms(b: *mut wafer_batch, ms: *mut f32, steps: *mut u64) -> c_int;
     pub fn wafer_batch_kernel_name(b: *mut wafer_batch) -> *const c_char;
+    // batched excited states: per-member state stores and the normalise / Gram-Schmidt tail of every step
+    pub fn wafer_batch_load_state(b: *mut wafer_batch, member: u32, idx: u32, state: *const f64) -> c_int;
+    pub fn wafer_batch_download_state(b: *mut wafer_batch, member: u32, idx: u32, out: *mut f64) -> c_int;
+    pub fn wafer_batch_push_state(b: *mut wafer_batch, active: *const u8) -> c_int;
+    pub fn wafer_batch_num_states(b: *mut wafer_batch, counts_out: *mut u32) -> c_int;
+    pub fn wafer_batch_clear_states(b: *mut wafer_batch, active: *const u8) -> c_int;
+    pub fn wafer_batch_clone_state_to_phi(b: *mut wafer_batch, active: *const u8, idx: u32) -> c_int;
+    pub fn wafer_batch_orthogonalise(b: *mut wafer_batch, active: *const u8, wnum: u32) -> c_int;
+    pub fn wafer_batch_norm2(b: *mut wafer_batch, out: *mut f64) -> c_int;
+    pub fn wafer_batch_evolve_state(b: *mut wafer_batch, active: *const u8, wnum: u32, n_steps: u64) -> c_int;
+    pub fn wafer_batch_solve_state(
+        b: *mut wafer_batch, wnum: u32, tolerance: f64, screen_update: u64, has_max_steps: c_int, max_steps: u64,
+        records: *mut wafer_block_record, max_records_per_member: usize, n_records: *mut usize, finals: *mut wafer_observables_output,
+        status: *mut c_int,
+    ) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

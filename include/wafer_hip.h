@@ -432,7 +432,8 @@ int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
  * launch per step advances every ACTIVE member (a workgroup table built from the active members only: a member that is not
  * active costs nothing); observables are one launch, one reduce launch and one small download for all members.  Every member
  * computes bit for bit what a single wafer_ctx with its wafer_params computes: phi after evolve, the observables (the single
- * context's partition and reduction order), normalisation and solve.  No z-slabs (z_count must be 0), no excited states.
+ * context's partition and reduction order), normalisation and solve.  No z-slabs (z_count must be 0).  Excited states: the
+ * wafer_batch_*_state calls further down.
  * Member arrays live in one allocation per array kind (phi ping-pong, V, pot_sub) with a member stride.
  * wafer_batch_create validates every member before any HIP call (WAFER_ERR_INVALID names the member and the field). */
 typedef struct wafer_batch wafer_batch;
@@ -464,6 +465,38 @@ int wafer_batch_solve(wafer_batch *b, double tolerance, uint64_t screen_update, 
 int wafer_batch_last_evolve_ms(wafer_batch *b, float *ms, uint64_t *steps);
 /* the kernel a batched step launches: wafer_k_batch_step */
 const char *wafer_batch_kernel_name(wafer_batch *b);
+
+/* ---- batched excited states ------------------------------------------------
+ * Every member has a state store (w_store) of its own, of capacity its wafer_params.max_states, on the device: slot l of all
+ * members is one allocation with the batch's member stride, made by the first push or load that needs it (a ground-state batch
+ * allocates none).  The calls mirror the single context's; where they take `active`, they act on the members with
+ * active[m] != 0 (NULL: all) and leave the others bit for bit as they are.  A call that cannot be carried out for one of its
+ * members (store full, store shorter than wnum or idx, phi not set) returns WAFER_ERR_STATE naming that member and changes
+ * nothing; wafer_batch_solve_state alone reports a short store per member instead.
+ * One excited step is 1 + 2 (1 + wnum) + 1 launches for the whole batch, with every scalar (norm2, the overlaps) on the
+ * device and no host synchronisation between steps.  Sums run over a partition fixed by the shape alone, in a fixed order:
+ * a member's bits do not depend on the batch size, on its index or on which other members are active. */
+int wafer_batch_load_state(wafer_batch *b, uint32_t member, uint32_t idx, const double *state);  /* as wafer_load_state: idx <= the member's count */
+int wafer_batch_download_state(wafer_batch *b, uint32_t member, uint32_t idx, double *out);
+int wafer_batch_push_state(wafer_batch *b, const uint8_t *active);          /* w_store.push(phi), grid.rs:241 */
+int wafer_batch_num_states(wafer_batch *b, uint32_t *counts_out);           /* n_members entries */
+int wafer_batch_clear_states(wafer_batch *b, const uint8_t *active);
+int wafer_batch_clone_state_to_phi(wafer_batch *b, const uint8_t *active, uint32_t idx);
+/* grid.rs:477-492: modified Gram-Schmidt of phi against the first wnum stored states of each active member */
+int wafer_batch_orthogonalise(wafer_batch *b, const uint8_t *active, uint32_t wnum);
+/* get_norm_squared of every member: out has n_members entries */
+int wafer_batch_norm2(wafer_batch *b, double *out);
+/* n_steps steps (0 takes one) of state wnum of the active members, grid.rs:544-687: the step, phi /= sqrt(norm2), then
+ * Gram-Schmidt against the member's first wnum states.  wnum = 0 is wafer_batch_evolve. */
+int wafer_batch_evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t n_steps);
+/* wafer_solve_state(ctx, wnum, ...) for every member at once; the arguments after wnum are wafer_batch_solve's and
+ * finals[m].state = wnum.  A member that converges has its phi pushed to its store (grid.rs:239-242); one that ends in
+ * WAFER_ERR_MAX_STEP or WAFER_ERR_STATE pushes nothing.  A member whose store holds fewer than wnum states, or is full when it
+ * converges, gets status WAFER_ERR_STATE; the first kind is not touched at all, and the others run.  wafer_batch_solve is
+ * this call with wnum = 0 except that it pushes nothing. */
+int wafer_batch_solve_state(wafer_batch *b, uint32_t wnum, double tolerance, uint64_t screen_update, int has_max_steps,
+                            uint64_t max_steps, wafer_block_record *records, size_t max_records_per_member, size_t *n_records,
+                            wafer_observables_output *finals, int *status);
 
 #ifdef __cplusplus
 }

@@ -227,6 +227,9 @@ static inline bool kernels_stream_ab(const wafer_ctx *c, int variant) { return v
 namespace wafer_eng __attribute__((visibility("hidden"))) {
 // ---- wafer_engine.hip
 int alloc_grid_array(wafer_ctx *c, void **logical, hipStream_t s);
+// a whole padded host array (reference layout) to / from the device array `dev` (a logical pointer); also used on a batch's member views
+int upload_padded(wafer_ctx *c, const double *host, void *dev);
+int download_padded(wafer_ctx *c, double *host, void *dev);
 int ensure_ab(wafer_ctx *c);
 int refresh_ab(wafer_ctx *c);
 int check_v_range(wafer_ctx *c);

@@ -373,14 +373,16 @@ static int convert_host_array(wafer_ctx *c, double *host, int sx, int sy, int sz
     return WAFER_OK;
 }
 
-static int upload_padded(wafer_ctx *c, const double *host, void *dev)
+namespace wafer_eng __attribute__((visibility("hidden"))) {
+int upload_padded(wafer_ctx *c, const double *host, void *dev)
 {
     return convert_host_array<true>(c, const_cast<double *>(host), c->g.px, c->g.py, c->g.pzg, 0, 0, 0, dev);
 }
-static int download_padded(wafer_ctx *c, double *host, void *dev)
+int download_padded(wafer_ctx *c, double *host, void *dev)
 {
     return convert_host_array<false>(c, host, c->g.px, c->g.py, c->g.pzg, 0, 0, 0, dev);
 }
+} // namespace wafer_eng
 
 // ---- potentials ----------------------------------------------------------------
 extern "C" {

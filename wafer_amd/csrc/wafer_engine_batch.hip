@@ -1,5 +1,7 @@
-// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B ground-state problems of one shape on one
-// device, one launch per step over the active members (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip).
+// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B problems of one shape on one device, one
+// launch per step over the active members (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip), and for
+// excited states a per-member state store with the normalise / Gram-Schmidt tail of every step (wafer_gs_batch.hip.h,
+// wafer_tu_gs_batch.hip): 1 + 2 (1 + wnum) + 1 launches per step for the whole batch.
 //
 // Each member is also a context VIEW: a wafer_ctx whose arrays are the member's slices of the batch's allocations and whose
 // stream is the batch's.  Potentials, initial conditions, uploads and downloads go through the context entry points on that
@@ -7,6 +9,7 @@
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_batch.hip.h"
+#include "wafer_gs_batch.hip.h"
 
 struct wafer_batch {
     uint32_t n = 0;
@@ -35,6 +38,13 @@ struct wafer_batch {
     double *n2 = nullptr, *n2_host = nullptr;        // [member]
     uint64_t last_steps = 0;
     bool timing_valid = false;
+    // w_store: slot l of every member in one allocation with the member stride, made by the first push or load that needs it
+    std::vector<void *> slots;
+    std::vector<uint32_t> nst;                // states member m holds
+    // excited states: norm2 at gs_scal[m * gs_stride], the overlap with state l at [m * gs_stride + 1 + l]; made at first use
+    int gs_nb = 0, gs_stride = 0;
+    double *gs_partials = nullptr;            // [member][gs_nb]
+    double *gs_scal = nullptr, *gs_host = nullptr;
 };
 
 namespace {
@@ -78,10 +88,12 @@ void destroy(wafer_batch *b)
     for (wafer_ctx *v : b->views) delete v;   // views borrow every array and the stream
     for (void *p : b->alloc)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
-                    (void *)b->n2})
+    for (void *p : b->slots)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host})
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
+                    (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop})
         if (e) (void)hipEventDestroy(e);
@@ -241,6 +253,255 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     return WAFER_OK;
 }
 
+// ---- w_store ---------------------------------------------------------------------------------------------------------------
+// member m's state l as a logical pointer (plane 0, row 0), like the views' arrays
+void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
+{
+    return static_cast<char *>(b->slots[l]) + ((size_t)m * b->stride + (size_t)b->g.base_off) * 8;
+}
+
+// slots [0, n) exist (zeros: frames, pads and guard zones of every member)
+int ensure_slots(wafer_batch *b, uint32_t n)
+{
+    while (b->slots.size() < n) {
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, b->stride * b->n * 8));
+        b->slots.push_back(p);
+        HIP_TRY(hipMemsetAsync(p, 0, b->stride * b->n * 8, b->s));
+    }
+    return WAFER_OK;
+}
+
+int check_capacity(const wafer_batch *b, uint32_t m)
+{
+    if (b->nst[m] >= b->P[m].max_states) return fail(WAFER_ERR_STATE, "member %u: w_store is full (max_states = %u)", m, b->P[m].max_states);
+    return WAFER_OK;
+}
+
+// phi of the active members to the end of their stores; nothing changes unless every one of them can take it
+int push_states(wafer_batch *b, const uint8_t *active)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    uint32_t need = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+        TRY(check_capacity(b, m));
+        need = std::max(need, b->nst[m] + 1);
+    }
+    TRY(ensure_slots(b, need));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        const wafer_ctx *c = b->views[m];
+        HIP_TRY(hipMemcpyAsync(alloc_base(c, slot_ptr(b, b->nst[m], m)), alloc_base(c, c->phi[c->cur]), b->stride * 8, hipMemcpyDeviceToDevice, b->s));
+        ++b->nst[m];
+    }
+    return WAFER_OK;
+}
+
+// ---- excited states --------------------------------------------------------------------------------------------------------
+int ensure_gs(wafer_batch *b)
+{
+    if (b->gs_scal) return WAFER_OK;
+    const size_t nsc = (size_t)b->gs_stride * b->n;
+    HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * (size_t)b->gs_nb * b->n));
+    HIP_TRY(hipHostMalloc((void **)&b->gs_host, sizeof(double) * nsc, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&b->gs_scal, sizeof(double) * nsc));
+    HIP_TRY(hipMemsetAsync(b->gs_scal, 0, sizeof(double) * nsc, b->s));
+    return WAFER_OK;
+}
+
+int check_store(const wafer_batch *b, const uint8_t *active, uint32_t wnum)
+{
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+        if (wnum > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: wnum %u but w_store holds %u states", m, wnum, b->nst[m]);
+    }
+    return WAFER_OK;
+}
+
+// one elementwise launch (+ its reduce into slot out_slot) over the members in act_dev; lower, dotwith: store slots, -1 none
+int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int lower, int dotwith, int out_slot)
+{
+    WaferBatchGsArgs a;
+    a.g = b->g;
+    a.ntx = (b->g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    a.nty = (b->g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    a.flip = flip;
+    a.scal_stride = b->gs_stride;
+    a.coef_slot = coef_slot;
+    a.mstride = (long long)b->stride;
+    a.lower = lower >= 0 ? static_cast<const double *>(slot_ptr(b, (uint32_t)lower, 0)) : nullptr;
+    a.dotwith = dotwith >= 0 ? static_cast<const double *>(slot_ptr(b, (uint32_t)dotwith, 0)) : nullptr;
+    const hipError_t e = wafer_entry_batch_gs(mode, a, b->mem_dev, b->act_dev, nact, b->gs_scal, out_slot, b->gs_partials, b->s);
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram-Schmidt launch failed: %s", hipGetErrorString(e));
+    return WAFER_OK;
+}
+
+// grid.rs:679-680 (normalise: norm2 and the scaling first) and :477-492 on phi[cur ^ flip] of the members in act_dev
+int gs_chain(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_first)
+{
+    if (normalise_first) {
+        TRY(gs_launch(b, WAFER_GS_NORM2, nact, flip, 0, -1, -1, 0));
+        TRY(gs_launch(b, WAFER_GS_SCALE, nact, flip, 0, -1, wnum ? 0 : -1, 1));
+    } else if (wnum) {
+        TRY(gs_launch(b, WAFER_GS_DOT, nact, flip, 0, -1, 0, 1));
+    }
+    for (uint32_t l = 0; l < wnum; ++l)
+        TRY(gs_launch(b, WAFER_GS_AXPY, nact, flip, 1 + (int)l, (int)l, l + 1 < wnum ? (int)l + 1 : -1, 2 + (int)l));
+    return WAFER_OK;
+}
+
+int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t n_steps)
+{
+    if (wnum == 0) return evolve(b, active, n_steps);
+    HIP_TRY(hipSetDevice(b->device));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_pot || !b->views[m]->have_phi)
+            return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set before evolve", m);
+    }
+    TRY(check_store(b, active, wnum));
+    const uint64_t steps = n_steps == 0 ? 1 : n_steps;   // grid.rs:682-685
+    TRY(ensure_gs(b));
+    TRY(sync_members(b));
+    TRY(build_blocks(b, active));
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    RoctxRange range_("wafer_batch_evolve_state");
+    HIP_TRY(hipEventRecord(b->ev_start, b->s));
+    if (nact) {
+        for (uint64_t k = 0; k < steps; ++k) {   // no host synchronisation in here: every scalar stays on the device
+            const hipError_t e = wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), (int)(k & 1), b->s);
+            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
+            TRY(gs_chain(b, nact, (int)((k + 1) & 1), wnum, true));
+        }
+    }
+    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
+    b->last_steps = steps;
+    b->timing_valid = true;
+    if (steps & 1)
+        for (uint32_t m = 0; m < b->n; ++m)
+            if (!active || active[m]) b->views[m]->cur ^= 1;
+    return WAFER_OK;
+}
+
+int orthogonalise(wafer_batch *b, const uint8_t *active, uint32_t wnum)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    TRY(check_store(b, active, wnum));
+    if (wnum == 0) return WAFER_OK;
+    TRY(ensure_gs(b));
+    TRY(sync_members(b));
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    if (!nact) return WAFER_OK;
+    return gs_chain(b, nact, 0, wnum, false);
+}
+
+// grid.rs:50-246 for every member and one state number: the loop of wafer_solve_state with one launch per operation for all
+// running members.  push: a converged member's phi goes to its store (:239-242).
+int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t screen_update, int has_max_steps, uint64_t max_steps,
+          wafer_block_record *records, size_t max_records_per_member, size_t *n_records, wafer_observables_output *finals, int *status)
+{
+    const uint32_t n = b->n;
+    std::vector<uint8_t> run(n, 1), converged(n, 0);
+    std::vector<double> last_energy(n, DBL_MAX);   // grid.rs:124
+    std::vector<size_t> nrec(n, 0);
+    std::vector<wafer_observables_t> obs(n);
+    std::string first_state_error;
+    for (uint32_t m = 0; m < n; ++m) {
+        status[m] = WAFER_OK;
+        if (n_records) n_records[m] = 0;
+        if (finals) memset(&finals[m], 0, sizeof finals[m]);
+        if (wnum > b->nst[m]) {   // a short store is this member's error, not the call's: it is left as it stands
+            char msg[160];
+            snprintf(msg, sizeof msg, "member %u: wnum %u but w_store holds %u states", m, wnum, b->nst[m]);
+            if (first_state_error.empty()) first_state_error = msg;
+            status[m] = WAFER_ERR_STATE;
+            run[m] = 0;
+        }
+    }
+    uint64_t step = 0;
+    auto finish = [&](uint32_t m) { // output.rs:540-547
+        run[m] = 0;
+        if (!finals) return;
+        const wafer_observables_t &o = obs[m];
+        const double r_norm = std::sqrt(o.r2 / o.norm2);
+        finals[m].state = wnum;
+        finals[m].energy = o.energy / o.norm2;
+        finals[m].binding_energy = (o.energy - o.v_infinity) / o.norm2;
+        finals[m].r = r_norm;
+        finals[m].l_r = (double)b->P[m].nx / r_norm;
+    };
+    for (;;) {
+        bool any = false;
+        for (uint8_t r : run) any = any || r;
+        if (!any) break;
+        TRY(observables(b, run.data()));                          // :127
+        std::vector<uint8_t> norm(run);
+        for (uint32_t m = 0; m < n; ++m) {
+            if (!run[m]) continue;
+            obs_of(b, m, &obs[m]);
+            const double norm_energy = obs[m].energy / obs[m].norm2;   // :128
+            if (!std::isfinite(norm_energy)) {
+                char msg[256];
+                snprintf(msg, sizeof msg, "member %u, state %u: energy is not finite at step %llu (norm2 = %g): "
+                         "the wavefunction vanished or diverged", m, wnum, (unsigned long long)step, obs[m].norm2);
+                if (first_state_error.empty()) first_state_error = msg;
+                status[m] = WAFER_ERR_STATE;
+                run[m] = norm[m] = 0;
+            }
+        }
+        // :130, the members' norm2 straight from the sums on the device (the same doubles the host holds)
+        TRY(normalise(b, norm.data(), b->sums + 1, 4));
+        if (wnum) TRY(orthogonalise(b, norm.data(), wnum));        // :133-135
+        for (uint32_t m = 0; m < n; ++m) {
+            if (!run[m]) continue;
+            const double norm_energy = obs[m].energy / obs[m].norm2;
+            const double tau = (double)step * b->P[m].dt;           // :129
+            const double diff = std::fabs(norm_energy - last_energy[m]); // :161
+            if (records && nrec[m] < max_records_per_member) {
+                wafer_block_record &r = records[(size_t)m * max_records_per_member + nrec[m]];
+                r.step = step;
+                r.tau = tau;
+                r.obs = obs[m];
+                r.diff = diff;
+            }
+            ++nrec[m];
+            if (n_records) n_records[m] = nrec[m];
+            if (diff < tolerance) { // :162-192
+                converged[m] = 1;
+                finish(m);
+                continue;
+            }
+            last_energy[m] = norm_energy;                           // :194
+            if (has_max_steps && step > max_steps) {                // :211-213
+                status[m] = WAFER_ERR_MAX_STEP;
+                finish(m);
+            }
+        }
+        any = false;
+        for (uint8_t r : run) any = any || r;
+        if (!any) break;
+        TRY(evolve_state(b, run.data(), wnum, screen_update));      // :216
+        step += screen_update;                                      // :220
+    }
+    if (push) {   // :239-242; a member whose store is full keeps its result and gets the status
+        for (uint32_t m = 0; m < n; ++m) {
+            if (!converged[m] || check_capacity(b, m) == WAFER_OK) continue;
+            if (first_state_error.empty()) first_state_error = wafer_last_error();
+            status[m] = WAFER_ERR_STATE;
+            converged[m] = 0;
+        }
+        TRY(push_states(b, converged.data()));
+    }
+    HIP_TRY(hipStreamSynchronize(b->s));
+    if (!first_state_error.empty()) fail(WAFER_ERR_STATE, "%s", first_state_error.c_str());
+    return WAFER_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -274,6 +535,9 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     b->num_cus = cus > 0 ? cus : 256;
     b->tune = wafer_tuning_from_env();
     b->stride = (size_t)g.total;
+    b->nst.assign(n_members, 0);
+    b->gs_nb = wafer_gs_blocks(g);
+    for (uint32_t m = 0; m < n_members; ++m) b->gs_stride = std::max(b->gs_stride, 1 + (int)members[m].max_states);
 #define HIP_TRYB(expr)                                                                               \
     do {                                                                                             \
         hipError_t e_ = (expr);                                                                      \
@@ -422,85 +686,117 @@ int wafer_batch_normalise(wafer_batch *b, const uint8_t *active, const double *n
     return normalise(b, active, b->n2, 1);
 }
 
-// grid.rs:50-246 for every member, the loop of wafer_solve_state(ctx, 0, ...) with one launch per operation for all running members
 int wafer_batch_solve(wafer_batch *b, double tolerance, uint64_t screen_update, int has_max_steps, uint64_t max_steps,
                       wafer_block_record *records, size_t max_records_per_member, size_t *n_records,
                       wafer_observables_output *finals, int *status)
 {
     if (!b || !status) return fail(WAFER_ERR_INVALID, "null argument");
-    const uint32_t n = b->n;
-    std::vector<uint8_t> run(n, 1);
-    std::vector<double> last_energy(n, DBL_MAX);   // grid.rs:124
-    std::vector<size_t> nrec(n, 0);
-    std::vector<wafer_observables_t> obs(n);
-    for (uint32_t m = 0; m < n; ++m) {
-        status[m] = WAFER_OK;
-        if (n_records) n_records[m] = 0;
-        if (finals) memset(&finals[m], 0, sizeof finals[m]);
-    }
-    std::string first_state_error;
-    uint64_t step = 0;
-    auto finish = [&](uint32_t m) { // output.rs:540-547
-        run[m] = 0;
-        if (!finals) return;
-        const wafer_observables_t &o = obs[m];
-        const double r_norm = std::sqrt(o.r2 / o.norm2);
-        finals[m].state = 0;
-        finals[m].energy = o.energy / o.norm2;
-        finals[m].binding_energy = (o.energy - o.v_infinity) / o.norm2;
-        finals[m].r = r_norm;
-        finals[m].l_r = (double)b->P[m].nx / r_norm;
-    };
-    for (;;) {
-        TRY(observables(b, run.data()));                          // :127
-        std::vector<uint8_t> norm(run);
-        for (uint32_t m = 0; m < n; ++m) {
-            if (!run[m]) continue;
-            obs_of(b, m, &obs[m]);
-            const double norm_energy = obs[m].energy / obs[m].norm2;   // :128
-            if (!std::isfinite(norm_energy)) {
-                char msg[256];
-                snprintf(msg, sizeof msg, "member %u, state 0: energy is not finite at step %llu (norm2 = %g): "
-                         "the wavefunction vanished or diverged", m, (unsigned long long)step, obs[m].norm2);
-                if (first_state_error.empty()) first_state_error = msg;
-                status[m] = WAFER_ERR_STATE;
-                run[m] = norm[m] = 0;
-            }
-        }
-        // :130, the members' norm2 straight from the sums on the device (the same doubles the host holds)
-        TRY(normalise(b, norm.data(), b->sums + 1, 4));
-        for (uint32_t m = 0; m < n; ++m) {
-            if (!run[m]) continue;
-            const double norm_energy = obs[m].energy / obs[m].norm2;
-            const double tau = (double)step * b->P[m].dt;           // :129
-            const double diff = std::fabs(norm_energy - last_energy[m]); // :161
-            if (records && nrec[m] < max_records_per_member) {
-                wafer_block_record &r = records[(size_t)m * max_records_per_member + nrec[m]];
-                r.step = step;
-                r.tau = tau;
-                r.obs = obs[m];
-                r.diff = diff;
-            }
-            ++nrec[m];
-            if (n_records) n_records[m] = nrec[m];
-            if (diff < tolerance) { // :162-192
-                finish(m);
-                continue;
-            }
-            last_energy[m] = norm_energy;                           // :194
-            if (has_max_steps && step > max_steps) {                // :211-213
-                status[m] = WAFER_ERR_MAX_STEP;
-                finish(m);
-            }
-        }
-        bool any = false;
-        for (uint8_t r : run) any = any || r;
-        if (!any) break;
-        TRY(evolve(b, run.data(), screen_update));                  // :216
-        step += screen_update;                                      // :220
-    }
+    return solve(b, 0, false, tolerance, screen_update, has_max_steps, max_steps, records, max_records_per_member, n_records, finals, status);
+}
+
+int wafer_batch_solve_state(wafer_batch *b, uint32_t wnum, double tolerance, uint64_t screen_update, int has_max_steps,
+                            uint64_t max_steps, wafer_block_record *records, size_t max_records_per_member, size_t *n_records,
+                            wafer_observables_output *finals, int *status)
+{
+    if (!b || !status) return fail(WAFER_ERR_INVALID, "null argument");
+    return solve(b, wnum, true, tolerance, screen_update, has_max_steps, max_steps, records, max_records_per_member, n_records, finals, status);
+}
+
+int wafer_batch_evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t n_steps)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    return evolve_state(b, active, wnum, n_steps);
+}
+
+int wafer_batch_orthogonalise(wafer_batch *b, const uint8_t *active, uint32_t wnum)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    return orthogonalise(b, active, wnum);
+}
+
+int wafer_batch_norm2(wafer_batch *b, double *out)
+{
+    if (!b || !out) return fail(WAFER_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(b->device));
+    TRY(check_store(b, nullptr, 0));
+    TRY(ensure_gs(b));
+    TRY(sync_members(b));
+    int nact = 0;
+    TRY(upload_active(b, nullptr, &nact));
+    TRY(gs_launch(b, WAFER_GS_NORM2, nact, 0, 0, -1, -1, 0));
+    HIP_TRY(hipMemcpyAsync(b->gs_host, b->gs_scal, sizeof(double) * (size_t)b->gs_stride * b->n, hipMemcpyDeviceToHost, b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
-    if (!first_state_error.empty()) fail(WAFER_ERR_STATE, "%s", first_state_error.c_str());
+    for (uint32_t m = 0; m < b->n; ++m) out[m] = b->gs_host[(size_t)m * b->gs_stride];
+    return WAFER_OK;
+}
+
+int wafer_batch_push_state(wafer_batch *b, const uint8_t *active)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    return push_states(b, active);
+}
+
+int wafer_batch_load_state(wafer_batch *b, uint32_t member, uint32_t idx, const double *state)
+{
+    TRY(check_member_index(b, member));
+    if (!state) return fail(WAFER_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(b->device));
+    if (idx > b->nst[member]) return fail(WAFER_ERR_STATE, "member %u: states must be loaded in order", member);
+    if (idx == b->nst[member]) TRY(check_capacity(b, member));
+    TRY(ensure_slots(b, idx + 1));
+    TRY(upload_padded(b->views[member], state, slot_ptr(b, idx, member)));
+    if (idx == b->nst[member]) ++b->nst[member];
+    return WAFER_OK;
+}
+
+int wafer_batch_download_state(wafer_batch *b, uint32_t member, uint32_t idx, double *out)
+{
+    TRY(check_member_index(b, member));
+    if (!out) return fail(WAFER_ERR_INVALID, "null argument");
+    if (idx >= b->nst[member]) return fail(WAFER_ERR_STATE, "member %u: no state %u", member, idx);
+    HIP_TRY(hipSetDevice(b->device));
+    return download_padded(b->views[member], out, slot_ptr(b, idx, member));
+}
+
+int wafer_batch_num_states(wafer_batch *b, uint32_t *counts_out)
+{
+    if (!b || !counts_out) return fail(WAFER_ERR_INVALID, "null argument");
+    for (uint32_t m = 0; m < b->n; ++m) counts_out[m] = b->nst[m];
+    return WAFER_OK;
+}
+
+int wafer_batch_clear_states(wafer_batch *b, const uint8_t *active)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    uint32_t keep = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (!active || active[m]) b->nst[m] = 0;
+        keep = std::max(keep, b->nst[m]);
+    }
+    if (b->slots.size() > keep) {   // slots no member uses any more go back
+        HIP_TRY(hipStreamSynchronize(b->s));
+        while (b->slots.size() > keep) {
+            (void)hipFree(b->slots.back());
+            b->slots.pop_back();
+        }
+    }
+    return WAFER_OK;
+}
+
+int wafer_batch_clone_state_to_phi(wafer_batch *b, const uint8_t *active, uint32_t idx)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    for (uint32_t m = 0; m < b->n; ++m)
+        if ((!active || active[m]) && idx >= b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: no state %u", m, idx);
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        wafer_ctx *c = b->views[m];
+        HIP_TRY(hipMemcpyAsync(alloc_base(c, c->phi[c->cur]), alloc_base(c, slot_ptr(b, idx, m)), b->stride * 8, hipMemcpyDeviceToDevice, b->s));
+        c->have_phi = true;
+        c->halo_valid = 0;
+    }
     return WAFER_OK;
 }
 

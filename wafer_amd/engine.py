@@ -51,6 +51,9 @@ EXPORTS = [
     "wafer_batch_set_potential_host", "wafer_batch_set_initial_condition", "wafer_batch_upload_phi", "wafer_batch_download_phi",
     "wafer_batch_evolve", "wafer_batch_observables", "wafer_batch_normalise", "wafer_batch_solve", "wafer_batch_last_evolve_ms",
     "wafer_batch_kernel_name",
+    "wafer_batch_load_state", "wafer_batch_download_state", "wafer_batch_push_state", "wafer_batch_num_states",
+    "wafer_batch_clear_states", "wafer_batch_clone_state_to_phi", "wafer_batch_orthogonalise", "wafer_batch_norm2",
+    "wafer_batch_evolve_state", "wafer_batch_solve_state",
 ]
 
 
@@ -231,6 +234,17 @@ def load_library():
     L.wafer_batch_last_evolve_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     L.wafer_batch_kernel_name.argtypes = [vp]
     L.wafer_batch_kernel_name.restype = C.c_char_p
+    L.wafer_batch_load_state.argtypes = [vp, C.c_uint32, C.c_uint32, dp]
+    L.wafer_batch_download_state.argtypes = [vp, C.c_uint32, C.c_uint32, dp]
+    L.wafer_batch_push_state.argtypes = [vp, u8p]
+    L.wafer_batch_num_states.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.wafer_batch_clear_states.argtypes = [vp, u8p]
+    L.wafer_batch_clone_state_to_phi.argtypes = [vp, u8p, C.c_uint32]
+    L.wafer_batch_orthogonalise.argtypes = [vp, u8p, C.c_uint32]
+    L.wafer_batch_norm2.argtypes = [vp, dp]
+    L.wafer_batch_evolve_state.argtypes = [vp, u8p, C.c_uint32, C.c_uint64]
+    L.wafer_batch_solve_state.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(_Record), C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(_ObsOut), C.POINTER(C.c_int)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -640,8 +654,18 @@ class Context:
 
 
 class Batch:
-    """B independent ground-state problems of one shape on one device (wafer_batch_*): one launch per step advances every
-    active member, and each member computes bit for bit what a Context with its Params computes."""
+    """B independent problems of one shape on one device (wafer_batch_*): one launch per step advances every active member,
+    and each member's ground state computes bit for bit what a Context with its Params computes.
+
+    Excited states: every member has a state store of its own (capacity Params.max_states; load_state, push_state, ...), and
+    evolve(steps, wnum=k) / solve_state(k, ...) normalise and project each member against its first k stored states after
+    every step, as Context.evolve(k, steps) does, in 1 + 2 (1 + k) + 1 launches per step for the whole batch.  A member's
+    bits do not depend on the batch size, its index or the active set; against a Context they agree to the excited-state
+    tolerances (1e-13 per cell), not bit for bit: the sums are partitioned differently.  Measured (ThreePoint
+    fp64, 50^3 and 64^3, wnum 1 and 2): 1.7-3.2 times B contexts one after another from B = 8 on, 0.4 times at B = 1 -- for one
+    problem use a Context.
+    A sweep over states is solve_state(0), solve_state(1), ...: a member whose store is too short for a call gets the status
+    WAFER_ERR_STATE, is left as it is, and the others run."""
 
     def __init__(self, members: list):
         self._L = load_library()
@@ -710,10 +734,66 @@ class Batch:
         return out
 
     # -- hot path ----------------------------------------------------------------------
-    def evolve(self, steps: int, active=None) -> None:
-        """`steps` ground-state steps of the active members (None: all)"""
+    def evolve(self, steps: int, active=None, wnum: int = 0) -> None:
+        """`steps` steps of state `wnum` of the active members (None: all); wnum = 0: ground-state steps"""
+        a, wnum = self._mask(active), self._wnum(wnum)
+        if wnum == 0:
+            self._check(self._L.wafer_batch_evolve(self._h, self._u8(a), steps))
+        else:
+            self._check(self._L.wafer_batch_evolve_state(self._h, self._u8(a), wnum, steps))
+
+    def _wnum(self, wnum) -> int:
+        wnum = int(wnum)
+        if not 0 <= wnum <= max(m.max_states for m in self.members):
+            raise ValueError("wnum %d is outside 0 .. max_states = %d" % (wnum, max(m.max_states for m in self.members)))
+        return wnum
+
+    def _member(self, i) -> int:
+        i = int(i)
+        if not 0 <= i < len(self.members):
+            raise ValueError("member %d out of range (the batch has %d)" % (i, len(self.members)))
+        return i
+
+    def orthogonalise(self, wnum: int, active=None) -> None:
+        """grid.rs:477-492 for the active members, each against its own first `wnum` stored states"""
+        a, wnum = self._mask(active), self._wnum(wnum)
+        self._check(self._L.wafer_batch_orthogonalise(self._h, self._u8(a), wnum))
+
+    def norm2(self) -> list:
+        """grid.rs:454-457 of every member"""
+        out = np.zeros(len(self.members))
+        self._check(self._L.wafer_batch_norm2(self._h, _dp(out)))
+        return [float(x) for x in out]
+
+    # -- w_store, per member ---------------------------------------------------------------
+    def load_state(self, i: int, idx: int, state: np.ndarray) -> None:
+        i = self._member(i)
+        if state.shape != self.members[i].padded_shape:
+            raise ValueError("member %d: state has shape %s, not the padded shape %s" % (i, state.shape, self.members[i].padded_shape))
+        self._check(self._L.wafer_batch_load_state(self._h, i, idx, _dp(state)))
+
+    def download_state(self, i: int, idx: int) -> np.ndarray:
+        i = self._member(i)
+        out = np.zeros(self.members[i].padded_shape)
+        self._check(self._L.wafer_batch_download_state(self._h, i, idx, _dp(out)))
+        return out
+
+    def push_state(self, active=None) -> None:
         a = self._mask(active)
-        self._check(self._L.wafer_batch_evolve(self._h, self._u8(a), steps))
+        self._check(self._L.wafer_batch_push_state(self._h, self._u8(a)))
+
+    def num_states(self) -> list:
+        n = (C.c_uint32 * len(self.members))()
+        self._check(self._L.wafer_batch_num_states(self._h, n))
+        return [int(x) for x in n]
+
+    def clear_states(self, active=None) -> None:
+        a = self._mask(active)
+        self._check(self._L.wafer_batch_clear_states(self._h, self._u8(a)))
+
+    def clone_state_to_phi(self, idx: int, active=None) -> None:
+        a = self._mask(active)
+        self._check(self._L.wafer_batch_clone_state_to_phi(self._h, self._u8(a), idx))
 
     def observables(self) -> list:
         """compute_observables (un-normalised) of every member"""
@@ -731,7 +811,16 @@ class Batch:
     def solve(self, tolerance: float, screen_update: int, max_steps=None, max_records: int | None = None) -> list:
         """-> per member (rows, final, converged, status) in Context.solve_state's format; status is WAFER_OK,
         WAFER_ERR_MAX_STEP or WAFER_ERR_STATE.  max_records (rows kept per member; None: every row a run bounded by max_steps
-        can produce, else 100000 shared out over the members, at least 1000 each)"""
+        can produce, else 100000 shared out over the members, at least 1000 each).  Pushes no state."""
+        return self._solve(None, tolerance, screen_update, max_steps, max_records)
+
+    def solve_state(self, wnum: int, tolerance: float, screen_update: int, max_steps=None, max_records: int | None = None) -> list:
+        """solve() for state `wnum`, each member against its own first `wnum` stored states; a member that converges has its phi
+        pushed to its store.  A member whose store holds fewer than `wnum` states gets the status WAFER_ERR_STATE and is left
+        as it is."""
+        return self._solve(self._wnum(wnum), tolerance, screen_update, max_steps, max_records)
+
+    def _solve(self, wnum, tolerance, screen_update, max_steps, max_records) -> list:
         B = len(self.members)
         if max_records is None:
             if max_steps is not None:   # rows at steps 0, su, 2 su, ... up to the first step past max_steps
@@ -742,8 +831,12 @@ class Batch:
         n = (C.c_size_t * B)()
         fin = (_ObsOut * B)()
         st = (C.c_int * B)()
-        self._check(self._L.wafer_batch_solve(self._h, tolerance, screen_update, 0 if max_steps is None else 1,
-                                              0 if max_steps is None else int(max_steps), recs, max_records, n, fin, st))
+        tail = (tolerance, screen_update, 0 if max_steps is None else 1, 0 if max_steps is None else int(max_steps), recs,
+                max_records, n, fin, st)
+        if wnum is None:
+            self._check(self._L.wafer_batch_solve(self._h, *tail))
+        else:
+            self._check(self._L.wafer_batch_solve_state(self._h, wnum, *tail))
         out = []
         for m in range(B):
             rows = []
