@@ -124,6 +124,8 @@ struct wafer_ctx {
     bool have_pot = false, have_phi = false;
     WaferDivPlanF div_plan_f;   // ... in fp32, for WAFER_F32_FAST contexts (checked = 0 elsewhere)
     WaferDivPlan div_plan;   // x / (c dn^2 m) in the step kernels (wafer_divplan.h), made once, at wafer_ctx_create
+    bool v_ysym = false;     // V[x, y, z] and V[x, ny-1-y, z] hold the same BITS on every work cell of every plane this context holds: compared on the
+                             // array after every write of V (check_v_range), never inferred from the potential's name
     bool v_in_range = false; // 2^-400 < |1 + dt*V/2| < 2^400 everywhere (wafer_recip's short form is exact)
     int x2_agreed[4] = {-1, -1, -1, -1}; // [k]: every rank can take the two-step excited pass with k stored states (-1: not agreed yet; x2_agree)
     int vgen_type = 0;       // V was generated from this closed form (Coulomb / SimpleCornell / Harmonic), else 0: kernels may re-evaluate it instead of streaming it
@@ -235,7 +237,8 @@ int refresh_ab(wafer_ctx *c);
 int check_v_range(wafer_ctx *c);
 // ---- wafer_engine_schedules.hip
 enum { X2_SUM_SLOT = 18 };   // scal[18 .. 18 + 1 + 2k): the sums of a two-step pass
-enum { F3_PLAIN = 0, F3_MIXED = 1, F3_HALVES = 2, F3_WHOLE = 3 };
+enum { V_YSYM_SLOT = SCAL_SLOTS - 1 };   // scal[31]: the word wafer_k_v_ysym ORs into (check_v_range); no pass reaches it: wnum + 2 <= SCAL_SLOTS, the x2 sums end at 24
+enum { F3_PLAIN = 0, F3_MIXED = 1, F3_HALVES = 2, F3_WHOLE = 3, F3_PLAIN_FOLD = 4 /* F3_PLAIN with the tile rows in folded order: the VS launches */ };
 int reduce_to_scal(wafer_ctx *c, int nq, long long n, int slot, hipStream_t s);
 int read_scal(wafer_ctx *c, int slot, int n, double *out, hipStream_t s);
 int active_variant(const wafer_ctx *c);

@@ -100,23 +100,38 @@ int refresh_ab(wafer_ctx *c)
     HIP_TRY(hipGetLastError());
     return WAFER_OK;
 }
-// after V changed: may the kernels that form a, b from V use the short reciprocal?
+// after V changed (every writer of c->v ends here): may the kernels that form a, b from V use the short reciprocal?  And is the
+// array its own mirror image in y (wafer_ctx::v_ysym: the three-step kernel then reads it once per mirrored pair of tiles)?  The
+// flag is off from before the writer's first store into V (every writer clears it there: an error between the store and this
+// function must not leave the new array with the old answer) until the comparison has come back clean.
 int check_v_range(wafer_ctx *c)
 {
+    c->v_ysym = false;
     unsigned long long *d = reinterpret_cast<unsigned long long *>(c->scal + 16);
-    unsigned long long init[2] = {~0ull, 0ull}, got[2];
+    unsigned long long *dsym = reinterpret_cast<unsigned long long *>(c->scal + V_YSYM_SLOT);
+    unsigned long long init[2] = {~0ull, 0ull}, got[2], differ = 1;
     HIP_TRY(hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, c->s_main));
+    HIP_TRY(hipMemsetAsync(dsym, 0, sizeof *dsym, c->s_main));
+    {
+        const long long pairs = (long long)c->g.lz * (c->g.ny / 2);
+        const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(pairs, (long long)c->num_cus * 8)));
+        if (c->f32) hipLaunchKernelGGL((wafer_k_v_ysym<float>), grid, dim3(256), 0, c->s_main, c->g, as<float>(c->v), dsym);
+        else hipLaunchKernelGGL((wafer_k_v_ysym<double>), grid, dim3(256), 0, c->s_main, c->g, as<double>(c->v), dsym);
+        HIP_TRY(hipGetLastError());
+    }
     if (c->f32)
         hipLaunchKernelGGL((wafer_k_v_range<float>), dim3(c->num_cus * 4), dim3(256), 0, c->s_main, as<float>(alloc_base(c, c->v)), c->g.total, c->P.dt, d);
     else
         hipLaunchKernelGGL((wafer_k_v_range<double>), dim3(c->num_cus * 4), dim3(256), 0, c->s_main, as<double>(alloc_base(c, c->v)), c->g.total, c->P.dt, d);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(got, d, sizeof got, hipMemcpyDeviceToHost, c->s_main));
+    HIP_TRY(hipMemcpyAsync(&differ, dsym, sizeof differ, hipMemcpyDeviceToHost, c->s_main));
     HIP_TRY(hipStreamSynchronize(c->s_main));
     double lo, hi;
     memcpy(&lo, &got[0], 8);
     memcpy(&hi, &got[1], 8);
     c->v_in_range = (lo > 0x1p-400) && (hi < 0x1p400); // a NaN anywhere makes hi a NaN: false
+    c->v_ysym = differ == 0;
     for (int &a : c->x2_agreed) a = -1;
     return WAFER_OK;
 }
@@ -418,6 +433,7 @@ int wafer_set_potential_builtin(wafer_ctx *c, int potential)
     HIP_TRY(hipSetDevice(c->P.device));
     WaferPotArgs a = pot_args(c, potential);
     const dim3 grid(c->bx, c->by, c->g.lz), block(64, 4);
+    c->v_ysym = false;   // V is about to change: check_v_range re-establishes it
     if (c->f32)
         hipLaunchKernelGGL((wafer_k_potential<float>), grid, block, 0, c->s_main, a, as<float>(c->v), as<float>(c->a), as<float>(c->b));
     else
@@ -459,6 +475,7 @@ int wafer_set_potential_host(wafer_ctx *c, const double *v, int potsub_kind, dou
     if (potsub_kind < 0 || potsub_kind > 2) return fail(WAFER_ERR_INVALID, "bad potsub_kind");
     if (potsub_kind == WAFER_POTSUB_ARRAY && !potsub) return fail(WAFER_ERR_INVALID, "potsub array missing");
     HIP_TRY(hipSetDevice(c->P.device));
+    c->v_ysym = false;   // V is about to change: check_v_range re-establishes it
     TRY(upload_padded(c, v, c->v));
     TRY(refresh_ab(c));
     c->vgen_type = 0;
@@ -621,6 +638,7 @@ int wafer_set_potential_resampled(wafer_ctx *c, const double *src, uint32_t sx, 
 {
     if (!c || !src) return fail(WAFER_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->P.device));
+    c->v_ysym = false;   // V is about to change: check_v_range re-establishes it
     TRY(resample_into(c, src, sx, sy, sz, basis, c->v));
     TRY(refresh_ab(c));
     c->vgen_type = 0;

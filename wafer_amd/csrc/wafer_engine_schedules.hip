@@ -226,8 +226,9 @@ int f3_table(wafer_ctx *c, int kind, int lz_lo, int lz_hi, int aux, const wafer_
     wafer_step3_tile(type_combo(c, true), &tx_, &ty_);
     const int ntx = (c->g.nx + tx_ - 1) / tx_, nty = (c->g.ny + ty_ - 1) / ty_;
     std::vector<WaferF3Block> host;
-    if (kind == F3_PLAIN) {
-        wafer_f3_schedule_plain(host, ntx, nty, lz_lo, lz_hi, aux /* planes per workgroup */, c->tune.swz != 0, c->tune.f3_plain_down != 0);
+    if (kind == F3_PLAIN || kind == F3_PLAIN_FOLD) {
+        wafer_f3_schedule_plain(host, ntx, nty, lz_lo, lz_hi, aux /* planes per workgroup */, c->tune.swz != 0, c->tune.f3_plain_down != 0,
+                                kind == F3_PLAIN_FOLD);
     } else if (kind == F3_MIXED) {
         wafer_f3_schedule_mixed(host, ntx, nty, lz_lo, lz_hi, aux /* short workgroups per tile */);
     } else if (kind == F3_WHOLE) {
@@ -276,6 +277,20 @@ int f3_table(wafer_ctx *c, int kind, int lz_lo, int lz_hi, int aux, const wafer_
     return WAFER_OK;
 }
 
+// A plain launch reads V once per mirrored pair of tiles (the VS instantiation on the folded tile order, wafer_stencil_fused3.hip.h)
+// when the ARRAY is its own mirror image in y (v_ysym, re-established after every write of V), the grid is whole tiles in x and y
+// with at least two tile rows, and the columns march up.  Evaluated at every launch: a context whose potential is replaced follows.
+// fp32 storage and all-fp32 are bound inside the CU, not by their bytes: WAFER_F3_VSYM=1 runs them for measurements only.
+// Slabs of a decomposed grid keep their schedules (halves, whole, mixed and the plain one): not measured here.
+static bool f3_vsym_applies(const wafer_ctx *c, int tx, int ty)
+{
+    if (c->tune.f3_vsym == 0 || !c->v_ysym || c->sharded() || c->tune.f3_xs == 0 || c->tune.f3_plain_down != 0) return false;
+    // (without the XCD-aware tile map the two tiles of a pair land on XCDs b % 8 and (b + ntx) % 8: nothing to share, so the plain pass)
+    if (c->tune.swz == 0) return false;
+    if (c->f32 && c->tune.f3_vsym < 1) return false;
+    return c->g.nx % tx == 0 && c->g.ny % ty == 0 && c->g.ny / ty >= 2;
+}
+
 // three fused steps over planes [lz_lo, lz_hi): phi[dst] = step(step(step(phi[src])))
 // short_tail: the interior launch of a split slab pass (see wafer_f3_schedule_mixed)
 int launch_step3(wafer_ctx *c, int src, int dst, int lz_lo, int lz_hi, hipStream_t s, bool short_tail = false)
@@ -288,14 +303,15 @@ int launch_step3(wafer_ctx *c, int src, int dst, int lz_lo, int lz_hi, hipStream
     const wafer_ctx::F3Table *tab = nullptr;
     if (short_tail && lz_hi - lz_lo >= 8 * 4) TRY(f3_table(c, F3_MIXED, lz_lo, lz_hi, 4, &tab));
     else if (c->tune.f3_sched == 1 && !c->sharded() && lz_hi - lz_lo >= 16) TRY(f3_table(c, F3_HALVES, lz_lo, lz_hi, 2 /* no flags, no counters */, &tab));
-    else TRY(f3_table(c, F3_PLAIN, lz_lo, lz_hi, wafer_f3_zchunk(c->tune, ntx, nty, lz_hi - lz_lo, c->num_cus), &tab));
+    else TRY(f3_table(c, f3_vsym_applies(c, tx_, ty_) ? F3_PLAIN_FOLD : F3_PLAIN, lz_lo, lz_hi, wafer_f3_zchunk(c->tune, ntx, nty, lz_hi - lz_lo, c->num_cus), &tab));
+    const int vsym = tab->kind == F3_PLAIN_FOLD ? 1 : 0;   // (the table's kind is part of its cache key: never the other state's order)
     // More workgroups than CUs and whole rounds of them per layer of tiles: one launch per round of CUs (wafer_f3_zchunk says why).  The
     // table hands XCD k a contiguous band in blocks of 8, so a sub-range that starts at a multiple of 8 keeps every workgroup on the XCD the table meant it for.
     const int slots = c->tune.target_blocks > 0 ? c->tune.target_blocks : c->num_cus;
-    const int per_launch = (tab->kind == F3_PLAIN && slots % 8 == 0 && wafer_f3_by_rounds(c->tune, (long long)ntx * nty, lz_hi - lz_lo, slots)) ? slots : tab->nblocks;
+    const int per_launch = ((tab->kind == F3_PLAIN || tab->kind == F3_PLAIN_FOLD) && slots % 8 == 0 && wafer_f3_by_rounds(c->tune, (long long)ntx * nty, lz_hi - lz_lo, slots)) ? slots : tab->nblocks;
     for (int first = 0; first < tab->nblocks; first += per_launch) {
         const int nb = std::min(per_launch, tab->nblocks - first);
-        if (wafer_entry_step3_fused(type_combo(c, true), c->tune, a, tab->dev + first, nb, WaferF3Sync(), c->phi[src], c->v, c->phi[dst], s, tab->dir) != hipSuccess)
+        if (wafer_entry_step3_fused(type_combo(c, true), c->tune, a, tab->dev + first, nb, WaferF3Sync(), c->phi[src], c->v, c->phi[dst], s, tab->dir, vsym) != hipSuccess)
             return fail(WAFER_ERR_HIP, "three-step stencil launch failed: %s", hipGetErrorString(hipGetLastError()));
     }
     c->last_instance_valid = true;

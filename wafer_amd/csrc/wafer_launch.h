@@ -50,10 +50,12 @@ hipError_t wafer_entry_step2_wide(int tc, const WaferTuning &t, const WaferStepA
 // three fused ground-state steps (ThreePoint; every type combination), table-driven
 // dir: 1 = every workgroup of the table marches up, 2 = every one down, 0 = both occur (picks the kernel that carries only the
 // copy of the plane loop it needs)
+// vsym: the caller has verified on the array that V equals its mirror image in y and asks for the instantiation that reads the
+// canonical row of each mirrored pair (plain launches over whole tiles with dir == 1 only: anything else is refused)
 hipError_t wafer_entry_step3_fused(int tc, const WaferTuning &t, const WaferStepArgs &a, const WaferF3Block *table, int nblocks,
-                                   const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir = 0);
+                                   const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir = 0, int vsym = 0);
 hipError_t wafer_entry_step3_fused_wide(const WaferTuning &t, const WaferStepArgs &a, const WaferF3Block *table, int nblocks,
-                                        const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir);
+                                        const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir, int vsym);
 void wafer_step3_tile(int tc, int *tx, int *ty);
 // the template-id of the instantiation this thread's last wafer_entry_step3_fused launched, as rocprofv3 prints it
 // ("wafer_k_step3_fused<double, double, true, 0, true, 1>"); empty before the first launch

@@ -377,6 +377,25 @@ __global__ __launch_bounds__(256) void wafer_k_trilerp(WaferResampleArgs a, cons
     dst[g.at(lzp, j + g.R, i + g.R)] = (T)op(c0, c1, zd);
 }
 
+// Is V its own mirror image in y?  ORs 1 into *out when V[x, y, z] and V[x, ny-1-y, z] differ in any BIT on a work cell of any local
+// plane (ghost planes included; -0.0 against 0.0 and two NaNs count as different).  One workgroup per pair of rows, grid-stride.
+template <typename T>
+__global__ __launch_bounds__(256) void wafer_k_v_ysym(WaferGeom g, const T *__restrict__ v, unsigned long long *__restrict__ out)
+{
+    const int half = g.ny / 2;
+    const long long pairs = (long long)g.lz * half;
+    bool differ = false;
+    for (long long p = blockIdx.x; p < pairs; p += gridDim.x) {
+        const int lzp = (int)(p / half), y = (int)(p % half);
+        const T *lo = v + g.at(lzp, y + g.R, g.R), *hi = v + g.at(lzp, g.ny - 1 - y + g.R, g.R);
+        for (int x = threadIdx.x; x < g.nx; x += blockDim.x) {
+            if constexpr (sizeof(T) == 8) differ |= __double_as_longlong((double)lo[x]) != __double_as_longlong((double)hi[x]);
+            else differ |= __float_as_uint((float)lo[x]) != __float_as_uint((float)hi[x]);
+        }
+    }
+    if (differ) atomicOr(out, 1ull);
+}
+
 // min / max of |1 + dt*V/2| over a whole allocation (guard cells hold V = 0 -> 1), as the bit
 // patterns of the non-negative doubles (their unsigned order is their numeric order; NaN sorts
 // above +inf).  out[0] = min (start at ~0ull), out[1] = max (start at 0).

@@ -214,7 +214,13 @@ __device__ __forceinline__ const volatile WaferF3Sync *wafer_f3_sync_in_kernarg(
 // makes every wave sit out the completion of the two stores it issued a few hundred cycles earlier, once per plane (the
 // ablations of profiles/NOTES.md: the kernel without its stores 0.202 ms/step, without its loads 0.215, with both 0.253, without
 // either 0.192).  While the pipeline fills, the two stores go to the column's first plane, which the first real store overwrites.
-template <typename TS, typename C, bool VIR, bool DOWN, int MODE, bool XS = false, bool RING_T = false>
+// VS ("V symmetric in y"; plain XS launches of a context whose potential the host has COMPARED, bit by bit, with its own mirror
+// image in y: check_v_range in wafer_engine.hip): every request for V -- the two main rows, the extra slot's halo row, the
+// halo-column cells -- asks for the canonical row min(y, ny - 1 - y) in place of row y.  The same lanes, the same vector, the
+// same arithmetic, another row ADDRESS: the two tiles (tx, ty) and (tx, nty - 1 - ty) then ask the XCD's L2 for the same lines of
+// V, and the folded schedule (wafer_f3_schedule_plain) runs them side by side, so that V leaves HBM once per pair.  The V offsets
+// are formed once per workgroup, in front of the plane loop; phi's requests, LDS, queues, arithmetic and stores are untouched.
+template <typename TS, typename C, bool VIR, bool DOWN, int MODE, bool XS = false, bool RING_T = false, bool VS = false>
 __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const WaferF3Block &blk, int ntx, const WaferF3Sync &sy,
                                                   const typename WaferF3Store<TS>::S *__restrict__ phi, const typename WaferF3Store<TS>::S *__restrict__ pv,
                                                   typename WaferF3Store<TS>::S *__restrict__ out,
@@ -285,6 +291,12 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
         rowwk[r] = y < g.ny;
         rowoff[r] = (long long)(y + R) * g.pitch + g.xoff + R + x0;
     }
+    // the row V of work row y is read from (VS: the canonical one of y and its mirror image; rows outside the work area are never
+    // asked for -- their requests go to a row of the tile, below)
+    auto vrow = [&](int y) { return VS ? min(y, g.ny - 1 - y) : y; };
+    long long vrowoff[RY];
+#pragma unroll
+    for (int r = 0; r < RY; ++r) vrowoff[r] = VS ? (long long)(vrow(yrow[r]) + R) * g.pitch + g.xoff + R + x0 : rowoff[r];
     // ---- the extra halo row
     const int xy = wave == 0 ? y0 - 1 : wave == 1 ? y0 - 2 : wave == 6 ? y0 + TY + 1 : y0 + TY;
     const bool xwk = x_row && xy >= 0 && xy < g.ny;
@@ -292,6 +304,7 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
     //  own first row again and takes zeros)
     const bool xy_out = xy < 0 || xy >= g.ny;
     const long long xoff_row = xy_out ? rowoff[0] : (long long)(xy + R) * g.pitch + g.xoff + R + x0;
+    const long long xvoff_row = !VS ? xoff_row : xy_out ? vrowoff[0] : (long long)(vrow(xy) + R) * g.pitch + g.xoff + R + x0;
     // ---- outermost phi0 halo rows y0-3 / y0+18 (plain vector loads staged through LDS)
     const int oy = wave == 1 ? y0 - 3 : y0 + TY + 2;
     const bool oy_out = oy < 0 || oy >= g.ny;
@@ -317,9 +330,17 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
     const bool c_xout = cxw < 0 || cxw >= g.nx || cy < 0 || cy >= g.ny;
     const long long c_off = (long long)((cy < 0 ? y0 : cy >= g.ny ? y0 + TY - 1 : cy) + R) * g.pitch + g.xoff + R +
                             ((cxw < 0 || cxw >= g.nx) ? (ck < Cfg::HC0 ? x0 : x0 + TX - 1) : cxw);
+    const long long c_voff = !VS ? c_off
+                                 : (long long)(vrow(cy < 0 ? y0 : cy >= g.ny ? y0 + TY - 1 : cy) + R) * g.pitch + g.xoff + R +
+                                       ((cxw < 0 || cxw >= g.nx) ? (ck < Cfg::HC0 ? x0 : x0 + TX - 1) : cxw);
     const int c_lds0 = crow * LP0 + HX0 + clc, c_lds1 = (crow - 1) * LP1 + HX1 + clc, c_lds2 = (crow - 2) * LP2 + HX2 + clc;
     // per-lane element offsets of the extra slot's requests inside a plane (see the prefetch at the top of the plane loop)
     const long long xslot_off = x_row ? xoff_row + (long long)xlu : c_off;
+    const long long xslot_voff = !VS ? xslot_off : x_row ? xvoff_row + (long long)xlu : c_voff;
+    // (VS: as pointers, so that V's base itself need not stay live beside them in a kernel that is out of scalar registers)
+    [[maybe_unused]] const ST *const pv_row[RY] = {pv + vrowoff[0], pv + vrowoff[RY - 1]};
+    [[maybe_unused]] const ST *const pv_xslot = pv + xslot_voff;
+    static_assert(RY == 2, "pv_row");
     const long long orow_slot_off = has_orow ? orow_off + (long long)xlu : xslot_off;
 
     auto work_plane = [&](int p) {
@@ -362,9 +383,9 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
     {
         const long long po = (long long)z1 * g.plane;
 #pragma unroll
-        for (int r = 0; r < RY; ++r) vcur[r] = gload((pv + po + rowoff[r]) + xlu);
-        if (x_row) xv = gload((pv + po + xoff_row) + xlu);
-        else xv[0] = (T)pv[po + c_off];
+        for (int r = 0; r < RY; ++r) vcur[r] = gload((pv + po + vrowoff[r]) + xlu);
+        if (x_row) xv = gload((pv + po + xvoff_row) + xlu);
+        else xv[0] = (T)pv[po + c_voff];
     }
     for (int i = tid; i < 2 * Cfg::TILE0; i += Cfg::NT_) lds0[i] = T(0);
     for (int i = tid; i < 2 * Cfg::TILE1; i += Cfg::NT_) lds1[i] = T(0);
@@ -567,6 +588,24 @@ __global__ __launch_bounds__((WaferF3Cfg<typename WaferF3Store<T>::Q>::NT_)) voi
     else wafer_step3_body<T, C, VIR, false, MODE, XS, RING>(a, blk, ntx, sy, phi, pv, out, lds0, lds1, lds2);
 }
 
+// The VS instantiation (see wafer_step3_body): a second template of the same name with one more argument, so that every
+// instantiation of the first keeps its symbol and its template-id -- the key of every profile and counter record of this project --
+// and this one reads "wafer_k_step3_fused<double, double, true, 0, true, 1, true>".  Plain launches over whole tiles, marching up.
+template <typename T, typename C, bool VIR, int MODE, bool XS, int DIR, bool VS>
+__global__ __launch_bounds__((WaferF3Cfg<typename WaferF3Store<T>::Q>::NT_)) void wafer_k_step3_fused(WaferStepArgs a, int ntx, const WaferF3Block *__restrict__ table,
+                                                                              WaferF3Sync sy, const typename WaferF3Store<T>::S *__restrict__ phi,
+                                                                              const typename WaferF3Store<T>::S *__restrict__ pv, typename WaferF3Store<T>::S *__restrict__ out)
+{
+    static_assert(VS && XS && MODE == 0 && DIR == 1, "the VS instantiation: plain launches over whole tiles, marching up");
+    using Q = typename WaferF3Store<T>::Q;
+    using Cfg = WaferF3Cfg<Q>;
+    __shared__ __attribute__((aligned(16))) Q lds0[2 * Cfg::TILE0];
+    __shared__ __attribute__((aligned(16))) Q lds1[2 * Cfg::TILE1];
+    __shared__ __attribute__((aligned(16))) Q lds2[2 * Cfg::TILE2];
+    const WaferF3Block blk = table[blockIdx.x];
+    wafer_step3_body<T, C, VIR, false, 0, true, true, true>(a, blk, ntx, sy, phi, pv, out, lds0, lds1, lds2);
+}
+
 
 // ---- schedules (host) ---------------------------------------------------------------------------------------------
 #include <vector>
@@ -582,7 +621,14 @@ static inline int wafer_f3_xcd_slot(int b, int n)
 
 // Planes [lz_lo, lz_hi) of every tile, cut into chunks of `zchunk` planes, all marching up: the schedule of an
 // undecomposed grid (one workgroup per CU marching a long column) and of every unsplit pass.
-static inline void wafer_f3_schedule_plain(std::vector<WaferF3Block> &out, int ntx, int nty, int lz_lo, int lz_hi, int zchunk, bool swz, bool down = false)
+// fold (the VS instantiation's launches): the tile rows of a z-chunk are visited in the order 0, nty-1, 1, nty-2, ... (x fastest
+// inside a row) BEFORE the sequence is cut into XCD-contiguous ranges, so that every XCD gets a band of rows plus its mirror image
+// and the two tiles that ask for the same lines of V are ntx entries apart in ONE XCD's queue (8 * ntx dispatch slots: workgroup b
+// runs on XCD b % 8) -- also where the sequence then goes out as one launch per round of CUs (launch_step3).  Only a pair that an
+// XCD's range ends inside is split (tests/test_f3_folded_order.py counts them).  An odd nty leaves the middle row without a partner.
+static inline int wafer_f3_folded_row(int j, int nty) { return (j & 1) ? nty - 1 - (j >> 1) : (j >> 1); }
+static inline void wafer_f3_schedule_plain(std::vector<WaferF3Block> &out, int ntx, int nty, int lz_lo, int lz_hi, int zchunk, bool swz, bool down = false,
+                                           bool fold = false)
 {
     const int nplanes = lz_hi - lz_lo, nch = (nplanes + zchunk - 1) / zchunk, n = ntx * nty * nch;
     out.resize((size_t)n);
@@ -590,6 +636,7 @@ static inline void wafer_f3_schedule_plain(std::vector<WaferF3Block> &out, int n
         const int id = swz ? wafer_f3_xcd_slot(b, n) : b;     // x fastest, then y, then z-chunk
         WaferF3Block k{};
         k.tile = id % (ntx * nty);
+        if (fold) k.tile = wafer_f3_folded_row(k.tile / ntx, nty) * ntx + k.tile % ntx;
         k.zs = lz_lo + (id / (ntx * nty)) * zchunk;
         k.ze = k.zs + zchunk < lz_hi ? k.zs + zchunk : lz_hi;
         k.down = down ? 1 : 0;
@@ -737,6 +784,7 @@ struct WaferF3Instance {
     int tsize = 0, csize = 0;   // sizeof storage / arithmetic type (0: nothing launched yet)
     bool vir = false, xs = false;
     int mode = 0, dir = 0;
+    bool vs = false;            // the instantiation that reads a y-symmetric V once per mirrored pair of tiles
 };
 inline WaferF3Instance &wafer_f3_last_instance()
 {
@@ -748,7 +796,7 @@ inline WaferF3Instance &wafer_f3_last_instance()
 template <typename T, typename C>
 static inline hipError_t wafer_launch_step3_fused(const WaferTuning &t, const WaferStepArgs &a, const WaferF3Block *table, int nblocks,
                                                   const WaferF3Sync &sy, const typename WaferF3Store<T>::S *phi, const typename WaferF3Store<T>::S *pv,
-                                                  typename WaferF3Store<T>::S *out, hipStream_t s, int dir = 0)
+                                                  typename WaferF3Store<T>::S *out, hipStream_t s, int dir = 0, int vsym = 0)
 {
     using Cfg = WaferF3Cfg<typename WaferF3Store<T>::Q>;
     const int ntx = (a.g.nx + Cfg::TX - 1) / Cfg::TX;
@@ -757,11 +805,22 @@ static inline hipError_t wafer_launch_step3_fused(const WaferTuning &t, const Wa
     const int mode = sy.peer ? 2 : (sy.flag != nullptr ? 1 : 0);
     // exact store counts (XS): plain launches over grids made of whole tiles (every store a full vector of work cells)
     const bool xs = t.f3_xs != 0 && a.g.nx % Cfg::TX == 0 && a.g.ny % Cfg::TY == 0;
+    // vsym: the caller has verified V[x, y, z] == V[x, ny - 1 - y, z] on the array (wafer_ctx::v_ysym) and built the table in folded
+    // order.  The instantiation exists for plain launches over whole tiles that march up; a caller that asks for it elsewhere is wrong.
+    if (vsym != 0 && !(xs && mode == 0 && dir == 1)) return hipErrorInvalidValue;
 #define WAFER_F3_LAUNCH3(VIR_, MODE_, XS_, DIR_)                                                                                                  \
     do {                                                                                                                                          \
         hipLaunchKernelGGL((wafer_k_step3_fused<T, C, VIR_, MODE_, XS_, DIR_>), grid, block, 0, s, a, ntx, table, sy, phi, pv, out); \
         WaferF3Instance &li_ = wafer_f3_last_instance();                                                                                          \
         li_.tsize = std::is_same<T, wafer_f32_wide>::value ? -4 : (int)sizeof(T); li_.csize = (int)sizeof(C); li_.vir = (VIR_); li_.mode = (MODE_); li_.xs = (XS_); li_.dir = (DIR_);           \
+        li_.vs = false;                                                                                                                           \
+    } while (0)
+#define WAFER_F3_LAUNCH_VS(VIR_)                                                                                                                  \
+    do {                                                                                                                                          \
+        hipLaunchKernelGGL((wafer_k_step3_fused<T, C, VIR_, 0, true, 1, true>), grid, block, 0, s, a, ntx, table, sy, phi, pv, out);             \
+        WaferF3Instance &li_ = wafer_f3_last_instance();                                                                                          \
+        li_.tsize = std::is_same<T, wafer_f32_wide>::value ? -4 : (int)sizeof(T); li_.csize = (int)sizeof(C); li_.vir = (VIR_); li_.mode = 0; li_.xs = true; li_.dir = 1;                       \
+        li_.vs = true;                                                                                                                            \
     } while (0)
     // (the single-direction kernels exist for the instantiations that need them: plain XS launches, peer-store passes)
 #define WAFER_F3_LAUNCH(VIR_, MODE_, XS_)                                              \
@@ -770,7 +829,10 @@ static inline hipError_t wafer_launch_step3_fused(const WaferTuning &t, const Wa
         else if ((XS_) && (MODE_) != 1 && dir == 2) WAFER_F3_LAUNCH3(VIR_, MODE_, XS_, ((XS_) && (MODE_) != 1) ? 2 : 0); \
         else WAFER_F3_LAUNCH3(VIR_, MODE_, XS_, 0);                                    \
     } while (0)
-    if (a.v_in_range != 0) {
+    if (vsym != 0) {
+        if (a.v_in_range != 0) WAFER_F3_LAUNCH_VS(true);
+        else WAFER_F3_LAUNCH_VS(false);
+    } else if (a.v_in_range != 0) {
         if (mode == 2 && xs) WAFER_F3_LAUNCH(true, 2, true);
         else if (mode == 2) WAFER_F3_LAUNCH(true, 2, false);
         else if (mode == 1 && xs) WAFER_F3_LAUNCH(true, 1, true);
@@ -786,6 +848,7 @@ static inline hipError_t wafer_launch_step3_fused(const WaferTuning &t, const Wa
         else WAFER_F3_LAUNCH(false, 0, false);
     }
 #undef WAFER_F3_LAUNCH
+#undef WAFER_F3_LAUNCH_VS
 #undef WAFER_F3_LAUNCH3
     return hipGetLastError();
 }

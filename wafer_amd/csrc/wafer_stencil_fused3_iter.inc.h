@@ -43,18 +43,20 @@
         auto issue_B = [&]() {
 #pragma unroll
             for (int r = 0; r < RY; ++r) {
-                if constexpr (DIRECT) vcur[r] = gload((pv + zo + SD * g.plane + rowoff[r]) + xlu);
-                else pre_v[r] = gload_raw((pv + zo + SD * g.plane + rowoff[r]) + xlu);
+                if constexpr (VS && DIRECT) vcur[r] = gload((pv_row[r] + zo + SD * g.plane) + xlu);
+                else if constexpr (DIRECT) vcur[r] = gload((pv + zo + SD * g.plane + rowoff[r]) + xlu);
+                else pre_v[r] = gload_raw((pv + zo + SD * g.plane + vrowoff[r]) + xlu);
             }
         };
         auto issue_C = [&]() {
             if constexpr (DIRECT) {
                 xq0[WAFER_F3_Q0(0)] = gload(phi + zo + SD * 2 * g.plane + xslot_off);
-                xv = gload(pv + zo + SD * g.plane + xslot_off);
+                if constexpr (VS) xv = gload(pv_xslot + zo + SD * g.plane);
+                else xv = gload(pv + zo + SD * g.plane + xslot_off);
                 orow_nxt = gload(phi + zo + SD * 2 * g.plane + orow_slot_off);
             } else {
                 xpre = gload_raw(phi + zo + SD * 2 * g.plane + xslot_off);
-                xpre_v = gload_raw(pv + zo + SD * g.plane + xslot_off);
+                xpre_v = gload_raw(pv + zo + SD * g.plane + xslot_voff);
                 orow_pre = gload_raw(phi + zo + SD * 2 * g.plane + orow_slot_off);
             }
         };

@@ -5,17 +5,17 @@
 #include "wafer_stencil_fused3.hip.h"
 
 hipError_t wafer_entry_step3_fused(int tc, const WaferTuning &t, const WaferStepArgs &a, const WaferF3Block *table, int nblocks,
-                                   const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir)
+                                   const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir, int vsym)
 {
     switch (tc) {
     case WAFER_TC_F64:
         return wafer_launch_step3_fused<double, double>(t, a, table, nblocks, sy, static_cast<const double *>(phi), static_cast<const double *>(pv),
-                                                        static_cast<double *>(out), s, dir);
+                                                        static_cast<double *>(out), s, dir, vsym);
     case WAFER_TC_F32_F32:   // a and b ride between the levels in the arithmetic type: fp32 here, as in the two-step kernel
         return wafer_launch_step3_fused<float, float>(t, a, table, nblocks, sy, static_cast<const float *>(phi), static_cast<const float *>(pv),
-                                                      static_cast<float *>(out), s, dir);
+                                                      static_cast<float *>(out), s, dir, vsym);
     case WAFER_TC_F32_F64:   // fp32 storage, fp64 arithmetic: float in HBM, the fp64 kernel's registers and LDS (its own unit: wafer_tu_fused3_wide.hip)
-        return wafer_entry_step3_fused_wide(t, a, table, nblocks, sy, phi, pv, out, s, dir);
+        return wafer_entry_step3_fused_wide(t, a, table, nblocks, sy, phi, pv, out, s, dir, vsym);
     default:
         return hipErrorInvalidValue;
     }
@@ -34,8 +34,8 @@ void wafer_step3_last_instance(char *buf, size_t n)
     if (n == 0) return;
     buf[0] = 0;
     if (li.tsize == 0) return;
-    snprintf(buf, n, "wafer_k_step3_fused<%s, %s, %s, %d, %s, %d>", li.tsize == 8 ? "double" : li.tsize == -4 ? "wafer_f32_wide" : "float", li.csize == 8 ? "double" : "float",
-             li.vir ? "true" : "false", li.mode, li.xs ? "true" : "false", li.dir);
+    snprintf(buf, n, "wafer_k_step3_fused<%s, %s, %s, %d, %s, %d%s>", li.tsize == 8 ? "double" : li.tsize == -4 ? "wafer_f32_wide" : "float", li.csize == 8 ? "double" : "float",
+             li.vir ? "true" : "false", li.mode, li.xs ? "true" : "false", li.dir, li.vs ? ", true" : "");
 }
 
 #if WAFER_DIAG & 1

@@ -4,8 +4,8 @@
 #include "wafer_stencil_fused3.hip.h"
 
 hipError_t wafer_entry_step3_fused_wide(const WaferTuning &t, const WaferStepArgs &a, const WaferF3Block *table, int nblocks,
-                                        const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir)
+                                        const WaferF3Sync &sy, const void *phi, const void *pv, void *out, hipStream_t s, int dir, int vsym)
 {
     return wafer_launch_step3_fused<wafer_f32_wide, double>(t, a, table, nblocks, sy, static_cast<const float *>(phi), static_cast<const float *>(pv),
-                                                            static_cast<float *>(out), s, dir);
+                                                            static_cast<float *>(out), s, dir, vsym);
 }

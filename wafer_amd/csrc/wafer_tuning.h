@@ -51,6 +51,9 @@ struct WaferTuning {
     int f3_plain_down = 0;  // WAFER_F3_PLAIN_DOWN: 1 = the plain schedule's workgroups march their columns downwards (the same bits; the two directions are separate copies of the loop, and the compiler's register allocation differs between them)
     int f3_rounds = -1;     // WAFER_F3_ROUNDS: a plain launch of the three-step kernel with more workgroups than CUs goes as one launch per round of CUs, its
                             // columns cut to at most 384 planes (-1: yes; 0: one launch, columns as long as the makespan rule says -- rounds 1-4)
+    int f3_vsym = -1;       // WAFER_F3_VSYM: a potential that equals its own mirror image in y (compared on the array: wafer_ctx::v_ysym) is read once per mirrored pair
+                            // of tiles -- the VS instantiation of the three-step kernel on the folded tile order.  -1 = where it was measured to win (fp64),
+                            // 0 = never, 1 = every dtype (A/B runs)
     int f3_sched = 0;       // WAFER_F3_SCHED: 1 = undecomposed launches use the two-halves schedule as well (timing experiments)
 };
 
@@ -87,6 +90,7 @@ static inline WaferTuning wafer_tuning_from_env()
     t.f3_plain_down = wafer_env_int("WAFER_F3_PLAIN_DOWN", t.f3_plain_down);
     t.f3_rounds = wafer_env_int("WAFER_F3_ROUNDS", t.f3_rounds);
     t.f3_xs = wafer_env_int("WAFER_F3_XS", t.f3_xs);
+    t.f3_vsym = wafer_env_int("WAFER_F3_VSYM", t.f3_vsym);
     t.hv_layout = wafer_env_int("WAFER_HV_LAYOUT", t.hv_layout);
     t.hv_whole_max = wafer_env_int("WAFER_HV_WHOLE_MAX", t.hv_whole_max);
     t.hv_wait_ms = wafer_env_int("WAFER_HV_WAIT_MS", t.hv_wait_ms);
