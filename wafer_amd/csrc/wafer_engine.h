@@ -4,6 +4,7 @@
 //   wafer_engine_schedules.hip  which kernel advances what: variants, workgroup tables, launches, reductions, wafer_evolve, observables
 //   wafer_engine_comm.hip       z-slabs: halo exchange through the hooks, the single-launch pass, peer stores
 //   wafer_engine_solve.hip      grid.rs:50-246 for one state (host loop)
+//   wafer_passes.h              which pass of wafer_evolve comes next, from what every rank of a decomposed run shares (plain C++)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -27,6 +28,7 @@
 #include "wafer_stencil_fused3.hip.h"
 #include "wafer_launch.h"
 #include "wafer_tuning.h"
+#include "wafer_passes.h"
 
 namespace wafer_eng __attribute__((visibility("hidden"))) {
 // sets the thread's last-error message and returns `code`
@@ -256,7 +258,7 @@ int recompute_gram(wafer_ctx *c);
 int exchange_halo_array(wafer_ctx *c, void *array, hipStream_t s, int planes);
 int exchange_halo(wafer_ctx *c, int buf, hipStream_t s, int planes);
 int exchange_halo_side(wafer_ctx *c, int buf, hipStream_t s, int planes, int side);
-int copy_exchange(wafer_ctx *c, int buf, hipStream_t s, int planes, bool send_lo, bool send_hi, bool recv_lo, bool recv_hi);
+int copy_exchange(wafer_ctx *c, int buf, hipStream_t s, int planes, const bool send[2], const bool recv[2]);
 int ensure_halo(wafer_ctx *c, int need);
 int ensure_hv(wafer_ctx *c);
 int check_hv_err(wafer_ctx *c);

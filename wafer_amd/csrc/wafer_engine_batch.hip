@@ -108,6 +108,19 @@ int check_member_index(const wafer_batch *b, uint32_t m)
     return WAFER_OK;
 }
 
+// every active member has phi (and, with need_pot, a potential: `what` ends that message) and at least wnum stored states
+int check_ready(const wafer_batch *b, const uint8_t *active, bool need_pot, const char *what, uint32_t wnum)
+{
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        const wafer_ctx *c = b->views[m];
+        if (need_pot && (!c->have_pot || !c->have_phi)) return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set%s", m, what);
+        if (!c->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+        if (wnum > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: wnum %u but w_store holds %u states", m, wnum, b->nst[m]);
+    }
+    return WAFER_OK;
+}
+
 // the member table as the views stand now (potential range, pot_sub, current buffer), to the device if it changed
 int sync_members(wafer_batch *b)
 {
@@ -178,42 +191,11 @@ int build_blocks(wafer_batch *b, const uint8_t *active)
     return WAFER_OK;
 }
 
-int evolve(wafer_batch *b, const uint8_t *active, uint64_t n_steps)
-{
-    HIP_TRY(hipSetDevice(b->device));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (!b->views[m]->have_pot || !b->views[m]->have_phi)
-            return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set before evolve", m);
-    }
-    const uint64_t steps = n_steps == 0 ? 1 : n_steps;   // grid.rs:682-685
-    TRY(sync_members(b));
-    TRY(build_blocks(b, active));
-    RoctxRange range_("wafer_batch_evolve");
-    HIP_TRY(hipEventRecord(b->ev_start, b->s));
-    if (!b->blk.empty()) {
-        for (uint64_t k = 0; k < steps; ++k) {
-            const hipError_t e = wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), (int)(k & 1), b->s);
-            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
-    b->last_steps = steps;
-    b->timing_valid = true;
-    if (steps & 1)
-        for (uint32_t m = 0; m < b->n; ++m)
-            if (!active || active[m]) b->views[m]->cur ^= 1;
-    return WAFER_OK;
-}
-
 // the four raw sums of the active members into sums_host[m * 4 ..]
 int observables(wafer_batch *b, const uint8_t *active)
 {
     HIP_TRY(hipSetDevice(b->device));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (!b->views[m]->have_pot || !b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set", m);
-    }
+    TRY(check_ready(b, active, true, "", 0));
     TRY(sync_members(b));
     int nact = 0;
     TRY(upload_active(b, active, &nact));
@@ -240,10 +222,7 @@ void obs_of(const wafer_batch *b, uint32_t m, wafer_observables_t *o)
 int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, int stride)
 {
     HIP_TRY(hipSetDevice(b->device));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (!b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
-    }
+    TRY(check_ready(b, active, false, "", 0));
     TRY(sync_members(b));
     int nact = 0;
     TRY(upload_active(b, active, &nact));
@@ -311,16 +290,6 @@ int ensure_gs(wafer_batch *b)
     return WAFER_OK;
 }
 
-int check_store(const wafer_batch *b, const uint8_t *active, uint32_t wnum)
-{
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (!b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
-        if (wnum > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: wnum %u but w_store holds %u states", m, wnum, b->nst[m]);
-    }
-    return WAFER_OK;
-}
-
 // one elementwise launch (+ its reduce into slot out_slot) over the members in act_dev; lower, dotwith: store slots, -1 none
 int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int lower, int dotwith, int out_slot)
 {
@@ -353,29 +322,25 @@ int gs_chain(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_f
     return WAFER_OK;
 }
 
+// n_steps steps of the active members, each followed by the normalise / Gram-Schmidt chain when wnum > 0 (grid.rs:544-687)
 int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t n_steps)
 {
-    if (wnum == 0) return evolve(b, active, n_steps);
     HIP_TRY(hipSetDevice(b->device));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (!b->views[m]->have_pot || !b->views[m]->have_phi)
-            return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set before evolve", m);
-    }
-    TRY(check_store(b, active, wnum));
+    TRY(check_ready(b, active, true, " before evolve", 0));
+    if (wnum) TRY(check_ready(b, active, false, "", wnum));
     const uint64_t steps = n_steps == 0 ? 1 : n_steps;   // grid.rs:682-685
-    TRY(ensure_gs(b));
+    if (wnum) TRY(ensure_gs(b));
     TRY(sync_members(b));
     TRY(build_blocks(b, active));
     int nact = 0;
-    TRY(upload_active(b, active, &nact));
-    RoctxRange range_("wafer_batch_evolve_state");
+    if (wnum) TRY(upload_active(b, active, &nact));   // (the chain's member list; synchronises the stream, which a ground-state call must not)
+    RoctxRange range_(wnum ? "wafer_batch_evolve_state" : "wafer_batch_evolve");
     HIP_TRY(hipEventRecord(b->ev_start, b->s));
-    if (nact) {
+    if (!b->blk.empty()) {   // (no active member: no workgroup)
         for (uint64_t k = 0; k < steps; ++k) {   // no host synchronisation in here: every scalar stays on the device
             const hipError_t e = wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), (int)(k & 1), b->s);
             if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
-            TRY(gs_chain(b, nact, (int)((k + 1) & 1), wnum, true));
+            if (wnum) TRY(gs_chain(b, nact, (int)((k + 1) & 1), wnum, true));
         }
     }
     HIP_TRY(hipEventRecord(b->ev_stop, b->s));
@@ -390,7 +355,7 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
 int orthogonalise(wafer_batch *b, const uint8_t *active, uint32_t wnum)
 {
     HIP_TRY(hipSetDevice(b->device));
-    TRY(check_store(b, active, wnum));
+    TRY(check_ready(b, active, false, "", wnum));
     if (wnum == 0) return WAFER_OK;
     TRY(ensure_gs(b));
     TRY(sync_members(b));
@@ -665,7 +630,7 @@ int wafer_batch_download_phi(wafer_batch *b, uint32_t member, double *phi)
 int wafer_batch_evolve(wafer_batch *b, const uint8_t *active, uint64_t n_steps)
 {
     if (!b) return fail(WAFER_ERR_INVALID, "null batch");
-    return evolve(b, active, n_steps);
+    return evolve_state(b, active, 0, n_steps);
 }
 
 int wafer_batch_observables(wafer_batch *b, wafer_observables_t *out)
@@ -718,7 +683,7 @@ int wafer_batch_norm2(wafer_batch *b, double *out)
 {
     if (!b || !out) return fail(WAFER_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    TRY(check_store(b, nullptr, 0));
+    TRY(check_ready(b, nullptr, false, "", 0));
     TRY(ensure_gs(b));
     TRY(sync_members(b));
     int nact = 0;

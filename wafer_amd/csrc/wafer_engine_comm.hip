@@ -7,29 +7,49 @@ namespace wafer_eng __attribute__((visibility("hidden"))) {
 // ---------------------------------------------------------------------------
 // halo exchange through the host-installed hook
 // ---------------------------------------------------------------------------
-// the first / last `planes` owned planes of any grid array (logical pointer) to the z-neighbours' ghost planes
-int exchange_halo_array(wafer_ctx *c, void *array, hipStream_t s, int planes)
+// What an exchange of `planes` planes of a grid array (logical pointer) moves: send[n], the owned planes next to neighbour n
+// (0 below, 1 above), and recv[n], the ghost planes on that side -- null where the caller's `send` / `recv` say no.
+struct HaloPlanes {
+    void *send[2] = {nullptr, nullptr}, *recv[2] = {nullptr, nullptr};
+    size_t bytes = 0;
+};
+static int halo_planes(const wafer_ctx *c, void *array, int planes, const bool send[2], const bool recv[2], HaloPlanes *h)
 {
-    if (!c->sharded()) return WAFER_OK;
-    // overlap mode 4: phi's ghost planes travel as device copies into the neighbours' buffers (the stored states and their images,
-    // exchanged once per change of w_store, keep the hook: the peers map each other's two phi buffers only)
-    if (c->halo_copy && (array == c->phi[0] || array == c->phi[1]))
-        return copy_exchange(c, array == c->phi[0] ? 0 : 1, s, planes, c->has_lo(), c->has_hi(), c->has_lo(), c->has_hi());
-    if (!c->halo_hook) return fail(WAFER_ERR_COMM, "context owns a z-slab but no halo hook is installed");
-    RoctxRange range_("wafer_halo_exchange");
     const WaferGeom &g = c->g;
     if (planes > g.G || planes > g.nzl) return fail(WAFER_ERR_INVALID, "halo exchange deeper than the slab allows");
     char *base = static_cast<char *>(array);
     const size_t plane_b = (size_t)g.plane * c->esz;
     // from row 0 of the first plane to the last padded row of the last plane (guard rows in between ride along)
-    const size_t bytes = ((size_t)(planes - 1) * (size_t)g.plane + (size_t)g.py * (size_t)g.pitch) * c->esz;
-    void *send_lo = c->has_lo() ? base + (size_t)g.G * plane_b : nullptr;
-    void *recv_lo = c->has_lo() ? base + (size_t)(g.G - planes) * plane_b : nullptr;
-    void *send_hi = c->has_hi() ? base + (size_t)(g.G + g.nzl - planes) * plane_b : nullptr;
-    void *recv_hi = c->has_hi() ? base + (size_t)(g.G + g.nzl) * plane_b : nullptr;
-    if (c->halo_hook(c->hook_user, send_lo, send_hi, recv_lo, recv_hi, bytes, (void *)s) != 0)
+    h->bytes = ((size_t)(planes - 1) * (size_t)g.plane + (size_t)g.py * (size_t)g.pitch) * c->esz;
+    if (send[0]) h->send[0] = base + (size_t)g.G * plane_b;
+    if (recv[0]) h->recv[0] = base + (size_t)(g.G - planes) * plane_b;
+    if (send[1]) h->send[1] = base + (size_t)(g.G + g.nzl - planes) * plane_b;
+    if (recv[1]) h->recv[1] = base + (size_t)(g.G + g.nzl) * plane_b;
+    return WAFER_OK;
+}
+
+// ... through the host's hook, which is not called when nothing is to be sent or received
+static int hook_exchange(wafer_ctx *c, void *array, hipStream_t s, int planes, const bool send[2], const bool recv[2])
+{
+    if (!c->halo_hook) return fail(WAFER_ERR_COMM, "context owns a z-slab but no halo hook is installed");
+    RoctxRange range_("wafer_halo_exchange");
+    HaloPlanes h;
+    TRY(halo_planes(c, array, planes, send, recv, &h));
+    if (!h.send[0] && !h.send[1] && !h.recv[0] && !h.recv[1]) return WAFER_OK;
+    if (c->halo_hook(c->hook_user, h.send[0], h.send[1], h.recv[0], h.recv[1], h.bytes, (void *)s) != 0)
         return fail(WAFER_ERR_COMM, "halo hook failed");
     return WAFER_OK;
+}
+
+// the first / last `planes` owned planes of any grid array (logical pointer) to the z-neighbours' ghost planes
+int exchange_halo_array(wafer_ctx *c, void *array, hipStream_t s, int planes)
+{
+    if (!c->sharded()) return WAFER_OK;
+    const bool sides[2] = {c->has_lo(), c->has_hi()};
+    // overlap mode 4: phi's ghost planes travel as device copies into the neighbours' buffers (the stored states and their images,
+    // exchanged once per change of w_store, keep the hook: the peers map each other's two phi buffers only)
+    if (c->halo_copy && (array == c->phi[0] || array == c->phi[1])) return copy_exchange(c, array == c->phi[0] ? 0 : 1, s, planes, sides, sides);
+    return hook_exchange(c, array, s, planes, sides, sides);
 }
 
 int exchange_halo(wafer_ctx *c, int buf, hipStream_t s, int planes) { return exchange_halo_array(c, c->phi[buf], s, planes); }
@@ -39,23 +59,9 @@ int exchange_halo(wafer_ctx *c, int buf, hipStream_t s, int planes) { return exc
 // rank calls the same side at the same point of a pass, so the sends and receives pair up.
 int exchange_halo_side(wafer_ctx *c, int buf, hipStream_t s, int planes, int side)
 {
-    if (c->halo_copy)
-        return copy_exchange(c, buf, s, planes, side == 0 && c->has_lo(), side == 1 && c->has_hi(), side == 1 && c->has_lo(), side == 0 && c->has_hi());
-    if (!c->halo_hook) return fail(WAFER_ERR_COMM, "context owns a z-slab but no halo hook is installed");
-    RoctxRange range_("wafer_halo_exchange");
-    const WaferGeom &g = c->g;
-    if (planes > g.G || planes > g.nzl) return fail(WAFER_ERR_INVALID, "halo exchange deeper than the slab allows");
-    char *base = static_cast<char *>(c->phi[buf]);
-    const size_t plane_b = (size_t)g.plane * c->esz;
-    const size_t bytes = ((size_t)(planes - 1) * (size_t)g.plane + (size_t)g.py * (size_t)g.pitch) * c->esz;
-    void *send_lo = (side == 0 && c->has_lo()) ? base + (size_t)g.G * plane_b : nullptr;
-    void *recv_hi = (side == 0 && c->has_hi()) ? base + (size_t)(g.G + g.nzl) * plane_b : nullptr;
-    void *send_hi = (side == 1 && c->has_hi()) ? base + (size_t)(g.G + g.nzl - planes) * plane_b : nullptr;
-    void *recv_lo = (side == 1 && c->has_lo()) ? base + (size_t)(g.G - planes) * plane_b : nullptr;
-    if (!send_lo && !send_hi && !recv_lo && !recv_hi) return WAFER_OK;
-    if (c->halo_hook(c->hook_user, send_lo, send_hi, recv_lo, recv_hi, bytes, (void *)s) != 0)
-        return fail(WAFER_ERR_COMM, "halo hook failed");
-    return WAFER_OK;
+    const bool send[2] = {side == 0 && c->has_lo(), side == 1 && c->has_hi()}, recv[2] = {side == 1 && c->has_lo(), side == 0 && c->has_hi()};
+    if (c->halo_copy) return copy_exchange(c, buf, s, planes, send, recv);
+    return hook_exchange(c, c->phi[buf], s, planes, send, recv);
 }
 
 // makes at least `need` ghost planes of phi[cur] current
@@ -215,18 +221,15 @@ __global__ __launch_bounds__(64) void wafer_k_rendezvous(WaferRendezvous r, unsi
     if (waited) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // what the neighbour's copy wrote is visible to what follows in the stream
 }
 
-int copy_exchange(wafer_ctx *c, int buf, hipStream_t s, int planes, bool send_lo, bool send_hi, bool recv_lo, bool recv_hi)
+int copy_exchange(wafer_ctx *c, int buf, hipStream_t s, int planes, const bool send[2], const bool recv[2])
 {
-    if (!send_lo && !send_hi && !recv_lo && !recv_hi) return WAFER_OK;
+    if (!send[0] && !send[1] && !recv[0] && !recv[1]) return WAFER_OK;
     if (!c->peer_ready) return fail(WAFER_ERR_STATE, "overlap mode 4 (peer copies) needs wafer_peer_connect first");
     RoctxRange range_("wafer_halo_exchange_copy");
     const WaferGeom &g = c->g;
-    if (planes > g.G || planes > g.nzl) return fail(WAFER_ERR_INVALID, "halo exchange deeper than the slab allows");
+    HaloPlanes h;
+    TRY(halo_planes(c, c->phi[buf], planes, send, recv, &h));
     const size_t plane_b = (size_t)g.plane * c->esz;
-    // from row 0 of the first plane to the last padded row of the last plane (guard rows in between ride along)
-    const size_t bytes = ((size_t)(planes - 1) * (size_t)g.plane + (size_t)g.py * (size_t)g.pitch) * c->esz;
-    char *mine = static_cast<char *>(c->phi[buf]);
-    const bool recv[2] = {recv_lo, recv_hi}, send[2] = {send_lo, send_hi};
     auto launch = [&](const WaferRendezvous &r) -> int {
         hipLaunchKernelGGL(wafer_k_rendezvous, dim3(1), dim3(64), 0, s, r, c->hv_err, hv_spins(c, 4));
         HIP_TRY(hipGetLastError());
@@ -248,9 +251,8 @@ int copy_exchange(wafer_ctx *c, int buf, hipStream_t s, int planes, bool send_lo
     for (int n = 0; n < 2; ++n) {
         if (!send[n]) continue;
         // my lowest planes fill the lower neighbour's UPPER ghost planes [G + nzl_n, ...); my highest its upper neighbour's LOWER [G - planes, G)
-        const char *src = mine + (size_t)(n == 0 ? g.G : g.G + g.nzl - planes) * plane_b;
         char *dst = static_cast<char *>(c->peer[n].phi[buf]) + (size_t)(n == 0 ? g.G + c->peer[n].nzl : g.G - planes) * plane_b;
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dst, h.send[n], h.bytes, hipMemcpyDeviceToDevice, s));
         post.set_word[n] = c->peer[n].flags + (PEER_WORD_ARRIVED + (1 - n)) * WAFER_F3_SYNC_STRIDE;   // "copy number k has landed"
         post.set_value[n] = ++c->cp_sent[n];
     }

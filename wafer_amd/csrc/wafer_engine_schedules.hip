@@ -458,29 +458,45 @@ int excited_step_launch(wafer_ctx *c, int src, int dst, uint32_t wnum, bool tran
     return reduce_to_scal(c, 1 + (int)wnum, nb, 0, s);
 }
 
-// z-slabs: the R boundary planes of each side first, on the second stream, their (raw) halo exchange
-// behind the interior launch; the sums wait for all three launches
-int excited_step_launch_overlapped(wafer_ctx *c, int src, int dst, uint32_t wnum, bool transform_on_load)
+// The boundary-first split of a slab pass, `depth` planes deep.  Second stream: the boundary planes of every side that has a
+// neighbour, then their exchange.  Main stream: the interior, released by an event recorded after the boundary kernels.  The
+// exchange is enqueued BEFORE the interior launch and needs no event hop, so its kernels reach the CUs first; the interior then
+// fills what is left.  (Without the dependency the interior started first, filled every CU for a whole round, and the boundary
+// kernels -- and the exchange behind them -- finished only with the pass; with the exchange merely enqueued second, RCCL's
+// workgroups waited 0.35 ms for CUs: profiles/r01_slab_overlap_timeline.txt.)
+// launch(zlo, zhi, stream, interior) is called for the lower boundary, the upper boundary and the interior, in this order.
+template <typename Launch>
+static int boundary_first(wafer_ctx *c, int dst, int depth, Launch &&launch)
 {
-    const WaferGeom &g = c->g;
-    const int R = g.R, lo = g.G, hi = g.G + g.nzl;
-    long long nb_lo = 0, nb_hi = 0, nb_in = 0;
-    const hipStream_t sb = c->s_aux;
+    const int lo = c->g.G, hi = c->g.G + c->g.nzl;
     HIP_TRY(hipEventRecord(c->ev_fork, c->s_main));
     HIP_TRY(hipStreamWaitEvent(c->s_aux, c->ev_fork, 0));
-    if (c->has_lo()) TRY(excited_stencil_launch(c, src, dst, wnum, transform_on_load, lo, lo + R, 0, sb, &nb_lo));
-    if (c->has_hi()) TRY(excited_stencil_launch(c, src, dst, wnum, transform_on_load, hi - R, hi, nb_lo, sb, &nb_hi));
-    HIP_TRY(hipEventRecord(c->ev_bdry, sb));
-    TRY(exchange_halo(c, dst, c->s_aux, R));        // enqueued before the interior: its kernels reach the CUs first
+    if (c->has_lo()) TRY(launch(lo, lo + depth, c->s_aux, false));
+    if (c->has_hi()) TRY(launch(hi - depth, hi, c->s_aux, false));
+    HIP_TRY(hipEventRecord(c->ev_bdry, c->s_aux));
+    TRY(exchange_halo(c, dst, c->s_aux, depth));
     HIP_TRY(hipEventRecord(c->ev_join, c->s_aux));
     HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_bdry, 0));
-    // (one long workgroup per tile here: shorter ones -- the fused ground-state split's answer to CUs
+    TRY(launch(c->has_lo() ? lo + depth : lo, c->has_hi() ? hi - depth : hi, c->s_main, true));
+    HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_join, 0));
+    return WAFER_OK;
+}
+
+// z-slabs: the R boundary planes of each side first, their (raw) halo exchange behind the interior launch; the three launches'
+// partials lie one behind the other, and the sums wait for all of them
+int excited_step_launch_overlapped(wafer_ctx *c, int src, int dst, uint32_t wnum, bool transform_on_load)
+{
+    long long nb_all = 0;
+    // (one long workgroup per tile in the interior too: shorter ones -- the fused ground-state split's answer to CUs
     //  held by the exchange -- cost this kernel more in pipeline refills than the tail they avoid:
     //  k = 1 0.98 vs 1.01 ms, k = 3 1.57 vs 1.53 under an 8-channel RCCL kernel)
-    TRY(excited_stencil_launch(c, src, dst, wnum, transform_on_load, c->has_lo() ? lo + R : lo, c->has_hi() ? hi - R : hi,
-                               nb_lo + nb_hi, c->s_main, &nb_in));
-    HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_join, 0));
-    return reduce_to_scal(c, 1 + (int)wnum, nb_lo + nb_hi + nb_in, 0, c->s_main);
+    TRY(boundary_first(c, dst, c->g.R, [&](int zlo, int zhi, hipStream_t st, bool) {
+        long long nb = 0;
+        TRY(excited_stencil_launch(c, src, dst, wnum, transform_on_load, zlo, zhi, nb_all, st, &nb));
+        nb_all += nb;
+        return (int)WAFER_OK;
+    }));
+    return reduce_to_scal(c, 1 + (int)wnum, nb_all, 0, c->s_main);
 }
 
 // ---- two excited-state steps per pass (wafer_stencil_x2.hip.h) ------------------------------------------------------
@@ -600,9 +616,7 @@ int x2_run(wafer_ctx *c, uint32_t wnum, uint64_t pairs, hipStream_t s)
     if (wafer_entry_x2_apply(type_combo(c, false), g, g.G, g.G + g.nzl, k, c->phi[c->cur], l, m, c->x2coef, c->partials, c->partials_stride, c->num_cus, s, &nap) != hipSuccess)
         return fail(WAFER_ERR_HIP, "apply launch failed");
     TRY(reduce_to_scal(c, 1, nap, X2_SUM_SLOT, s));
-    TRY(launch_normalise(c, c->cur, c->scal + X2_SUM_SLOT, 0.0, nullptr, 0, s));
-    c->halo_valid = 0;
-    return WAFER_OK;
+    return launch_normalise(c, c->cur, c->scal + X2_SUM_SLOT, 0.0, nullptr, 0, s);   // (no ghost plane of phi is current now: wafer_passes.h)
 }
 
 int excited_apply(wafer_ctx *c, int buf, uint32_t wnum, hipStream_t s)
@@ -630,6 +644,161 @@ int excited_apply(wafer_ctx *c, int buf, uint32_t wnum, hipStream_t s)
 }
 
 
+// ---- the passes of wafer_evolve (which one comes next: wafer_passes.h) ------------------------------------------------------
+static WaferPassFacts pass_facts(const wafer_ctx *c, uint32_t wnum, bool x2)
+{
+    WaferPassFacts f;
+    f.wnum = wnum;
+    // more than one step per pass where nothing happens between steps (ground state) and, when the grid is sharded, the slab
+    // carries the ghost planes
+    f.fuse2 = fuse2_applies(c);
+    f.fuse3 = fuse3_applies(c);
+    f.R = c->g.R;
+    f.G = c->g.G;
+    f.halo_cycle = c->halo_cycle;
+    f.sched = c->sched;
+    f.decomposed = c->sharded();
+    f.x2 = x2;
+    f.one_pass = c->tune.one_pass != 0;
+    f.excited_fused = wnum <= WAFER_MAX_LOW && active_variant(c) >= 1;
+    return f;
+}
+
+// Single-launch passes in flight: their last exchanges have not been waited for by the main stream.
+struct SingleLaunch {
+    bool active = false, peer = false;
+    int depth = 0;
+    int drain(wafer_ctx *c)
+    {
+        if (!active) return WAFER_OK;
+        if (peer) {
+            TRY(peer_drain(c));
+        } else {
+            HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_ex[0], 0));
+            HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_ex[1], 0));
+        }
+        active = false;
+        c->halo_valid = depth;
+        return WAFER_OK;
+    }
+};
+
+// schedules 2 and 3: the whole slab in one launch (every rank takes this pass or none: wafer_passes.h)
+static int launch_single(wafer_ctx *c, const WaferPass &p, int src, int dst, SingleLaunch &hv)
+{
+    const bool peer = p.kind == WAFER_PASS_PEER;
+    if (!hv.active) {
+        TRY(ensure_hv(c));
+        // the first pass's ghost planes: a plain exchange in stream order.  (Peer mode: always, also when they are
+        // current -- the collective is the rendezvous that keeps a rank from storing into a neighbour's buffers while
+        // that neighbour is still busy with whatever preceded this call.)
+        // (stream order suffices: my first pass follows my exchange, which completes only when the neighbour's stream has
+        //  reached its own)
+        if (p.rendezvous) c->halo_valid = 0;
+        TRY(ensure_halo(c, p.need));
+        hv.active = true;
+        hv.peer = peer;
+        hv.depth = p.exchange;
+    }
+    return peer ? launch_peer_pass(c, src, dst, p.exchange) : launch_halves_pass(c, src, dst, p.exchange);
+}
+
+// A pass over the owned planes and the exchange of its `depth` boundary planes.  Whether the pass is split is LOCAL (the slab's
+// thickness): nothing the ranks share may depend on it, and both forms call the halo hook once.
+template <typename Launch>
+static int pass_and_exchange(wafer_ctx *c, int dst, int depth, Launch &&launch)
+{
+    if (c->sharded() && c->sched != 0 && c->g.nzl > 2 * depth) return boundary_first(c, dst, depth, launch);
+    TRY(launch(c->g.G, c->g.G + c->g.nzl, c->s_main, false));
+    return exchange_halo(c, dst, c->s_main, depth);
+}
+
+static int launch_fused(wafer_ctx *c, const WaferPass &p, int src, int dst)
+{
+    const int lo = c->g.G, hi = c->g.G + c->g.nzl;
+    // The interior launch of a split pass goes with a short tail.  The exchange's kernels hold a few CUs for as long as the links
+    // need (RCCL's workgroups cannot share a CU with a stencil workgroup).  With one long workgroup per tile every
+    // displaced workgroup would add a whole extra round at the end of the pass (measured with
+    // an 8-channel RCCL kernel of realistic length: 0.465 ms/step, worse than no overlap).
+    // Cutting EVERY tile into four workgroups fixes that at 3 planes of pipeline fill per
+    // workgroup (0.396); cutting only the last 1/16 of the tiles -- dispatched last, they
+    // fill the holes -- keeps the long workgroups' efficiency.
+    auto launch = [&](int zlo, int zhi, hipStream_t st, bool short_tail) {
+        return p.steps == 3 ? launch_step3(c, src, dst, zlo, zhi, st, short_tail) : launch_step2(c, src, dst, zlo, zhi, st, short_tail);
+    };
+    TRY(ensure_halo(c, p.need));
+    // deep halos: unsplit, over the ghost planes that are still good for one more pass as well; no exchange
+    if (p.extend) return launch(c->has_lo() ? lo - p.extend : lo, c->has_hi() ? hi + p.extend : hi, c->s_main, false);
+    return pass_and_exchange(c, dst, p.exchange, launch);
+}
+
+static int launch_ground_step(wafer_ctx *c, const WaferPass &p, int src, int dst)
+{
+    TRY(ensure_halo(c, p.need));
+    return pass_and_exchange(c, dst, p.exchange, [&](int zlo, int zhi, hipStream_t st, bool) { return launch_step(c, src, dst, zlo, zhi, false, st); });
+}
+
+// One pass per step: the raw result travels to the next step, which normalises and projects it on load; phi is materialised once
+// after the last step.  (WAFER_ONE_PASS=0: every step materialises phi.)
+static int launch_excited(wafer_ctx *c, const WaferPass &p, int src, int dst, uint32_t wnum)
+{
+    const WaferGeom &g = c->g;
+    const bool one_pass = c->tune.one_pass != 0;
+    TRY(ensure_halo(c, p.need));
+    if (one_pass && p.first) {
+        hipLaunchKernelGGL(wafer_k_identity_scalars, dim3(1), dim3(64), 0, c->s_main, c->scal, 1 + (int)wnum);
+        HIP_TRY(hipGetLastError());
+    }
+    // z-slabs, one-pass scheme, not the last step: the raw result's halo exchange hides behind
+    // the interior launch (the last step's phi is materialised first and exchanged on demand)
+    // (only when asked for by mode 1.  One plane per side and step is a short exchange, and its kernels take CUs
+    //  from an interior launch that packs the CUs exactly: the interior ends later by about the exchange's own
+    //  duration, and the two thin boundary launches come on top -- bench slab, native RCCL to the same rank,
+    //  k = 1: 0.772 ms/step split against 0.718 unsplit (undecomposed 0.643); k = 3: 1.210 against 1.121 (1.033).)
+    // The split depends on the LOCAL slab thickness (slab.partition hands out uneven slabs: 3, 2, 2, 2 planes of 9), so
+    // both branches call the hooks in the SAME ORDER -- the halo exchange first, the all-reduce of the sums second --
+    // or ranks that took different branches would queue a send / receive and a collective on one communicator in
+    // different orders and wait for each other for ever (found by tests/fuzz_slabs.py, round 5, with the in-process
+    // fabric; RCCL would have hung).
+    if (one_pass && !p.last) {
+        if (c->sharded() && c->sched == 1 && g.nzl > 2 * g.R) return excited_step_launch_overlapped(c, src, dst, wnum, one_pass);
+        long long nb = 0;
+        TRY(excited_stencil_launch(c, src, dst, wnum, one_pass, g.G, g.G + g.nzl, 0, c->s_main, &nb));
+        TRY(exchange_halo(c, dst, c->s_main, g.R));                       // the raw result's planes (stream order: behind the launch)
+        return reduce_to_scal(c, 1 + (int)wnum, nb, 0, c->s_main);
+    }
+    TRY(excited_step_launch(c, src, dst, wnum, one_pass, c->s_main));
+    TRY(excited_apply(c, dst, wnum, c->s_main));
+    return one_pass ? WAFER_OK : exchange_halo(c, dst, c->s_main, g.R);   // (the last one-pass step: its planes travel on demand)
+}
+
+// step + sum phi'^2 (grid.rs:675-678), normalise (:679), Gram-Schmidt (:680) as row operations: more stored states than the
+// fused-overlap kernel carries, or the direct kernel
+static int launch_excited_rows(wafer_ctx *c, const WaferPass &p, int src, int dst, uint32_t wnum)
+{
+    const int lo = c->g.G, hi = c->g.G + c->g.nzl;
+    TRY(ensure_halo(c, p.need));
+    TRY(launch_step(c, src, dst, lo, hi, true, c->s_main));
+    TRY(reduce_to_scal(c, 1, step_partials_count(c, lo, hi), 0, c->s_main));
+    TRY(launch_normalise(c, dst, c->scal + 0, 0.0, c->states[0], 1, c->s_main));
+    TRY(gs_chain(c, dst, wnum, true, c->s_main));
+    return exchange_halo(c, dst, c->s_main, c->g.R);
+}
+
+static int launch_pass(wafer_ctx *c, const WaferPass &p, uint32_t wnum, SingleLaunch &hv)
+{
+    const int src = c->cur, dst = c->cur ^ 1;
+    switch (p.kind) {
+    case WAFER_PASS_HALVES:
+    case WAFER_PASS_PEER: return launch_single(c, p, src, dst, hv);
+    case WAFER_PASS_FUSED: return launch_fused(c, p, src, dst);
+    case WAFER_PASS_STEP: return launch_ground_step(c, p, src, dst);
+    case WAFER_PASS_EXCITED: return launch_excited(c, p, src, dst, wnum);
+    case WAFER_PASS_EXCITED_ROWS: return launch_excited_rows(c, p, src, dst, wnum);
+    default: return x2_run(c, wnum, p.steps / 2, c->s_main);   // WAFER_PASS_X2_TAIL (asks for its two ghost planes itself, behind its coefficient kernel)
+    }
+}
+
 } // namespace wafer_eng
 
 extern "C" {
@@ -642,197 +811,27 @@ int wafer_evolve(wafer_ctx *c, uint32_t wnum, uint64_t n_steps)
     if (wnum + 2 > SCAL_SLOTS) return fail(WAFER_ERR_INVALID, "wnum too large");
     HIP_TRY(hipSetDevice(c->P.device));
     RoctxRange range_(wnum ? "wafer_evolve_excited" : "wafer_evolve_ground");
-    const WaferGeom &g = c->g;
-    const int R = g.R;
-    const int lo = g.G, hi = g.G + g.nzl;
     const uint64_t steps = n_steps == 0 ? 1 : n_steps; // grid.rs:682-685
-    // two steps per pass where nothing happens between steps (ground state) and, when the grid
-    // is sharded, the slab carries 2R ghost planes
-    const bool fuse = wnum == 0 && fuse2_applies(c);
-    const bool fuse3 = wnum == 0 && fuse3_applies(c);
-    // Excited states, two steps per pass: the first two steps (three for an odd count) run one per pass -- whatever the
-    // caller hands over (a clone of a stored state, an un-normalised start) is normalised and projected by the reference's own
-    // sequence before the regrouped sums take over -- then pairs; phi is materialised after the last pass.
+    // Excited states, two steps per pass: a collective decision, and the images of the stored states it needs
     bool x2 = false;
     if (wnum > 0 && steps >= 4) TRY(x2_agree(c, wnum, &x2));
-    const uint64_t x2_head = x2 ? 2 + (steps & 1) : steps;
     if (x2) TRY(ensure_x2(c, wnum));
+    const WaferPassFacts facts = pass_facts(c, wnum, x2);
     HIP_TRY(hipEventRecord(c->ev_start, c->s_main));
-    // single-launch passes in flight: their last exchanges have not been waited for by the main stream
-    bool hv_active = false, hv_peer = false;
-    int hv_depth = 0;
-    auto hv_drain = [&]() -> int {
-        if (!hv_active) return WAFER_OK;
-        if (hv_peer) {
-            TRY(peer_drain(c));
-        } else {
-            HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_ex[0], 0));
-            HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_ex[1], 0));
-        }
-        hv_active = false;
-        c->halo_valid = hv_depth;
-        return WAFER_OK;
-    };
+    SingleLaunch hv;
     for (uint64_t s = 0; s < steps;) {
-        const int src = c->cur, dst = c->cur ^ 1;
-        if ((fuse3 && steps - s >= 3) || (fuse && steps - s >= 2)) {
-            // K time steps per pass: three on the three-step kernel while at least three remain, else two
-            const int K = (fuse3 && steps - s >= 3) ? 3 : 2, H = K * R; // H: ghost planes one pass consumes per side
-            auto launch_pass = [&](int zlo, int zhi, hipStream_t st, bool short_tail) {
-                return K == 3 ? launch_step3(c, src, dst, zlo, zhi, st, short_tail) : launch_step2(c, src, dst, zlo, zhi, st, short_tail);
-            };
-            // Deep halos: with E = H * halo_cycle ghost planes exchanged at once, only every halo_cycle-th
-            // pass needs boundary-first kernels, an exchange and the event hops around them.  The passes in
-            // between run UNSPLIT over the owned planes plus the ghost planes that are still good for one more
-            // pass: each fused pass consumes H planes of validity per side (the neighbour computes the
-            // same cells from the same values, so the bits agree).  E is a whole number of passes' worth and the same
-            // on every rank (the neighbours receive what this one sends).
-            const int E = c->sharded() ? std::max(H, std::min(g.G, H * c->halo_cycle) / H * H) : H;
-            // Mode 2: the whole slab in one launch (three-step passes with one exchange per pass; every rank takes this
-            // branch or none: K, E and H depend on nothing local)
-            if (c->sharded() && (c->sched == 2 || c->sched == 3) && K == 3 && E == H) {
-                const bool peer = c->sched == 3;
-                if (!hv_active) {
-                    TRY(ensure_hv(c));
-                    // the first pass's ghost planes: a plain exchange in stream order.  (Peer mode: always, also when they are
-                    // current -- the collective is the rendezvous that keeps a rank from storing into a neighbour's buffers while
-                    // that neighbour is still busy with whatever preceded this call.)
-                    // (stream order suffices: my first pass follows my exchange, which completes only when the neighbour's stream has
-                    //  reached its own)
-                    if (peer) c->halo_valid = 0;
-                    TRY(ensure_halo(c, E));
-                    hv_active = true;
-                    hv_peer = peer;
-                    hv_depth = E;
-                }
-                if (peer) TRY(launch_peer_pass(c, src, dst, E));
-                else TRY(launch_halves_pass(c, src, dst, E));
-                c->halo_valid = 0;   // (inside the mode; hv_drain restores the invariant)
-                c->cur = dst;
-                s += K;
-                continue;
-            }
-            TRY(hv_drain());
-            if (c->sharded() && c->halo_valid < H) TRY(ensure_halo(c, E));
-            if (c->sharded() && c->halo_valid >= 2 * H) {
-                const int ext = c->halo_valid - H; // ghost planes still valid after this pass
-                TRY(launch_pass(c->has_lo() ? lo - ext : lo, c->has_hi() ? hi + ext : hi, c->s_main, false));
-                c->halo_valid = ext;
-                c->cur = dst;
-                s += K;
-                continue;
-            }
-            const bool split = c->sharded() && c->sched != 0 && g.nzl > 2 * E;
-            if (split) {
-                // Mode 1.  Second stream: boundary planes, then their exchange.  Main stream: the interior, released
-                // by an event recorded after the boundary kernels.  The exchange is enqueued BEFORE the
-                // interior launch and needs no event hop, so its kernels reach the CUs first; the interior
-                // then fills what is left.  (Without the dependency the interior started first, filled
-                // every CU for a whole round, and the boundary kernels -- and the exchange behind them --
-                // finished only with the pass; with the exchange merely enqueued second, RCCL's
-                // workgroups waited 0.35 ms for CUs: profiles/r01_slab_overlap_timeline.txt.)
-                HIP_TRY(hipEventRecord(c->ev_fork, c->s_main));
-                HIP_TRY(hipStreamWaitEvent(c->s_aux, c->ev_fork, 0));
-                if (c->has_lo()) TRY(launch_pass(lo, lo + E, c->s_aux, false));
-                if (c->has_hi()) TRY(launch_pass(hi - E, hi, c->s_aux, false));
-                HIP_TRY(hipEventRecord(c->ev_bdry, c->s_aux));
-                TRY(exchange_halo(c, dst, c->s_aux, E));
-                HIP_TRY(hipEventRecord(c->ev_join, c->s_aux));
-                HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_bdry, 0));
-                // The exchange's kernels hold a few CUs for as long as the links need (RCCL's workgroups
-                // cannot share a CU with a stencil workgroup).  With one long workgroup per tile every
-                // displaced workgroup would add a whole extra round at the end of the pass (measured with
-                // an 8-channel RCCL kernel of realistic length: 0.465 ms/step, worse than no overlap).
-                // Cutting EVERY tile into four workgroups fixes that at 3 planes of pipeline fill per
-                // workgroup (0.396); cutting only the last 1/16 of the tiles -- dispatched last, they
-                // fill the holes -- keeps the long workgroups' efficiency.
-                TRY(launch_pass(c->has_lo() ? lo + E : lo, c->has_hi() ? hi - E : hi, c->s_main, true));
-                HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_join, 0));
-            } else {
-                TRY(launch_pass(lo, hi, c->s_main, false));
-                TRY(exchange_halo(c, dst, c->s_main, E));
-            }
-            c->halo_valid = c->sharded() ? E : H;
-            c->cur = dst;
-            s += K;
+        const WaferPass p = wafer_next_pass(facts, s, steps, c->halo_valid, hv.active);
+        if (p.drain_first) {   // before any other kind of pass; the planner is asked again with the ghost planes the drain leaves
+            TRY(hv.drain(c));
             continue;
         }
-        TRY(hv_drain());
-        TRY(ensure_halo(c, R));
-        if (wnum == 0) {
-            const bool split = c->sharded() && c->sched != 0 && g.nzl > 2 * R;
-            if (split) {
-                // boundary planes and their exchange on the second stream, the interior behind an event (as above)
-                HIP_TRY(hipEventRecord(c->ev_fork, c->s_main));
-                HIP_TRY(hipStreamWaitEvent(c->s_aux, c->ev_fork, 0));
-                if (c->has_lo()) TRY(launch_step(c, src, dst, lo, lo + R, false, c->s_aux));
-                if (c->has_hi()) TRY(launch_step(c, src, dst, hi - R, hi, false, c->s_aux));
-                HIP_TRY(hipEventRecord(c->ev_bdry, c->s_aux));
-                TRY(exchange_halo(c, dst, c->s_aux, R));
-                HIP_TRY(hipEventRecord(c->ev_join, c->s_aux));
-                HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_bdry, 0));
-                TRY(launch_step(c, src, dst, c->has_lo() ? lo + R : lo, c->has_hi() ? hi - R : hi, false, c->s_main));
-                HIP_TRY(hipStreamWaitEvent(c->s_main, c->ev_join, 0));
-            } else {
-                TRY(launch_step(c, src, dst, lo, hi, false, c->s_main));
-                TRY(exchange_halo(c, dst, c->s_main, R));
-            }
-        } else {
-            // step + sum phi'^2 (grid.rs:675-678), normalise (:679), Gram-Schmidt (:680)
-            if (x2 && s == x2_head) {
-                TRY(x2_run(c, wnum, (steps - x2_head) / 2, c->s_main));
-                s = steps;
-                continue;
-            }
-            if (wnum <= WAFER_MAX_LOW && active_variant(c) >= 1) {
-                // one pass per step: the raw result travels to the next step, which normalises and
-                // projects it on load; phi is materialised once after the last step
-                const bool one_pass = c->tune.one_pass != 0;
-                const bool last = s + 1 == steps;   // (never within the head of a two-steps-per-pass run)
-                if (one_pass && s == 0) {
-                    hipLaunchKernelGGL(wafer_k_identity_scalars, dim3(1), dim3(64), 0, c->s_main, c->scal, 1 + (int)wnum);
-                    HIP_TRY(hipGetLastError());
-                }
-                // z-slabs, one-pass scheme, not the last step: the raw result's halo exchange hides behind
-                // the interior launch (the last step's phi is materialised first and exchanged on demand)
-                // (only when asked for by mode 1.  One plane per side and step is a short exchange, and its kernels take CUs
-                //  from an interior launch that packs the CUs exactly: the interior ends later by about the exchange's own
-                //  duration, and the two thin boundary launches come on top -- bench slab, native RCCL to the same rank,
-                //  k = 1: 0.772 ms/step split against 0.718 unsplit (undecomposed 0.643); k = 3: 1.210 against 1.121 (1.033).)
-                // The split depends on the LOCAL slab thickness (slab.partition hands out uneven slabs: 3, 2, 2, 2 planes of 9), so
-                // both branches call the hooks in the SAME ORDER -- the halo exchange first, the all-reduce of the sums second --
-                // or ranks that took different branches would queue a send / receive and a collective on one communicator in
-                // different orders and wait for each other for ever (found by tests/fuzz_slabs.py, round 5, with the in-process
-                // fabric; RCCL would have hung).
-                const bool split = one_pass && !last && c->sharded() && c->sched == 1 && g.nzl > 2 * R;
-                if (split) {
-                    TRY(excited_step_launch_overlapped(c, src, dst, wnum, one_pass));
-                } else if (one_pass && !last) {
-                    long long nb = 0;
-                    TRY(excited_stencil_launch(c, src, dst, wnum, one_pass, g.G, g.G + g.nzl, 0, c->s_main, &nb));
-                    TRY(exchange_halo(c, dst, c->s_main, R));                       // the raw result's planes (stream order: behind the launch)
-                    TRY(reduce_to_scal(c, 1 + (int)wnum, nb, 0, c->s_main));
-                } else {
-                    TRY(excited_step_launch(c, src, dst, wnum, one_pass, c->s_main));
-                    if (!one_pass || last) TRY(excited_apply(c, dst, wnum, c->s_main));
-                    if (!last || !one_pass) TRY(exchange_halo(c, dst, c->s_main, R));
-                }
-                c->halo_valid = (one_pass && last) ? 0 : R;
-                c->cur = dst;
-                s += 1;
-                continue;
-            }
-            TRY(launch_step(c, src, dst, lo, hi, true, c->s_main));
-            TRY(reduce_to_scal(c, 1, step_partials_count(c, lo, hi), 0, c->s_main));
-            TRY(launch_normalise(c, dst, c->scal + 0, 0.0, c->states[0], 1, c->s_main));
-            TRY(gs_chain(c, dst, wnum, true, c->s_main));
-            TRY(exchange_halo(c, dst, c->s_main, R));
-        }
-        c->halo_valid = R;
-        c->cur = dst;
-        s += 1;
+        const int dst = c->cur ^ 1;
+        TRY(launch_pass(c, p, wnum, hv));
+        if (p.kind != WAFER_PASS_X2_TAIL) c->cur = dst;   // (x2_run has moved cur itself, once per pass)
+        c->halo_valid = p.valid_after;
+        s += p.steps;
     }
-    TRY(hv_drain());
+    TRY(hv.drain(c));   // ... and before ev_stop, and before anything that follows this call on the main stream
     HIP_TRY(hipEventRecord(c->ev_stop, c->s_main));
     c->last_steps = steps;
     c->timing_valid = true;
@@ -905,13 +904,18 @@ int wafer_diag_dispatch(wafer_ctx *c, uint32_t wnum, char *buf, size_t n)
         const char *kernel = wafer_stencil_kernel_name(c);
         int tx = 0, ty = 0;
         if (K == 3) wafer_step3_tile(type_combo(c, true), &tx, &ty);
-        // what advances the steps a whole pass does not cover (wafer_evolve: three while three remain, then two, then one)
+        // what advances the steps a whole pass does not cover: the planner's answers with two steps left and with one
         const char *single = active_variant(c) == 0 ? "wafer_k_step_direct" : "wafer_k_step_lds";
-        const char *two = (fuse2_applies(c) && K == 3) ? "wafer_k_step2_fused" : nullptr;
+        const WaferPassFacts facts = pass_facts(c, 0, false);
+        const char *rem[2] = {nullptr, nullptr};
+        for (int left = K - 1, n = 0; left >= 1; --left) {
+            const char *name = wafer_next_pass(facts, 0, (uint64_t)left, 0, false).kind == WAFER_PASS_FUSED ? "wafer_k_step2_fused" : single;
+            if (n == 0 || strcmp(rem[n - 1], name) != 0) rem[n++] = name;
+        }
         char tile[32] = "";
         if (tx) snprintf(tile, sizeof tile, " tile=%dx%d", tx, ty);
         snprintf(buf, n, "wnum=0 stencil=%d dtype=%s kernel=%s steps_per_pass=%d ghost_planes_per_pass=%d%s v=%s remainder=%s%s%s", R, dtype, kernel, K, K * R,
-                 tile, "streamed", K >= 2 ? (two ? two : single) : "-", (K == 3 && two) ? "," : "", (K == 3 && two) ? single : "");
+                 tile, "streamed", rem[0] ? rem[0] : "-", rem[1] ? "," : "", rem[1] ? rem[1] : "");
         return WAFER_OK;
     }
     const int vg = closed_form_vg(c);
