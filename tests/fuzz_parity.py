@@ -2,13 +2,14 @@
 """Randomised parity sweep of the HIP path against the oracle (a development aid next to the
 fixed cases of tests/test_gpu_parity.py): random shapes incl. 1-cell axes, stencil orders,
 potentials, step counts and kernel variants; ground state bit for bit, excited states (random
-stored states, Gram-Schmidt every step) to 1e-10; on fp32 storage (one and two steps per pass) to the fp32-storage bar.   N=200 SEED=3 python tests/fuzz_parity.py   (it lives under tests/ because it drives the oracle)"""
+stored states, Gram-Schmidt every step) to 1e-10; the ground state on fp32 storage bit for bit against tests/fp32_reference.py; excited states on fp32 storage (one and two steps per pass) to the fp32-storage bar.   N=200 SEED=3 python tests/fuzz_parity.py   (it lives under tests/ because it drives the oracle)"""
 import os, sys, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import wafer_amd as wa
 from oracle import wafer_oracle as wo
 from gpu_common import make_pair, random_phi
+import fp32_reference as ref
 wo.set_threads(8)
 rng = np.random.default_rng(int(os.environ.get("SEED", "1")))
 bad = 0
@@ -50,10 +51,15 @@ for it in range(int(os.environ.get("N", "60"))):
     except Exception as e:
         bad += 1
         print("ERROR", shape, ext, pot, steps, variant, repr(e)[:200], flush=True)
-# fp32 storage (fp64 or fp32 step arithmetic): no oracle to the bit, but every kernel family must give the single-step kernel's bits --
-# the three-step kernel (float in HBM, double in the CU), the FivePoint two-step kernel on 128 x 16 tiles, the two-step kernel
+# fp32 storage (fp64 or fp32 step arithmetic): every kernel family must give the single-step kernel's bits -- the three-step kernel (float in
+# HBM, double in the CU), the FivePoint two-step kernel on 128 x 16 tiles, the two-step kernel -- AND every run the bits of tests/fp32_reference.py
+# evolved from the state and the potential the device holds (SevenPoint: the LDS kernel and the direct kernel, which streams the stored a, b)
+rng_ext = np.random.default_rng(7000 + int(os.environ.get("SEED", "1")))   # (a stream of its own: the draws of `rng` stay what they were)
+compared = 0
 for it in range(int(os.environ.get("N", "60")) // 3):
-    ext = int(rng.integers(1, 3))
+    ext0 = ext = int(rng.integers(1, 3))
+    if rng_ext.random() < 0.3:
+        ext = 3
     shape = (int(rng.choice([64, 128, 130, 200, 256, 257, 300, 512])), int(rng.choice([1, 8, 16, 17, 32, 37, 48])), int(rng.integers(1, 30)))
     dtype = str(rng.choice(["f32", "f32fast"]))
     steps = int(rng.integers(1, 12))
@@ -62,20 +68,34 @@ for it in range(int(os.environ.get("N", "60")) // 3):
     os.environ["WAFER_F2_WIDE"] = "1"
     got = {}
     try:
-        for variant in (3 if ext == 1 else 2, 1):
+        cfg = wo.Config(*shape, ext=ext, potential=pot, dn=0.2, dt=0.004, mass=1.3, sig=0.3)
+        for variant in ({1: 3, 2: 2, 3: 0}[ext], 1):
             os.environ["WAFER_ZCHUNK"] = str(rng.choice([0, 1, 2, 3, 5])) if variant != 1 else "0"
-            os.environ["WAFER_F3_PLAIN_DOWN"] = str(rng.choice([0, 1])) if variant == 3 else "0"
+            os.environ["WAFER_F3_PLAIN_DOWN"] = str(rng.choice([0, 1])) if variant != 1 and ext0 == 1 else "0"
             with wa.Context(wa.Params(*shape, dn=0.2, dt=0.004, mass=1.3, sig=0.3, central_difference=ext, dtype=dtype)) as ctx:
                 ctx.set_stencil_variant(variant)
-                ctx.set_potential(pot); ctx.set_initial_condition("Gaussian", seed=it + 1); ctx.evolve(0, steps)
+                ctx.set_potential(pot); ctx.set_initial_condition("Gaussian", seed=it + 1)
+                start, v = ctx.download_phi(), ctx.download_array("v")
+                ctx.evolve(0, steps)
                 got[variant] = ctx.download_phi()
+            want, div = ref.evolve(wo, cfg, v, start, [steps], dtype, "stored" if variant == 0 else "registers")
+            # (f32fast: the model is the kernels' to the bit where the planned division is the IEEE one, |x / den| >= 2^-100)
+            if div is None or (2.0 ** -100 <= min(div.x_min, div.q_min) and max(div.x_max, div.q_max) < 2.0 ** 101):
+                compared += 1
+                msg = ref.describe_mismatch(got[variant], want[steps], ext)
+                if msg:
+                    bad += 1
+                    print("MISMATCH fp32 storage against the reference", shape, ext, dtype, pot, steps, variant, msg, flush=True)
+            else:
+                print("fp32 storage: outside the planned division's range, not compared", shape, ext, dtype, pot, steps, div, flush=True)
         a_, b_ = got.values()
-        if not np.array_equal(a_, b_, equal_nan=True):
+        if ext != 3 and not np.array_equal(a_, b_, equal_nan=True):
             bad += 1
             print("MISMATCH fp32 storage", shape, ext, dtype, pot, steps, float(np.max(np.abs(a_ - b_))), flush=True)
     except Exception as e:
         bad += 1
         print("ERROR fp32 storage", shape, ext, dtype, pot, steps, repr(e)[:200], flush=True)
+print("fp32 storage: runs compared with the reference =", compared, flush=True)
 # excited states: normalise + modified Gram-Schmidt after every step (grid.rs:674-681)
 for it in range(int(os.environ.get("N", "60")) // 2):
     ext = int(rng.integers(1, 4))

@@ -1001,9 +1001,10 @@ def test_two_excited_steps_per_pass_vs_oracle(wo, wa, wnum, potential, steps, mo
 @pytest.mark.parametrize("wnum", [1, 2, 3])
 def test_two_excited_steps_per_pass_on_fp32_storage(wo, wa, wnum, dtype, monkeypatch):
     """round 6: wafer_k_xstep2 on the storage tag of the three-step kernel (dtype f32, and f32fast, whose excited-state steps compute
-    in fp64 too): the raw pass result, V, the stored states and their images are float in HBM, queues / LDS / sums double.  No
-    bit-level reference exists for it (the regrouped sums differ from the one-step kernel's by construction, and every pass rounds
-    what it stores to float): held to the fp32-storage bar -- per cell within 3e-6 of the largest value of the fp64 ORACLE's state
+    in fp64 too): the raw pass result, V, the stored states and their images are float in HBM, queues / LDS / sums double.  The
+    GROUND-state steps on this storage have a bit-level reference (tests/test_gpu_fp32_reference.py); these excited-state passes do
+    not (the regrouped sums differ from the one-step kernel's by construction, and every pass rounds what it stores to float):
+    held to the fp32-storage bar -- per cell within 3e-6 of the largest value of the fp64 ORACLE's state
     after 12 steps, and no further from it than the one-step fp32-storage kernels are; ragged tiles, whole tiles, a grid smaller
     than a tile, every stored-state count; norm to 1e-5."""
     monkeypatch.setenv("WAFER_X2_MAX_K", "3")
@@ -1350,10 +1351,11 @@ def test_f32_path_tracks_f64(wo, wa):
 @pytest.mark.parametrize("ext", [1, 2])
 @pytest.mark.parametrize("dtype", ["f32", "f32fast"])
 def test_f32_storage_every_kernel_gives_the_same_bits(wa, dtype, ext):
-    """fp32 storage is not a bit-for-bit path against the fp64 oracle, but it must not depend on WHICH kernel advances the
-    steps: the fused two-step kernel against the single-step kernel, every cell's bits (round 3: the fused kernel used to
-    hand its second step fp32-rounded a, b).  (The plain kernel, variant 0, streams the STORED a, b arrays -- fp32 like every
-    stored array -- and is a different, equally legitimate reading of "fp32 storage"; it is not part of this comparison.)"""
+    """fp32 storage must not depend on WHICH kernel advances the steps: the fused two-step kernel against the single-step
+    kernel, every cell's bits (round 3: the fused kernel used to hand its second step fp32-rounded a, b).  (The plain kernel,
+    variant 0, streams the STORED a, b arrays -- fp32 like every stored array -- and is a different, equally legitimate reading
+    of "fp32 storage"; it is not part of this comparison.)  Kernel against kernel only: what the bits have to BE -- the oracle's
+    with V and every step's result rounded to float, for either reading of a, b -- is held by tests/test_gpu_fp32_reference.py."""
     shape = (200, 37, 29)
     out = {}
     for variant in (2, 1):
