@@ -219,6 +219,10 @@ extern "C" {
     ) -> c_int;
     pub fn wafer_batch_last_evolve_ms(b: *mut wafer_batch, ms: *mut f32, steps: *mut u64) -> c_int;
     pub fn wafer_batch_kernel_name(b: *mut wafer_batch) -> *const c_char;
+    pub fn wafer_batch_steps_per_launch(b: *mut wafer_batch) -> c_int;
+    pub fn wafer_batch_set_step_variant(b: *mut wafer_batch, variant: c_int) -> c_int;
+    pub fn wafer_batch_diag_dispatch(b: *mut wafer_batch, buf: *mut c_char, n: usize) -> c_int;
+    pub fn wafer_batch_diag_passes(b: *mut wafer_batch, fused_passes: *mut u64, single_steps: *mut u64) -> c_int;
     // batched excited states: per-member state stores and the normalise / Gram-Schmidt tail of every step
     pub fn wafer_batch_load_state(b: *mut wafer_batch, member: u32, idx: u32, state: *const f64) -> c_int;
     pub fn wafer_batch_download_state(b: *mut wafer_batch, member: u32, idx: u32, out: *mut f64) -> c_int;

@@ -430,7 +430,9 @@ int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
  * A batch holds B independent ground-state problems ("members") on one device, all with the same work-area shape, the same
  * central_difference and dtype WAFER_F64, each with its own dn, dt, mass, sig, flags, potential, pot_sub and wavefunction.  One
  * launch per step advances every ACTIVE member (a workgroup table built from the active members only: a member that is not
- * active costs nothing); observables are one launch, one reduce launch and one small download for all members.  Every member
+ * active costs nothing) -- or one launch per PASS of K ground-state steps where a fused pass is selected
+ * (wafer_batch_set_step_variant; ThreePoint K = 3, FivePoint K = 2, the intermediate steps never leave the CU, the same bits);
+ * observables are one launch, one reduce launch and one small download for all members.  Every member
  * computes bit for bit what a single wafer_ctx with its wafer_params computes: phi after evolve, the observables (the single
  * context's partition and reduction order), normalisation and solve.  No z-slabs (z_count must be 0).  Excited states: the
  * wafer_batch_*_state calls further down.
@@ -463,8 +465,18 @@ int wafer_batch_solve(wafer_batch *b, double tolerance, uint64_t screen_update, 
                       wafer_observables_output *finals, int *status);
 /* HIP-event time of the step launches of the last wafer_batch_evolve and its step count (blocks until they finish) */
 int wafer_batch_last_evolve_ms(wafer_batch *b, float *ms, uint64_t *steps);
-/* the kernel a batched step launches: wafer_k_batch_step */
+/* the one-step kernel of a batched step; the pass kernel: wafer_batch_diag_dispatch */
 const char *wafer_batch_kernel_name(wafer_batch *b);
+/* K of the pass a ground-state evolve of at least K steps launches (1: the one-step kernel) */
+int wafer_batch_steps_per_launch(wafer_batch *b);
+/* -1: default dispatch; 0: one step per launch; 1: fused passes of K steps wherever an instantiation exists (a call's
+ * remainder runs as shorter passes and single steps).  Every variant computes the same bits. */
+int wafer_batch_set_step_variant(wafer_batch *b, int variant);
+/* one line of key=value pairs -- stencil= kernel= steps_per_pass= tile= lds_bytes= remainder= variant= -- from the launch path's
+ * own predicates; launches nothing */
+int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n);
+/* launches since creation: fused passes (more than one step each) and one-step launches */
+int wafer_batch_diag_passes(wafer_batch *b, uint64_t *fused_passes, uint64_t *single_steps);
 
 /* ---- batched excited states ------------------------------------------------
  * Every member has a state store (w_store) of its own, of capacity its wafer_params.max_states, on the device: slot l of all

@@ -11,15 +11,17 @@ dt) advanced by one wafer_batch_evolve, by B Contexts one after another from one
 gups: grid-point updates per second (members x work cells x steps / time), 1e9.
 --wnum K: excited-state steps instead -- every member gets an orthonormal store of K states (seeded random, orthonormalised on
 the host), the batch runs evolve(steps, wnum=K), the contexts evolve(K, steps); the same columns and clocks plus "wnum", and
-parity becomes max |batch - context| <= 1e-13 over member 0's cells, the value itself in "parity_max_abs"."""
+parity becomes max |batch - context| <= 1e-13 over member 0's cells, the value itself in "parity_max_abs".
+--variant V: Batch.set_step_variant(V) before the first step (-1 default dispatch, 0 one step per launch, 1 fused passes); the
+row records "variant", "steps_per_launch", the dispatch line and the launch counts of the timed call."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import wafer_amd
 
 
-def members(n, B):
-    return [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0) for k in range(B)]
+def members(n, B, ext=1):
+    return [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext) for k in range(B)]
 
 
 def store(par, wnum, seed=0):
@@ -35,10 +37,10 @@ def store(par, wnum, seed=0):
     return out
 
 
-def row(n, B, steps, warmup, only_batch=False, wnum=0):
-    pars = members(n, B)
+def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1):
+    pars = members(n, B, ext)
     cells = n ** 3
-    out = {"shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "stencil": "ThreePoint", "dtype": "f64",
+    out = {"shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": "f64",
            "potential": "Harmonic"}
     if wnum:
         out["wnum"] = wnum
@@ -49,8 +51,11 @@ def row(n, B, steps, warmup, only_batch=False, wnum=0):
             b.set_initial_condition(k, "Gaussian")
             for i in range(wnum):
                 b.load_state(k, i, stores[k % len(stores)][i])
+        b.set_step_variant(variant)
+        out["variant"], out["steps_per_launch"], out["dispatch"] = variant, b.steps_per_launch(), b.dispatch()
         b.evolve(warmup, wnum=wnum)
         b.last_evolve_ms()   # (waits for the warm-up)
+        p0 = b.passes()
         t0 = time.perf_counter()
         b.evolve(steps, wnum=wnum)
         ms, st = b.last_evolve_ms()   # blocks until the last step has finished
@@ -58,6 +63,7 @@ def row(n, B, steps, warmup, only_batch=False, wnum=0):
         out["batch_host_us_per_step"] = 1e6 * t / steps
         out["batch_host_gups"] = B * cells * steps / t / 1e9
         out["kernel"] = b.kernel_name()
+        out["fused_passes"], out["single_steps"] = [x - y for x, y in zip(b.passes(), p0)]
         out["batch_us_per_step"] = 1e3 * ms / st
         out["batch_gups"] = B * cells * st / (ms * 1e-3) / 1e9
         if only_batch:
@@ -121,10 +127,12 @@ def main():
     ap.add_argument("--out", help="also append the lines to this file")
     ap.add_argument("--only-batch", action="store_true", help="the batch alone, no contexts (counter runs)")
     ap.add_argument("--wnum", type=int, default=0, help="excited-state steps against K stored states per member (default 0: ground state)")
+    ap.add_argument("--ext", type=int, choices=[1, 2, 3], default=1, help="central difference: 1 ThreePoint (default), 2 FivePoint, 3 SevenPoint")
+    ap.add_argument("--variant", type=int, choices=[-1, 0, 1], default=-1, help="Batch.set_step_variant: -1 default dispatch, 0 one step per launch, 1 fused passes")
     a = ap.parse_args()
     for n in a.sizes:
         for B in a.batch:
-            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum).items()})
+            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum, a.variant, a.ext).items()})
             print(line, flush=True)
             if a.out:
                 with open(a.out, "a") as f:

@@ -1,0 +1,130 @@
+// wafer_batch_plan.h -- the host-side plan of a batched ground-state evolve (wafer_engine_batch.hip): which passes a call of
+// `steps` steps launches, and the workgroup table of the fused K-step pass (wafer_k_batch_stepk, wafer_stencil_batch.hip.h).
+// Plain C++ with no HIP in it, so the host compiler and the sanitizers can run it (tests/test_batch_plan.py).
+#pragma once
+#include <stdint.h>
+#include <vector>
+#if !defined(__HIPCC__) && !defined(__host__)   // wafer_geom.h marks its accessors for both sides; the host compiler has neither word
+#define __host__
+#define __device__
+#endif
+#include "wafer_geom.h"
+
+// one workgroup of a batched step: tile (x0, y0) of work cells, local planes [z0, z1) of member `member`
+struct WaferBatchBlock {
+    int member, x0, y0, z0, z1, pad;
+};
+
+// the fused pass's tile of work cells: 64 columns (one wave across x) by 12 rows
+#define WAFER_BATCHK_TX 64
+#define WAFER_BATCHK_TY 12
+
+// The fused pass's cell order.  Level k of a K-step pass is needed on the tile grown by (K-k) R cells on every side; the cells of
+// the largest region (level 0: the tile grown by K R) are numbered so that EVERY level's region is a prefix: first the tile
+// row by row, then ring after ring outwards (each R cells thick: R rows above, R rows below, then R columns left and right
+// of the rows between).  Cell c -> its position (lx, ly) in the level-0 region, a (TX + 2 K R) x (TY + 2 K R) layout.
+__host__ __device__ inline void wafer_batchk_cell(int R, int K, int c, int &lx, int &ly)
+{
+    const int TX = WAFER_BATCHK_TX, TY = WAFER_BATCHK_TY, H = K * R;
+    lx = H + (c % TX);
+    ly = H + (c / TX);
+    if (c < TX * TY) return;
+    for (int j = K - 1; j >= 0; --j) {   // the ring that makes level j's region out of level j+1's
+        const int mj = (K - j) * R, Wj = TX + 2 * mj, Hj = TY + 2 * mj, inner = (Wj - 2 * R) * (Hj - 2 * R);
+        if (c >= Wj * Hj) continue;
+        int i = c - inner;
+        const int o = H - mj;
+        if (i < 2 * R * Wj) {
+            const int row = i / Wj, col = i % Wj;
+            lx = o + col;
+            ly = o + (row < R ? row : Hj - 2 * R + row);
+        } else {
+            i -= 2 * R * Wj;
+            const int row = i / (2 * R), k = i % (2 * R);
+            lx = o + (k < R ? k : Wj - 2 * R + k);
+            ly = o + R + row;
+        }
+        return;
+    }
+}
+
+// ---- pass sequence ---------------------------------------------------------------------------------------------------------
+// The next launch of a call with `remaining` > 0 steps to go advances this many steps: K while at least K remain (K > 1: the
+// fused pass), then one two-step pass if that instantiation exists (have2) and two remain, then single steps.  Never 0, never
+// more than `remaining`.
+static inline int wafer_batch_next_pass(uint64_t remaining, int K, bool have2)
+{
+    if (K > 1 && remaining >= (uint64_t)K) return K;
+    if (have2 && remaining >= 2) return 2;
+    return 1;
+}
+
+// steps of every launch of a call of n_steps steps (a call of 0 steps takes one: grid.rs:682-685)
+static inline std::vector<int> wafer_batch_pass_sequence(uint64_t n_steps, int K, bool have2)
+{
+    std::vector<int> seq;
+    uint64_t left = n_steps == 0 ? 1 : n_steps;
+    while (left > 0) {
+        const int k = wafer_batch_next_pass(left, K, have2);
+        seq.push_back(k);
+        left -= (uint64_t)k;
+    }
+    return seq;
+}
+
+// launches of that call, in closed form: the source buffer flips once per launch, so every active member's `cur` flips iff
+// this is odd.  fused (may be null): how many of them advance more than one step.
+static inline uint64_t wafer_batch_launch_count(uint64_t n_steps, int K, bool have2, uint64_t *fused)
+{
+    const uint64_t steps = n_steps == 0 ? 1 : n_steps;
+    uint64_t nf = K > 1 ? steps / (uint64_t)K : 0;
+    uint64_t rem = K > 1 ? steps % (uint64_t)K : steps;
+    uint64_t n = nf;
+    if (have2) {   // (K == 2: rem < 2 here; K == 1: every pair of steps is a two-step pass)
+        nf += rem / 2;
+        n += rem / 2;
+        rem %= 2;
+    }
+    if (fused) *fused = nf;
+    return n + rem;
+}
+
+// ---- the fused pass's workgroup table --------------------------------------------------------------------------------------
+// The number of z-chunks.  A chunk of L planes computes K L + R K (K-1) level-planes for K L useful ones, so the recomputed share
+// is R (K-1) / (L + R (K-1)).  Rule: cut z so that the active members together give about two workgroups per CU (what a CU
+// holds of this kernel, by LDS and by VGPRs), but no chunk shorter than 4 R (K-1) planes: the recomputed share stays <= 1/5,
+// and it gets that high only where the device would otherwise stand partly idle.  A grid thinner than that is one chunk.
+// The planes are shared out evenly (chunk i is [i nzl / n, (i+1) nzl / n)), so no chunk is a short remainder.
+static inline int wafer_batch_fused_nchunks(int nzl, long long layer, int num_cus, int R, int K)
+{
+    const int min_chunk = 4 * R * (K - 1) > 1 ? 4 * R * (K - 1) : 1;
+    const long long target = 2LL * (num_cus > 0 ? num_cus : 1);
+    long long nch = layer > 0 ? (target + layer - 1) / layer : 1;
+    const long long most = nzl / min_chunk > 1 ? nzl / min_chunk : 1;
+    if (nch > most) nch = most;
+    if (nch < 1) nch = 1;
+    return (int)nch;
+}
+
+// The table: a pure function of the geometry, the active set (null: all of n_members), the CU count and the tile.  Members in
+// order, within a member z-chunks, tile rows, tiles: the workgroups of one member are neighbours in the dispatch order and
+// share its halo planes in L2.  A frozen member has no entry.
+static inline std::vector<WaferBatchBlock> wafer_batch_fused_table(const WaferGeom &g, const uint8_t *active, uint32_t n_members,
+                                                                   int num_cus, int K, int tx, int ty)
+{
+    std::vector<WaferBatchBlock> t;
+    long long nact = 0;
+    for (uint32_t m = 0; m < n_members; ++m) nact += (!active || active[m]) ? 1 : 0;
+    if (nact == 0 || g.nzl < 1) return t;
+    const int ntx = (g.nx + tx - 1) / tx, nty = (g.ny + ty - 1) / ty;
+    const int nch = wafer_batch_fused_nchunks(g.nzl, nact * ntx * nty, num_cus, g.R, K);
+    for (uint32_t m = 0; m < n_members; ++m) {
+        if (active && !active[m]) continue;
+        for (int c = 0; c < nch; ++c) {
+            const int z0 = g.G + (int)((long long)c * g.nzl / nch), z1 = g.G + (int)((long long)(c + 1) * g.nzl / nch);
+            for (int j = 0; j < nty; ++j)
+                for (int i = 0; i < ntx; ++i) t.push_back(WaferBatchBlock{(int)m, i * tx, j * ty, z0, z1, 0});
+        }
+    }
+    return t;
+}

@@ -1,5 +1,6 @@
 // wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B problems of one shape on one device, one
-// launch per step over the active members (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip), and for
+// launch per step over the active members -- or, for ground-state steps, one launch per pass of K steps (wafer_batch_plan.h) --
+// (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip), and for
 // excited states a per-member state store with the normalise / Gram-Schmidt tail of every step (wafer_gs_batch.hip.h,
 // wafer_tu_gs_batch.hip): 1 + 2 (1 + wnum) + 1 launches per step for the whole batch.
 //
@@ -30,6 +31,14 @@ struct wafer_batch {
     WaferBatchBlock *blk_dev = nullptr;
     size_t blk_cap = 0;
     std::vector<uint8_t> blk_key;             // the active set the device block table was built for
+    // the fused pass (wafer_k_batch_stepk): its own table, for the same active set
+    std::vector<WaferBatchBlock> blkk;
+    WaferBatchBlock *blkk_dev = nullptr;
+    size_t blkk_cap = 0;
+    std::vector<uint8_t> blkk_key;
+    int blkk_K = 0;
+    int step_variant = -1;                    // wafer_batch_set_step_variant
+    uint64_t n_fused_passes = 0, n_single_steps = 0;   // launches since creation (wafer_batch_diag_passes)
     int *act_dev = nullptr, *act_host = nullptr;
     // observables: the single context's partition
     int obs_ntx = 0, obs_nty = 0, obs_zchunk = 0, obs_nb = 0, swz = 0;
@@ -90,7 +99,7 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->blkk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host})
@@ -188,6 +197,41 @@ int build_blocks(wafer_batch *b, const uint8_t *active)
     }
     if (!b->blk.empty()) HIP_TRY(hipMemcpy(b->blk_dev, b->blk.data(), sizeof(WaferBatchBlock) * b->blk.size(), hipMemcpyHostToDevice));
     b->blk_key = key;
+    return WAFER_OK;
+}
+
+// Steps per launch of a ground-state evolve: the fused pass where an instantiation exists and the variant asks for it.
+// The default (-1), per stencil (index R), follows the measured rows of DESIGN.md section 5 "Batches".
+constexpr bool WAFER_BATCH_FUSED_BY_DEFAULT[4] = {false, false, false, false};
+int steps_per_pass(const wafer_batch *b)
+{
+    const int R = b->g.R;
+    const int K = R == 1 ? 3 : 2;
+    const bool fused = b->step_variant < 0 ? WAFER_BATCH_FUSED_BY_DEFAULT[R] : b->step_variant == 1;
+    if (!fused || wafer_batch_stepk_lds_bytes(R, K) == 0) return 1;
+    return K;
+}
+
+// a call's remainder of two steps is one pass where the two-step instantiation exists beside the K-step one
+bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->g.R, 2) != 0; }
+
+// the fused pass's workgroup table (wafer_batch_fused_table) on the device, for this active set
+int build_blocks_fused(wafer_batch *b, const uint8_t *active, int K)
+{
+    std::vector<uint8_t> key(b->n);
+    for (uint32_t m = 0; m < b->n; ++m) key[m] = (!active || active[m]) ? 1 : 0;
+    if (key == b->blkk_key && K == b->blkk_K && b->blkk_dev) return WAFER_OK;
+    b->blkk = wafer_batch_fused_table(b->g, key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY);
+    HIP_TRY(hipStreamSynchronize(b->s));
+    if (b->blkk.size() > b->blkk_cap || !b->blkk_dev) {
+        if (b->blkk_dev) HIP_TRY(hipFree(b->blkk_dev));
+        b->blkk_dev = nullptr;
+        b->blkk_cap = std::max<size_t>(b->blkk.size(), 1);
+        HIP_TRY(hipMalloc((void **)&b->blkk_dev, sizeof(WaferBatchBlock) * b->blkk_cap));
+    }
+    if (!b->blkk.empty()) HIP_TRY(hipMemcpy(b->blkk_dev, b->blkk.data(), sizeof(WaferBatchBlock) * b->blkk.size(), hipMemcpyHostToDevice));
+    b->blkk_key = key;
+    b->blkk_K = K;
     return WAFER_OK;
 }
 
@@ -322,7 +366,9 @@ int gs_chain(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_f
     return WAFER_OK;
 }
 
-// n_steps steps of the active members, each followed by the normalise / Gram-Schmidt chain when wnum > 0 (grid.rs:544-687)
+// n_steps steps of the active members, each followed by the normalise / Gram-Schmidt chain when wnum > 0 (grid.rs:544-687).
+// wnum == 0: the call's pass sequence (wafer_batch_plan.h) -- passes of K steps, then the remainder; the source buffer flips
+// once per launch.
 int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t n_steps)
 {
     HIP_TRY(hipSetDevice(b->device));
@@ -332,21 +378,32 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
     if (wnum) TRY(ensure_gs(b));
     TRY(sync_members(b));
     TRY(build_blocks(b, active));
+    const int K = wnum ? 1 : steps_per_pass(b);
+    const bool have2 = have_two_step(b, K);
+    if (K > 1) TRY(build_blocks_fused(b, active, K));
     int nact = 0;
     if (wnum) TRY(upload_active(b, active, &nact));   // (the chain's member list; synchronises the stream, which a ground-state call must not)
     RoctxRange range_(wnum ? "wafer_batch_evolve_state" : "wafer_batch_evolve");
     HIP_TRY(hipEventRecord(b->ev_start, b->s));
+    uint64_t launches = 0;
     if (!b->blk.empty()) {   // (no active member: no workgroup)
-        for (uint64_t k = 0; k < steps; ++k) {   // no host synchronisation in here: every scalar stays on the device
-            const hipError_t e = wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), (int)(k & 1), b->s);
+        uint64_t left = steps;
+        while (left > 0) {   // no host synchronisation in here: every scalar stays on the device
+            const int k = wafer_batch_next_pass(left, K, have2);
+            const int flip = (int)(launches & 1);
+            const hipError_t e = k > 1 ? wafer_entry_batch_stepk(b->g.R, k, b->g, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
+                                       : wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s);
             if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
-            if (wnum) TRY(gs_chain(b, nact, (int)((k + 1) & 1), wnum, true));
+            ++launches;
+            ++(k > 1 ? b->n_fused_passes : b->n_single_steps);
+            left -= (uint64_t)k;
+            if (wnum) TRY(gs_chain(b, nact, (int)(launches & 1), wnum, true));
         }
     }
     HIP_TRY(hipEventRecord(b->ev_stop, b->s));
     b->last_steps = steps;
     b->timing_valid = true;
-    if (steps & 1)
+    if (wafer_batch_launch_count(steps, K, have2, nullptr) & 1)
         for (uint32_t m = 0; m < b->n; ++m)
             if (!active || active[m]) b->views[m]->cur ^= 1;
     return WAFER_OK;
@@ -779,6 +836,48 @@ const char *wafer_batch_kernel_name(wafer_batch *b)
 {
     (void)b;
     return "wafer_k_batch_step";
+}
+
+int wafer_batch_steps_per_launch(wafer_batch *b)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    return steps_per_pass(b);
+}
+
+int wafer_batch_set_step_variant(wafer_batch *b, int variant)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    if (variant < -1 || variant > 1) return fail(WAFER_ERR_INVALID, "step variant must be -1 (default), 0 (one step per launch) or 1 (fused passes)");
+    b->step_variant = variant;
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n)
+{
+    if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
+    static const char *const stencils[] = {"", "ThreePoint", "FivePoint", "SevenPoint"};
+    const int R = b->g.R, K = steps_per_pass(b);
+    char kernel[64], tile[32];
+    const char *remainder = "none";
+    if (K > 1) {
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d>", R, K);
+        snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCHK_TX, WAFER_BATCHK_TY);
+        remainder = have_two_step(b, K) ? "stepk2+step" : "step";
+    } else {
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d>", R);
+        snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCH_TX, WAFER_BATCH_TY);
+    }
+    snprintf(buf, n, "stencil=%s kernel=%s steps_per_pass=%d tile=%s lds_bytes=%d remainder=%s variant=%d", stencils[R], kernel, K, tile,
+             K > 1 ? wafer_batch_stepk_lds_bytes(R, K) : 0, remainder, b->step_variant);
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_passes(wafer_batch *b, uint64_t *fused_passes, uint64_t *single_steps)
+{
+    if (!b || !fused_passes || !single_steps) return fail(WAFER_ERR_INVALID, "null argument");
+    *fused_passes = b->n_fused_passes;
+    *single_steps = b->n_single_steps;
+    return WAFER_OK;
 }
 
 } // extern "C"

@@ -1,5 +1,6 @@
 // Batched ensembles (wafer_batch_*, include/wafer_hip.h): B independent ground-state problems of one shape on one device,
 // advanced by one launch per step over a workgroup table of (member, tile, z-chunk) entries built from the ACTIVE members only.
+// Ground-state steps may instead run as passes of K steps per launch (wafer_k_batch_stepk below; the same bits).
 //
 // Parity: every member gets exactly what a single wafer_ctx with its wafer_params computes.
 //  - step: the arithmetic of wafer_k_step2_fused, per cell -- wafer_stencil_sum, then a and b formed from V in registers and the
@@ -13,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wafer_geom.h"
+#include "wafer_batch_plan.h"
 #include "wafer_stencil.hip.h"
 #include "wafer_stencil_fused2.hip.h"
 
@@ -30,10 +32,7 @@ struct WaferBatchMember {
     int pad;
 };
 
-// one workgroup of a batched step: tile (x0, y0) of 64 x 4 work cells, local planes [z0, z1) of member `member`
-struct WaferBatchBlock {
-    int member, x0, y0, z0, z1, pad;
-};
+// one workgroup of a batched step: WaferBatchBlock (wafer_batch_plan.h); the one-step kernel's tiles are 64 x 4 work cells
 
 #define WAFER_BATCH_TX 64
 #define WAFER_BATCH_TY 4
@@ -76,6 +75,187 @@ __global__ __launch_bounds__(256) void wafer_k_batch_step(WaferGeom g, const Waf
         const double w = zq[R];
         const double S = wafer_stencil_sum<double, R>(xs, ys, zq, w);
         out[col + o] = wafer_update_v<double>(w, pv[col + o], dt, S, den, sf);
+    }
+}
+
+// ---- K steps per launch ----------------------------------------------------------------------------------------------------
+// wafer_k_batch_stepk<R, K>: phi0 --step--> phi1 ... --step--> phiK for every entry of a table built by wafer_batch_fused_table,
+// with phi1 .. phi(K-1) in registers and LDS only (the temporal blocking of wafer_k_step2_fused / wafer_k_step3_fused, in a
+// compact form for grids of 50^3 .. 128^3).
+//
+// Cells, not roles.  Level k (phi k) is needed on the tile grown by (K-k) R cells on every side; these regions are nested, so
+// the cells of the phi0 region are put in ONE order in which every region is a prefix: first the tile itself row by row (one
+// wave across a 64-cell row), then ring after ring outwards, each ring R cells thick.  Thread t owns the cells t, t + 256,
+// t + 512, ... of that order for every level: it carries the z-queues of its cells in registers (2R+1 planes of each of
+// phi0 .. phi(K-1), and V), computes level k for its cells below N_k = cells of level k's region, and so needs no halo-row or
+// halo-column role: a level's halo is the tail of the same list.  Waves whose cells all lie beyond N_k skip the level.
+// x and y neighbours come from LDS: phi0's plane z double-buffered, every intermediate level as a ring of R+1 planes, all in
+// the phi0 region's layout (W0 x H0).  One barrier per plane:
+//   iteration z:  prefetch phi0 plane z+R+1 and V plane z+1;  stage phi0 plane z+1 into the other buffer;
+//                 level 1 plane z, level 2 plane z-R, ..., level K plane z-(K-1)R -> global;  barrier;  rotate the queues.
+// The arithmetic per cell is the one-step kernel's, call for call: wafer_stencil_sum then wafer_update_v with the member's
+// WaferDen and its short-form flag, so the bits are those of K launches of wafer_k_batch_step.
+// Dirichlet frame: a cell of an intermediate level outside the work area (frame, pad, planes outside [G, G + nzl)) is set to 0,
+// never computed; the last level writes work cells only.
+// z-chunks: level k is computed on planes [z0 - (K-k) R, z1 + (K-k) R); phi0 is loaded from [z0 - K R, z1 + K R).
+template <int R, int K>
+struct WaferBatchKCfg {
+    static constexpr int TX = WAFER_BATCHK_TX, TY = WAFER_BATCHK_TY, NT = 256;
+    static constexpr int H = K * R;                              // phi0 halo per side
+    static constexpr int W0 = TX + 2 * H, H0 = TY + 2 * H;       // the LDS layout of every level: the phi0 region
+    static constexpr int PLANE = W0 * H0;
+    static constexpr int NB = R + 1;                             // ring depth of an intermediate level
+    static constexpr int ncells(int k) { return (TX + 2 * (K - k) * R) * (TY + 2 * (K - k) * R); }   // level k's region
+    static constexpr int cpt(int k) { return (ncells(k) + NT - 1) / NT; }                            // cells per thread
+    static constexpr int LDS_BYTES = 8 * PLANE * (2 + (K - 1) * NB);
+    // Loads carry no bounds predicates; the tile's overhang lies in the allocation's zero guard zone (wafer_geom.h), checked by
+    // hand for K R <= 6 (R <= 3, K <= 3 with K R <= gz = 3 R):
+    //  rows:    work rows y0 - K R .. y0 + TY - 1 + K R with y0 + TY - 1 <= ny + TY - 2, i.e. padded rows -(K-1) R .. ny + TY - 2
+    //           + (K+1) R; the allocation holds padded rows -gy .. ny + 2 R + gy - 1 with gy = 16 + 3 R: needs TY - 2 + (K+1) R
+    //           <= 5 R + 15, true for TY <= 16.
+    //  columns: element xoff + R + x = 16 + x for work x in -K R .. 64 ceil(nx / 64) + K R - 1: at least 16 - K R >= 10, at most
+    //           15 + 64 ceil(nx / 64) + K R <= 21 + 128 ceil(nx / 128) < pitch = 32 + 128 ceil(nx / 128).
+    //  planes:  z0 - K R >= G - K R >= -gz and z1 + K R - 1 <= G + nzl + K R - 1 < lz + gz = nzl + 2 G + 3 R.
+    static_assert(TX == 64 && TY <= 16 && K * R <= 6 && K <= 3, "the guard-zone check above");
+    static_assert(LDS_BYTES <= 65536, "static LDS");
+};
+
+template <int R, int K>
+__global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const WaferBatchMember *__restrict__ mem,
+                                                           const WaferBatchBlock *__restrict__ blocks, int flip)
+{
+    using Cfg = WaferBatchKCfg<R, K>;
+    constexpr int NT = Cfg::NT, W0 = Cfg::W0, PLANE = Cfg::PLANE, NB = Cfg::NB, H = Cfg::H;
+    constexpr int C0 = Cfg::cpt(0), C1 = Cfg::cpt(1), NQ = 2 * R + 1, NV = (K - 1) * R + 1;
+    __shared__ double lds0[2 * PLANE];
+    __shared__ double ldsk[(K - 1) * NB * PLANE];
+
+    const WaferBatchBlock bk = blocks[blockIdx.x];
+    const WaferBatchMember &m = mem[bk.member];
+    const int sel = (m.cur ^ flip) & 1;
+    const double *__restrict__ phi = static_cast<const double *>(m.phi[sel]);
+    double *__restrict__ out = static_cast<double *>(m.phi[sel ^ 1]);
+    const double *__restrict__ pv = static_cast<const double *>(m.v);
+    const bool sf = m.short_forms != 0;   // (workgroup-uniform: a scalar branch)
+    const WaferDen<double> den{m.den, m.zh, m.zl, sf};
+    const double dt = m.dt;
+    const int tid = threadIdx.x;
+
+    // ---- this thread's cells ---------------------------------------------------------------------
+    int lpos[C0], goff[C0];
+    unsigned work = 0;   // bit q: cell q is a work cell
+#pragma unroll
+    for (int q = 0; q < C0; ++q) {
+        const int c = min(tid + q * NT, Cfg::ncells(0) - 1);   // surplus threads repeat the last cell (same value, same place)
+        int lx, ly;
+        wafer_batchk_cell(R, K, c, lx, ly);   // (wafer_batch_plan.h)
+        const int x = bk.x0 - H + lx, y = bk.y0 - H + ly;
+        lpos[q] = ly * W0 + lx;
+        goff[q] = (y + R) * g.pitch + g.xoff + R + x;
+        if (x >= 0 && x < g.nx && y >= 0 && y < g.ny) work |= 1u << q;
+    }
+
+    // ---- prologue: level 1's first plane is zf; the phi0 queue holds planes zf - R .. zf + R ------
+    const int zf = bk.z0 - (K - 1) * R, zend = bk.z1 + (K - 1) * R;
+    double q0[NQ][C0];
+    double qk[K - 1][NQ][C1];   // levels 1 .. K-1, planes p - R .. p + R around the plane p the next level is computed on
+    double vq[NV][C1];          // V of planes z - (K-1) R .. z
+#pragma unroll
+    for (int mq = 0; mq < NQ; ++mq)
+#pragma unroll
+        for (int q = 0; q < C0; ++q) q0[mq][q] = phi[(long long)(zf - R + mq) * g.plane + goff[q]];
+#pragma unroll
+    for (int l = 0; l < K - 1; ++l)
+#pragma unroll
+        for (int mq = 0; mq < NQ; ++mq)
+#pragma unroll
+            for (int q = 0; q < C1; ++q) qk[l][mq][q] = 0.0;   // (zeros that never reach an output: a level starts on its first valid plane)
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int q = 0; q < C1; ++q) vq[j][q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < C1; ++q) vq[NV - 1][q] = pv[(long long)zf * g.plane + goff[q]];
+    {
+        double *t0 = lds0 + (zf & 1) * PLANE;
+#pragma unroll
+        for (int q = 0; q < C0; ++q) t0[lpos[q]] = q0[R][q];
+    }
+    __syncthreads();
+
+    for (int z = zf; z < zend; ++z) {
+        const bool more = z + 1 < zend;
+        const long long zo = (long long)z * g.plane;
+        // ---- 1. prefetch phi0 plane z + R + 1 and V plane z + 1 ------------------------------------
+        double pre[C0], pre_v[C1];
+#pragma unroll
+        for (int q = 0; q < C0; ++q) pre[q] = 0.0;
+#pragma unroll
+        for (int q = 0; q < C1; ++q) pre_v[q] = 0.0;
+        if (more) {
+#pragma unroll
+            for (int q = 0; q < C0; ++q) pre[q] = phi[zo + (long long)(R + 1) * g.plane + goff[q]];
+#pragma unroll
+            for (int q = 0; q < C1; ++q) pre_v[q] = pv[zo + g.plane + goff[q]];
+            // ---- 2. stage phi0 plane z + 1 ----------------------------------------------------------
+            double *nt = lds0 + ((z + 1) & 1) * PLANE;
+#pragma unroll
+            for (int q = 0; q < C0; ++q) nt[lpos[q]] = q0[R + 1][q];
+        }
+        // ---- 3. level k on plane p = z - (k-1) R, k = 1 .. K ------------------------------------------
+#pragma unroll
+        for (int k = 1; k <= K; ++k) {
+            const int p = z - (k - 1) * R;
+            const int Ck = Cfg::cpt(k), Nk = Cfg::ncells(k);
+            const int kw = g.z_begin + (p - g.G);
+            // the plane is one this chunk needs of level k, and (intermediate levels) a work plane
+            const bool on = p >= bk.z0 - (K - k) * R && (k == K || (kw >= 0 && kw < g.nz));
+            const double *src = k == 1 ? lds0 + (z & 1) * PLANE : ldsk + ((k - 2) * NB + ((p % NB) + NB) % NB) * PLANE;
+            double *ring = ldsk + ((k - 1 < K - 1 ? k - 1 : 0) * NB + ((p % NB) + NB) % NB) * PLANE;
+            if (k < K) {
+#pragma unroll
+                for (int mq = 0; mq + 1 < NQ; ++mq)
+#pragma unroll
+                    for (int q = 0; q < C1; ++q) qk[k - 1 < K - 1 ? k - 1 : 0][mq][q] = qk[k - 1 < K - 1 ? k - 1 : 0][mq + 1][q];
+            }
+#pragma unroll
+            for (int q = 0; q < Ck; ++q) {
+                double val = 0.0;
+                const bool act = on && tid + q * NT < Nk && ((work >> q) & 1u);
+                if (act) {
+                    double xs[NQ], ys[NQ], zz[NQ];
+#pragma unroll
+                    for (int d = 0; d < NQ; ++d) zz[d] = k == 1 ? q0[d][q] : qk[k >= 2 ? k - 2 : 0][d][q];
+                    const double w = zz[R];
+#pragma unroll
+                    for (int d = -R; d <= R; ++d) {
+                        xs[d + R] = d == 0 ? w : src[lpos[q] + d];
+                        ys[d + R] = d == 0 ? w : src[lpos[q] + d * W0];
+                    }
+                    const double S = wafer_stencil_sum<double, R>(xs, ys, zz, w);
+                    val = wafer_update_v<double>(w, vq[(K - k) * R][q], dt, S, den, sf);
+                    if (k == K) out[(long long)p * g.plane + goff[q]] = val;
+                }
+                if (k < K) {
+                    qk[k - 1 < K - 1 ? k - 1 : 0][NQ - 1][q] = val;
+                    ring[lpos[q]] = val;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- 4. rotate ----------------------------------------------------------------------------------
+#pragma unroll
+        for (int mq = 0; mq + 1 < NQ; ++mq)
+#pragma unroll
+            for (int q = 0; q < C0; ++q) q0[mq][q] = q0[mq + 1][q];
+#pragma unroll
+        for (int q = 0; q < C0; ++q) q0[NQ - 1][q] = pre[q];
+#pragma unroll
+        for (int j = 0; j + 1 < NV; ++j)
+#pragma unroll
+            for (int q = 0; q < C1; ++q) vq[j][q] = vq[j + 1][q];
+#pragma unroll
+        for (int q = 0; q < C1; ++q) vq[NV - 1][q] = pre_v[q];
     }
 }
 
@@ -192,6 +372,10 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(WaferGeom 
 // entry points (wafer_tu_batch.hip)
 hipError_t wafer_entry_batch_step(int R, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks,
                                   int flip, hipStream_t s);
+// the fused pass of K steps; hipErrorInvalidValue where wafer_batch_stepk_lds_bytes(R, K) is 0 (no such instantiation)
+hipError_t wafer_entry_batch_stepk(int R, int K, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
+                                   int nblocks, int flip, hipStream_t s);
+int wafer_batch_stepk_lds_bytes(int R, int K);
 hipError_t wafer_entry_batch_observables(int R, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, int ntx,
                                          int nty, int nblocks, int zchunk, int swz, double *partials, double *out, hipStream_t s);
 hipError_t wafer_entry_batch_normalise(const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, const double *norm2,

@@ -14,6 +14,26 @@ hipError_t wafer_entry_batch_step(int R, const WaferGeom &g, const WaferBatchMem
     return hipGetLastError();
 }
 
+// the instantiations of the fused pass: ThreePoint 3 steps (and 2, for the remainder of a call), FivePoint 2 steps
+int wafer_batch_stepk_lds_bytes(int R, int K)
+{
+    if (R == 1 && K == 3) return WaferBatchKCfg<1, 3>::LDS_BYTES;
+    if (R == 1 && K == 2) return WaferBatchKCfg<1, 2>::LDS_BYTES;
+    if (R == 2 && K == 2) return WaferBatchKCfg<2, 2>::LDS_BYTES;
+    return 0;
+}
+
+hipError_t wafer_entry_batch_stepk(int R, int K, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
+                                   int nblocks, int flip, hipStream_t s)
+{
+    const dim3 grid((unsigned)nblocks), block(256);
+    if (R == 1 && K == 3) hipLaunchKernelGGL((wafer_k_batch_stepk<1, 3>), grid, block, 0, s, g, mem, blocks, flip);
+    else if (R == 1 && K == 2) hipLaunchKernelGGL((wafer_k_batch_stepk<1, 2>), grid, block, 0, s, g, mem, blocks, flip);
+    else if (R == 2 && K == 2) hipLaunchKernelGGL((wafer_k_batch_stepk<2, 2>), grid, block, 0, s, g, mem, blocks, flip);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 hipError_t wafer_entry_batch_observables(int R, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, int ntx,
                                          int nty, int nblocks, int zchunk, int swz, double *partials, double *out, hipStream_t s)
 {

@@ -50,7 +50,8 @@ EXPORTS = [
     "wafer_batch_create", "wafer_batch_destroy", "wafer_batch_size", "wafer_batch_set_potential_builtin",
     "wafer_batch_set_potential_host", "wafer_batch_set_initial_condition", "wafer_batch_upload_phi", "wafer_batch_download_phi",
     "wafer_batch_evolve", "wafer_batch_observables", "wafer_batch_normalise", "wafer_batch_solve", "wafer_batch_last_evolve_ms",
-    "wafer_batch_kernel_name",
+    "wafer_batch_kernel_name", "wafer_batch_steps_per_launch", "wafer_batch_set_step_variant", "wafer_batch_diag_dispatch",
+    "wafer_batch_diag_passes",
     "wafer_batch_load_state", "wafer_batch_download_state", "wafer_batch_push_state", "wafer_batch_num_states",
     "wafer_batch_clear_states", "wafer_batch_clone_state_to_phi", "wafer_batch_orthogonalise", "wafer_batch_norm2",
     "wafer_batch_evolve_state", "wafer_batch_solve_state",
@@ -234,6 +235,10 @@ def load_library():
     L.wafer_batch_last_evolve_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     L.wafer_batch_kernel_name.argtypes = [vp]
     L.wafer_batch_kernel_name.restype = C.c_char_p
+    L.wafer_batch_steps_per_launch.argtypes = [vp]
+    L.wafer_batch_set_step_variant.argtypes = [vp, C.c_int]
+    L.wafer_batch_diag_dispatch.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.wafer_batch_diag_passes.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.wafer_batch_load_state.argtypes = [vp, C.c_uint32, C.c_uint32, dp]
     L.wafer_batch_download_state.argtypes = [vp, C.c_uint32, C.c_uint32, dp]
     L.wafer_batch_push_state.argtypes = [vp, u8p]
@@ -655,7 +660,9 @@ class Context:
 
 class Batch:
     """B independent problems of one shape on one device (wafer_batch_*): one launch per step advances every active member,
-    and each member's ground state computes bit for bit what a Context with its Params computes.
+    and each member's ground state computes bit for bit what a Context with its Params computes.  set_step_variant(1) makes
+    a ground-state evolve one launch per pass of K steps (ThreePoint 3, FivePoint 2; steps_per_launch(), dispatch()): the
+    same bits.
 
     Excited states: every member has a state store of its own (capacity Params.max_states; load_state, push_state, ...), and
     evolve(steps, wnum=k) / solve_state(k, ...) normalise and project each member against its first k stored states after
@@ -856,3 +863,29 @@ class Batch:
 
     def kernel_name(self) -> str:
         return self._L.wafer_batch_kernel_name(self._h).decode()
+
+    def steps_per_launch(self) -> int:
+        """K of the pass a ground-state evolve of at least K steps launches; 1: the one-step kernel"""
+        k = self._L.wafer_batch_steps_per_launch(self._h)
+        if k < 1:
+            self._check(k)
+        return k
+
+    def set_step_variant(self, variant: int) -> None:
+        """-1: default dispatch, 0: one step per launch, 1: fused passes wherever an instantiation exists (the same bits)"""
+        self._check(self._L.wafer_batch_set_step_variant(self._h, int(variant)))
+
+    def dispatch(self) -> dict:
+        """what a ground-state evolve would launch: stencil, kernel, steps_per_pass, tile, lds_bytes, remainder, variant"""
+        buf = C.create_string_buffer(512)
+        self._check(self._L.wafer_batch_diag_dispatch(self._h, buf, len(buf)))
+        d = dict(kv.split("=", 1) for kv in buf.value.decode().split())
+        for k in ("steps_per_pass", "lds_bytes", "variant"):
+            d[k] = int(d[k])
+        return d
+
+    def passes(self) -> tuple:
+        """(fused passes, one-step launches) since creation"""
+        f, s = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_passes(self._h, C.byref(f), C.byref(s)))
+        return f.value, s.value
