@@ -200,7 +200,8 @@ extern "C" {
     pub fn wafer_diag_div_planned_f32(ctx: *mut wafer_ctx, plan: *const wafer_div_plan_f32_t, lo_exp: c_int, hi_exp: c_int, mismatches: *mut u64) -> c_int;
     pub fn wafer_diag_div_planned(ctx: *mut wafer_ctx, plan: *const wafer_div_plan_t, seed: u64, n_random: u64, lo_exp: c_int, hi_exp: c_int,
                                   operands: *const f64, n_operands: usize, mismatches_random: *mut u64, mismatches_operands: *mut u64) -> c_int;
-    // batched ensembles: B ground-state problems of one shape, one launch per step (include/wafer_hip.h)
+    // batched ensembles: B ground-state problems of one shape and one dtype (WAFER_F64, WAFER_F32 or WAFER_F32_FAST in every member's
+    // wafer_params), one launch per step (include/wafer_hip.h)
     pub fn wafer_batch_create(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
     pub fn wafer_batch_destroy(b: *mut wafer_batch) -> c_int;
     pub fn wafer_batch_size(b: *mut wafer_batch, n_members: *mut u32) -> c_int;

@@ -428,7 +428,7 @@ int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
 
 /* ---- batched ensembles ------------------------------------------------------
  * A batch holds B independent ground-state problems ("members") on one device, all with the same work-area shape, the same
- * central_difference and dtype WAFER_F64, each with its own dn, dt, mass, sig, flags, potential, pot_sub and wavefunction.  One
+ * central_difference and the same dtype, each with its own dn, dt, mass, sig, flags, potential, pot_sub and wavefunction.  One
  * launch per step advances every ACTIVE member (a workgroup table built from the active members only: a member that is not
  * active costs nothing) -- or one launch per PASS of K ground-state steps where a fused pass is selected
  * (wafer_batch_set_step_variant; ThreePoint K = 3, FivePoint K = 2, the intermediate steps never leave the CU, the same bits);
@@ -437,7 +437,27 @@ int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
  * context's partition and reduction order), normalisation and solve.  No z-slabs (z_count must be 0).  Excited states: the
  * wafer_batch_*_state calls further down.
  * Member arrays live in one allocation per array kind (phi ping-pong, V, pot_sub) with a member stride.
- * wafer_batch_create validates every member before any HIP call (WAFER_ERR_INVALID names the member and the field). */
+ * wafer_batch_create validates every member before any HIP call (WAFER_ERR_INVALID names the member and the field).
+ *
+ * dtype: WAFER_F64, WAFER_F32 or WAFER_F32_FAST, ONE per batch -- a member whose dtype differs from member 0's, or lies outside
+ * the enum, is WAFER_ERR_INVALID naming the member and "dtype".  The other member rules do not depend on it.  On the two float
+ * dtypes every array and every store slot is float (half the bytes per cell; rows are padded to whole 1 KiB tiles as a context's
+ * are, so the allocation halves only where the row pitch does), host arrays at this ABI stay
+ * double -- uploads and state loads round to nearest even as a context's do, downloads widen -- and:
+ *  - ground state: bit for bit a wafer_ctx of the same wafer_params under its default dispatch, under the fused pass too.
+ *    a and b are formed from the STORED (float) V in the arithmetic type inside the kernel, and the result of EVERY step is
+ *    rounded to float (in a fused pass each intermediate level is rounded before the next one reads it).  WAFER_F32: fp64
+ *    arithmetic.  WAFER_F32_FAST: every operand and operation of the step is float, the division by c dn^2 m is the member's
+ *    own fp32 plan (wafer_div_plan_f32 of (float)den; checked or not as for a context; WAFER_FLAG_UNPLANNED_DIV is honoured).
+ *  - observables, normalise and solve compute in fp64 on the float arrays, on the partition and in the reduction order of a
+ *    context of that dtype (16 bytes per lane: tiles twice as wide as on doubles): bit for bit that context.  normalise
+ *    rounds its quotient to float.
+ *  - excited states (the *_state calls, orthogonalise, evolve_state, solve_state): fp64 arithmetic throughout on both float
+ *    dtypes (a WAFER_F32_FAST batch takes the fp64-arithmetic step there, as a context does), float stores, and phi rounded to
+ *    float where each kernel writes it: after the step, after the scale, after each projection.  The guarantees below carry
+ *    over unchanged (no dependence on B, index or active set; frozen members untouched; no floating-point atomics).
+ *    wafer_batch_norm2 on the float dtypes sums in fp64 on the partition and in the order of wafer_norm2 of a context of that
+ *    dtype: the same double, bit for bit.  (On WAFER_F64 it keeps the batch's own partition: rel 1e-12 against a context.) */
 typedef struct wafer_batch wafer_batch;
 int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out);
 int wafer_batch_destroy(wafer_batch *b);
@@ -472,8 +492,9 @@ int wafer_batch_steps_per_launch(wafer_batch *b);
 /* -1: default dispatch; 0: one step per launch; 1: fused passes of K steps wherever an instantiation exists (a call's
  * remainder runs as shorter passes and single steps).  Every variant computes the same bits. */
 int wafer_batch_set_step_variant(wafer_batch *b, int variant);
-/* one line of key=value pairs -- stencil= kernel= steps_per_pass= tile= lds_bytes= remainder= variant= -- from the launch path's
- * own predicates; launches nothing */
+/* one line of key=value pairs -- stencil= kernel= steps_per_pass= tile= lds_bytes= remainder= variant= dtype= -- from the launch
+ * path's own predicates; launches nothing.  kernel= names the instantiation: wafer_k_batch_step<R> / wafer_k_batch_stepk<R,K> on
+ * fp64, with the storage and arithmetic types appended on the float dtypes (<R,float,double>, <R,K,float,float>, ...). */
 int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n);
 /* launches since creation: fused passes (more than one step each) and one-step launches */
 int wafer_batch_diag_passes(wafer_batch *b, uint64_t *fused_passes, uint64_t *single_steps);

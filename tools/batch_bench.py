@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Batched ensembles against what a user does today: B members of one shape (Harmonic, ThreePoint fp64, members differing in
+"""Batched ensembles against what a user does today: B members of one shape (Harmonic, ThreePoint, members differing in
 dt) advanced by one wafer_batch_evolve, by B Contexts one after another from one thread, and by B Contexts on B Python threads
 (ctypes releases the GIL).  One JSON line per (shape, B):
   batch_us_per_step / batch_gups  HIP events around the batch's step launches, after warm-up
@@ -13,15 +13,19 @@ gups: grid-point updates per second (members x work cells x steps / time), 1e9.
 the host), the batch runs evolve(steps, wnum=K), the contexts evolve(K, steps); the same columns and clocks plus "wnum", and
 parity becomes max |batch - context| <= 1e-13 over member 0's cells, the value itself in "parity_max_abs".
 --variant V: Batch.set_step_variant(V) before the first step (-1 default dispatch, 0 one step per launch, 1 fused passes); the
-row records "variant", "steps_per_launch", the dispatch line and the launch counts of the timed call."""
+row records "variant", "steps_per_launch", the dispatch line and the launch counts of the timed call.
+--dtype D: f64 (default), f32 (float storage, fp64 arithmetic) or f32fast (float arithmetic in the ground-state step) for the
+batch and the contexts alike; the row records "dtype".  On the float dtypes the excited-state parity bar is 4 float spacings at
+max |phi| (the two partition their sums differently, and a last-bit difference of a scalar can flip a float rounding), the
+ground-state parity stays bit for bit."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import wafer_amd
 
 
-def members(n, B, ext=1):
-    return [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext) for k in range(B)]
+def members(n, B, ext=1, dtype="f64"):
+    return [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype) for k in range(B)]
 
 
 def store(par, wnum, seed=0):
@@ -37,10 +41,10 @@ def store(par, wnum, seed=0):
     return out
 
 
-def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1):
-    pars = members(n, B, ext)
+def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1, dtype="f64"):
+    pars = members(n, B, ext, dtype)
     cells = n ** 3
-    out = {"shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": "f64",
+    out = {"shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype,
            "potential": "Harmonic"}
     if wnum:
         out["wnum"] = wnum
@@ -76,8 +80,10 @@ def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1):
             ctx.evolve(wnum, warmup)
             ctx.evolve(wnum, steps)
             if wnum:   # the project's excited-state bar, 1e-13 per cell (the two partition their sums differently: not bit for bit)
-                err = float(np.max(np.abs(ctx.download_phi() - b.download_phi(0))))
-                out["parity"], out["parity_max_abs"] = bool(err <= 1e-13), "%.2e" % err
+                want = ctx.download_phi()
+                err = float(np.max(np.abs(want - b.download_phi(0))))
+                bar = 1e-13 if dtype == "f64" else 4.0 * float(np.spacing(np.float32(np.max(np.abs(want)))))
+                out["parity"], out["parity_max_abs"] = bool(err <= bar), "%.2e" % err
             else:
                 out["parity"] = bool(np.array_equal(ctx.download_phi().view(np.int64), b.download_phi(0).view(np.int64)))
     ctxs = [wafer_amd.Context(p) for p in pars]
@@ -128,11 +134,12 @@ def main():
     ap.add_argument("--only-batch", action="store_true", help="the batch alone, no contexts (counter runs)")
     ap.add_argument("--wnum", type=int, default=0, help="excited-state steps against K stored states per member (default 0: ground state)")
     ap.add_argument("--ext", type=int, choices=[1, 2, 3], default=1, help="central difference: 1 ThreePoint (default), 2 FivePoint, 3 SevenPoint")
+    ap.add_argument("--dtype", choices=["f64", "f32", "f32fast"], default="f64", help="storage / arithmetic of the batch and the contexts")
     ap.add_argument("--variant", type=int, choices=[-1, 0, 1], default=-1, help="Batch.set_step_variant: -1 default dispatch, 0 one step per launch, 1 fused passes")
     a = ap.parse_args()
     for n in a.sizes:
         for B in a.batch:
-            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum, a.variant, a.ext).items()})
+            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum, a.variant, a.ext, a.dtype).items()})
             print(line, flush=True)
             if a.out:
                 with open(a.out, "a") as f:

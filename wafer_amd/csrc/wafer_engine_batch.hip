@@ -7,6 +7,11 @@
 // Each member is also a context VIEW: a wafer_ctx whose arrays are the member's slices of the batch's allocations and whose
 // stream is the batch's.  Potentials, initial conditions, uploads and downloads go through the context entry points on that
 // view, so a member is set up by the very code that sets up a single context.  The views own nothing.
+//
+// One dtype per batch (member 0's): f64, f32 (float arrays, fp64 arithmetic) or f32fast (float arrays, float arithmetic in the
+// ground-state step).  Every array and store slot is allocated in the element size `esz`, the geometry is the one a context of
+// that dtype builds (wafer_make_geom with that element size: the context's set-up kernels run on the views), and the entry
+// points of the kernels take the dtype.
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_batch.hip.h"
@@ -21,6 +26,9 @@ struct wafer_batch {
     hipStream_t s = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     size_t stride = 0;                        // elements per member in each array allocation
+    int dtype = WAFER_F64;                    // every member's (check_member)
+    bool f32 = false;                         // float storage (f32 and f32fast)
+    size_t esz = 8;                           // bytes per element of every array and store slot
     void *alloc[4] = {nullptr, nullptr, nullptr, nullptr};   // phi[0], phi[1], V, pot_sub
     std::vector<wafer_ctx *> views;
     double *view_scal = nullptr, *view_scal_host = nullptr;  // SCAL_SLOTS per view
@@ -52,6 +60,7 @@ struct wafer_batch {
     std::vector<uint32_t> nst;                // states member m holds
     // excited states: norm2 at gs_scal[m * gs_stride], the overlap with state l at [m * gs_stride + 1 + l]; made at first use
     int gs_nb = 0, gs_stride = 0;
+    int n2_nb = 0;                            // float storage: workgroups per member of wafer_batch_norm2 (a context's wafer_norm2 partition)
     double *gs_partials = nullptr;            // [member][gs_nb]
     double *gs_scal = nullptr, *gs_host = nullptr;
 };
@@ -65,7 +74,8 @@ int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0)
     if (m->nx < 1 || m->ny < 1 || m->nz < 1) return fail(WAFER_ERR_INVALID, "member %u: grid size must be >= 1", i);
     if (m->central_difference < 1 || m->central_difference > 3)
         return fail(WAFER_ERR_INVALID, "member %u: central_difference must be 1 (Three), 2 (Five) or 3 (SevenPoint)", i);
-    if (m->dtype != WAFER_F64) return fail(WAFER_ERR_INVALID, "member %u: dtype must be f64 (WAFER_F64) in a batch", i);
+    if (m->dtype != WAFER_F64 && m->dtype != WAFER_F32 && m->dtype != WAFER_F32_FAST)
+        return fail(WAFER_ERR_INVALID, "member %u: bad dtype %d (f64 = 0, f32 = 1, f32fast = 2)", i, (int)m->dtype);
     if (m->z_count != 0) return fail(WAFER_ERR_INVALID, "member %u: z_count must be 0 (a batch holds no z-slabs)", i);
     if (!(m->dn > 0) || !(m->dt > 0) || !(m->mass > 0)) return fail(WAFER_ERR_INVALID, "member %u: dn, dt, mass must be > 0", i);
     const double den = wafer_stencil_den(m->central_difference, m->dn, m->mass);
@@ -77,6 +87,8 @@ int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0)
     if (m->halo_depth != 0 && (int)m->halo_depth < m->central_difference)
         return fail(WAFER_ERR_INVALID, "member %u: halo_depth must be >= ext", i);
     if (m0) {
+        if (m->dtype != m0->dtype)
+            return fail(WAFER_ERR_INVALID, "member %u: dtype = %d differs from member 0's %d (a batch holds one dtype)", i, (int)m->dtype, (int)m0->dtype);
         if (m->nx != m0->nx) return fail(WAFER_ERR_INVALID, "member %u: nx = %u differs from member 0's %u", i, m->nx, m0->nx);
         if (m->ny != m0->ny) return fail(WAFER_ERR_INVALID, "member %u: ny = %u differs from member 0's %u", i, m->ny, m0->ny);
         if (m->nz != m0->nz) return fail(WAFER_ERR_INVALID, "member %u: nz = %u differs from member 0's %u", i, m->nz, m0->nz);
@@ -208,12 +220,12 @@ int steps_per_pass(const wafer_batch *b)
     const int R = b->g.R;
     const int K = R == 1 ? 3 : 2;
     const bool fused = b->step_variant < 0 ? WAFER_BATCH_FUSED_BY_DEFAULT[R] : b->step_variant == 1;
-    if (!fused || wafer_batch_stepk_lds_bytes(R, K) == 0) return 1;
+    if (!fused || wafer_batch_stepk_lds_bytes(b->dtype, R, K) == 0) return 1;
     return K;
 }
 
 // a call's remainder of two steps is one pass where the two-step instantiation exists beside the K-step one
-bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->g.R, 2) != 0; }
+bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->dtype, b->g.R, 2) != 0; }
 
 // the fused pass's workgroup table (wafer_batch_fused_table) on the device, for this active set
 int build_blocks_fused(wafer_batch *b, const uint8_t *active, int K)
@@ -245,7 +257,7 @@ int observables(wafer_batch *b, const uint8_t *active)
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
     RoctxRange range_("wafer_batch_observables");
-    const hipError_t e = wafer_entry_batch_observables(b->g.R, b->g, b->mem_dev, b->act_dev, nact, b->obs_ntx, b->obs_nty, b->obs_nb,
+    const hipError_t e = wafer_entry_batch_observables(b->f32, b->g.R, b->g, b->mem_dev, b->act_dev, nact, b->obs_ntx, b->obs_nty, b->obs_nb,
                                                        b->obs_zchunk, b->swz, b->partials, b->sums, b->s);
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched observables launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(b->sums_host, b->sums, sizeof(double) * 4 * b->n, hipMemcpyDeviceToHost, b->s));
@@ -271,7 +283,7 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     int nact = 0;
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
-    const hipError_t e = wafer_entry_batch_normalise(b->g, b->mem_dev, b->act_dev, nact, norm2_dev, stride, b->s);
+    const hipError_t e = wafer_entry_batch_normalise(b->f32, b->g, b->mem_dev, b->act_dev, nact, norm2_dev, stride, b->s);
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -280,7 +292,7 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
 // member m's state l as a logical pointer (plane 0, row 0), like the views' arrays
 void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
 {
-    return static_cast<char *>(b->slots[l]) + ((size_t)m * b->stride + (size_t)b->g.base_off) * 8;
+    return static_cast<char *>(b->slots[l]) + ((size_t)m * b->stride + (size_t)b->g.base_off) * b->esz;
 }
 
 // slots [0, n) exist (zeros: frames, pads and guard zones of every member)
@@ -288,9 +300,9 @@ int ensure_slots(wafer_batch *b, uint32_t n)
 {
     while (b->slots.size() < n) {
         void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, b->stride * b->n * 8));
+        HIP_TRY(hipMalloc(&p, b->stride * b->n * b->esz));
         b->slots.push_back(p);
-        HIP_TRY(hipMemsetAsync(p, 0, b->stride * b->n * 8, b->s));
+        HIP_TRY(hipMemsetAsync(p, 0, b->stride * b->n * b->esz, b->s));
     }
     return WAFER_OK;
 }
@@ -316,7 +328,7 @@ int push_states(wafer_batch *b, const uint8_t *active)
     for (uint32_t m = 0; m < b->n; ++m) {
         if (active && !active[m]) continue;
         const wafer_ctx *c = b->views[m];
-        HIP_TRY(hipMemcpyAsync(alloc_base(c, slot_ptr(b, b->nst[m], m)), alloc_base(c, c->phi[c->cur]), b->stride * 8, hipMemcpyDeviceToDevice, b->s));
+        HIP_TRY(hipMemcpyAsync(alloc_base(c, slot_ptr(b, b->nst[m], m)), alloc_base(c, c->phi[c->cur]), b->stride * b->esz, hipMemcpyDeviceToDevice, b->s));
         ++b->nst[m];
     }
     return WAFER_OK;
@@ -327,7 +339,7 @@ int ensure_gs(wafer_batch *b)
 {
     if (b->gs_scal) return WAFER_OK;
     const size_t nsc = (size_t)b->gs_stride * b->n;
-    HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * (size_t)b->gs_nb * b->n));
+    HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * (size_t)std::max(b->gs_nb, b->n2_nb) * b->n));
     HIP_TRY(hipHostMalloc((void **)&b->gs_host, sizeof(double) * nsc, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->gs_scal, sizeof(double) * nsc));
     HIP_TRY(hipMemsetAsync(b->gs_scal, 0, sizeof(double) * nsc, b->s));
@@ -345,9 +357,9 @@ int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int l
     a.scal_stride = b->gs_stride;
     a.coef_slot = coef_slot;
     a.mstride = (long long)b->stride;
-    a.lower = lower >= 0 ? static_cast<const double *>(slot_ptr(b, (uint32_t)lower, 0)) : nullptr;
-    a.dotwith = dotwith >= 0 ? static_cast<const double *>(slot_ptr(b, (uint32_t)dotwith, 0)) : nullptr;
-    const hipError_t e = wafer_entry_batch_gs(mode, a, b->mem_dev, b->act_dev, nact, b->gs_scal, out_slot, b->gs_partials, b->s);
+    a.lower = lower >= 0 ? slot_ptr(b, (uint32_t)lower, 0) : nullptr;
+    a.dotwith = dotwith >= 0 ? slot_ptr(b, (uint32_t)dotwith, 0) : nullptr;
+    const hipError_t e = wafer_entry_batch_gs(b->f32, mode, a, b->mem_dev, b->act_dev, nact, b->gs_scal, out_slot, b->gs_partials, b->s);
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram-Schmidt launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -379,6 +391,8 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
     TRY(sync_members(b));
     TRY(build_blocks(b, active));
     const int K = wnum ? 1 : steps_per_pass(b);
+    // excited steps compute in fp64 on every dtype, as a context's do: an f32fast batch takes the f32 step there
+    const int step_dtype = (wnum && b->dtype == WAFER_F32_FAST) ? (int)WAFER_F32 : b->dtype;
     const bool have2 = have_two_step(b, K);
     if (K > 1) TRY(build_blocks_fused(b, active, K));
     int nact = 0;
@@ -391,8 +405,8 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
         while (left > 0) {   // no host synchronisation in here: every scalar stays on the device
             const int k = wafer_batch_next_pass(left, K, have2);
             const int flip = (int)(launches & 1);
-            const hipError_t e = k > 1 ? wafer_entry_batch_stepk(b->g.R, k, b->g, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
-                                       : wafer_entry_batch_step(b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s);
+            const hipError_t e = k > 1 ? wafer_entry_batch_stepk(step_dtype, b->g.R, k, b->g, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
+                                       : wafer_entry_batch_step(step_dtype, b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s);
             if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
             ++launches;
             ++(k > 1 ? b->n_fused_passes : b->n_single_steps);
@@ -536,9 +550,11 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     const wafer_params &p0 = members[0];
     const int R = p0.central_difference;
     const int G = p0.halo_depth ? (int)p0.halo_depth : R;
-    const WaferGeom g = wafer_make_geom((int)p0.nx, (int)p0.ny, (int)p0.nz, R, G, 0, (int)p0.nz, 8);
+    const bool f32 = p0.dtype != WAFER_F64;
+    const size_t esz = f32 ? 4 : 8;
+    const WaferGeom g = wafer_make_geom((int)p0.nx, (int)p0.ny, (int)p0.nz, R, G, 0, (int)p0.nz, (int)esz);   // wafer_ctx_create's
     size_t bytes = 0;
-    if (__builtin_mul_overflow((size_t)g.total, (size_t)n_members, &bytes) || __builtin_mul_overflow(bytes, (size_t)8, &bytes))
+    if (__builtin_mul_overflow((size_t)g.total, (size_t)n_members, &bytes) || __builtin_mul_overflow(bytes, esz, &bytes))
         return fail(WAFER_ERR_INVALID, "%u members of %lld padded cells overflow the size of one allocation", n_members, (long long)g.total);
 
     int ndev = 0;
@@ -557,8 +573,12 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     b->num_cus = cus > 0 ? cus : 256;
     b->tune = wafer_tuning_from_env();
     b->stride = (size_t)g.total;
+    b->dtype = (int)p0.dtype;
+    b->f32 = f32;
+    b->esz = esz;
     b->nst.assign(n_members, 0);
     b->gs_nb = wafer_gs_blocks(g);
+    b->n2_nb = f32 ? wafer_rownorm2_blocks(g, (int)esz, b->num_cus) : 0;
     for (uint32_t m = 0; m < n_members; ++m) b->gs_stride = std::max(b->gs_stride, 1 + (int)members[m].max_states);
 #define HIP_TRYB(expr)                                                                               \
     do {                                                                                             \
@@ -580,13 +600,20 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     HIP_TRYB(hipMemsetAsync(b->view_scal, 0, sizeof(double) * SCAL_SLOTS * n_members, b->s));
     HIP_TRYB(hipHostMalloc((void **)&b->view_scal_host, sizeof(double) * SCAL_SLOTS * n_members, hipHostMallocDefault));
 
-    // observables: the partition wafer_launch_observables_lds gives a single context of this shape
+    // observables: the partition wafer_launch_observables_lds gives a single context of this shape and storage type -- 16 bytes
+    // per lane, so tiles 128 wide on doubles and 256 wide on floats (WaferLdsCfg::TX), and the z-chunk that follows from them
     {
         const int NW = R <= 2 ? 8 : 4;
-        const int TX = 128, TY = 2 * NW;
-        b->obs_zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, 2 * (NW / 4), b->num_cus)
-                        : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, 2 * (NW / 4), b->num_cus)
-                                 : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, 2 * (NW / 4), b->num_cus);
+        const int TX = f32 ? WaferLdsCfg<float, 1, 2>::TX : WaferLdsCfg<double, 1, 2>::TX, TY = 2 * NW;
+        const int ry = 2 * (NW / 4);
+        if (f32)
+            b->obs_zchunk = R == 1   ? wafer_lds_zchunk<float, 1>(b->tune, g, g.nzl, ry, b->num_cus)
+                            : R == 2 ? wafer_lds_zchunk<float, 2>(b->tune, g, g.nzl, ry, b->num_cus)
+                                     : wafer_lds_zchunk<float, 3>(b->tune, g, g.nzl, ry, b->num_cus);
+        else
+            b->obs_zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, ry, b->num_cus)
+                            : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, ry, b->num_cus)
+                                     : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, ry, b->num_cus);
         b->obs_ntx = (g.nx + TX - 1) / TX;
         b->obs_nty = (g.ny + TY - 1) / TY;
         b->obs_nb = b->obs_ntx * b->obs_nty * ((g.nzl + b->obs_zchunk - 1) / b->obs_zchunk);
@@ -608,17 +635,20 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
         b->views.push_back(c);
         c->P = members[m];
         c->g = g;
-        c->esz = 8;
+        c->f32 = f32;   // as wafer_ctx_create sets them
+        c->f32_arith = members[m].dtype == WAFER_F32_FAST;
+        c->esz = esz;
         c->num_cus = b->num_cus;
         c->tune = b->tune;
         c->bx = (g.px + 63) / 64;
         c->by = (g.py + 3) / 4;
         c->s_main = c->s_aux = b->s;
         c->div_plan = wafer_divplan_make(wafer_stencil_den(R, members[m].dn, members[m].mass));
-        if (members[m].flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = 0;
+        if (c->f32_arith) c->div_plan_f = wafer_divplan_make_f32((float)wafer_stencil_den(R, members[m].dn, members[m].mass));
+        if (members[m].flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = c->div_plan_f.checked = 0;
         void **arr[4] = {&c->phi[0], &c->phi[1], &c->v, &c->potsub};
         for (int k = 0; k < 4; ++k)
-            *arr[k] = static_cast<char *>(b->alloc[k]) + ((size_t)m * b->stride + (size_t)g.base_off) * 8;
+            *arr[k] = static_cast<char *>(b->alloc[k]) + ((size_t)m * b->stride + (size_t)g.base_off) * esz;
         c->scal = b->view_scal + (size_t)m * SCAL_SLOTS;
         c->scal_host = b->view_scal_host + (size_t)m * SCAL_SLOTS;
         c->kernel_name = "wafer_k_batch_step";
@@ -632,6 +662,9 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
         e.den = c->div_plan.den;
         e.zh = c->div_plan.zh;
         e.zl = c->div_plan.zl;
+        e.den_f = (float)c->div_plan.den;   // (wafer_den<float> of a context's WaferStepArgs)
+        e.zh_f = c->div_plan_f.checked ? c->div_plan_f.zh : 0.f;
+        e.zl_f = c->div_plan_f.checked ? c->div_plan_f.zl : 0.f;
     }
     HIP_TRYB(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * n_members, hipMemcpyHostToDevice));
     HIP_TRYB(hipStreamSynchronize(b->s));
@@ -745,7 +778,12 @@ int wafer_batch_norm2(wafer_batch *b, double *out)
     TRY(sync_members(b));
     int nact = 0;
     TRY(upload_active(b, nullptr, &nact));
-    TRY(gs_launch(b, WAFER_GS_NORM2, nact, 0, 0, -1, -1, 0));
+    if (b->f32) {   // the partition of a context's wafer_norm2: the same double (fp64 keeps the batch's own partition)
+        const hipError_t e = wafer_entry_batch_rownorm2(b->g, b->mem_dev, b->act_dev, nact, b->n2_nb, b->gs_scal, b->gs_stride, 0, b->gs_partials, b->s);
+        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
+    } else {
+        TRY(gs_launch(b, WAFER_GS_NORM2, nact, 0, 0, -1, -1, 0));
+    }
     HIP_TRY(hipMemcpyAsync(b->gs_host, b->gs_scal, sizeof(double) * (size_t)b->gs_stride * b->n, hipMemcpyDeviceToHost, b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
     for (uint32_t m = 0; m < b->n; ++m) out[m] = b->gs_host[(size_t)m * b->gs_stride];
@@ -815,7 +853,7 @@ int wafer_batch_clone_state_to_phi(wafer_batch *b, const uint8_t *active, uint32
     for (uint32_t m = 0; m < b->n; ++m) {
         if (active && !active[m]) continue;
         wafer_ctx *c = b->views[m];
-        HIP_TRY(hipMemcpyAsync(alloc_base(c, c->phi[c->cur]), alloc_base(c, slot_ptr(b, idx, m)), b->stride * 8, hipMemcpyDeviceToDevice, b->s));
+        HIP_TRY(hipMemcpyAsync(alloc_base(c, c->phi[c->cur]), alloc_base(c, slot_ptr(b, idx, m)), b->stride * b->esz, hipMemcpyDeviceToDevice, b->s));
         c->have_phi = true;
         c->halo_valid = 0;
     }
@@ -856,19 +894,21 @@ int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n)
 {
     if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
     static const char *const stencils[] = {"", "ThreePoint", "FivePoint", "SevenPoint"};
+    static const char *const dtypes[] = {"f64", "f32", "f32fast"};
+    static const char *const types[] = {"", ",float,double", ",float,float"};   // the kernels' <.., T, C> beside the fp64 default
     const int R = b->g.R, K = steps_per_pass(b);
     char kernel[64], tile[32];
     const char *remainder = "none";
     if (K > 1) {
-        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d>", R, K);
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d%s>", R, K, types[b->dtype]);
         snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCHK_TX, WAFER_BATCHK_TY);
         remainder = have_two_step(b, K) ? "stepk2+step" : "step";
     } else {
-        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d>", R);
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d%s>", R, types[b->dtype]);
         snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCH_TX, WAFER_BATCH_TY);
     }
-    snprintf(buf, n, "stencil=%s kernel=%s steps_per_pass=%d tile=%s lds_bytes=%d remainder=%s variant=%d", stencils[R], kernel, K, tile,
-             K > 1 ? wafer_batch_stepk_lds_bytes(R, K) : 0, remainder, b->step_variant);
+    snprintf(buf, n, "stencil=%s kernel=%s steps_per_pass=%d tile=%s lds_bytes=%d remainder=%s variant=%d dtype=%s", stencils[R], kernel, K, tile,
+             K > 1 ? wafer_batch_stepk_lds_bytes(b->dtype, R, K) : 0, remainder, b->step_variant, dtypes[b->dtype]);
     return WAFER_OK;
 }
 

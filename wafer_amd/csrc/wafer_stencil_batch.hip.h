@@ -11,6 +11,12 @@
 //    partial per workgroup at the same index -- then wafer_k_reduce's tree, per member.  The values are loaded straight from
 //    global memory instead of through the LDS tile; the sums see the same operands.
 //  - normalise: wafer_k_row_op<2>'s expression, x / sqrt(norm2) by wafer_div_invariant.
+//
+// Storage and arithmetic types.  T is what the arrays hold, C what the step computes in: <double, double> (dtype f64),
+// <float, double> (f32: float arrays, every operand widened, the result of EVERY step rounded to float) and <float, float>
+// (f32fast: dt, den, V, a, b and every operation of the step are float; the member's own fp32 division plan).  a and b are formed
+// from the stored V in C, as the single context's default kernels form them.  Observables, normalise and the sums compute in
+// double on whatever the arrays hold; normalise rounds its quotient to T.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wafer_geom.h"
@@ -26,11 +32,19 @@ struct WaferBatchMember {
     double dt;
     double den, zh, zl;      // the member's division plan (WaferDivPlan of c dn^2 m)
     double potsub_scalar;
+    float den_f, zh_f, zl_f; // the member's fp32 plan (f32fast: WaferDivPlanF of (float)den; zh_f == 0: none, or not checked)
     int short_forms;         // v_in_range && the plan is checked (WaferStepArgs::v_in_range of a single context)
     int potsub_kind;
     int cur;                 // which phi buffer holds the wavefunction
-    int pad;
 };
+
+// the member's division by c dn^2 m in the arithmetic type C (wafer_den of a single context's WaferStepArgs)
+template <typename C>
+__device__ __forceinline__ WaferDen<C> wafer_batch_den(const WaferBatchMember &m, bool sf)
+{
+    if constexpr (std::is_same_v<C, double>) return WaferDen<double>{m.den, m.zh, m.zl, sf};
+    else return WaferDen<float>{m.den_f, m.zh_f, m.zl_f, sf && m.zh_f != 0.f};
+}
 
 // one workgroup of a batched step: WaferBatchBlock (wafer_batch_plan.h); the one-step kernel's tiles are 64 x 4 work cells
 
@@ -40,41 +54,41 @@ struct WaferBatchMember {
 // One time step of every member in the table.  Block (64, 4): one work cell per lane, marching its z-chunk with a register
 // queue of 2R+1 planes along z; x and y neighbours come from global memory (the rows of the tile and its halo are L1 / L2
 // hits).  flip: the step's parity within the call (the source buffer of a member is phi[cur ^ flip]).
-template <int R>
+template <int R, typename T = double, typename C = double>
 __global__ __launch_bounds__(256) void wafer_k_batch_step(WaferGeom g, const WaferBatchMember *__restrict__ mem,
                                                           const WaferBatchBlock *__restrict__ blocks, int flip)
 {
     const WaferBatchBlock bk = blocks[blockIdx.x];
     const WaferBatchMember &m = mem[bk.member];
     const int sel = (m.cur ^ flip) & 1;
-    const double *__restrict__ phi = static_cast<const double *>(m.phi[sel]);
-    double *__restrict__ out = static_cast<double *>(m.phi[sel ^ 1]);
-    const double *__restrict__ pv = static_cast<const double *>(m.v);
+    const T *__restrict__ phi = static_cast<const T *>(m.phi[sel]);
+    T *__restrict__ out = static_cast<T *>(m.phi[sel ^ 1]);
+    const T *__restrict__ pv = static_cast<const T *>(m.v);
     const int i = bk.x0 + threadIdx.x;
     const int j = bk.y0 + threadIdx.y;
     if (i >= g.nx || j >= g.ny) return;
     const bool sf = m.short_forms != 0;   // (a scalar load: the branches it selects are scalar too)
-    const WaferDen<double> den{m.den, m.zh, m.zl, sf};
-    const double dt = m.dt;
+    const WaferDen<C> den = wafer_batch_den<C>(m, sf);
+    const C dt = (C)m.dt;
     const long long col = (long long)(j + R) * g.pitch + g.xoff + (i + R);
-    const double *p = phi + col;
-    double zq[2 * R + 1];
+    const T *p = phi + col;
+    C zq[2 * R + 1];
 #pragma unroll
-    for (int q = 1; q <= 2 * R; ++q) zq[q] = p[(long long)(bk.z0 + q - 1 - R) * g.plane];
+    for (int q = 1; q <= 2 * R; ++q) zq[q] = (C)p[(long long)(bk.z0 + q - 1 - R) * g.plane];
     for (int z = bk.z0; z < bk.z1; ++z) {
 #pragma unroll
         for (int q = 0; q < 2 * R; ++q) zq[q] = zq[q + 1];
         const long long o = (long long)z * g.plane;
-        zq[2 * R] = p[o + (long long)R * g.plane];
-        double xs[2 * R + 1], ys[2 * R + 1];
+        zq[2 * R] = (C)p[o + (long long)R * g.plane];
+        C xs[2 * R + 1], ys[2 * R + 1];
 #pragma unroll
         for (int d = -R; d <= R; ++d) {
-            xs[d + R] = (d == 0) ? zq[R] : p[o + d];
-            ys[d + R] = (d == 0) ? zq[R] : p[o + (long long)d * g.pitch];
+            xs[d + R] = (d == 0) ? zq[R] : (C)p[o + d];
+            ys[d + R] = (d == 0) ? zq[R] : (C)p[o + (long long)d * g.pitch];
         }
-        const double w = zq[R];
-        const double S = wafer_stencil_sum<double, R>(xs, ys, zq, w);
-        out[col + o] = wafer_update_v<double>(w, pv[col + o], dt, S, den, sf);
+        const C w = zq[R];
+        const C S = wafer_stencil_sum<C, R>(xs, ys, zq, w);
+        out[col + o] = (T)wafer_update_v<C>(w, (C)pv[col + o], dt, S, den, sf);
     }
 }
 
@@ -98,7 +112,12 @@ __global__ __launch_bounds__(256) void wafer_k_batch_step(WaferGeom g, const Waf
 // Dirichlet frame: a cell of an intermediate level outside the work area (frame, pad, planes outside [G, G + nzl)) is set to 0,
 // never computed; the last level writes work cells only.
 // z-chunks: level k is computed on planes [z0 - (K-k) R, z1 + (K-k) R); phi0 is loaded from [z0 - K R, z1 + K R).
-template <int R, int K>
+// Float storage (T = float): global loads and stores are float, the queues and the LDS planes hold the arithmetic type C --
+// double for f32 (the arrangement of wafer_f32_wide, wafer_storage.h: nothing inside the CU differs from the fp64 kernel),
+// float for f32fast (half the LDS) -- and every level's result is rounded to float AS IT IS PRODUCED, before it enters a queue or
+// a ring: the next level reads what a single step would have stored and loaded again, so the bits are those of K single steps.
+// QB: bytes of a queue / LDS element (sizeof(C)).
+template <int R, int K, int QB = 8>
 struct WaferBatchKCfg {
     static constexpr int TX = WAFER_BATCHK_TX, TY = WAFER_BATCHK_TY, NT = 256;
     static constexpr int H = K * R;                              // phi0 halo per side
@@ -107,38 +126,44 @@ struct WaferBatchKCfg {
     static constexpr int NB = R + 1;                             // ring depth of an intermediate level
     static constexpr int ncells(int k) { return (TX + 2 * (K - k) * R) * (TY + 2 * (K - k) * R); }   // level k's region
     static constexpr int cpt(int k) { return (ncells(k) + NT - 1) / NT; }                            // cells per thread
-    static constexpr int LDS_BYTES = 8 * PLANE * (2 + (K - 1) * NB);
+    static constexpr int LDS_BYTES = QB * PLANE * (2 + (K - 1) * NB);
     // Loads carry no bounds predicates; the tile's overhang lies in the allocation's zero guard zone (wafer_geom.h), checked by
     // hand for K R <= 6 (R <= 3, K <= 3 with K R <= gz = 3 R):
     //  rows:    work rows y0 - K R .. y0 + TY - 1 + K R with y0 + TY - 1 <= ny + TY - 2, i.e. padded rows -(K-1) R .. ny + TY - 2
     //           + (K+1) R; the allocation holds padded rows -gy .. ny + 2 R + gy - 1 with gy = 16 + 3 R: needs TY - 2 + (K+1) R
     //           <= 5 R + 15, true for TY <= 16.
-    //  columns: element xoff + R + x = 16 + x for work x in -K R .. 64 ceil(nx / 64) + K R - 1: at least 16 - K R >= 10, at most
-    //           15 + 64 ceil(nx / 64) + K R <= 21 + 128 ceil(nx / 128) < pitch = 32 + 128 ceil(nx / 128).
+    //  columns: (8-byte elements, wafer_make_geom(..., 8)) element xoff + R + x = 16 + x for work x in -K R .. 64 ceil(nx / 64)
+    //           + K R - 1: at least 16 - K R >= 10, at most 15 + 64 ceil(nx / 64) + K R <= 21 + 128 ceil(nx / 128) < pitch =
+    //           32 + 128 ceil(nx / 128).
+    //           (4-byte elements, wafer_make_geom(..., 4): xoff = 32 - R, rows of 256-element tiles, pitch = 64 + 256 ceil(nx /
+    //           256)) element 32 + x: at least 32 - K R >= 26, at most 31 + 64 ceil(nx / 64) + K R <= 37 + 256 ceil(nx / 256)
+    //           < pitch.
+    //  rows and planes count elements, not bytes (gy, gz, G do not depend on the element size): the same for both geometries.
     //  planes:  z0 - K R >= G - K R >= -gz and z1 + K R - 1 <= G + nzl + K R - 1 < lz + gz = nzl + 2 G + 3 R.
-    static_assert(TX == 64 && TY <= 16 && K * R <= 6 && K <= 3, "the guard-zone check above");
+    static_assert(TX == 64 && TY <= 16 && K * R <= 6 && K <= 3, "the guard-zone check above (both the 8-byte and the 4-byte geometry)");
+    static_assert(QB == 8 || QB == 4, "queues and LDS hold double or float");
     static_assert(LDS_BYTES <= 65536, "static LDS");
 };
 
-template <int R, int K>
+template <int R, int K, typename T = double, typename C = double>
 __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const WaferBatchMember *__restrict__ mem,
                                                            const WaferBatchBlock *__restrict__ blocks, int flip)
 {
-    using Cfg = WaferBatchKCfg<R, K>;
+    using Cfg = WaferBatchKCfg<R, K, (int)sizeof(C)>;
     constexpr int NT = Cfg::NT, W0 = Cfg::W0, PLANE = Cfg::PLANE, NB = Cfg::NB, H = Cfg::H;
     constexpr int C0 = Cfg::cpt(0), C1 = Cfg::cpt(1), NQ = 2 * R + 1, NV = (K - 1) * R + 1;
-    __shared__ double lds0[2 * PLANE];
-    __shared__ double ldsk[(K - 1) * NB * PLANE];
+    __shared__ C lds0[2 * PLANE];
+    __shared__ C ldsk[(K - 1) * NB * PLANE];
 
     const WaferBatchBlock bk = blocks[blockIdx.x];
     const WaferBatchMember &m = mem[bk.member];
     const int sel = (m.cur ^ flip) & 1;
-    const double *__restrict__ phi = static_cast<const double *>(m.phi[sel]);
-    double *__restrict__ out = static_cast<double *>(m.phi[sel ^ 1]);
-    const double *__restrict__ pv = static_cast<const double *>(m.v);
+    const T *__restrict__ phi = static_cast<const T *>(m.phi[sel]);
+    T *__restrict__ out = static_cast<T *>(m.phi[sel ^ 1]);
+    const T *__restrict__ pv = static_cast<const T *>(m.v);
     const bool sf = m.short_forms != 0;   // (workgroup-uniform: a scalar branch)
-    const WaferDen<double> den{m.den, m.zh, m.zl, sf};
-    const double dt = m.dt;
+    const WaferDen<C> den = wafer_batch_den<C>(m, sf);
+    const C dt = (C)m.dt;
     const int tid = threadIdx.x;
 
     // ---- this thread's cells ---------------------------------------------------------------------
@@ -157,27 +182,27 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
 
     // ---- prologue: level 1's first plane is zf; the phi0 queue holds planes zf - R .. zf + R ------
     const int zf = bk.z0 - (K - 1) * R, zend = bk.z1 + (K - 1) * R;
-    double q0[NQ][C0];
-    double qk[K - 1][NQ][C1];   // levels 1 .. K-1, planes p - R .. p + R around the plane p the next level is computed on
-    double vq[NV][C1];          // V of planes z - (K-1) R .. z
+    C q0[NQ][C0];
+    C qk[K - 1][NQ][C1];   // levels 1 .. K-1, planes p - R .. p + R around the plane p the next level is computed on
+    C vq[NV][C1];          // V of planes z - (K-1) R .. z
 #pragma unroll
     for (int mq = 0; mq < NQ; ++mq)
 #pragma unroll
-        for (int q = 0; q < C0; ++q) q0[mq][q] = phi[(long long)(zf - R + mq) * g.plane + goff[q]];
+        for (int q = 0; q < C0; ++q) q0[mq][q] = (C)phi[(long long)(zf - R + mq) * g.plane + goff[q]];
 #pragma unroll
     for (int l = 0; l < K - 1; ++l)
 #pragma unroll
         for (int mq = 0; mq < NQ; ++mq)
 #pragma unroll
-            for (int q = 0; q < C1; ++q) qk[l][mq][q] = 0.0;   // (zeros that never reach an output: a level starts on its first valid plane)
+            for (int q = 0; q < C1; ++q) qk[l][mq][q] = C(0);   // (zeros that never reach an output: a level starts on its first valid plane)
 #pragma unroll
     for (int j = 0; j < NV; ++j)
 #pragma unroll
-        for (int q = 0; q < C1; ++q) vq[j][q] = 0.0;
+        for (int q = 0; q < C1; ++q) vq[j][q] = C(0);
 #pragma unroll
-    for (int q = 0; q < C1; ++q) vq[NV - 1][q] = pv[(long long)zf * g.plane + goff[q]];
+    for (int q = 0; q < C1; ++q) vq[NV - 1][q] = (C)pv[(long long)zf * g.plane + goff[q]];
     {
-        double *t0 = lds0 + (zf & 1) * PLANE;
+        C *t0 = lds0 + (zf & 1) * PLANE;
 #pragma unroll
         for (int q = 0; q < C0; ++q) t0[lpos[q]] = q0[R][q];
     }
@@ -187,18 +212,18 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
         const bool more = z + 1 < zend;
         const long long zo = (long long)z * g.plane;
         // ---- 1. prefetch phi0 plane z + R + 1 and V plane z + 1 ------------------------------------
-        double pre[C0], pre_v[C1];
+        C pre[C0], pre_v[C1];
 #pragma unroll
-        for (int q = 0; q < C0; ++q) pre[q] = 0.0;
+        for (int q = 0; q < C0; ++q) pre[q] = C(0);
 #pragma unroll
-        for (int q = 0; q < C1; ++q) pre_v[q] = 0.0;
+        for (int q = 0; q < C1; ++q) pre_v[q] = C(0);
         if (more) {
 #pragma unroll
-            for (int q = 0; q < C0; ++q) pre[q] = phi[zo + (long long)(R + 1) * g.plane + goff[q]];
+            for (int q = 0; q < C0; ++q) pre[q] = (C)phi[zo + (long long)(R + 1) * g.plane + goff[q]];
 #pragma unroll
-            for (int q = 0; q < C1; ++q) pre_v[q] = pv[zo + g.plane + goff[q]];
+            for (int q = 0; q < C1; ++q) pre_v[q] = (C)pv[zo + g.plane + goff[q]];
             // ---- 2. stage phi0 plane z + 1 ----------------------------------------------------------
-            double *nt = lds0 + ((z + 1) & 1) * PLANE;
+            C *nt = lds0 + ((z + 1) & 1) * PLANE;
 #pragma unroll
             for (int q = 0; q < C0; ++q) nt[lpos[q]] = q0[R + 1][q];
         }
@@ -210,8 +235,8 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
             const int kw = g.z_begin + (p - g.G);
             // the plane is one this chunk needs of level k, and (intermediate levels) a work plane
             const bool on = p >= bk.z0 - (K - k) * R && (k == K || (kw >= 0 && kw < g.nz));
-            const double *src = k == 1 ? lds0 + (z & 1) * PLANE : ldsk + ((k - 2) * NB + ((p % NB) + NB) % NB) * PLANE;
-            double *ring = ldsk + ((k - 1 < K - 1 ? k - 1 : 0) * NB + ((p % NB) + NB) % NB) * PLANE;
+            const C *src = k == 1 ? lds0 + (z & 1) * PLANE : ldsk + ((k - 2) * NB + ((p % NB) + NB) % NB) * PLANE;
+            C *ring = ldsk + ((k - 1 < K - 1 ? k - 1 : 0) * NB + ((p % NB) + NB) % NB) * PLANE;
             if (k < K) {
 #pragma unroll
                 for (int mq = 0; mq + 1 < NQ; ++mq)
@@ -220,21 +245,22 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
             }
 #pragma unroll
             for (int q = 0; q < Ck; ++q) {
-                double val = 0.0;
+                C val = C(0);
                 const bool act = on && tid + q * NT < Nk && ((work >> q) & 1u);
                 if (act) {
-                    double xs[NQ], ys[NQ], zz[NQ];
+                    C xs[NQ], ys[NQ], zz[NQ];
 #pragma unroll
                     for (int d = 0; d < NQ; ++d) zz[d] = k == 1 ? q0[d][q] : qk[k >= 2 ? k - 2 : 0][d][q];
-                    const double w = zz[R];
+                    const C w = zz[R];
 #pragma unroll
                     for (int d = -R; d <= R; ++d) {
                         xs[d + R] = d == 0 ? w : src[lpos[q] + d];
                         ys[d + R] = d == 0 ? w : src[lpos[q] + d * W0];
                     }
-                    const double S = wafer_stencil_sum<double, R>(xs, ys, zz, w);
-                    val = wafer_update_v<double>(w, vq[(K - k) * R][q], dt, S, den, sf);
-                    if (k == K) out[(long long)p * g.plane + goff[q]] = val;
+                    const C S = wafer_stencil_sum<C, R>(xs, ys, zz, w);
+                    const T stored = (T)wafer_update_v<C>(w, vq[(K - k) * R][q], dt, S, den, sf);   // every level rounds to the storage type
+                    val = (C)stored;
+                    if (k == K) out[(long long)p * g.plane + goff[q]] = stored;
                 }
                 if (k < K) {
                     qk[k - 1 < K - 1 ? k - 1 : 0][NQ - 1][q] = val;
@@ -260,15 +286,17 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
 }
 
 // compute_observables (grid.rs:303-445) for the members act[blockIdx.y], on the partition of the single context's observables
-// launch (wafer_launch_observables_lds: NW waves x RY = 2 rows x VEC = 2 cells per lane, tiles of 128 x 2 NW, z-chunks of
-// `zchunk` planes, gridDim.x workgroups per member, swizzled as wafer_k_step_lds swizzles them).  partials[(member * 4 + q) *
+// launch (wafer_launch_observables_lds: NW waves x RY = 2 rows x VEC cells per lane -- 16 bytes of the storage type T: 2 doubles,
+// 4 floats -- so tiles of 64 VEC x 2 NW, i.e. 128 x 2 NW (fp64) or 256 x 2 NW (float storage), z-chunks of `zchunk` planes,
+// gridDim.x workgroups per member, swizzled as wafer_k_step_lds swizzles them).  Float values are widened; every product and sum
+// is fp64, as in the context's kernel (its C is double for every dtype).  partials[(member * 4 + q) *
 // gridDim.x + workgroup]: the four sums energy, norm2, pot_sub, r2.
-template <int R, int NW>
+template <int R, int NW, typename T = double>
 __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(WaferGeom g, const WaferBatchMember *__restrict__ mem,
                                                                      const int *__restrict__ act, int ntx, int nty, int zchunk,
                                                                      int swz, double *__restrict__ partials)
 {
-    constexpr int VEC = 2, RY = 2, TX = 64 * VEC, TY = NW * RY;
+    constexpr int VEC = 16 / (int)sizeof(T), RY = 2, TX = 64 * VEC, TY = NW * RY;
     __shared__ double red[NW];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
@@ -287,9 +315,9 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(WaferGeom g
     const int xi = x0 + xl;
     const int zs = g.G + tz_i * zchunk;
     const int ze = min(zs + zchunk, g.G + g.nzl);
-    const double *__restrict__ phi = static_cast<const double *>(m.phi[m.cur]);
-    const double *__restrict__ pv = static_cast<const double *>(m.v);
-    const double *__restrict__ ps = static_cast<const double *>(m.potsub);
+    const T *__restrict__ phi = static_cast<const T *>(m.phi[m.cur]);
+    const T *__restrict__ pv = static_cast<const T *>(m.v);
+    const T *__restrict__ ps = static_cast<const T *>(m.potsub);
     const WaferDen<double> den{m.den, m.zh, m.zl, m.short_forms != 0};
     const int pk = m.potsub_kind;
     const double pscal = m.potsub_scalar;
@@ -305,18 +333,18 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(WaferGeom g
                 if (y < g.ny && xi + v < g.nx) {
                     const long long c = zo + (long long)(y + R) * g.pitch + g.xoff + R + xi + v;
                     double xs[2 * R + 1], ys[2 * R + 1], zz[2 * R + 1];
-                    const double w = phi[c];
+                    const double w = (double)phi[c];
 #pragma unroll
                     for (int d = -R; d <= R; ++d) {
-                        xs[d + R] = d == 0 ? w : phi[c + d];
-                        ys[d + R] = d == 0 ? w : phi[c + (long long)d * g.pitch];
-                        zz[d + R] = d == 0 ? w : phi[c + (long long)d * g.plane];
+                        xs[d + R] = d == 0 ? w : (double)phi[c + d];
+                        ys[d + R] = d == 0 ? w : (double)phi[c + (long long)d * g.pitch];
+                        zz[d + R] = d == 0 ? w : (double)phi[c + (long long)d * g.plane];
                     }
                     const double S = wafer_stencil_sum<double, R>(xs, ys, zz, w);
-                    const double vv = pv[c];
+                    const double vv = (double)pv[c];
                     ob_e += vv * w * w - wafer_div_invariant<double>(w * S, den); // grid.rs:325-332
                     ob_n += w * w;                                                // grid.rs:407
-                    if (pk == 2) ob_v += w * w * ps[c];                          // grid.rs:410-418
+                    if (pk == 2) ob_v += w * w * (double)ps[c];                          // grid.rs:410-418
                     else if (pk == 1) ob_v += w * w * pscal;                     // grid.rs:419-424
                     const double dx = (double)(xi + v) - ((double)g.nx + 1.) / 2.;
                     const double dy = (double)y - ((double)g.ny + 1.) / 2.;
@@ -354,7 +382,9 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_reduce(const double 
 }
 
 // normalise_wavefunction (grid.rs:465-468) of the members act[blockIdx.z]: phi /= sqrt(norm2[member * n2_stride]), the
-// expression of wafer_k_row_op<2>.  Block (64, 4) over a 64 x 4 tile of one work plane (blockIdx.y).
+// expression of wafer_k_row_op<2> (the quotient in fp64, rounded to the storage type).  Block (64, 4) over a 64 x 4 tile of one
+// work plane (blockIdx.y).
+template <typename T = double>
 static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(WaferGeom g, const WaferBatchMember *__restrict__ mem,
                                                                       const int *__restrict__ act, int ntx,
                                                                       const double *__restrict__ norm2, int n2_stride)
@@ -365,18 +395,20 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(WaferGeom 
     const int j = (blockIdx.x / ntx) * WAFER_BATCH_TY + threadIdx.y;
     if (i >= g.nx || j >= g.ny) return;
     const double coef = sqrt(norm2[(size_t)member * n2_stride]);
-    double *p = static_cast<double *>(m.phi[m.cur]) + g.at(g.G + (int)blockIdx.y, j + g.R, i + g.R);
-    *p = wafer_div_invariant<double>(*p, coef);
+    T *p = static_cast<T *>(m.phi[m.cur]) + g.at(g.G + (int)blockIdx.y, j + g.R, i + g.R);
+    *p = (T)wafer_div_invariant<double>((double)*p, coef);
 }
 
-// entry points (wafer_tu_batch.hip)
-hipError_t wafer_entry_batch_step(int R, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks,
-                                  int flip, hipStream_t s);
-// the fused pass of K steps; hipErrorInvalidValue where wafer_batch_stepk_lds_bytes(R, K) is 0 (no such instantiation)
-hipError_t wafer_entry_batch_stepk(int R, int K, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
+// entry points (wafer_tu_batch.hip).  dtype: the batch's wafer_dtype as an int -- 0 f64, 1 f32 (float storage, fp64 arithmetic),
+// 2 f32fast (float storage, float arithmetic in the ground-state step).
+hipError_t wafer_entry_batch_step(int dtype, int R, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
+                                  int nblocks, int flip, hipStream_t s);
+// the fused pass of K steps; hipErrorInvalidValue where wafer_batch_stepk_lds_bytes(dtype, R, K) is 0 (no such instantiation)
+hipError_t wafer_entry_batch_stepk(int dtype, int R, int K, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
                                    int nblocks, int flip, hipStream_t s);
-int wafer_batch_stepk_lds_bytes(int R, int K);
-hipError_t wafer_entry_batch_observables(int R, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, int ntx,
-                                         int nty, int nblocks, int zchunk, int swz, double *partials, double *out, hipStream_t s);
-hipError_t wafer_entry_batch_normalise(const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, const double *norm2,
-                                       int n2_stride, hipStream_t s);
+int wafer_batch_stepk_lds_bytes(int dtype, int R, int K);
+// f32 is true for float storage (dtype 1 and 2 alike: observables and normalise compute in fp64)
+hipError_t wafer_entry_batch_observables(bool f32, int R, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact,
+                                         int ntx, int nty, int nblocks, int zchunk, int swz, double *partials, double *out, hipStream_t s);
+hipError_t wafer_entry_batch_normalise(bool f32, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact,
+                                       const double *norm2, int n2_stride, hipStream_t s);

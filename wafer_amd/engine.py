@@ -664,6 +664,12 @@ class Batch:
     a ground-state evolve one launch per pass of K steps (ThreePoint 3, FivePoint 2; steps_per_launch(), dispatch()): the
     same bits.
 
+    dtype: every member's Params.dtype must be the same -- "f64", "f32" (float arrays, fp64 arithmetic) or "f32fast" (float
+    arithmetic in the ground-state step too).  On the float dtypes the arrays and state stores take half the bytes per cell, numpy
+    arrays stay float64 (uploads and load_state round to float, downloads widen), the ground state, observables, normalise
+    and solve are bit for bit a Context of that dtype (every step's result rounded to float, under fused passes as well), and
+    the excited-state calls compute in fp64 with phi rounded to float after the step, the scale and each projection.
+
     Excited states: every member has a state store of its own (capacity Params.max_states; load_state, push_state, ...), and
     evolve(steps, wnum=k) / solve_state(k, ...) normalise and project each member against its first k stored states after
     every step, as Context.evolve(k, steps) does, in 1 + 2 (1 + k) + 1 launches per step for the whole batch.  A member's
@@ -876,7 +882,7 @@ class Batch:
         self._check(self._L.wafer_batch_set_step_variant(self._h, int(variant)))
 
     def dispatch(self) -> dict:
-        """what a ground-state evolve would launch: stencil, kernel, steps_per_pass, tile, lds_bytes, remainder, variant"""
+        """what a ground-state evolve would launch: stencil, kernel, steps_per_pass, tile, lds_bytes, remainder, variant, dtype"""
         buf = C.create_string_buffer(512)
         self._check(self._L.wafer_batch_diag_dispatch(self._h, buf, len(buf)))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split())
