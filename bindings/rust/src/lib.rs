@@ -239,6 +239,9 @@ extern "C" {
         records: *mut wafer_block_record, max_records_per_member: usize, n_records: *mut usize, finals: *mut wafer_observables_output,
         status: *mut c_int,
     ) -> c_int;
+    pub fn wafer_batch_set_gs_variant(b: *mut wafer_batch, variant: c_int) -> c_int;
+    pub fn wafer_batch_diag_gs(b: *mut wafer_batch, wnum: u32, buf: *mut c_char, n: usize) -> c_int;
+    pub fn wafer_batch_diag_gs_steps(b: *mut wafer_batch, onepass: *mut u64, sequential: *mut u64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

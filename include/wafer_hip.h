@@ -508,7 +508,23 @@ int wafer_batch_diag_passes(wafer_batch *b, uint64_t *fused_passes, uint64_t *si
  * nothing; wafer_batch_solve_state alone reports a short store per member instead.
  * One excited step is 1 + 2 (1 + wnum) + 1 launches for the whole batch, with every scalar (norm2, the overlaps) on the
  * device and no host synchronisation between steps.  Sums run over a partition fixed by the shape alone, in a fixed order:
- * a member's bits do not depend on the batch size, on its index or on which other members are active. */
+ * a member's bits do not depend on the batch size, on its index or on which other members are active.
+ *
+ * The one-pass form (wafer_batch_set_gs_variant(b, 1); opt-in, for wnum <= 4): the step, one pass that sums phi'^2 and the raw
+ * overlaps t_j = sum l_j phi' on the un-normalised phi', one reduce, and one apply pass that forms norm = sqrt(sum phi'^2) and
+ * s_j = t_j / norm - sum_{i<j} s_i G_ji from the member's Gram matrix G_ji = sum l_j l_i and writes phi = phi' / norm - sum_j l_j s_j
+ * (subtractions in storage order, unfused): 4 launches per step whatever wnum and B.  The Gram matrix lives on the device, is
+ * recomputed lazily in stream order after load_state, push_state, clear_states or a solve_state that pushed, and nothing is
+ * allocated or launched for it unless the form is selected.  A call with wnum > 4 runs the sequential form.  Its contract:
+ *  - WAFER_F64: every member within 1e-13 per cell of the reference's excited-state evolve and of a wafer_ctx, norm2 within
+ *    rel 1e-12.  NOT the sequential form's bits: the overlaps come from the recurrence, not from the projected phi.
+ *  - float dtypes: every operand widened, every operation fp64, phi rounded to float ONCE per step after the step kernel's own
+ *    store (the sequential form rounds it 1 + wnum times): up to a few float spacings from the sequential form.  A
+ *    WAFER_F32_FAST batch computes WAFER_F32's bits.
+ *  - as for the sequential form: a member's bits do not depend on B, its index or the active set; frozen members and every
+ *    stored state are untouched bit for bit; the same call from the same start gives the same bits; no floating-point atomics
+ *    and no host synchronisation between steps.
+ * wafer_batch_orthogonalise under it: the same three launches without the division (norm = 1). */
 int wafer_batch_load_state(wafer_batch *b, uint32_t member, uint32_t idx, const double *state);  /* as wafer_load_state: idx <= the member's count */
 int wafer_batch_download_state(wafer_batch *b, uint32_t member, uint32_t idx, double *out);
 int wafer_batch_push_state(wafer_batch *b, const uint8_t *active);          /* w_store.push(phi), grid.rs:241 */
@@ -530,6 +546,16 @@ int wafer_batch_evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnu
 int wafer_batch_solve_state(wafer_batch *b, uint32_t wnum, double tolerance, uint64_t screen_update, int has_max_steps,
                             uint64_t max_steps, wafer_block_record *records, size_t max_records_per_member, size_t *n_records,
                             wafer_observables_output *finals, int *status);
+/* the form of the excited step and of orthogonalise: -1 default dispatch (the sequential form), 0 the sequential form, 1 the
+ * one-pass form wherever wnum <= 4 (a call with a larger wnum runs sequentially).  Anything else: WAFER_ERR_INVALID. */
+int wafer_batch_set_gs_variant(wafer_batch *b, int variant);
+/* one line of key=value pairs -- wnum= form=sequential|onepass launches_per_step= kernels= variant= dtype= onepass_bytes= -- from the
+ * launch path's own predicates for an excited step with this wnum; launches nothing.  onepass_bytes: device memory the one-pass
+ * form has allocated beyond the sequential form's (Gram matrices, their partials and member lists, the wider sums partials):
+ * 0 until it first runs. */
+int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n);
+/* excited steps and orthogonalise calls run in each form since creation */
+int wafer_batch_diag_gs_steps(wafer_batch *b, uint64_t *onepass, uint64_t *sequential);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,10 @@ row records "variant", "steps_per_launch", the dispatch line and the launch coun
 --dtype D: f64 (default), f32 (float storage, fp64 arithmetic) or f32fast (float arithmetic in the ground-state step) for the
 batch and the contexts alike; the row records "dtype".  On the float dtypes the excited-state parity bar is 4 float spacings at
 max |phi| (the two partition their sums differently, and a last-bit difference of a scalar can flip a float rounding), the
-ground-state parity stays bit for bit."""
+ground-state parity stays bit for bit.
+--gs-variant V: Batch.set_gs_variant(V) before the first step (-1 default dispatch, 0 the sequential normalise / Gram-Schmidt chain,
+1 the one-pass form for wnum <= 4); the row records "gs_variant", the gs_dispatch line for its wnum and the excited steps the timed
+call ran in each form ("gs_onepass_steps", "gs_sequential_steps")."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -41,7 +44,7 @@ def store(par, wnum, seed=0):
     return out
 
 
-def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1, dtype="f64"):
+def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1, dtype="f64", gs_variant=-1):
     pars = members(n, B, ext, dtype)
     cells = n ** 3
     out = {"shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype,
@@ -57,9 +60,11 @@ def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1, dtype=
                 b.load_state(k, i, stores[k % len(stores)][i])
         b.set_step_variant(variant)
         out["variant"], out["steps_per_launch"], out["dispatch"] = variant, b.steps_per_launch(), b.dispatch()
+        b.set_gs_variant(gs_variant)
+        out["gs_variant"], out["gs_dispatch"] = gs_variant, b.gs_dispatch(wnum)
         b.evolve(warmup, wnum=wnum)
         b.last_evolve_ms()   # (waits for the warm-up)
-        p0 = b.passes()
+        p0, g0 = b.passes(), b.gs_steps()
         t0 = time.perf_counter()
         b.evolve(steps, wnum=wnum)
         ms, st = b.last_evolve_ms()   # blocks until the last step has finished
@@ -68,6 +73,7 @@ def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1, dtype=
         out["batch_host_gups"] = B * cells * steps / t / 1e9
         out["kernel"] = b.kernel_name()
         out["fused_passes"], out["single_steps"] = [x - y for x, y in zip(b.passes(), p0)]
+        out["gs_onepass_steps"], out["gs_sequential_steps"] = [x - y for x, y in zip(b.gs_steps(), g0)]
         out["batch_us_per_step"] = 1e3 * ms / st
         out["batch_gups"] = B * cells * st / (ms * 1e-3) / 1e9
         if only_batch:
@@ -136,10 +142,12 @@ def main():
     ap.add_argument("--ext", type=int, choices=[1, 2, 3], default=1, help="central difference: 1 ThreePoint (default), 2 FivePoint, 3 SevenPoint")
     ap.add_argument("--dtype", choices=["f64", "f32", "f32fast"], default="f64", help="storage / arithmetic of the batch and the contexts")
     ap.add_argument("--variant", type=int, choices=[-1, 0, 1], default=-1, help="Batch.set_step_variant: -1 default dispatch, 0 one step per launch, 1 fused passes")
+    ap.add_argument("--gs-variant", type=int, choices=[-1, 0, 1], default=-1,
+                    help="Batch.set_gs_variant: -1 default dispatch, 0 the sequential chain, 1 the one-pass form (wnum <= 4)")
     a = ap.parse_args()
     for n in a.sizes:
         for B in a.batch:
-            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum, a.variant, a.ext, a.dtype).items()})
+            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum, a.variant, a.ext, a.dtype, a.gs_variant).items()})
             print(line, flush=True)
             if a.out:
                 with open(a.out, "a") as f:

@@ -2,7 +2,8 @@
 // launch per step over the active members -- or, for ground-state steps, one launch per pass of K steps (wafer_batch_plan.h) --
 // (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip), and for
 // excited states a per-member state store with the normalise / Gram-Schmidt tail of every step (wafer_gs_batch.hip.h,
-// wafer_tu_gs_batch.hip): 1 + 2 (1 + wnum) + 1 launches per step for the whole batch.
+// wafer_tu_gs_batch.hip): 1 + 2 (1 + wnum) + 1 launches per step for the whole batch -- or, where wafer_batch_set_gs_variant
+// selects the one-pass form (wnum <= WAFER_MAX_LOW), 4: step, raw sums, reduce, one apply pass with the member's Gram matrix.
 //
 // Each member is also a context VIEW: a wafer_ctx whose arrays are the member's slices of the batch's allocations and whose
 // stream is the batch's.  Potentials, initial conditions, uploads and downloads go through the context entry points on that
@@ -63,6 +64,14 @@ struct wafer_batch {
     int n2_nb = 0;                            // float storage: workgroups per member of wafer_batch_norm2 (a context's wafer_norm2 partition)
     double *gs_partials = nullptr;            // [member][gs_nb]
     double *gs_scal = nullptr, *gs_host = nullptr;
+    // the one-pass form (wafer_batch_set_gs_variant); everything below is made by its first use (ensure_onepass)
+    int gs_variant = -1;
+    uint64_t n_onepass = 0, n_sequential = 0;   // excited steps and orthogonalise calls in each form (wafer_batch_diag_gs_steps)
+    bool onepass_ready = false;               // gs_partials holds WAFER_GS_ONE_ROWS rows per member, the Gram storage exists
+    double *gram = nullptr;                   // [member][WAFER_MAX_LOW^2]: G_ji = <state j | state i>, i < j
+    double *gram_partials = nullptr;          // [member][WAFER_GRAM_PAIRS][gs_nb]
+    int *gram_list_dev = nullptr, *gram_list_host = nullptr;   // the members to recompute, then their state counts: 2 n ints
+    std::vector<uint8_t> gram_stale;          // member m's store changed since its Gram matrix was formed
 };
 
 namespace {
@@ -112,9 +121,10 @@ void destroy(wafer_batch *b)
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->blkk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
-                    (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal})
+                    (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
+                    (void *)b->gram_list_dev})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host})
+    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop})
         if (e) (void)hipEventDestroy(e);
@@ -313,6 +323,12 @@ int check_capacity(const wafer_batch *b, uint32_t m)
     return WAFER_OK;
 }
 
+// member m's store changed: its Gram matrix (the one-pass form's, if it exists) is recomputed before the next one-pass call
+void mark_gram_stale(wafer_batch *b, uint32_t m)
+{
+    if (!b->gram_stale.empty()) b->gram_stale[m] = 1;
+}
+
 // phi of the active members to the end of their stores; nothing changes unless every one of them can take it
 int push_states(wafer_batch *b, const uint8_t *active)
 {
@@ -330,6 +346,7 @@ int push_states(wafer_batch *b, const uint8_t *active)
         const wafer_ctx *c = b->views[m];
         HIP_TRY(hipMemcpyAsync(alloc_base(c, slot_ptr(b, b->nst[m], m)), alloc_base(c, c->phi[c->cur]), b->stride * b->esz, hipMemcpyDeviceToDevice, b->s));
         ++b->nst[m];
+        mark_gram_stale(b, m);
     }
     return WAFER_OK;
 }
@@ -364,6 +381,87 @@ int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int l
     return WAFER_OK;
 }
 
+// ---- the one-pass form ---------------------------------------------------------------------------------------------------------
+// the launch path's predicate: which form a call with this wnum takes
+bool use_onepass(const wafer_batch *b, uint32_t wnum) { return b->gs_variant == 1 && wnum >= 1 && wnum <= WAFER_MAX_LOW; }
+
+// bytes of gs_partials under the one-pass form: WAFER_GS_ONE_ROWS rows per member (or the float norm2's partition, if wider)
+size_t onepass_partials_bytes(const wafer_batch *b)
+{
+    return sizeof(double) * std::max((size_t)WAFER_GS_ONE_ROWS * (size_t)b->gs_nb, (size_t)b->n2_nb) * b->n;
+}
+
+// gs_partials grown to the sums kernel's rows, and the Gram storage; every member's matrix is stale
+int ensure_onepass(wafer_batch *b)
+{
+    if (b->onepass_ready) return WAFER_OK;
+    TRY(ensure_gs(b));
+    double *wider = nullptr;   // (the new buffer first: a failed allocation leaves the sequential form's partials in place)
+    HIP_TRY(hipMalloc((void **)&wider, onepass_partials_bytes(b)));
+    const hipError_t e = hipStreamSynchronize(b->s);   // no launch in flight writes the partials that go back
+    if (e != hipSuccess) {
+        (void)hipFree(wider);
+        return fail(WAFER_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(b->gs_partials);
+    b->gs_partials = wider;
+    if (!b->gram) {
+        HIP_TRY(hipMalloc((void **)&b->gram, sizeof(double) * WAFER_MAX_LOW * WAFER_MAX_LOW * b->n));
+        HIP_TRY(hipMemsetAsync(b->gram, 0, sizeof(double) * WAFER_MAX_LOW * WAFER_MAX_LOW * b->n, b->s));
+    }
+    if (!b->gram_partials) HIP_TRY(hipMalloc((void **)&b->gram_partials, sizeof(double) * WAFER_GRAM_PAIRS * (size_t)b->gs_nb * b->n));
+    if (!b->gram_list_dev) HIP_TRY(hipMalloc((void **)&b->gram_list_dev, sizeof(int) * 2 * b->n));
+    if (!b->gram_list_host) HIP_TRY(hipHostMalloc((void **)&b->gram_list_host, sizeof(int) * 2 * b->n, hipHostMallocDefault));
+    b->gram_stale.assign(b->n, 1);
+    b->onepass_ready = true;
+    return WAFER_OK;
+}
+
+WaferBatchGsOneArgs onepass_args(const wafer_batch *b, int flip, uint32_t nslots)
+{
+    WaferBatchGsOneArgs a;
+    a.g = b->g;
+    a.ntx = (b->g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    a.nty = (b->g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    a.flip = flip;
+    a.scal_stride = b->gs_stride;
+    a.mstride = (long long)b->stride;
+    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? slot_ptr(b, l, 0) : nullptr;
+    return a;
+}
+
+// the Gram matrices of the active members whose stores changed since they were formed: one launch and its reduce, in stream
+// order behind the copies that changed the stores.  (Called once per call, before its first step, after upload_active's
+// synchronisation: gram_list_host is not read by an earlier call's copy any more.)
+int refresh_gram(wafer_batch *b, const uint8_t *active)
+{
+    int nlist = 0, nl = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if ((active && !active[m]) || !b->gram_stale[m]) continue;
+        b->gram_stale[m] = 0;
+        const int cnt = (int)std::min<uint32_t>(b->nst[m], WAFER_MAX_LOW);
+        if (cnt < 2) continue;   // no pair
+        b->gram_list_host[nlist++] = (int)m;
+        nl = std::max(nl, cnt);
+    }
+    if (!nlist) return WAFER_OK;
+    for (int k = 0; k < nlist; ++k) b->gram_list_host[nlist + k] = (int)std::min<uint32_t>(b->nst[b->gram_list_host[k]], WAFER_MAX_LOW);
+    HIP_TRY(hipMemcpyAsync(b->gram_list_dev, b->gram_list_host, sizeof(int) * 2 * nlist, hipMemcpyHostToDevice, b->s));
+    const hipError_t e = wafer_entry_batch_gram(b->f32, nl, onepass_args(b, 0, (uint32_t)nl), b->gram_list_dev, b->gram_list_dev + nlist, nlist, b->gram,
+                                                b->gram_partials, b->s);
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram matrix launch failed: %s", hipGetErrorString(e));
+    return WAFER_OK;
+}
+
+// sums, reduce, apply on phi[cur ^ flip] of the members in act_dev: the step's tail (normalise_first) or orthogonalise alone
+int gs_onepass(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_first)
+{
+    const hipError_t e = wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, onepass_args(b, flip, wnum), b->mem_dev, b->act_dev, nact,
+                                                      b->gs_scal, b->gram, b->gs_partials, b->s);
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched one-pass Gram-Schmidt launch failed: %s", hipGetErrorString(e));
+    return WAFER_OK;
+}
+
 // grid.rs:679-680 (normalise: norm2 and the scaling first) and :477-492 on phi[cur ^ flip] of the members in act_dev
 int gs_chain(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_first)
 {
@@ -388,6 +486,8 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
     if (wnum) TRY(check_ready(b, active, false, "", wnum));
     const uint64_t steps = n_steps == 0 ? 1 : n_steps;   // grid.rs:682-685
     if (wnum) TRY(ensure_gs(b));
+    const bool onepass = use_onepass(b, wnum);
+    if (onepass) TRY(ensure_onepass(b));
     TRY(sync_members(b));
     TRY(build_blocks(b, active));
     const int K = wnum ? 1 : steps_per_pass(b);
@@ -397,6 +497,7 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
     if (K > 1) TRY(build_blocks_fused(b, active, K));
     int nact = 0;
     if (wnum) TRY(upload_active(b, active, &nact));   // (the chain's member list; synchronises the stream, which a ground-state call must not)
+    if (onepass && nact) TRY(refresh_gram(b, active));
     RoctxRange range_(wnum ? "wafer_batch_evolve_state" : "wafer_batch_evolve");
     HIP_TRY(hipEventRecord(b->ev_start, b->s));
     uint64_t launches = 0;
@@ -411,7 +512,9 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
             ++launches;
             ++(k > 1 ? b->n_fused_passes : b->n_single_steps);
             left -= (uint64_t)k;
-            if (wnum) TRY(gs_chain(b, nact, (int)(launches & 1), wnum, true));
+            if (onepass) TRY(gs_onepass(b, nact, (int)(launches & 1), wnum, true));
+            else if (wnum) TRY(gs_chain(b, nact, (int)(launches & 1), wnum, true));
+            if (wnum) ++(onepass ? b->n_onepass : b->n_sequential);
         }
     }
     HIP_TRY(hipEventRecord(b->ev_stop, b->s));
@@ -433,6 +536,13 @@ int orthogonalise(wafer_batch *b, const uint8_t *active, uint32_t wnum)
     int nact = 0;
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
+    if (use_onepass(b, wnum)) {
+        TRY(ensure_onepass(b));
+        TRY(refresh_gram(b, active));
+        ++b->n_onepass;
+        return gs_onepass(b, nact, 0, wnum, false);
+    }
+    ++b->n_sequential;
     return gs_chain(b, nact, 0, wnum, false);
 }
 
@@ -806,6 +916,7 @@ int wafer_batch_load_state(wafer_batch *b, uint32_t member, uint32_t idx, const 
     TRY(ensure_slots(b, idx + 1));
     TRY(upload_padded(b->views[member], state, slot_ptr(b, idx, member)));
     if (idx == b->nst[member]) ++b->nst[member];
+    mark_gram_stale(b, member);
     return WAFER_OK;
 }
 
@@ -831,7 +942,10 @@ int wafer_batch_clear_states(wafer_batch *b, const uint8_t *active)
     HIP_TRY(hipSetDevice(b->device));
     uint32_t keep = 0;
     for (uint32_t m = 0; m < b->n; ++m) {
-        if (!active || active[m]) b->nst[m] = 0;
+        if (!active || active[m]) {
+            b->nst[m] = 0;
+            mark_gram_stale(b, m);
+        }
         keep = std::max(keep, b->nst[m]);
     }
     if (b->slots.size() > keep) {   // slots no member uses any more go back
@@ -917,6 +1031,49 @@ int wafer_batch_diag_passes(wafer_batch *b, uint64_t *fused_passes, uint64_t *si
     if (!b || !fused_passes || !single_steps) return fail(WAFER_ERR_INVALID, "null argument");
     *fused_passes = b->n_fused_passes;
     *single_steps = b->n_single_steps;
+    return WAFER_OK;
+}
+
+int wafer_batch_set_gs_variant(wafer_batch *b, int variant)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    if (variant < -1 || variant > 1) return fail(WAFER_ERR_INVALID, "gs variant must be -1 (default), 0 (sequential) or 1 (one pass)");
+    b->gs_variant = variant;
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n)
+{
+    if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
+    static const char *const dtypes[] = {"f64", "f32", "f32fast"};
+    const char *T = b->f32 ? "float" : "double";
+    // what the one-pass form allocated on first use: the Gram matrices, their partials, the member lists, and the growth of gs_partials
+    const size_t onepass_bytes = !b->onepass_ready ? 0
+        : sizeof(double) * (WAFER_MAX_LOW * WAFER_MAX_LOW + WAFER_GRAM_PAIRS * (size_t)b->gs_nb) * b->n + sizeof(int) * 2 * b->n +
+              onepass_partials_bytes(b) - sizeof(double) * (size_t)std::max(b->gs_nb, b->n2_nb) * b->n;
+    char kernels[256];
+    int launches = 1;
+    const bool onepass = use_onepass(b, wnum);
+    if (onepass) {
+        launches = 4;
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs_sums<%u,%s>+wafer_k_batch_gs_reduce_sums+wafer_k_batch_gs_apply<%u,%s,true>",
+                 wnum, T, wnum, T);
+    } else if (wnum) {
+        launches = 1 + 2 * (1 + (int)wnum) + 1;
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs<NORM2|SCALE|AXPY,%s>+wafer_k_batch_gs_reduce", T);
+    } else {
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step");
+    }
+    snprintf(buf, n, "wnum=%u form=%s launches_per_step=%d kernels=%s variant=%d dtype=%s onepass_bytes=%zu", wnum, onepass ? "onepass" : "sequential",
+             launches, kernels, b->gs_variant, dtypes[b->dtype], onepass_bytes);
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_gs_steps(wafer_batch *b, uint64_t *onepass, uint64_t *sequential)
+{
+    if (!b || !onepass || !sequential) return fail(WAFER_ERR_INVALID, "null argument");
+    *onepass = b->n_onepass;
+    *sequential = b->n_sequential;
     return WAFER_OK;
 }
 

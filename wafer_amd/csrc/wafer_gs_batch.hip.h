@@ -166,6 +166,200 @@ __global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(WaferRowArgs a, co
     if (threadIdx.x == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
 }
 
+// ---- the one-pass form (wafer_batch_set_gs_variant(b, 1), wnum <= WAFER_MAX_LOW) ---------------------------------------------------
+// The single context's wafer_k_gs_apply for every active member: raw sums on the un-normalised phi', the Gram matrix of the
+// member's stored states, one apply pass.  Schedule of one step, 4 launches whatever wnum and B:
+//   wafer_k_batch_step                      (unchanged)
+//   wafer_k_batch_gs_sums<NLOW>             sum phi'^2 and t_j = sum l_j phi', j < NLOW: 1 + NLOW partials per workgroup
+//   wafer_k_batch_gs_reduce_sums            grid (active members, 1 + NLOW): scal[member * scal_stride + q], q = 0: norm2, 1 + j: t_j
+//   wafer_k_batch_gs_apply<NLOW>            norm = sqrt(scal[0]), s_j = t_j / norm - sum_{i<j} s_i G_ji (every thread, identically),
+//                                           x = phi' / norm, x = x - l_j s_j (j = 0 .. NLOW-1, unfused), one store
+// Bytes per cell on doubles: 24 (step) + 8 (1 + wnum) (sums) + 8 (2 + wnum) (apply), against 48 + 32 wnum of the chain.
+// The partition is the chain's (tiles of 64 x 4 work cells x WAFER_GS_ZC planes, grid (wafer_gs_blocks, active members)), a
+// partial lies at partials[(member * (1 + WAFER_MAX_LOW) + q) * nb + workgroup], and a member's Gram matrix at
+// gram[member * WAFER_MAX_LOW^2 + j * WAFER_MAX_LOW + i] (i < j) is summed over the same partition (wafer_k_batch_gram): nothing a
+// sum sees depends on B, the member's index or the active set.  No floating-point atomics.
+// Float storage: every operand widened, every operation fp64; phi is rounded to float ONCE per step after the step kernel's own
+// store -- at the apply kernel's store -- where the chain rounds it 1 + wnum times.  Not the chain's bits on any dtype: the
+// overlaps are formed by the recurrence instead of on the projected phi (rel ~1e-16 on the scalars).
+struct WaferBatchGsOneArgs {
+    WaferGeom g;
+    int ntx, nty;                       // tiles of 64 x 4 work cells per plane
+    int flip;                           // the wavefunction of member m is phi[m.cur ^ flip]
+    int scal_stride;                    // doubles per member in scal
+    long long mstride;                  // elements per member in a store slot's allocation
+    const void *low[WAFER_MAX_LOW];     // store slot j (member 0's logical pointer, of the storage type)
+};
+
+#define WAFER_GS_ONE_ROWS (1 + WAFER_MAX_LOW)                        // partial rows per member of the sums kernel
+#define WAFER_GRAM_PAIRS (WAFER_MAX_LOW * (WAFER_MAX_LOW - 1) / 2)   // partial rows per member of the Gram kernel
+
+// Block (64, 4), grid (wafer_gs_blocks, active members).  All loads of a lane before the arithmetic: 4 planes x (1 + NLOW) arrays.
+template <int NLOW, typename T>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
+                                                             const int *__restrict__ act, double *__restrict__ partials)
+{
+    __shared__ double red[4];
+    const WaferGeom &g = a.g;
+    const int member = act[blockIdx.y];
+    const WaferBatchMember &m = mem[member];
+    const T *__restrict__ phi = static_cast<const T *>(m.phi[(m.cur ^ a.flip) & 1]);
+    const long long moff = (long long)member * a.mstride;
+    const int bid = blockIdx.x;
+    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    const int tid = threadIdx.y * WAFER_BATCH_TX + threadIdx.x;
+    double acc[1 + NLOW];
+#pragma unroll
+    for (int q = 0; q <= NLOW; ++q) acc[q] = 0.0;
+    if (i < g.nx && j < g.ny) {
+        const long long col = (long long)(j + g.R) * g.pitch + g.xoff + (i + g.R);
+        double w[WAFER_GS_ZC], l[NLOW][WAFER_GS_ZC];
+#pragma unroll
+        for (int k = 0; k < WAFER_GS_ZC; ++k) {
+            const bool in = z0 + k < g.G + g.nzl;
+            const long long p = col + (long long)(z0 + k) * g.plane;
+            w[k] = in ? (double)phi[p] : 0.0;
+#pragma unroll
+            for (int s = 0; s < NLOW; ++s) l[s][k] = in ? (double)__builtin_nontemporal_load(static_cast<const T *>(a.low[s]) + moff + p) : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < WAFER_GS_ZC; ++k) {
+            if (!(z0 + k < g.G + g.nzl)) continue;
+            acc[0] += w[k] * w[k];                                  // grid.rs:454-457, as wafer_k_batch_gs<NORM2>
+#pragma unroll
+            for (int s = 0; s < NLOW; ++s) acc[1 + s] += l[s][k] * w[k];   // grid.rs:482-487 on the un-normalised phi'
+        }
+    }
+#pragma unroll
+    for (int q = 0; q <= NLOW; ++q) {
+        const double s = wafer_block_sum<4>(acc[q], red, tid);
+        if (tid == 0) partials[((size_t)member * WAFER_GS_ONE_ROWS + q) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// Block (64, 4), grid (wafer_gs_blocks, active members).  NORMALISE = false (wafer_batch_orthogonalise): no division, norm = 1.
+template <int NLOW, typename T, bool NORMALISE>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
+                                                              const int *__restrict__ act, const double *__restrict__ scal,
+                                                              const double *__restrict__ gram)
+{
+    const WaferGeom &g = a.g;
+    const int member = act[blockIdx.y];
+    const WaferBatchMember &m = mem[member];
+    T *__restrict__ phi = static_cast<T *>(m.phi[(m.cur ^ a.flip) & 1]);
+    const long long moff = (long long)member * a.mstride;
+    const double *__restrict__ sc = scal + (size_t)member * a.scal_stride;
+    const double *__restrict__ gm = gram + (size_t)member * (WAFER_MAX_LOW * WAFER_MAX_LOW);
+    const double norm = NORMALISE ? sqrt(sc[0]) : 1.0;
+    double sj[NLOW];
+#pragma unroll
+    for (int jj = 0; jj < NLOW; ++jj) {   // the recurrence of wafer_k_gs_apply
+        double s = NORMALISE ? sc[1 + jj] / norm : sc[1 + jj];
+#pragma unroll
+        for (int ii = 0; ii < jj; ++ii) s -= sj[ii] * gm[jj * WAFER_MAX_LOW + ii];
+        sj[jj] = s;
+    }
+    const int bid = blockIdx.x;
+    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    if (i >= g.nx || j >= g.ny) return;
+    const long long col = (long long)(j + g.R) * g.pitch + g.xoff + (i + g.R);
+    double w[WAFER_GS_ZC], l[NLOW][WAFER_GS_ZC];
+#pragma unroll
+    for (int k = 0; k < WAFER_GS_ZC; ++k) {
+        const bool in = z0 + k < g.G + g.nzl;
+        const long long p = col + (long long)(z0 + k) * g.plane;
+        w[k] = in ? (double)phi[p] : 0.0;
+#pragma unroll
+        for (int s = 0; s < NLOW; ++s) l[s][k] = in ? (double)__builtin_nontemporal_load(static_cast<const T *>(a.low[s]) + moff + p) : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < WAFER_GS_ZC; ++k) {
+        if (!(z0 + k < g.G + g.nzl)) continue;
+        double x = w[k];
+        if (NORMALISE) x = wafer_div_invariant<double>(x, norm);   // grid.rs:467
+#pragma unroll
+        for (int s = 0; s < NLOW; ++s) x = x - l[s][k] * sj[s];    // grid.rs:488-490
+        phi[col + (long long)(z0 + k) * g.plane] = (T)x;
+    }
+}
+
+// G_ji = sum l_j l_i, i < j < cnt[blockIdx.y] <= NL, of the members in list: every stored state read once, all pairs formed.
+// Partial row q = j (j - 1) / 2 + i at partials[(member * WAFER_GRAM_PAIRS + q) * nb + workgroup]; rows with j >= the member's
+// count come out zero.  Block (64, 4), grid (wafer_gs_blocks, listed members).
+template <int NL, typename T>
+__global__ __launch_bounds__(256) void wafer_k_batch_gram(WaferBatchGsOneArgs a, const int *__restrict__ list, const int *__restrict__ cnt,
+                                                          double *__restrict__ partials)
+{
+    __shared__ double red[4];
+    constexpr int NP = NL * (NL - 1) / 2;
+    const WaferGeom &g = a.g;
+    const int member = list[blockIdx.y], count = cnt[blockIdx.y];
+    const long long moff = (long long)member * a.mstride;
+    const int bid = blockIdx.x;
+    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    const int tid = threadIdx.y * WAFER_BATCH_TX + threadIdx.x;
+    double acc[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) acc[q] = 0.0;
+    if (i < g.nx && j < g.ny) {
+        const long long col = (long long)(j + g.R) * g.pitch + g.xoff + (i + g.R);
+        double l[NL][WAFER_GS_ZC];
+#pragma unroll
+        for (int k = 0; k < WAFER_GS_ZC; ++k) {
+            const bool in = z0 + k < g.G + g.nzl;
+            const long long p = col + (long long)(z0 + k) * g.plane;
+#pragma unroll
+            for (int s = 0; s < NL; ++s) l[s][k] = (in && s < count) ? (double)__builtin_nontemporal_load(static_cast<const T *>(a.low[s]) + moff + p) : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < WAFER_GS_ZC; ++k)
+#pragma unroll
+            for (int jj = 1; jj < NL; ++jj)
+#pragma unroll
+                for (int ii = 0; ii < jj; ++ii) acc[jj * (jj - 1) / 2 + ii] += l[jj][k] * l[ii][k];
+    }
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const double s = wafer_block_sum<4>(acc[q], red, tid);
+        if (tid == 0) partials[((size_t)member * WAFER_GRAM_PAIRS + q) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// wafer_k_reduce for every listed member and partial row at once: block (slot, q) sums the n partials of row q of member
+// act[slot] in wafer_k_reduce's order.  GRAM = false: `rows` = WAFER_GS_ONE_ROWS, into out[member * out_stride + q] (the scalars);
+// GRAM = true: `rows` = WAFER_GRAM_PAIRS, row q = j (j - 1) / 2 + i into out[member * out_stride + j * WAFER_MAX_LOW + i].
+template <bool GRAM>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double *__restrict__ partials, const int *__restrict__ act, int n,
+                                                                    int rows, double *__restrict__ out, int out_stride)
+{
+    __shared__ double sh[256];
+    const int member = act[blockIdx.x], q = blockIdx.y;
+    const double *p = partials + ((size_t)member * rows + q) * n;
+    double s = 0.0;
+    for (int r = threadIdx.x; r < n; r += 256) s += p[r];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    int slot = q;
+    if (GRAM) {
+        static_assert(WAFER_MAX_LOW == 4, "the row -> (j, i) mapping below lists the six pairs of four states");
+        const int jj = q < 1 ? 1 : (q < 3 ? 2 : 3);
+        slot = jj * WAFER_MAX_LOW + (q - jj * (jj - 1) / 2);
+    }
+    out[(size_t)member * out_stride + slot] = sh[0];
+}
+
 // entry points (wafer_tu_gs_batch.hip).  One elementwise launch of `mode` over the active members and, where it sums
 // (NORM2, or dotwith given), the reduce into scal[member * scal_stride + out_slot].  f32: float storage.
 hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, const WaferBatchMember *mem, const int *act, int nact,
@@ -174,3 +368,11 @@ hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, c
 // wafer_rownorm2_blocks workgroups per member; partials holds nb doubles per member of the batch)
 hipError_t wafer_entry_batch_rownorm2(const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, int nb, double *scal,
                                       int scal_stride, int out_slot, double *partials, hipStream_t s);
+// the one-pass form: sums, reduce and apply (normalise: evolve; else orthogonalise) over the members in act.  1 <= nlow <= WAFER_MAX_LOW;
+// partials holds WAFER_GS_ONE_ROWS * wafer_gs_blocks doubles per member of the batch, gram WAFER_MAX_LOW^2.
+hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem,
+                                        const int *act, int nact, double *scal, const double *gram, double *partials, hipStream_t s);
+// the Gram matrices of the nlist members in list (cnt: states of each, 2 <= cnt <= nl <= WAFER_MAX_LOW) into gram; partials holds
+// WAFER_GRAM_PAIRS * wafer_gs_blocks doubles per member of the batch
+hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgs &a, const int *list, const int *cnt, int nlist, double *gram,
+                                  double *partials, hipStream_t s);

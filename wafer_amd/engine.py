@@ -55,6 +55,7 @@ EXPORTS = [
     "wafer_batch_load_state", "wafer_batch_download_state", "wafer_batch_push_state", "wafer_batch_num_states",
     "wafer_batch_clear_states", "wafer_batch_clone_state_to_phi", "wafer_batch_orthogonalise", "wafer_batch_norm2",
     "wafer_batch_evolve_state", "wafer_batch_solve_state",
+    "wafer_batch_set_gs_variant", "wafer_batch_diag_gs", "wafer_batch_diag_gs_steps",
 ]
 
 
@@ -250,6 +251,9 @@ def load_library():
     L.wafer_batch_evolve_state.argtypes = [vp, u8p, C.c_uint32, C.c_uint64]
     L.wafer_batch_solve_state.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(_Record), C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(_ObsOut), C.POINTER(C.c_int)]
+    L.wafer_batch_set_gs_variant.argtypes = [vp, C.c_int]
+    L.wafer_batch_diag_gs.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.wafer_batch_diag_gs_steps.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -677,6 +681,9 @@ class Batch:
     tolerances (1e-13 per cell), not bit for bit: the sums are partitioned differently.  Measured (ThreePoint
     fp64, 50^3 and 64^3, wnum 1 and 2): 1.7-3.2 times B contexts one after another from B = 8 on, 0.4 times at B = 1 -- for one
     problem use a Context.
+    set_gs_variant(1) selects the one-pass form for wnum <= 4 (opt-in): step, raw sums, reduce and one apply pass with the
+    member's Gram matrix, 4 launches per step whatever k and B; the same tolerances against the oracle and a Context, phi rounded
+    to float once per step on the float dtypes, not the sequential form's bits (gs_dispatch(wnum), gs_steps()).
     A sweep over states is solve_state(0), solve_state(1), ...: a member whose store is too short for a call gets the status
     WAFER_ERR_STATE, is left as it is, and the others run."""
 
@@ -895,3 +902,22 @@ class Batch:
         f, s = C.c_uint64(0), C.c_uint64(0)
         self._check(self._L.wafer_batch_diag_passes(self._h, C.byref(f), C.byref(s)))
         return f.value, s.value
+
+    def set_gs_variant(self, variant: int) -> None:
+        """the form of excited steps and orthogonalise: -1 default dispatch (sequential), 0 sequential, 1 one pass (wnum <= 4)"""
+        self._check(self._L.wafer_batch_set_gs_variant(self._h, int(variant)))
+
+    def gs_dispatch(self, wnum: int) -> dict:
+        """what an excited step with `wnum` would launch: wnum, form, launches_per_step, kernels, variant, dtype, onepass_bytes"""
+        buf = C.create_string_buffer(768)
+        self._check(self._L.wafer_batch_diag_gs(self._h, int(wnum), buf, len(buf)))
+        d = dict(kv.split("=", 1) for kv in buf.value.decode().split())
+        for k in ("wnum", "launches_per_step", "variant", "onepass_bytes"):
+            d[k] = int(d[k])
+        return d
+
+    def gs_steps(self) -> tuple:
+        """(one-pass, sequential) excited steps and orthogonalise calls since creation"""
+        o, s = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_gs_steps(self._h, C.byref(o), C.byref(s)))
+        return o.value, s.value
