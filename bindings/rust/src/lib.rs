@@ -203,6 +203,10 @@ extern "C" {
     // batched ensembles: B ground-state problems of one shape and one dtype (WAFER_F64, WAFER_F32 or WAFER_F32_FAST in every member's
     // wafer_params), one launch per step (include/wafer_hip.h)
     pub fn wafer_batch_create(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
+    /// as `wafer_batch_create`, but nx, ny, nz may differ from member to member (ground-state calls; see wafer_hip.h)
+    pub fn wafer_batch_create_mixed(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
+    /// number of distinct (nx, ny, nz) among the members
+    pub fn wafer_batch_num_shapes(b: *mut wafer_batch, n_shapes: *mut u32) -> c_int;
     pub fn wafer_batch_destroy(b: *mut wafer_batch) -> c_int;
     pub fn wafer_batch_size(b: *mut wafer_batch, n_members: *mut u32) -> c_int;
     pub fn wafer_batch_set_potential_builtin(b: *mut wafer_batch, member: u32, potential: c_int) -> c_int;

@@ -427,7 +427,8 @@ typedef struct wafer_device_info {
 int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
 
 /* ---- batched ensembles ------------------------------------------------------
- * A batch holds B independent ground-state problems ("members") on one device, all with the same work-area shape, the same
+ * A batch holds B independent ground-state problems ("members") on one device, all with the same work-area shape
+ * (wafer_batch_create; wafer_batch_create_mixed lifts that: "Mixed-shape batches" below), the same
  * central_difference and the same dtype, each with its own dn, dt, mass, sig, flags, potential, pot_sub and wavefunction.  One
  * launch per step advances every ACTIVE member (a workgroup table built from the active members only: a member that is not
  * active costs nothing) -- or one launch per PASS of K ground-state steps where a fused pass is selected
@@ -460,6 +461,36 @@ int wafer_get_device_info(wafer_ctx *ctx, wafer_device_info *out);
  *    dtype: the same double, bit for bit.  (On WAFER_F64 it keeps the batch's own partition: rel 1e-12 against a context.) */
 typedef struct wafer_batch wafer_batch;
 int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out);
+/* ---- Mixed-shape batches ----
+ * As wafer_batch_create, but nx, ny, nz may differ from member to member (a convergence study: one problem at several N and dn,
+ * side by side in one batch).  central_difference, dtype, device, halo_depth are still the batch's (member 0's), z_count is
+ * still 0, every other member rule is unchanged and reported with the same messages before any HIP call; the overflow check is
+ * on the SUM of the members' allocation sizes.  Members lie in one allocation per array kind at the prefix sums of their own
+ * padded sizes, each with its own guard rows and planes.
+ * One distinct shape among the members: the batch behaves in every call like one made by wafer_batch_create, excited states and
+ * the one-pass form included, and wafer_batch_diag_dispatch gives the same line.
+ * More than one distinct shape ("mixed-shape"), the ground-state path:
+ *  - evolve: every member computes, bit for bit, what a wafer_ctx with its own wafer_params computes -- with the one-step kernel
+ *    and under wafer_batch_set_step_variant(b, 1) (the fused pass), on WAFER_F64, WAFER_F32 and WAFER_F32_FAST.
+ *  - wafer_batch_observables follows the context's partition and reduction order FOR THAT MEMBER'S SHAPE: all four sums are the
+ *    context's doubles.  wafer_batch_normalise and wafer_batch_solve give the context's bits.  wafer_batch_norm2 gives the
+ *    context's double on the float dtypes; on WAFER_F64 it keeps the batch's own partition (per shape), rel 1e-12.
+ *  - launches: ONE per step, or per fused pass, covers all active members whatever their shapes (not one per shape: the workgroup
+ *    table runs over all of them and every entry names its member's geometry); observables stay one launch plus one reduce
+ *    launch, normalise one launch.  wafer_batch_diag_passes counts launches: n single steps add n.
+ *  - a member's bits do not depend on the batch size, its index, the other members' shapes or the active set; a frozen member is
+ *    untouched bit for bit.  No floating-point atomics, no host synchronisation between steps.
+ *  - the calls that need the state stores return WAFER_ERR_INVALID with a message that contains "mixed-shape" and names the call,
+ *    and change nothing: wafer_batch_load_state, _download_state, _push_state, _clear_states, _clone_state_to_phi, _orthogonalise,
+ *    _evolve_state with wnum > 0, _solve_state with any wnum, and wafer_batch_set_gs_variant(b, 1).  (Excited states on several
+ *    shapes are not built yet.)  wafer_batch_evolve_state(.., 0, ..) is wafer_batch_evolve, wafer_batch_num_states gives zeros,
+ *    wafer_batch_diag_gs still answers.
+ *  - wafer_batch_diag_dispatch: kernel= names the instantiation actually launched, which reads its geometry from the batch's device
+ *    table -- wafer_k_batch_step<R,T,C,WaferBatchGeomTable> / wafer_k_batch_stepk<R,K,T,C,WaferBatchGeomTable> -- and the line ends
+ *    with " shapes=N".  wafer_batch_kernel_name gives that one-step instantiation's name. */
+int wafer_batch_create_mixed(const wafer_params *members, uint32_t n_members, wafer_batch **out);
+/* number of distinct (nx, ny, nz) among the members */
+int wafer_batch_num_shapes(wafer_batch *b, uint32_t *n_shapes);
 int wafer_batch_destroy(wafer_batch *b);
 int wafer_batch_size(wafer_batch *b, uint32_t *n_members);
 /* per member, as wafer_set_potential_builtin / wafer_set_potential_host / wafer_set_initial_condition / wafer_upload_phi /

@@ -20,7 +20,11 @@ max |phi| (the two partition their sums differently, and a last-bit difference o
 ground-state parity stays bit for bit.
 --gs-variant V: Batch.set_gs_variant(V) before the first step (-1 default dispatch, 0 the sequential normalise / Gram-Schmidt chain,
 1 the one-pass form for wnum <= 4); the row records "gs_variant", the gs_dispatch line for its wnum and the excited steps the timed
-call ran in each form ("gs_onepass_steps", "gs_sequential_steps")."""
+call ran in each form ("gs_onepass_steps", "gs_sequential_steps").
+--mixed "64,50,37x50x23": one line per B instead -- the members cycle through these shapes (N is N x N x N) in ONE mixed-shape batch
+(Batch(members, mixed_shapes=True)), timed as above ("mixed_*"), and the same members run as one uniform batch per shape, one
+batch after another ("uniform": a row per shape; "uniform_sum_*": their times added).  "ratio_host" / "ratio_events": the uniform
+batches' summed time over the mixed batch's; "parity": every member's phi bit-identical in both."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -130,6 +134,73 @@ def row(n, B, steps, warmup, only_batch=False, wnum=0, variant=-1, ext=1, dtype=
     return out
 
 
+def parse_shapes(text):
+    out = []
+    for tok in text.split(","):
+        d = [int(x) for x in tok.strip().lower().split("x")]
+        if len(d) not in (1, 3) or min(d) < 1:
+            raise SystemExit("--mixed: a shape is N or NXxNYxNZ, got %r" % tok)
+        out.append(tuple(d * 3 if len(d) == 1 else d))
+    return out
+
+
+def timed_batch(pars, steps, warmup, variant, mixed):
+    """-> (timings, [phi of every member]) of one batch of these members after warmup + steps ground-state steps"""
+    cells = sum(p.nx * p.ny * p.nz for p in pars)
+    with wafer_amd.Batch(pars, mixed_shapes=mixed) as b:
+        for k in range(len(pars)):
+            b.set_potential(k, "Harmonic")
+            b.set_initial_condition(k, "Gaussian")
+        b.set_step_variant(variant)
+        out = {"B": len(pars), "dispatch": b.dispatch(), "shapes": b.num_shapes()}
+        b.evolve(warmup)
+        b.last_evolve_ms()
+        p0 = b.passes()
+        t0 = time.perf_counter()
+        b.evolve(steps)
+        ms, st = b.last_evolve_ms()
+        t = time.perf_counter() - t0
+        out["host_us_per_step"] = 1e6 * t / steps
+        out["host_gups"] = cells * steps / t / 1e9
+        out["us_per_step"] = 1e3 * ms / st
+        out["gups"] = cells * st / (ms * 1e-3) / 1e9
+        out["fused_passes"], out["single_steps"] = [x - y for x, y in zip(b.passes(), p0)]
+        return out, [b.download_phi(k) for k in range(len(pars))]
+
+
+def mixed_row(shapes, B, steps, warmup, variant=-1, ext=1, dtype="f64"):
+    pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype)
+            for k in range(B)]
+    out = {"mixed": [list(s) for s in shapes], "B": B, "steps": steps, "warmup": warmup, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1],
+           "dtype": dtype, "potential": "Harmonic", "variant": variant}
+    m, phis = timed_batch(pars, steps, warmup, variant, True)
+    out.update({"mixed_" + k: v for k, v in m.items() if k != "B"})
+    out["uniform"], parity = [], True
+    for s in dict.fromkeys(shapes):   # one uniform batch per distinct shape, one after another
+        idx = [k for k in range(B) if shapes[k % len(shapes)] == s]
+        if not idx:
+            continue
+        u, uphis = timed_batch([pars[k] for k in idx], steps, warmup, variant, False)
+        u["shape"] = list(s)
+        u["dispatch"] = u["dispatch"]["kernel"]
+        out["uniform"].append(u)
+        parity = parity and all(np.array_equal(phis[k].view(np.int64), uphis[j].view(np.int64)) for j, k in enumerate(idx))
+    for key in ("host_us_per_step", "us_per_step"):
+        out["uniform_sum_" + key] = sum(u[key] for u in out["uniform"])
+    out["ratio_host"] = out["uniform_sum_host_us_per_step"] / out["mixed_host_us_per_step"]
+    out["ratio_events"] = out["uniform_sum_us_per_step"] / out["mixed_us_per_step"]
+    out["parity"] = bool(parity)
+    return out
+
+
+def rounded(d):
+    if isinstance(d, dict):
+        return {k: rounded(v) for k, v in d.items()}
+    if isinstance(d, list):
+        return [rounded(v) for v in d]
+    return round(d, 4) if isinstance(d, float) else d
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[50, 64])
@@ -144,7 +215,17 @@ def main():
     ap.add_argument("--variant", type=int, choices=[-1, 0, 1], default=-1, help="Batch.set_step_variant: -1 default dispatch, 0 one step per launch, 1 fused passes")
     ap.add_argument("--gs-variant", type=int, choices=[-1, 0, 1], default=-1,
                     help="Batch.set_gs_variant: -1 default dispatch, 0 the sequential chain, 1 the one-pass form (wnum <= 4)")
+    ap.add_argument("--mixed", metavar="SHAPES", help='e.g. "64,50,37x50x23": the members cycle through these shapes in one mixed-shape batch, compared '
+                    "with one uniform batch per shape run one after another (ground state; --sizes, --wnum and --only-batch do not apply)")
     a = ap.parse_args()
+    if a.mixed:
+        for B in a.batch:
+            line = json.dumps(rounded(mixed_row(parse_shapes(a.mixed), B, a.steps, a.warmup, a.variant, a.ext, a.dtype)))
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+        return
     for n in a.sizes:
         for B in a.batch:
             line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row(n, B, a.steps, a.warmup, a.only_batch, a.wnum, a.variant, a.ext, a.dtype, a.gs_variant).items()})

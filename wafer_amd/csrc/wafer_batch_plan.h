@@ -1,5 +1,6 @@
 // wafer_batch_plan.h -- the host-side plan of a batched ground-state evolve (wafer_engine_batch.hip): which passes a call of
-// `steps` steps launches, and the workgroup table of the fused K-step pass (wafer_k_batch_stepk, wafer_stencil_batch.hip.h).
+// `steps` steps launches, the workgroup table of the one-step kernel (wafer_k_batch_step) and the one of the fused K-step pass
+// (wafer_k_batch_stepk, wafer_stencil_batch.hip.h), for batches of one shape and of several.
 // Plain C++ with no HIP in it, so the host compiler and the sanitizers can run it (tests/test_batch_plan.py).
 #pragma once
 #include <stdint.h>
@@ -10,9 +11,10 @@
 #endif
 #include "wafer_geom.h"
 
-// one workgroup of a batched step: tile (x0, y0) of work cells, local planes [z0, z1) of member `member`
+// one workgroup of a batched step: tile (x0, y0) of work cells, local planes [z0, z1) of member `member`, whose geometry is
+// entry `shape` of the batch's table of distinct geometries (0 in a batch of one shape)
 struct WaferBatchBlock {
-    int member, x0, y0, z0, z1, pad;
+    int member, x0, y0, z0, z1, shape;
 };
 
 // the fused pass's tile of work cells: 64 columns (one wave across x) by 12 rows
@@ -124,6 +126,73 @@ static inline std::vector<WaferBatchBlock> wafer_batch_fused_table(const WaferGe
             const int z0 = g.G + (int)((long long)c * g.nzl / nch), z1 = g.G + (int)((long long)(c + 1) * g.nzl / nch);
             for (int j = 0; j < nty; ++j)
                 for (int i = 0; i < ntx; ++i) t.push_back(WaferBatchBlock{(int)m, i * tx, j * ty, z0, z1, 0});
+        }
+    }
+    return t;
+}
+
+// ---- tables over several shapes ----------------------------------------------------------------------------------------------
+// A batch keeps a table of its distinct geometries; shape_of[m] is member m's entry.  Both tables below cut z by ONE layer for
+// the whole launch: layer = sum over the active members of that member's tiles per plane, so the launch as a whole fills the
+// device whatever mix of shapes is active.  An entry carries its member's shape index.
+
+static inline long long wafer_batch_layer(const WaferGeom *geoms, const int *shape_of, const uint8_t *active, uint32_t n_members, int tx, int ty)
+{
+    long long layer = 0;
+    for (uint32_t m = 0; m < n_members; ++m) {
+        if (active && !active[m]) continue;
+        const WaferGeom &g = geoms[shape_of[m]];
+        layer += (long long)((g.nx + tx - 1) / tx) * ((g.ny + ty - 1) / ty);
+    }
+    return layer;
+}
+
+// The one-step kernel's table: tx x ty tiles (64 x 4) of every active member's work area, z cut into chunks so that the active
+// members together give ~8 workgroups per CU (a CU holds 8 of these 256-thread workgroups), no chunk shorter than 8 planes:
+//   nch_m = clamp(ceil(8 CUs / layer), 1, (nz_m + 7) / 8),  zchunk_m = ceil(nz_m / nch_m).
+// Members in order, within a member z-chunks, tile rows, tiles.  A frozen member has no entry.
+static inline std::vector<WaferBatchBlock> wafer_batch_step_table(const WaferGeom *geoms, const int *shape_of, const uint8_t *active,
+                                                                  uint32_t n_members, int num_cus, int tx, int ty)
+{
+    std::vector<WaferBatchBlock> t;
+    const long long layer = wafer_batch_layer(geoms, shape_of, active, n_members, tx, ty);
+    const long long target = 8LL * num_cus;
+    for (uint32_t m = 0; m < n_members; ++m) {
+        if (active && !active[m]) continue;
+        const int sh = shape_of[m];
+        const WaferGeom &g = geoms[sh];
+        const int ntx = (g.nx + tx - 1) / tx, nty = (g.ny + ty - 1) / ty;
+        long long nch = layer > 0 ? (target + layer - 1) / layer : 1;
+        const long long most = (long long)(g.nzl + 7) / 8;
+        if (nch > most) nch = most;
+        if (nch < 1) nch = 1;
+        const int zchunk = (int)((g.nzl + nch - 1) / nch);
+        for (int z0 = g.G; z0 < g.G + g.nzl; z0 += zchunk)
+            for (int j = 0; j < nty; ++j)
+                for (int i = 0; i < ntx; ++i)
+                    t.push_back(WaferBatchBlock{(int)m, i * tx, j * ty, z0, z0 + zchunk < g.G + g.nzl ? z0 + zchunk : g.G + g.nzl, sh});
+    }
+    return t;
+}
+
+// The fused pass's table over several shapes: wafer_batch_fused_table's rule with the summed layer, every member's planes shared
+// out evenly over its own wafer_batch_fused_nchunks(nz_m, layer, ...) chunks.  For one shape: wafer_batch_fused_table's entries.
+static inline std::vector<WaferBatchBlock> wafer_batch_fused_table_mixed(const WaferGeom *geoms, const int *shape_of, const uint8_t *active,
+                                                                         uint32_t n_members, int num_cus, int K, int tx, int ty)
+{
+    std::vector<WaferBatchBlock> t;
+    const long long layer = wafer_batch_layer(geoms, shape_of, active, n_members, tx, ty);
+    for (uint32_t m = 0; m < n_members; ++m) {
+        if (active && !active[m]) continue;
+        const int sh = shape_of[m];
+        const WaferGeom &g = geoms[sh];
+        if (g.nzl < 1) continue;
+        const int ntx = (g.nx + tx - 1) / tx, nty = (g.ny + ty - 1) / ty;
+        const int nch = wafer_batch_fused_nchunks(g.nzl, layer, num_cus, g.R, K);
+        for (int c = 0; c < nch; ++c) {
+            const int z0 = g.G + (int)((long long)c * g.nzl / nch), z1 = g.G + (int)((long long)(c + 1) * g.nzl / nch);
+            for (int j = 0; j < nty; ++j)
+                for (int i = 0; i < ntx; ++i) t.push_back(WaferBatchBlock{(int)m, i * tx, j * ty, z0, z1, sh});
         }
     }
     return t;

@@ -1,4 +1,5 @@
-// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B problems of one shape on one device, one
+// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B problems on one device -- of one shape, or
+// (wafer_batch_create_mixed, ground-state calls only) of several: "Several shapes" below -- one
 // launch per step over the active members -- or, for ground-state steps, one launch per pass of K steps (wafer_batch_plan.h) --
 // (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip), and for
 // excited states a per-member state store with the normalise / Gram-Schmidt tail of every step (wafer_gs_batch.hip.h,
@@ -13,6 +14,17 @@
 // ground-state step).  Every array and store slot is allocated in the element size `esz`, the geometry is the one a context of
 // that dtype builds (wafer_make_geom with that element size: the context's set-up kernels run on the views), and the entry
 // points of the kernels take the dtype.
+//
+// Several shapes (wafer_batch_create_mixed with more than one distinct nx, ny, nz).  The batch keeps a table of its distinct
+// geometries (`geoms`, each the one wafer_ctx_create builds for that shape; on the device too) and every member an index into it.
+// Storage is still one allocation per array kind, member m at element offset off[m] = the sum of the totals of the members
+// before it, every member with its own guard rows and planes.  The step tables are built over all active members at once
+// (wafer_batch_plan.h) and every entry carries its member's shape index, so a step or a fused pass is ONE launch whatever the
+// shapes; the kernels are the same templates instantiated with the geometry read from the device table (wafer_tu_batch_mixed.hip).
+// Observables, norm2 and normalise run on grids of (workgroup, member) as wide as the largest member needs, each member on the
+// partition a context of its shape gets (recorded in its WaferBatchMember).  A batch of one shape takes none of this: b->mixed is
+// false and every call runs what wafer_batch_create's batches run.  The state stores have no layout for several shapes yet, so the
+// excited-state calls are refused there (refuse_mixed).
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_batch.hip.h"
@@ -26,7 +38,14 @@ struct wafer_batch {
     WaferTuning tune;
     hipStream_t s = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    size_t stride = 0;                        // elements per member in each array allocation
+    size_t stride = 0;                        // elements per member in each array allocation (one shape)
+    // the distinct geometries, in order of first appearance; g is geoms[0].  mixed: more than one
+    std::vector<WaferGeom> geoms;
+    std::vector<int> shape_of;                // member m's entry in geoms
+    std::vector<size_t> off;                  // member m's element offset in each array allocation (== m * stride for one shape)
+    WaferGeom *geoms_dev = nullptr;
+    bool mixed = false;
+    std::string kernel_name = "wafer_k_batch_step";
     int dtype = WAFER_F64;                    // every member's (check_member)
     bool f32 = false;                         // float storage (f32 and f32fast)
     size_t esz = 8;                           // bytes per element of every array and store slot
@@ -76,7 +95,7 @@ struct wafer_batch {
 
 namespace {
 
-int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0)
+int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0, bool same_shape = true)
 {
     if (m->struct_size != sizeof(wafer_params))
         return fail(WAFER_ERR_INVALID, "member %u: wafer_params.struct_size %u != %zu (ABI mismatch)", i, m->struct_size, sizeof(wafer_params));
@@ -98,9 +117,11 @@ int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0)
     if (m0) {
         if (m->dtype != m0->dtype)
             return fail(WAFER_ERR_INVALID, "member %u: dtype = %d differs from member 0's %d (a batch holds one dtype)", i, (int)m->dtype, (int)m0->dtype);
-        if (m->nx != m0->nx) return fail(WAFER_ERR_INVALID, "member %u: nx = %u differs from member 0's %u", i, m->nx, m0->nx);
-        if (m->ny != m0->ny) return fail(WAFER_ERR_INVALID, "member %u: ny = %u differs from member 0's %u", i, m->ny, m0->ny);
-        if (m->nz != m0->nz) return fail(WAFER_ERR_INVALID, "member %u: nz = %u differs from member 0's %u", i, m->nz, m0->nz);
+        if (same_shape) {   // (wafer_batch_create_mixed: every member its own)
+            if (m->nx != m0->nx) return fail(WAFER_ERR_INVALID, "member %u: nx = %u differs from member 0's %u", i, m->nx, m0->nx);
+            if (m->ny != m0->ny) return fail(WAFER_ERR_INVALID, "member %u: ny = %u differs from member 0's %u", i, m->ny, m0->ny);
+            if (m->nz != m0->nz) return fail(WAFER_ERR_INVALID, "member %u: nz = %u differs from member 0's %u", i, m->nz, m0->nz);
+        }
         if (m->central_difference != m0->central_difference)
             return fail(WAFER_ERR_INVALID, "member %u: central_difference = %d differs from member 0's %d", i, m->central_difference,
                         m0->central_difference);
@@ -120,7 +141,7 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->blk_dev, (void *)b->blkk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk_dev, (void *)b->blkk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
                     (void *)b->gram_list_dev})
         if (p) (void)hipFree(p);
@@ -137,6 +158,14 @@ int check_member_index(const wafer_batch *b, uint32_t m)
     if (!b) return fail(WAFER_ERR_INVALID, "null batch");
     if (m >= b->n) return fail(WAFER_ERR_INVALID, "member %u out of range (the batch has %u)", m, b->n);
     return WAFER_OK;
+}
+
+// the calls that need the state stores: not on a batch of several shapes; nothing has changed when this returns
+int refuse_mixed(const wafer_batch *b, const char *call)
+{
+    if (!b->mixed) return WAFER_OK;
+    return fail(WAFER_ERR_INVALID, "%s: not available on a mixed-shape batch (%zu distinct shapes): excited states need one shape per batch",
+                call, b->geoms.size());
 }
 
 // every active member has phi (and, with need_pot, a potential: `what` ends that message) and at least wnum stored states
@@ -186,30 +215,13 @@ int upload_active(wafer_batch *b, const uint8_t *active, int *nact)
     return WAFER_OK;
 }
 
-// The step's workgroup table: 64 x 4 tiles of the work area, z cut into chunks so that the active members together give
-// ~8 workgroups per CU (a CU holds 8 of these 256-thread workgroups), no chunk shorter than 8 planes.
+// The step's workgroup table (wafer_batch_step_table, wafer_batch_plan.h) on the device, for this active set
 int build_blocks(wafer_batch *b, const uint8_t *active)
 {
     std::vector<uint8_t> key(b->n);
     for (uint32_t m = 0; m < b->n; ++m) key[m] = (!active || active[m]) ? 1 : 0;
     if (key == b->blk_key && b->blk_dev) return WAFER_OK;
-    const WaferGeom &g = b->g;
-    const int ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX, nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    long long nact = 0;
-    for (uint8_t a : key) nact += a;
-    const long long layer = nact * ntx * nty;
-    const long long target = 8LL * b->num_cus;
-    long long nch = layer > 0 ? (target + layer - 1) / layer : 1;
-    nch = std::max(1LL, std::min(nch, (long long)(g.nzl + 7) / 8));
-    const int zchunk = (int)((g.nzl + nch - 1) / nch);
-    b->blk.clear();
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (!key[m]) continue;
-        for (int z0 = g.G; z0 < g.G + g.nzl; z0 += zchunk)
-            for (int ty = 0; ty < nty; ++ty)
-                for (int tx = 0; tx < ntx; ++tx)
-                    b->blk.push_back(WaferBatchBlock{(int)m, tx * WAFER_BATCH_TX, ty * WAFER_BATCH_TY, z0, std::min(z0 + zchunk, g.G + g.nzl), 0});
-    }
+    b->blk = wafer_batch_step_table(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, WAFER_BATCH_TX, WAFER_BATCH_TY);
     HIP_TRY(hipStreamSynchronize(b->s));
     if (b->blk.size() > b->blk_cap) {
         if (b->blk_dev) HIP_TRY(hipFree(b->blk_dev));
@@ -243,7 +255,9 @@ int build_blocks_fused(wafer_batch *b, const uint8_t *active, int K)
     std::vector<uint8_t> key(b->n);
     for (uint32_t m = 0; m < b->n; ++m) key[m] = (!active || active[m]) ? 1 : 0;
     if (key == b->blkk_key && K == b->blkk_K && b->blkk_dev) return WAFER_OK;
-    b->blkk = wafer_batch_fused_table(b->g, key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY);
+    b->blkk = b->mixed ? wafer_batch_fused_table_mixed(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX,
+                                                       WAFER_BATCHK_TY)
+                       : wafer_batch_fused_table(b->g, key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY);
     HIP_TRY(hipStreamSynchronize(b->s));
     if (b->blkk.size() > b->blkk_cap || !b->blkk_dev) {
         if (b->blkk_dev) HIP_TRY(hipFree(b->blkk_dev));
@@ -267,8 +281,12 @@ int observables(wafer_batch *b, const uint8_t *active)
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
     RoctxRange range_("wafer_batch_observables");
-    const hipError_t e = wafer_entry_batch_observables(b->f32, b->g.R, b->g, b->mem_dev, b->act_dev, nact, b->obs_ntx, b->obs_nty, b->obs_nb,
-                                                       b->obs_zchunk, b->swz, b->partials, b->sums, b->s);
+    int max_nb = 0;   // (several shapes: the grid is as wide as the largest launched member's partition)
+    for (int k = 0; k < nact; ++k) max_nb = std::max(max_nb, b->mem[b->act_host[k]].obs_nb);
+    const hipError_t e = b->mixed ? wafer_entry_batchm_observables(b->f32, b->g.R, b->geoms_dev, b->mem_dev, b->act_dev, nact, max_nb, b->swz,
+                                                                   b->partials, b->sums, b->s)
+                                  : wafer_entry_batch_observables(b->f32, b->g.R, b->g, b->mem_dev, b->act_dev, nact, b->obs_ntx, b->obs_nty,
+                                                                  b->obs_nb, b->obs_zchunk, b->swz, b->partials, b->sums, b->s);
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched observables launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(b->sums_host, b->sums, sizeof(double) * 4 * b->n, hipMemcpyDeviceToHost, b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
@@ -293,7 +311,15 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     int nact = 0;
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
-    const hipError_t e = wafer_entry_batch_normalise(b->f32, b->g, b->mem_dev, b->act_dev, nact, norm2_dev, stride, b->s);
+    int max_tiles = 0, max_planes = 0;
+    for (int k = 0; k < nact; ++k) {
+        const WaferGeom &g = b->geoms[b->shape_of[b->act_host[k]]];
+        max_tiles = std::max(max_tiles, ((g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
+        max_planes = std::max(max_planes, g.nzl);
+    }
+    const hipError_t e = b->mixed ? wafer_entry_batchm_normalise(b->f32, b->geoms_dev, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, norm2_dev,
+                                                                 stride, b->s)
+                                  : wafer_entry_batch_normalise(b->f32, b->g, b->mem_dev, b->act_dev, nact, norm2_dev, stride, b->s);
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -356,7 +382,9 @@ int ensure_gs(wafer_batch *b)
 {
     if (b->gs_scal) return WAFER_OK;
     const size_t nsc = (size_t)b->gs_stride * b->n;
-    HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * (size_t)std::max(b->gs_nb, b->n2_nb) * b->n));
+    size_t npart = (size_t)std::max(b->gs_nb, b->n2_nb) * b->n;
+    if (b->mixed) npart = (size_t)(b->mem[b->n - 1].n2_off + b->mem[b->n - 1].n2_nb);   // every member's own norm2 partition, end to end
+    HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * npart));
     HIP_TRY(hipHostMalloc((void **)&b->gs_host, sizeof(double) * nsc, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->gs_scal, sizeof(double) * nsc));
     HIP_TRY(hipMemsetAsync(b->gs_scal, 0, sizeof(double) * nsc, b->s));
@@ -481,6 +509,7 @@ int gs_chain(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_f
 // once per launch.
 int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t n_steps)
 {
+    if (wnum) TRY(refuse_mixed(b, "wafer_batch_evolve_state"));
     HIP_TRY(hipSetDevice(b->device));
     TRY(check_ready(b, active, true, " before evolve", 0));
     if (wnum) TRY(check_ready(b, active, false, "", wnum));
@@ -506,8 +535,11 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
         while (left > 0) {   // no host synchronisation in here: every scalar stays on the device
             const int k = wafer_batch_next_pass(left, K, have2);
             const int flip = (int)(launches & 1);
-            const hipError_t e = k > 1 ? wafer_entry_batch_stepk(step_dtype, b->g.R, k, b->g, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
-                                       : wafer_entry_batch_step(step_dtype, b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s);
+            const hipError_t e =
+                b->mixed ? (k > 1 ? wafer_entry_batchm_stepk(step_dtype, b->g.R, k, b->geoms_dev, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
+                                  : wafer_entry_batchm_step(step_dtype, b->g.R, b->geoms_dev, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s))
+                         : (k > 1 ? wafer_entry_batch_stepk(step_dtype, b->g.R, k, b->g, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
+                                  : wafer_entry_batch_step(step_dtype, b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s));
             if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
             ++launches;
             ++(k > 1 ? b->n_fused_passes : b->n_single_steps);
@@ -528,6 +560,7 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
 
 int orthogonalise(wafer_batch *b, const uint8_t *active, uint32_t wnum)
 {
+    TRY(refuse_mixed(b, "wafer_batch_orthogonalise"));
     HIP_TRY(hipSetDevice(b->device));
     TRY(check_ready(b, active, false, "", wnum));
     if (wnum == 0) return WAFER_OK;
@@ -652,20 +685,34 @@ int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t s
 
 extern "C" {
 
-int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out)
+// wafer_batch_create (same_shape) and wafer_batch_create_mixed
+static int create_batch(const wafer_params *members, uint32_t n_members, bool same_shape, wafer_batch **out)
 {
     if (!members || !out) return fail(WAFER_ERR_INVALID, "null argument");
     if (n_members == 0) return fail(WAFER_ERR_INVALID, "a batch needs at least one member (n_members = 0)");
-    for (uint32_t i = 0; i < n_members; ++i) TRY(check_member(&members[i], i, i ? &members[0] : nullptr));
+    for (uint32_t i = 0; i < n_members; ++i) TRY(check_member(&members[i], i, i ? &members[0] : nullptr, same_shape));
     const wafer_params &p0 = members[0];
     const int R = p0.central_difference;
     const int G = p0.halo_depth ? (int)p0.halo_depth : R;
     const bool f32 = p0.dtype != WAFER_F64;
     const size_t esz = f32 ? 4 : 8;
-    const WaferGeom g = wafer_make_geom((int)p0.nx, (int)p0.ny, (int)p0.nz, R, G, 0, (int)p0.nz, (int)esz);   // wafer_ctx_create's
-    size_t bytes = 0;
-    if (__builtin_mul_overflow((size_t)g.total, (size_t)n_members, &bytes) || __builtin_mul_overflow(bytes, esz, &bytes))
-        return fail(WAFER_ERR_INVALID, "%u members of %lld padded cells overflow the size of one allocation", n_members, (long long)g.total);
+    // the distinct geometries in order of first appearance, each wafer_ctx_create's for that shape; members at the prefix sums of
+    // their totals (one shape: m * g.total)
+    std::vector<WaferGeom> geoms;
+    std::vector<int> shape_of(n_members);
+    std::vector<size_t> off(n_members);
+    size_t cells = 0, bytes = 0;
+    for (uint32_t m = 0; m < n_members; ++m) {
+        const wafer_params &p = members[m];
+        size_t k = 0;
+        while (k < geoms.size() && !(geoms[k].nx == (int)p.nx && geoms[k].ny == (int)p.ny && geoms[k].nz == (int)p.nz)) ++k;
+        if (k == geoms.size()) geoms.push_back(wafer_make_geom((int)p.nx, (int)p.ny, (int)p.nz, R, G, 0, (int)p.nz, (int)esz));
+        shape_of[m] = (int)k;
+        off[m] = cells;
+        if (__builtin_add_overflow(cells, (size_t)geoms[k].total, &cells) || __builtin_mul_overflow(cells, esz, &bytes))
+            return fail(WAFER_ERR_INVALID, "%u members of %zu padded cells up to member %u overflow the size of one allocation", n_members, cells, m);
+    }
+    const WaferGeom g = geoms[0];
 
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
@@ -683,6 +730,10 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     b->num_cus = cus > 0 ? cus : 256;
     b->tune = wafer_tuning_from_env();
     b->stride = (size_t)g.total;
+    b->mixed = geoms.size() > 1;
+    b->geoms = geoms;
+    b->shape_of = shape_of;
+    b->off = off;
     b->dtype = (int)p0.dtype;
     b->f32 = f32;
     b->esz = esz;
@@ -712,24 +763,57 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
 
     // observables: the partition wafer_launch_observables_lds gives a single context of this shape and storage type -- 16 bytes
     // per lane, so tiles 128 wide on doubles and 256 wide on floats (WaferLdsCfg::TX), and the z-chunk that follows from them
-    {
+    // -- per shape; the batch's own fields are shape 0's (all a batch of one shape reads)
+    struct ObsPart {
+        int ntx, nty, zchunk, nb;
+    };
+    auto obs_partition = [&](const WaferGeom &g) {
+        ObsPart o;
         const int NW = R <= 2 ? 8 : 4;
         const int TX = f32 ? WaferLdsCfg<float, 1, 2>::TX : WaferLdsCfg<double, 1, 2>::TX, TY = 2 * NW;
         const int ry = 2 * (NW / 4);
         if (f32)
-            b->obs_zchunk = R == 1   ? wafer_lds_zchunk<float, 1>(b->tune, g, g.nzl, ry, b->num_cus)
-                            : R == 2 ? wafer_lds_zchunk<float, 2>(b->tune, g, g.nzl, ry, b->num_cus)
-                                     : wafer_lds_zchunk<float, 3>(b->tune, g, g.nzl, ry, b->num_cus);
+            o.zchunk = R == 1   ? wafer_lds_zchunk<float, 1>(b->tune, g, g.nzl, ry, b->num_cus)
+                       : R == 2 ? wafer_lds_zchunk<float, 2>(b->tune, g, g.nzl, ry, b->num_cus)
+                                : wafer_lds_zchunk<float, 3>(b->tune, g, g.nzl, ry, b->num_cus);
         else
-            b->obs_zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, ry, b->num_cus)
-                            : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, ry, b->num_cus)
-                                     : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, ry, b->num_cus);
-        b->obs_ntx = (g.nx + TX - 1) / TX;
-        b->obs_nty = (g.ny + TY - 1) / TY;
-        b->obs_nb = b->obs_ntx * b->obs_nty * ((g.nzl + b->obs_zchunk - 1) / b->obs_zchunk);
+            o.zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, ry, b->num_cus)
+                       : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, ry, b->num_cus)
+                                : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, ry, b->num_cus);
+        o.ntx = (g.nx + TX - 1) / TX;
+        o.nty = (g.ny + TY - 1) / TY;
+        o.nb = o.ntx * o.nty * ((g.nzl + o.zchunk - 1) / o.zchunk);
+        return o;
+    };
+    {
+        const ObsPart o = obs_partition(g);
+        b->obs_zchunk = o.zchunk;
+        b->obs_ntx = o.ntx;
+        b->obs_nty = o.nty;
+        b->obs_nb = o.nb;
         b->swz = wafer_lds_opts(b->tune).swz;
     }
-    HIP_TRYB(hipMalloc((void **)&b->partials, sizeof(double) * 4 * (size_t)b->obs_nb * n_members));
+    // the members' partition records and the places of their partials: [4][obs_nb] per member, end to end (one shape: member m's at
+    // m * 4 * obs_nb, as the single-shape kernels index them)
+    b->mem.resize(n_members);
+    size_t obs_total = 0, n2_total = 0;
+    for (uint32_t m = 0; m < n_members; ++m) {
+        WaferBatchMember &e = b->mem[m];
+        memset(&e, 0, sizeof e);
+        const WaferGeom &gm = b->geoms[shape_of[m]];
+        const ObsPart o = obs_partition(gm);
+        e.shape = shape_of[m];
+        e.obs_ntx = o.ntx;
+        e.obs_nty = o.nty;
+        e.obs_zchunk = o.zchunk;
+        e.obs_nb = o.nb;
+        e.n2_nb = f32 ? wafer_rownorm2_blocks(gm, (int)esz, b->num_cus) : wafer_gs_blocks(gm);
+        e.obs_off = (long long)obs_total;
+        e.n2_off = (long long)n2_total;
+        obs_total += 4 * (size_t)o.nb;
+        n2_total += (size_t)e.n2_nb;
+    }
+    HIP_TRYB(hipMalloc((void **)&b->partials, sizeof(double) * obs_total));
     HIP_TRYB(hipMalloc((void **)&b->sums, sizeof(double) * 4 * n_members));
     HIP_TRYB(hipHostMalloc((void **)&b->sums_host, sizeof(double) * 4 * n_members, hipHostMallocDefault));
     HIP_TRYB(hipMalloc((void **)&b->n2, sizeof(double) * n_members));
@@ -737,12 +821,20 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     HIP_TRYB(hipMalloc((void **)&b->act_dev, sizeof(int) * n_members));
     HIP_TRYB(hipHostMalloc((void **)&b->act_host, sizeof(int) * n_members, hipHostMallocDefault));
     HIP_TRYB(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
+    HIP_TRYB(hipMalloc((void **)&b->geoms_dev, sizeof(WaferGeom) * b->geoms.size()));
+    HIP_TRYB(hipMemcpy(b->geoms_dev, b->geoms.data(), sizeof(WaferGeom) * b->geoms.size(), hipMemcpyHostToDevice));
+    if (b->mixed) {
+        static const char *const types[] = {"double,double", "float,double", "float,float"};
+        char name[96];
+        snprintf(name, sizeof name, "wafer_k_batch_step<%d,%s,WaferBatchGeomTable>", R, types[b->dtype]);
+        b->kernel_name = name;
+    }
 
     b->views.reserve(n_members);
-    b->mem.resize(n_members);
     for (uint32_t m = 0; m < n_members; ++m) {
         wafer_ctx *c = new wafer_ctx();
         b->views.push_back(c);
+        const WaferGeom &g = b->geoms[shape_of[m]];   // (the member's own from here on)
         c->P = members[m];
         c->g = g;
         c->f32 = f32;   // as wafer_ctx_create sets them
@@ -758,12 +850,11 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
         if (members[m].flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = c->div_plan_f.checked = 0;
         void **arr[4] = {&c->phi[0], &c->phi[1], &c->v, &c->potsub};
         for (int k = 0; k < 4; ++k)
-            *arr[k] = static_cast<char *>(b->alloc[k]) + ((size_t)m * b->stride + (size_t)g.base_off) * esz;
+            *arr[k] = static_cast<char *>(b->alloc[k]) + (b->off[m] + (size_t)g.base_off) * esz;
         c->scal = b->view_scal + (size_t)m * SCAL_SLOTS;
         c->scal_host = b->view_scal_host + (size_t)m * SCAL_SLOTS;
         c->kernel_name = "wafer_k_batch_step";
         WaferBatchMember &e = b->mem[m];
-        memset(&e, 0, sizeof e);
         e.phi[0] = c->phi[0];
         e.phi[1] = c->phi[1];
         e.v = c->v;
@@ -780,6 +871,23 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
     HIP_TRYB(hipStreamSynchronize(b->s));
 #undef HIP_TRYB
     *out = b;
+    return WAFER_OK;
+}
+
+int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out)
+{
+    return create_batch(members, n_members, true, out);
+}
+
+int wafer_batch_create_mixed(const wafer_params *members, uint32_t n_members, wafer_batch **out)
+{
+    return create_batch(members, n_members, false, out);
+}
+
+int wafer_batch_num_shapes(wafer_batch *b, uint32_t *n_shapes)
+{
+    if (!b || !n_shapes) return fail(WAFER_ERR_INVALID, "null argument");
+    *n_shapes = (uint32_t)b->geoms.size();
     return WAFER_OK;
 }
 
@@ -864,6 +972,7 @@ int wafer_batch_solve_state(wafer_batch *b, uint32_t wnum, double tolerance, uin
                             wafer_observables_output *finals, int *status)
 {
     if (!b || !status) return fail(WAFER_ERR_INVALID, "null argument");
+    TRY(refuse_mixed(b, "wafer_batch_solve_state"));
     return solve(b, wnum, true, tolerance, screen_update, has_max_steps, max_steps, records, max_records_per_member, n_records, finals, status);
 }
 
@@ -888,7 +997,13 @@ int wafer_batch_norm2(wafer_batch *b, double *out)
     TRY(sync_members(b));
     int nact = 0;
     TRY(upload_active(b, nullptr, &nact));
-    if (b->f32) {   // the partition of a context's wafer_norm2: the same double (fp64 keeps the batch's own partition)
+    if (b->mixed) {   // every member on its own shape's partition: wafer_rownorm2_blocks (float storage) or wafer_gs_blocks (doubles)
+        int max_nb = 0;
+        for (uint32_t m = 0; m < b->n; ++m) max_nb = std::max(max_nb, b->mem[m].n2_nb);
+        const hipError_t e = wafer_entry_batchm_norm2(b->f32, b->geoms_dev, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, b->gs_stride, 0,
+                                                      b->gs_partials, b->s);
+        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
+    } else if (b->f32) {   // the partition of a context's wafer_norm2: the same double (fp64 keeps the batch's own partition)
         const hipError_t e = wafer_entry_batch_rownorm2(b->g, b->mem_dev, b->act_dev, nact, b->n2_nb, b->gs_scal, b->gs_stride, 0, b->gs_partials, b->s);
         if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
     } else {
@@ -903,6 +1018,7 @@ int wafer_batch_norm2(wafer_batch *b, double *out)
 int wafer_batch_push_state(wafer_batch *b, const uint8_t *active)
 {
     if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    TRY(refuse_mixed(b, "wafer_batch_push_state"));
     return push_states(b, active);
 }
 
@@ -910,6 +1026,7 @@ int wafer_batch_load_state(wafer_batch *b, uint32_t member, uint32_t idx, const 
 {
     TRY(check_member_index(b, member));
     if (!state) return fail(WAFER_ERR_INVALID, "null argument");
+    TRY(refuse_mixed(b, "wafer_batch_load_state"));
     HIP_TRY(hipSetDevice(b->device));
     if (idx > b->nst[member]) return fail(WAFER_ERR_STATE, "member %u: states must be loaded in order", member);
     if (idx == b->nst[member]) TRY(check_capacity(b, member));
@@ -924,6 +1041,7 @@ int wafer_batch_download_state(wafer_batch *b, uint32_t member, uint32_t idx, do
 {
     TRY(check_member_index(b, member));
     if (!out) return fail(WAFER_ERR_INVALID, "null argument");
+    TRY(refuse_mixed(b, "wafer_batch_download_state"));
     if (idx >= b->nst[member]) return fail(WAFER_ERR_STATE, "member %u: no state %u", member, idx);
     HIP_TRY(hipSetDevice(b->device));
     return download_padded(b->views[member], out, slot_ptr(b, idx, member));
@@ -939,6 +1057,7 @@ int wafer_batch_num_states(wafer_batch *b, uint32_t *counts_out)
 int wafer_batch_clear_states(wafer_batch *b, const uint8_t *active)
 {
     if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    TRY(refuse_mixed(b, "wafer_batch_clear_states"));
     HIP_TRY(hipSetDevice(b->device));
     uint32_t keep = 0;
     for (uint32_t m = 0; m < b->n; ++m) {
@@ -961,6 +1080,7 @@ int wafer_batch_clear_states(wafer_batch *b, const uint8_t *active)
 int wafer_batch_clone_state_to_phi(wafer_batch *b, const uint8_t *active, uint32_t idx)
 {
     if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    TRY(refuse_mixed(b, "wafer_batch_clone_state_to_phi"));
     HIP_TRY(hipSetDevice(b->device));
     for (uint32_t m = 0; m < b->n; ++m)
         if ((!active || active[m]) && idx >= b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: no state %u", m, idx);
@@ -986,8 +1106,7 @@ int wafer_batch_last_evolve_ms(wafer_batch *b, float *ms, uint64_t *steps)
 
 const char *wafer_batch_kernel_name(wafer_batch *b)
 {
-    (void)b;
-    return "wafer_k_batch_step";
+    return b ? b->kernel_name.c_str() : "wafer_k_batch_step";
 }
 
 int wafer_batch_steps_per_launch(wafer_batch *b)
@@ -1010,19 +1129,23 @@ int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n)
     static const char *const stencils[] = {"", "ThreePoint", "FivePoint", "SevenPoint"};
     static const char *const dtypes[] = {"f64", "f32", "f32fast"};
     static const char *const types[] = {"", ",float,double", ",float,float"};   // the kernels' <.., T, C> beside the fp64 default
+    static const char *const types_mixed[] = {",double,double,WaferBatchGeomTable", ",float,double,WaferBatchGeomTable",
+                                              ",float,float,WaferBatchGeomTable"};   // several shapes: the geometry source after them
+    const char *const *tn = b->mixed ? types_mixed : types;
     const int R = b->g.R, K = steps_per_pass(b);
-    char kernel[64], tile[32];
+    char kernel[96], tile[32];
     const char *remainder = "none";
     if (K > 1) {
-        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d%s>", R, K, types[b->dtype]);
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d%s>", R, K, tn[b->dtype]);
         snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCHK_TX, WAFER_BATCHK_TY);
         remainder = have_two_step(b, K) ? "stepk2+step" : "step";
     } else {
-        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d%s>", R, types[b->dtype]);
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d%s>", R, tn[b->dtype]);
         snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCH_TX, WAFER_BATCH_TY);
     }
-    snprintf(buf, n, "stencil=%s kernel=%s steps_per_pass=%d tile=%s lds_bytes=%d remainder=%s variant=%d dtype=%s", stencils[R], kernel, K, tile,
-             K > 1 ? wafer_batch_stepk_lds_bytes(b->dtype, R, K) : 0, remainder, b->step_variant, dtypes[b->dtype]);
+    const int len = snprintf(buf, n, "stencil=%s kernel=%s steps_per_pass=%d tile=%s lds_bytes=%d remainder=%s variant=%d dtype=%s", stencils[R], kernel, K,
+                             tile, K > 1 ? wafer_batch_stepk_lds_bytes(b->dtype, R, K) : 0, remainder, b->step_variant, dtypes[b->dtype]);
+    if (b->mixed && len > 0 && (size_t)len < n) snprintf(buf + len, n - (size_t)len, " shapes=%zu", b->geoms.size());
     return WAFER_OK;
 }
 
@@ -1038,6 +1161,7 @@ int wafer_batch_set_gs_variant(wafer_batch *b, int variant)
 {
     if (!b) return fail(WAFER_ERR_INVALID, "null batch");
     if (variant < -1 || variant > 1) return fail(WAFER_ERR_INVALID, "gs variant must be -1 (default), 0 (sequential) or 1 (one pass)");
+    if (variant == 1) TRY(refuse_mixed(b, "wafer_batch_set_gs_variant"));
     b->gs_variant = variant;
     return WAFER_OK;
 }

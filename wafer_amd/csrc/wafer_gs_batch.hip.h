@@ -43,6 +43,18 @@ struct WaferBatchGsArgs {
     const void *dotwith;        // DOT, SCALE, AXPY: the state whose overlap with the resulting phi is summed; null: none
 };
 
+// A batch of several shapes (wafer_batch_norm2 on doubles is the one call that gets here: the excited-state calls are refused):
+// the geometry comes from the device table, the tile counts from it, the member's workgroup count and the place of its partials
+// from its record (WaferBatchMember::n2_nb, n2_off); a.g, a.ntx, a.nty and a.mstride are not read.
+struct WaferBatchGsArgsMixed : WaferBatchGsArgs {
+    const WaferGeom *geoms;
+};
+__device__ __forceinline__ const WaferGeom &wafer_gs_geom(const WaferBatchGsArgs &a, int) { return a.g; }
+__device__ __forceinline__ WaferGeom wafer_gs_geom(const WaferBatchGsArgsMixed &a, int shape)
+{
+    return a.geoms[__builtin_amdgcn_readfirstlane(shape)];
+}
+
 // workgroups per member
 static inline int wafer_gs_blocks(const WaferGeom &g)
 {
@@ -51,15 +63,22 @@ static inline int wafer_gs_blocks(const WaferGeom &g)
 }
 
 // Block (64, 4), grid (wafer_gs_blocks, active members).
-template <int MODE, typename T = double>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs(WaferBatchGsArgs a, const WaferBatchMember *__restrict__ mem,
+template <int MODE, typename T = double, typename A = WaferBatchGsArgs>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs(A a, const WaferBatchMember *__restrict__ mem,
                                                         const int *__restrict__ act, const double *__restrict__ scal,
                                                         double *__restrict__ partials)
 {
+    constexpr bool MIXED = std::is_same_v<A, WaferBatchGsArgsMixed>;
+    static_assert(!MIXED || MODE == WAFER_GS_NORM2, "the state stores of a batch of several shapes have no layout yet");
     __shared__ double red[4];
-    const WaferGeom &g = a.g;
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    if constexpr (MIXED) {   // the member's own partition; a workgroup beyond it leaves as a whole
+        if ((int)blockIdx.x >= m.n2_nb) return;
+        a.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+        a.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    }
     T *__restrict__ phi = static_cast<T *>(m.phi[(m.cur ^ a.flip) & 1]);
     const long long moff = (long long)member * a.mstride;
     const T *__restrict__ lower = (MODE == WAFER_GS_AXPY) ? static_cast<const T *>(a.lower) + moff : nullptr;
@@ -100,7 +119,11 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs(WaferBatchGsArgs a, cons
     }
     if (MODE == WAFER_GS_NORM2 || a.dotwith) {   // (uniform: a kernel argument)
         const double s = wafer_block_sum<4>(acc, red, tid);
-        if (tid == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
+        if constexpr (MIXED) {
+            if (tid == 0) partials[(size_t)m.n2_off + blockIdx.x] = s;
+        } else {
+            if (tid == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
+        }
     }
 }
 
@@ -111,17 +134,19 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce(const doub
 {
     __shared__ double sh[256];
     const int member = act[blockIdx.x];
-    const double *p = partials + (size_t)member * n;
-    double s = 0.0;
-    for (int q = threadIdx.x; q < n; q += 256) s += p[q];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-#pragma unroll
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) scal[(size_t)member * scal_stride + out_slot] = sh[0];
+    const double s = wafer_batch_reduce_tree(partials + (size_t)member * n, n, sh);
+    if (threadIdx.x == 0) scal[(size_t)member * scal_stride + out_slot] = s;
+}
+
+// several shapes: the member's own n2_nb partials, at its own offset
+static __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_mixed(const double *__restrict__ partials, const int *__restrict__ act,
+                                                                            const WaferBatchMember *__restrict__ mem, double *__restrict__ scal,
+                                                                            int scal_stride, int out_slot)
+{
+    __shared__ double sh[256];
+    const int member = act[blockIdx.x];
+    const double s = wafer_batch_reduce_tree(partials + mem[member].n2_off, mem[member].n2_nb, sh);
+    if (threadIdx.x == 0) scal[(size_t)member * scal_stride + out_slot] = s;
 }
 
 // wafer_batch_norm2 on float storage: get_norm_squared on the partition of a single context's wafer_norm2 -- wafer_k_row_op<T, double, 0>
@@ -137,22 +162,38 @@ static inline int wafer_rownorm2_blocks(const WaferGeom &g, int esz, int num_cus
     return (int)(nb > 1 ? nb : 1);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(WaferRowArgs a, const WaferBatchMember *__restrict__ mem,
+// Several shapes (A = WaferBatchGeomTable): the walk is dealt over the member's own n2_nb workgroups (wafer_rownorm2_blocks of ITS
+// shape), gridDim.x is the largest among the launched members, and the partials lie at partials[n2_off + workgroup].
+__device__ __forceinline__ const WaferGeom &wafer_row_geom(const WaferRowArgs &a, int) { return a.g; }
+__device__ __forceinline__ WaferGeom wafer_row_geom(const WaferBatchGeomTable &a, int shape) { return wafer_batch_geom(a, shape); }
+
+template <typename T, typename A = WaferRowArgs>
+__global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(A a, const WaferBatchMember *__restrict__ mem,
                                                               const int *__restrict__ act, double *__restrict__ partials)
 {
     using VT = typename WaferRowVec<T>::type;
     constexpr int VEC = WaferRowVec<T>::N;
+    constexpr bool MIXED = std::is_same_v<A, WaferBatchGeomTable>;
     __shared__ double red[4];
-    const WaferGeom &g = a.g;
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_row_geom(a, m.shape);
+    int nb = gridDim.x, lz_lo, lz_hi;
+    if constexpr (MIXED) {
+        nb = m.n2_nb;
+        if ((int)blockIdx.x >= nb) return;
+        lz_lo = g.G;
+        lz_hi = g.G + g.nzl;
+    } else {
+        lz_lo = a.lz_lo;
+        lz_hi = a.lz_hi;
+    }
     const T *__restrict__ phi = static_cast<const T *>(m.phi[m.cur]);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nsegx = (g.nx + 64 * VEC - 1) / (64 * VEC);
     const int wlim = g.pitch - g.xoff - g.R;
     double acc = 0.0;
-    WAFER_ROW_WALK_BEGIN(a, g)
+    WAFER_ROW_WALK_BEGIN_N(lz_lo, lz_hi, g, nb)
     for (int xs = 0; xs < nsegx; ++xs) {
         const int xi = xs * 64 * VEC + lane * VEC;
         if (xi >= wlim || xi >= g.nx) continue;
@@ -163,7 +204,11 @@ __global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(WaferRowArgs a, co
     }
     WAFER_ROW_WALK_END(g)
     const double s = wafer_block_sum<4>(acc, red, threadIdx.x);
-    if (threadIdx.x == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
+    if constexpr (MIXED) {
+        if (threadIdx.x == 0) partials[(size_t)m.n2_off + blockIdx.x] = s;
+    } else {
+        if (threadIdx.x == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
+    }
 }
 
 // ---- the one-pass form (wafer_batch_set_gs_variant(b, 1), wnum <= WAFER_MAX_LOW) ---------------------------------------------------
@@ -376,3 +421,7 @@ hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, cons
 // WAFER_GRAM_PAIRS * wafer_gs_blocks doubles per member of the batch
 hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgs &a, const int *list, const int *cnt, int nlist, double *gram,
                                   double *partials, hipStream_t s);
+// a batch of several shapes (wafer_tu_batch_mixed.hip): norm2 of the members in act into scal[member * scal_stride + out_slot], each
+// on its own partition (float storage: wafer_k_batch_rownorm2, doubles: wafer_k_batch_gs<NORM2>); max_nb: the largest n2_nb among them
+hipError_t wafer_entry_batchm_norm2(bool f32, const WaferGeom *geoms, const WaferBatchMember *mem, const int *act, int nact, int max_nb,
+                                    double *scal, int scal_stride, int out_slot, double *partials, hipStream_t s);

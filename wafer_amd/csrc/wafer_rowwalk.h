@@ -17,14 +17,16 @@ template <> struct WaferRowVec<float> { static constexpr int N = 4; typedef floa
 
 // rows [0, (lz_hi - lz_lo) * ny) dealt over the waves of the grid, four waves per workgroup; inside: `rowp`, the element
 // offset of the row's first work cell
-#define WAFER_ROW_WALK_BEGIN(a, g)                                                                                  \
+// (_N: local planes [lo, hi) dealt over nb workgroups, where the grid is wider than the walk: wafer_k_batch_rownorm2)
+#define WAFER_ROW_WALK_BEGIN_N(lo, hi, g, nb)                                                                       \
     {                                                                                                               \
-        const int rows_total_ = ((a).lz_hi - (a).lz_lo) * (g).ny, stride_ = (int)gridDim.x * 4;                     \
+        const int rows_total_ = ((hi) - (lo)) * (g).ny, stride_ = (int)(nb) * 4;                                    \
         int row_ = (int)blockIdx.x * 4 + wave;                                                                      \
         int y_ = row_ % (g).ny, z_ = row_ / (g).ny;                                                                 \
         const int sy_ = stride_ % (g).ny, sz_ = stride_ / (g).ny;                                                   \
         for (; row_ < rows_total_; row_ += stride_) {                                                               \
-            const long long rowp = (long long)((a).lz_lo + z_) * (g).plane + (long long)(y_ + (g).R) * (g).pitch + (g).xoff + (g).R;
+            const long long rowp = (long long)((lo) + z_) * (g).plane + (long long)(y_ + (g).R) * (g).pitch + (g).xoff + (g).R;
+#define WAFER_ROW_WALK_BEGIN(a, g) WAFER_ROW_WALK_BEGIN_N((a).lz_lo, (a).lz_hi, g, gridDim.x)
 #define WAFER_ROW_WALK_END(g)                                                                                       \
             y_ += sy_;                                                                                              \
             z_ += sz_;                                                                                              \

@@ -36,7 +36,28 @@ struct WaferBatchMember {
     int short_forms;         // v_in_range && the plan is checked (WaferStepArgs::v_in_range of a single context)
     int potsub_kind;
     int cur;                 // which phi buffer holds the wavefunction
+    // read by the kernels of a batch of several shapes only (WaferBatchGeomTable below)
+    int shape;               // the member's entry in the batch's table of distinct geometries
+    int obs_ntx, obs_nty, obs_zchunk, obs_nb;   // its observables partition: a single context's of that shape
+    int n2_nb;               // workgroups of its wafer_batch_norm2 (wafer_rownorm2_blocks on float storage, wafer_gs_blocks on doubles)
+    long long obs_off;       // where its [4][obs_nb] partials begin in the observables' partials buffer (doubles)
+    long long n2_off;        // where its n2_nb partials begin in the norm2 partials buffer
 };
+
+// Where a kernel takes its geometry from (the template parameter GS of the kernels below).  WaferGeom: the batch's one geometry, a
+// kernel argument -- a batch of one shape.  WaferBatchGeomTable: the batch's table of distinct geometries in device memory,
+// indexed by the workgroup's shape index -- a batch of several shapes.  The index is workgroup-uniform (it comes from the
+// workgroup's table entry or its member record), so the copy below is scalar loads into SGPRs, made once before any loop.
+// Everything after that copy is one text for both.
+struct WaferBatchGeomTable {
+    const WaferGeom *geoms;
+};
+__device__ __forceinline__ const WaferGeom &wafer_batch_geom(const WaferGeom &g, int) { return g; }
+__device__ __forceinline__ WaferGeom wafer_batch_geom(const WaferBatchGeomTable &t, int shape)
+{
+    return t.geoms[__builtin_amdgcn_readfirstlane(shape)];
+}
+template <typename GS> inline constexpr bool wafer_batch_mixed = !std::is_same_v<GS, WaferGeom>;
 
 // the member's division by c dn^2 m in the arithmetic type C (wafer_den of a single context's WaferStepArgs)
 template <typename C>
@@ -54,11 +75,12 @@ __device__ __forceinline__ WaferDen<C> wafer_batch_den(const WaferBatchMember &m
 // One time step of every member in the table.  Block (64, 4): one work cell per lane, marching its z-chunk with a register
 // queue of 2R+1 planes along z; x and y neighbours come from global memory (the rows of the tile and its halo are L1 / L2
 // hits).  flip: the step's parity within the call (the source buffer of a member is phi[cur ^ flip]).
-template <int R, typename T = double, typename C = double>
-__global__ __launch_bounds__(256) void wafer_k_batch_step(WaferGeom g, const WaferBatchMember *__restrict__ mem,
+template <int R, typename T = double, typename C = double, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_step(GS gs, const WaferBatchMember *__restrict__ mem,
                                                           const WaferBatchBlock *__restrict__ blocks, int flip)
 {
     const WaferBatchBlock bk = blocks[blockIdx.x];
+    const WaferGeom &g = wafer_batch_geom(gs, bk.shape);
     const WaferBatchMember &m = mem[bk.member];
     const int sel = (m.cur ^ flip) & 1;
     const T *__restrict__ phi = static_cast<const T *>(m.phi[sel]);
@@ -145,8 +167,8 @@ struct WaferBatchKCfg {
     static_assert(LDS_BYTES <= 65536, "static LDS");
 };
 
-template <int R, int K, typename T = double, typename C = double>
-__global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const WaferBatchMember *__restrict__ mem,
+template <int R, int K, typename T = double, typename C = double, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_stepk(GS gs, const WaferBatchMember *__restrict__ mem,
                                                            const WaferBatchBlock *__restrict__ blocks, int flip)
 {
     using Cfg = WaferBatchKCfg<R, K, (int)sizeof(C)>;
@@ -156,6 +178,7 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
     __shared__ C ldsk[(K - 1) * NB * PLANE];
 
     const WaferBatchBlock bk = blocks[blockIdx.x];
+    const WaferGeom &g = wafer_batch_geom(gs, bk.shape);
     const WaferBatchMember &m = mem[bk.member];
     const int sel = (m.cur ^ flip) & 1;
     const T *__restrict__ phi = static_cast<const T *>(m.phi[sel]);
@@ -291,8 +314,11 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(WaferGeom g, const Wa
 // gridDim.x workgroups per member, swizzled as wafer_k_step_lds swizzles them).  Float values are widened; every product and sum
 // is fp64, as in the context's kernel (its C is double for every dtype).  partials[(member * 4 + q) *
 // gridDim.x + workgroup]: the four sums energy, norm2, pot_sub, r2.
-template <int R, int NW, typename T = double>
-__global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(WaferGeom g, const WaferBatchMember *__restrict__ mem,
+// Several shapes (GS = WaferBatchGeomTable): the partition is the member's own (WaferBatchMember::obs_*: ntx, nty, zchunk and nb
+// workgroups, what a context of ITS shape gets), gridDim.x is the largest nb among the launched members, a workgroup beyond its
+// member's nb leaves as a whole before any load or barrier, and the partials lie at partials[obs_off + q * nb + workgroup].
+template <int R, int NW, typename T = double, typename GS = WaferGeom>
+__global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(GS gs, const WaferBatchMember *__restrict__ mem,
                                                                      const int *__restrict__ act, int ntx, int nty, int zchunk,
                                                                      int swz, double *__restrict__ partials)
 {
@@ -300,9 +326,18 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(WaferGeom g
     __shared__ double red[NW];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
+    int nb = gridDim.x;   // workgroups of this member
+    if constexpr (wafer_batch_mixed<GS>) {
+        nb = m.obs_nb;
+        if ((int)blockIdx.x >= nb) return;
+        ntx = m.obs_ntx;
+        nty = m.obs_nty;
+        zchunk = m.obs_zchunk;
+    }
     int bid = blockIdx.x;
     if (swz) {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, k = bid & 7;
+        const int n = nb, q = n >> 3, r = n & 7, k = bid & 7;
         bid = k * q + min(k, r) + (bid >> 3);
     }
     const int tx_i = bid % ntx;
@@ -357,20 +392,22 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(WaferGeom g
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const double s = wafer_block_sum<NW>(sums[q], red, tid);
-        if (tid == 0) partials[((size_t)member * 4 + q) * gridDim.x + blockIdx.x] = s;
+        if constexpr (wafer_batch_mixed<GS>) {
+            if (tid == 0) partials[(size_t)m.obs_off + (size_t)q * nb + blockIdx.x] = s;
+        } else {
+            if (tid == 0) partials[((size_t)member * 4 + q) * gridDim.x + blockIdx.x] = s;
+        }
     }
 }
 
 // wafer_k_reduce for every active member at once: block (q, slot) sums the n partials of quantity q of member act[slot] in
 // wafer_k_reduce's order into out[member * 4 + q].
-static __global__ __launch_bounds__(256) void wafer_k_batch_reduce(const double *__restrict__ partials, const int *__restrict__ act,
-                                                                   long long n, double *__restrict__ out)
+// wafer_k_reduce's order over the n doubles at p, by one workgroup of 256 threads: the sum, valid in thread 0
+template <typename I>
+__device__ __forceinline__ double wafer_batch_reduce_tree(const double *__restrict__ p, I n, double *sh)
 {
-    __shared__ double sh[256];
-    const int member = act[blockIdx.y];
-    const double *p = partials + ((size_t)member * 4 + blockIdx.x) * n;
     double s = 0.0;
-    for (long long q = threadIdx.x; q < n; q += 256) s += p[q];
+    for (I q = threadIdx.x; q < n; q += 256) s += p[q];
     sh[threadIdx.x] = s;
     __syncthreads();
 #pragma unroll
@@ -378,19 +415,45 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_reduce(const double 
         if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[(size_t)member * 4 + blockIdx.x] = sh[0];
+    return sh[0];
+}
+
+static __global__ __launch_bounds__(256) void wafer_k_batch_reduce(const double *__restrict__ partials, const int *__restrict__ act,
+                                                                   long long n, double *__restrict__ out)
+{
+    __shared__ double sh[256];
+    const int member = act[blockIdx.y];
+    const double s = wafer_batch_reduce_tree(partials + ((size_t)member * 4 + blockIdx.x) * n, n, sh);
+    if (threadIdx.x == 0) out[(size_t)member * 4 + blockIdx.x] = s;
+}
+
+// several shapes: the member's own nb partials per quantity, at its own offset
+static __global__ __launch_bounds__(256) void wafer_k_batch_reduce_mixed(const double *__restrict__ partials, const int *__restrict__ act,
+                                                                         const WaferBatchMember *__restrict__ mem, double *__restrict__ out)
+{
+    __shared__ double sh[256];
+    const int member = act[blockIdx.y];
+    const long long n = mem[member].obs_nb;
+    const double s = wafer_batch_reduce_tree(partials + mem[member].obs_off + (long long)blockIdx.x * n, n, sh);
+    if (threadIdx.x == 0) out[(size_t)member * 4 + blockIdx.x] = s;
 }
 
 // normalise_wavefunction (grid.rs:465-468) of the members act[blockIdx.z]: phi /= sqrt(norm2[member * n2_stride]), the
 // expression of wafer_k_row_op<2> (the quotient in fp64, rounded to the storage type).  Block (64, 4) over a 64 x 4 tile of one
-// work plane (blockIdx.y).
-template <typename T = double>
-static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(WaferGeom g, const WaferBatchMember *__restrict__ mem,
+// work plane (blockIdx.y).  Several shapes: the grid has the largest tile and plane counts among the launched members, and a
+// workgroup beyond its member's own leaves as a whole.
+template <typename T = double, typename GS = WaferGeom>
+static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, const WaferBatchMember *__restrict__ mem,
                                                                       const int *__restrict__ act, int ntx,
                                                                       const double *__restrict__ norm2, int n2_stride)
 {
     const int member = act[blockIdx.z];
     const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
+    if constexpr (wafer_batch_mixed<GS>) {
+        ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+        if ((int)blockIdx.y >= g.nzl || (int)blockIdx.x >= ntx * ((g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
+    }
     const int i = (blockIdx.x % ntx) * WAFER_BATCH_TX + threadIdx.x;
     const int j = (blockIdx.x / ntx) * WAFER_BATCH_TY + threadIdx.y;
     if (i >= g.nx || j >= g.ny) return;
@@ -412,3 +475,14 @@ hipError_t wafer_entry_batch_observables(bool f32, int R, const WaferGeom &g, co
                                          int ntx, int nty, int nblocks, int zchunk, int swz, double *partials, double *out, hipStream_t s);
 hipError_t wafer_entry_batch_normalise(bool f32, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact,
                                        const double *norm2, int n2_stride, hipStream_t s);
+
+// the same for a batch of several shapes (wafer_tu_batch_mixed.hip): the geometries come from the device table `geoms`, the
+// partitions from the member records; max_*: the largest per-member count among the launched members (the grid's extent)
+hipError_t wafer_entry_batchm_step(int dtype, int R, const WaferGeom *geoms, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
+                                   int nblocks, int flip, hipStream_t s);
+hipError_t wafer_entry_batchm_stepk(int dtype, int R, int K, const WaferGeom *geoms, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
+                                    int nblocks, int flip, hipStream_t s);
+hipError_t wafer_entry_batchm_observables(bool f32, int R, const WaferGeom *geoms, const WaferBatchMember *mem, const int *act, int nact,
+                                          int max_nb, int swz, double *partials, double *out, hipStream_t s);
+hipError_t wafer_entry_batchm_normalise(bool f32, const WaferGeom *geoms, const WaferBatchMember *mem, const int *act, int nact,
+                                        int max_tiles, int max_planes, const double *norm2, int n2_stride, hipStream_t s);

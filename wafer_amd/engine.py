@@ -56,6 +56,7 @@ EXPORTS = [
     "wafer_batch_clear_states", "wafer_batch_clone_state_to_phi", "wafer_batch_orthogonalise", "wafer_batch_norm2",
     "wafer_batch_evolve_state", "wafer_batch_solve_state",
     "wafer_batch_set_gs_variant", "wafer_batch_diag_gs", "wafer_batch_diag_gs_steps",
+    "wafer_batch_create_mixed", "wafer_batch_num_shapes",
 ]
 
 
@@ -221,6 +222,8 @@ def load_library():
     L.wafer_get_device_info.argtypes = [vp, C.POINTER(_DeviceInfo)]
     u8p = C.POINTER(C.c_uint8)
     L.wafer_batch_create.argtypes = [C.POINTER(_Params), C.c_uint32, C.POINTER(vp)]
+    L.wafer_batch_create_mixed.argtypes = [C.POINTER(_Params), C.c_uint32, C.POINTER(vp)]
+    L.wafer_batch_num_shapes.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.wafer_batch_destroy.argtypes = [vp]
     L.wafer_batch_size.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.wafer_batch_set_potential_builtin.argtypes = [vp, C.c_uint32, C.c_int]
@@ -685,14 +688,22 @@ class Batch:
     member's Gram matrix, 4 launches per step whatever k and B; the same tolerances against the oracle and a Context, phi rounded
     to float once per step on the float dtypes, not the sequential form's bits (gs_dispatch(wnum), gs_steps()).
     A sweep over states is solve_state(0), solve_state(1), ...: a member whose store is too short for a call gets the status
-    WAFER_ERR_STATE, is left as it is, and the others run."""
+    WAFER_ERR_STATE, is left as it is, and the others run.
 
-    def __init__(self, members: list):
+    mixed_shapes=True (wafer_batch_create_mixed): the members' nx, ny, nz may differ -- a convergence study in one batch.  The
+    ground-state path (evolve with wnum = 0 under both step variants, observables, norm2, normalise, solve) gives every member the
+    bits of a Context of its own Params on every dtype, in one launch per step or pass for all shapes together (num_shapes(),
+    dispatch()["shapes"]).  With more than one distinct shape the calls that need the state stores (load_state, download_state,
+    push_state, clear_states, clone_state_to_phi, orthogonalise, evolve with wnum > 0, solve_state, set_gs_variant(1)) raise
+    WaferError -1 with "mixed-shape" in the message; with one distinct shape the batch is a plain Batch in every call."""
+
+    def __init__(self, members: list, mixed_shapes: bool = False):
         self._L = load_library()
         self.members = list(members)
         self._h = C.c_void_p()
         arr = (_Params * max(1, len(self.members)))(*[m.c() for m in self.members])
-        self._check(self._L.wafer_batch_create(arr, len(self.members), C.byref(self._h)))
+        create = self._L.wafer_batch_create_mixed if mixed_shapes else self._L.wafer_batch_create
+        self._check(create(arr, len(self.members), C.byref(self._h)))
 
     def _check(self, rc: int) -> None:
         if rc != WAFER_OK:
@@ -717,6 +728,12 @@ class Batch:
 
     def __len__(self) -> int:
         return len(self.members)
+
+    def num_shapes(self) -> int:
+        """distinct (nx, ny, nz) among the members"""
+        n = C.c_uint32(0)
+        self._check(self._L.wafer_batch_num_shapes(self._h, C.byref(n)))
+        return n.value
 
     def _mask(self, active):
         if active is None:
@@ -889,7 +906,8 @@ class Batch:
         self._check(self._L.wafer_batch_set_step_variant(self._h, int(variant)))
 
     def dispatch(self) -> dict:
-        """what a ground-state evolve would launch: stencil, kernel, steps_per_pass, tile, lds_bytes, remainder, variant, dtype"""
+        """what a ground-state evolve would launch: stencil, kernel, steps_per_pass, tile, lds_bytes, remainder, variant, dtype,
+        and, on a batch of several shapes, shapes (their number, as the line gives it)"""
         buf = C.create_string_buffer(512)
         self._check(self._L.wafer_batch_diag_dispatch(self._h, buf, len(buf)))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split())
