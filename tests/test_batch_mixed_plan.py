@@ -1,5 +1,5 @@
-"""The workgroup tables of a batch of several shapes (wafer_batch_step_table, wafer_batch_fused_table_mixed,
-wafer_amd/csrc/wafer_batch_plan.h), compiled with g++ and the sanitizers as tests/test_batch_plan.py does.  No GPU."""
+"""The workgroup tables and the layout of a batch of several shapes (wafer_batch_step_table, wafer_batch_fused_table,
+wafer_batch_layout, wafer_amd/csrc/wafer_batch_plan.h), compiled with g++ and the sanitizers as tests/test_batch_plan.py does.  No GPU."""
 import itertools
 import os
 import subprocess
@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "wafer_amd", "csrc")
 
 # table kind R K cus mask nx,ny,nz ... -> "G gz TX TY", one "nx ny nz shape" line per member, "--", then one line per entry
-# kind: step (the one-step kernel's 64 x 4 tiles; K ignored), fused (64 x 12), fused1 (wafer_batch_fused_table on member 0's shape)
+# kind: step (the one-step kernel's 64 x 4 tiles; K ignored), fused (64 x 12);
+# layout (K, cus ignored, mask for the member count): after "--" one "off total" line per member, then "cells"
 DRIVER = r"""
 #include "wafer_batch_plan.h"
 #include <cstdio>
@@ -27,33 +28,34 @@ int main(int argc, char **argv)
     if ((uint32_t)(argc - 6) != n) return 2;
     std::vector<uint8_t> active(n);
     for (uint32_t m = 0; m < n; ++m) active[m] = mask[m] == '1';
-    std::vector<WaferGeom> geoms;
-    std::vector<int> shape_of(n);
-    for (uint32_t m = 0; m < n; ++m) {   // the engine's rule: distinct shapes in order of first appearance
-        int nx, ny, nz;
-        if (sscanf(argv[6 + m], "%d,%d,%d", &nx, &ny, &nz) != 3) return 2;
-        size_t k = 0;
-        while (k < geoms.size() && !(geoms[k].nx == nx && geoms[k].ny == ny && geoms[k].nz == nz)) ++k;
-        if (k == geoms.size()) geoms.push_back(wafer_make_geom(nx, ny, nz, R, R, 0, nz, 8));
-        shape_of[m] = (int)k;
-    }
+    std::vector<int> nxyz(3 * n);
+    for (uint32_t m = 0; m < n; ++m)
+        if (sscanf(argv[6 + m], "%d,%d,%d", &nxyz[3 * m], &nxyz[3 * m + 1], &nxyz[3 * m + 2]) != 3) return 2;
+    const WaferBatchLayout L = wafer_batch_layout(nxyz.data(), n, R, R, 8);   // the engine's
+    if (L.overflow) return 4;
+    const std::vector<WaferGeom> &geoms = L.geoms;
+    const std::vector<int> &shape_of = L.shape_of;
     const bool step = !strcmp(kind, "step");
     const int TX = step ? 64 : WAFER_BATCHK_TX, TY = step ? 4 : WAFER_BATCHK_TY;
     printf("%d %d %d %d\n", geoms[0].G, geoms[0].gz, TX, TY);
     for (uint32_t m = 0; m < n; ++m) printf("%d %d %d %d\n", geoms[shape_of[m]].nx, geoms[shape_of[m]].ny, geoms[shape_of[m]].nz, shape_of[m]);
     printf("--\n");
+    if (!strcmp(kind, "layout")) {
+        for (uint32_t m = 0; m < n; ++m) printf("%zu %lld\n", L.off[m], geoms[shape_of[m]].total);
+        printf("%zu\n", L.cells);
+        return 0;
+    }
     std::vector<WaferBatchBlock> t;
     if (step) t = wafer_batch_step_table(geoms.data(), shape_of.data(), active.data(), n, cus, TX, TY);
-    else if (!strcmp(kind, "fused")) t = wafer_batch_fused_table_mixed(geoms.data(), shape_of.data(), active.data(), n, cus, K, TX, TY);
-    else if (!strcmp(kind, "fused1")) t = wafer_batch_fused_table(geoms[0], active.data(), n, cus, K, TX, TY);
+    else if (!strcmp(kind, "fused")) t = wafer_batch_fused_table(geoms.data(), shape_of.data(), active.data(), n, cus, K, TX, TY);
     else return 2;
     for (const WaferBatchBlock &b : t) printf("%d %d %d %d %d %d\n", b.member, b.x0, b.y0, b.z0, b.z1, b.shape);
     // a null active set is every member
     std::vector<uint8_t> ones(n, 1);
     if (step && wafer_batch_step_table(geoms.data(), shape_of.data(), nullptr, n, cus, TX, TY).size() !=
                     wafer_batch_step_table(geoms.data(), shape_of.data(), ones.data(), n, cus, TX, TY).size()) return 3;
-    if (!strcmp(kind, "fused") && wafer_batch_fused_table_mixed(geoms.data(), shape_of.data(), nullptr, n, cus, K, TX, TY).size() !=
-                                      wafer_batch_fused_table_mixed(geoms.data(), shape_of.data(), ones.data(), n, cus, K, TX, TY).size()) return 3;
+    if (!strcmp(kind, "fused") && wafer_batch_fused_table(geoms.data(), shape_of.data(), nullptr, n, cus, K, TX, TY).size() !=
+                                      wafer_batch_fused_table(geoms.data(), shape_of.data(), ones.data(), n, cus, K, TX, TY).size()) return 3;
     return 0;
 }
 """
@@ -135,6 +137,28 @@ def todays_build_blocks(shape, R, mask, cus):
     return out
 
 
+def one_shape_fused_table(shape, R, K, mask, cus):
+    """the fused pass's table as it stood for one shape (G = R, nzl = nz), restated: the layer is nact ntx nty, the chunk count
+    wafer_batch_fused_nchunks's rule, chunk i is [G + i nz / n, G + (i + 1) nz / n)"""
+    nx, ny, nz = shape
+    G = R
+    ntx, nty = (nx + 63) // 64, (ny + 11) // 12
+    layer = mask.count("1") * ntx * nty
+    if layer == 0 or nz < 1:
+        return []
+    min_chunk = max(4 * R * (K - 1), 1)
+    nch = max(1, min((2 * max(cus, 1) + layer - 1) // layer, max(nz // min_chunk, 1)))
+    out = []
+    for m, c in enumerate(mask):
+        if c != "1":
+            continue
+        for i in range(nch):
+            for ty in range(nty):
+                for tx in range(ntx):
+                    out.append((m, tx * 64, ty * 12, G + i * nz // nch, G + (i + 1) * nz // nch, 0))
+    return out
+
+
 @pytest.mark.parametrize("R", [1, 2, 3])
 @pytest.mark.parametrize("shapes", [MIXED, UNIFORM], ids=["mixed", "uniform"])
 def test_step_table(plan, shapes, R):
@@ -164,8 +188,8 @@ def test_fused_table(plan, shapes, R):
         head, members, entries = plan("fused", R, K, cus, mask, shapes)
         check_cover(head, members, entries, mask, R, K, fused=True)
         if shapes is UNIFORM:
-            _, _, one = plan("fused1", R, K, cus, mask, shapes)
-            assert entries == one, (name, cus, K)   # wafer_batch_fused_table, entry for entry
+            one = one_shape_fused_table(shapes[0], R, K, mask, cus)
+            assert entries == one, (name, cus, K)   # the one-shape rule, entry for entry
         else:
             # chunk i of a member is [i nz / n, (i + 1) nz / n) for its own n
             for m, (s, c) in enumerate(zip(shapes, mask)):
@@ -175,3 +199,26 @@ def test_fused_table(plan, shapes, R):
                     continue
                 n = len(z)
                 assert z == [(R + i * s[2] // n, R + (i + 1) * s[2] // n) for i in range(n)], (name, cus, K, m)
+
+
+REPEATS = [MIXED[0], MIXED[2], MIXED[0], MIXED[3], MIXED[2]]   # shapes A, B, A, C, B
+
+
+@pytest.mark.parametrize("R", [1, 2, 3])
+def test_layout(plan, R):
+    """wafer_batch_layout: shapes numbered in order of first appearance, members at the prefix sums of their padded totals"""
+    for shapes in (MIXED, REPEATS, UNIFORM):
+        _, members, lines = plan("layout", R, 1, 1, "1" * len(shapes), shapes)
+        assert [m[:3] for m in members] == list(shapes)
+        first = list(dict.fromkeys(shapes))   # the distinct shapes in order of first appearance
+        numbers = [m[3] for m in members]
+        assert numbers == [first.index(s) for s in shapes]
+        if shapes is REPEATS:
+            assert numbers == [0, 1, 0, 2, 1]
+        off, totals = [l[0] for l in lines[:-1]], [l[1] for l in lines[:-1]]
+        assert len(off) == len(shapes) and all(t > 0 for t in totals)
+        assert len(set(zip(numbers, totals))) == len(first)   # one geometry, so one padded total, per distinct shape
+        assert off == [sum(totals[:m]) for m in range(len(shapes))]
+        assert lines[-1] == (sum(totals),)
+        if shapes is UNIFORM:
+            assert off == [m * totals[0] for m in range(len(shapes))]   # m * geoms[0].total

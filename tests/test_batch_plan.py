@@ -35,14 +35,18 @@ int main(int argc, char **argv)
         const uint32_t n = (uint32_t)strlen(mask);
         std::vector<uint8_t> active(n);
         for (uint32_t m = 0; m < n; ++m) active[m] = mask[m] == '1';
-        const WaferGeom g = wafer_make_geom(nx, ny, nz, R, G, 0, nz, 8);
+        std::vector<int> nxyz;
+        for (uint32_t m = 0; m < n; ++m) nxyz.insert(nxyz.end(), {nx, ny, nz});
+        const WaferBatchLayout L = wafer_batch_layout(nxyz.data(), n, R, G, 8);   // one geometry, shape_of all zero
+        if (L.overflow || L.geoms.size() != 1) return 4;
+        const WaferGeom &g = L.geoms[0];
         printf("%d %d %d %d %d %d\n", g.G, g.nzl, g.lz, g.gz, WAFER_BATCHK_TX, WAFER_BATCHK_TY);
-        for (const WaferBatchBlock &b : wafer_batch_fused_table(g, active.data(), n, cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY))
+        for (const WaferBatchBlock &b : wafer_batch_fused_table(&g, L.shape_of.data(), active.data(), n, cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY))
             printf("%d %d %d %d %d\n", b.member, b.x0, b.y0, b.z0, b.z1);
         // a null active set is every member
-        const size_t all = wafer_batch_fused_table(g, nullptr, n, cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY).size();
+        const size_t all = wafer_batch_fused_table(&g, L.shape_of.data(), nullptr, n, cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY).size();
         std::vector<uint8_t> ones(n, 1);
-        if (all != wafer_batch_fused_table(g, ones.data(), n, cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY).size()) return 3;
+        if (all != wafer_batch_fused_table(&g, L.shape_of.data(), ones.data(), n, cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY).size()) return 3;
         return 0;
     }
     if (argc >= 4 && !strcmp(argv[1], "cells")) {   // cells R K -> "lx ly" of every cell of the level-0 region, in order

@@ -1,8 +1,9 @@
 // wafer_batch_plan.h -- the host-side plan of a batched ground-state evolve (wafer_engine_batch.hip): which passes a call of
 // `steps` steps launches, the workgroup table of the one-step kernel (wafer_k_batch_step) and the one of the fused K-step pass
-// (wafer_k_batch_stepk, wafer_stencil_batch.hip.h), for batches of one shape and of several.
+// (wafer_k_batch_stepk, wafer_stencil_batch.hip.h), and the batch's layout (its distinct shapes, every member's offset).
 // Plain C++ with no HIP in it, so the host compiler and the sanitizers can run it (tests/test_batch_plan.py).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <vector>
 #if !defined(__HIPCC__) && !defined(__host__)   // wafer_geom.h marks its accessors for both sides; the host compiler has neither word
@@ -91,8 +92,8 @@ static inline uint64_t wafer_batch_launch_count(uint64_t n_steps, int K, bool ha
     return n + rem;
 }
 
-// ---- the fused pass's workgroup table --------------------------------------------------------------------------------------
-// The number of z-chunks.  A chunk of L planes computes K L + R K (K-1) level-planes for K L useful ones, so the recomputed share
+// ---- the fused pass's z-chunks -----------------------------------------------------------------------------------------------
+// Their number.  A chunk of L planes computes K L + R K (K-1) level-planes for K L useful ones, so the recomputed share
 // is R (K-1) / (L + R (K-1)).  Rule: cut z so that the active members together give about two workgroups per CU (what a CU
 // holds of this kernel, by LDS and by VGPRs), but no chunk shorter than 4 R (K-1) planes: the recomputed share stays <= 1/5,
 // and it gets that high only where the device would otherwise stand partly idle.  A grid thinner than that is one chunk.
@@ -108,33 +109,10 @@ static inline int wafer_batch_fused_nchunks(int nzl, long long layer, int num_cu
     return (int)nch;
 }
 
-// The table: a pure function of the geometry, the active set (null: all of n_members), the CU count and the tile.  Members in
-// order, within a member z-chunks, tile rows, tiles: the workgroups of one member are neighbours in the dispatch order and
-// share its halo planes in L2.  A frozen member has no entry.
-static inline std::vector<WaferBatchBlock> wafer_batch_fused_table(const WaferGeom &g, const uint8_t *active, uint32_t n_members,
-                                                                   int num_cus, int K, int tx, int ty)
-{
-    std::vector<WaferBatchBlock> t;
-    long long nact = 0;
-    for (uint32_t m = 0; m < n_members; ++m) nact += (!active || active[m]) ? 1 : 0;
-    if (nact == 0 || g.nzl < 1) return t;
-    const int ntx = (g.nx + tx - 1) / tx, nty = (g.ny + ty - 1) / ty;
-    const int nch = wafer_batch_fused_nchunks(g.nzl, nact * ntx * nty, num_cus, g.R, K);
-    for (uint32_t m = 0; m < n_members; ++m) {
-        if (active && !active[m]) continue;
-        for (int c = 0; c < nch; ++c) {
-            const int z0 = g.G + (int)((long long)c * g.nzl / nch), z1 = g.G + (int)((long long)(c + 1) * g.nzl / nch);
-            for (int j = 0; j < nty; ++j)
-                for (int i = 0; i < ntx; ++i) t.push_back(WaferBatchBlock{(int)m, i * tx, j * ty, z0, z1, 0});
-        }
-    }
-    return t;
-}
-
-// ---- tables over several shapes ----------------------------------------------------------------------------------------------
-// A batch keeps a table of its distinct geometries; shape_of[m] is member m's entry.  Both tables below cut z by ONE layer for
-// the whole launch: layer = sum over the active members of that member's tiles per plane, so the launch as a whole fills the
-// device whatever mix of shapes is active.  An entry carries its member's shape index.
+// ---- the workgroup tables ----------------------------------------------------------------------------------------------------
+// A batch keeps a table of its distinct geometries (one entry in a batch of one shape); shape_of[m] is member m's entry.  Both
+// tables below cut z by ONE layer for the whole launch: layer = sum over the active members of that member's tiles per plane, so
+// the launch as a whole fills the device whatever mix of shapes is active.  An entry carries its member's shape index.
 
 static inline long long wafer_batch_layer(const WaferGeom *geoms, const int *shape_of, const uint8_t *active, uint32_t n_members, int tx, int ty)
 {
@@ -175,10 +153,12 @@ static inline std::vector<WaferBatchBlock> wafer_batch_step_table(const WaferGeo
     return t;
 }
 
-// The fused pass's table over several shapes: wafer_batch_fused_table's rule with the summed layer, every member's planes shared
-// out evenly over its own wafer_batch_fused_nchunks(nz_m, layer, ...) chunks.  For one shape: wafer_batch_fused_table's entries.
-static inline std::vector<WaferBatchBlock> wafer_batch_fused_table_mixed(const WaferGeom *geoms, const int *shape_of, const uint8_t *active,
-                                                                         uint32_t n_members, int num_cus, int K, int tx, int ty)
+// The fused pass's table: a pure function of the geometries, the active set (null: all of n_members), the CU count and the tile.
+// wafer_batch_fused_nchunks's rule with the summed layer, every member's planes shared out evenly over its own
+// wafer_batch_fused_nchunks(nz_m, layer, ...) chunks.  Members in order, within a member z-chunks, tile rows, tiles: the
+// workgroups of one member are neighbours in the dispatch order and share its halo planes in L2.  A frozen member has no entry.
+static inline std::vector<WaferBatchBlock> wafer_batch_fused_table(const WaferGeom *geoms, const int *shape_of, const uint8_t *active,
+                                                                   uint32_t n_members, int num_cus, int K, int tx, int ty)
 {
     std::vector<WaferBatchBlock> t;
     const long long layer = wafer_batch_layer(geoms, shape_of, active, n_members, tx, ty);
@@ -196,4 +176,33 @@ static inline std::vector<WaferBatchBlock> wafer_batch_fused_table_mixed(const W
         }
     }
     return t;
+}
+
+// ---- the batch's layout ------------------------------------------------------------------------------------------------------
+// The distinct geometries of the members' shapes (nxyz: nx, ny, nz of member m at [3 m ..]) in order of first appearance, each the
+// one a context of that shape builds (ghost depth G, elements of esz bytes); shape_of[m]: member m's entry; off[m]: its element
+// offset in each array allocation = the sum of the padded totals of the members before it (one shape: m * geoms[0].total);
+// cells: the sum over all members.  overflow: cells, or cells * esz, passed the size of one allocation at member off.size() - 1,
+// where the walk stopped.
+struct WaferBatchLayout {
+    std::vector<WaferGeom> geoms;
+    std::vector<int> shape_of;
+    std::vector<size_t> off;
+    size_t cells = 0;
+    bool overflow = false;
+};
+
+static inline WaferBatchLayout wafer_batch_layout(const int *nxyz, uint32_t n_members, int R, int G, size_t esz)
+{
+    WaferBatchLayout L;
+    for (uint32_t m = 0; m < n_members && !L.overflow; ++m) {
+        const int nx = nxyz[3 * m], ny = nxyz[3 * m + 1], nz = nxyz[3 * m + 2];
+        size_t k = 0, bytes = 0;
+        while (k < L.geoms.size() && !(L.geoms[k].nx == nx && L.geoms[k].ny == ny && L.geoms[k].nz == nz)) ++k;
+        if (k == L.geoms.size()) L.geoms.push_back(wafer_make_geom(nx, ny, nz, R, G, 0, nz, (int)esz));
+        L.shape_of.push_back((int)k);
+        L.off.push_back(L.cells);
+        L.overflow = __builtin_add_overflow(L.cells, (size_t)L.geoms[k].total, &L.cells) || __builtin_mul_overflow(L.cells, esz, &bytes);
+    }
+    return L;
 }

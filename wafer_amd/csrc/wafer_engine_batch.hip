@@ -1,10 +1,9 @@
-// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B problems on one device -- of one shape, or
-// (wafer_batch_create_mixed, ground-state calls only) of several: "Several shapes" below -- one
-// launch per step over the active members -- or, for ground-state steps, one launch per pass of K steps (wafer_batch_plan.h) --
-// (kernels: wafer_stencil_batch.hip.h, instantiated in wafer_tu_batch.hip), and for
-// excited states a per-member state store with the normalise / Gram-Schmidt tail of every step (wafer_gs_batch.hip.h,
-// wafer_tu_gs_batch.hip): 1 + 2 (1 + wnum) + 1 launches per step for the whole batch -- or, where wafer_batch_set_gs_variant
-// selects the one-pass form (wnum <= WAFER_MAX_LOW), 4: step, raw sums, reduce, one apply pass with the member's Gram matrix.
+// wafer_engine_batch.hip -- batched ensembles (wafer_batch_*, include/wafer_hip.h): B problems on one device, one launch per step over
+// the active members -- or, for ground-state steps, one launch per pass of K steps (wafer_batch_plan.h) -- (kernels:
+// wafer_stencil_batch.hip.h), and for excited states a per-member state store with the normalise / Gram-Schmidt tail of every step
+// (wafer_gs_batch.hip.h, wafer_tu_gs_batch.hip): 1 + 2 (1 + wnum) + 1 launches per step for the whole batch -- or, where
+// wafer_batch_set_gs_variant selects the one-pass form (wnum <= WAFER_MAX_LOW), 4: step, raw sums, reduce, one apply pass with the
+// member's Gram matrix.
 //
 // Each member is also a context VIEW: a wafer_ctx whose arrays are the member's slices of the batch's allocations and whose
 // stream is the batch's.  Potentials, initial conditions, uploads and downloads go through the context entry points on that
@@ -15,16 +14,19 @@
 // that dtype builds (wafer_make_geom with that element size: the context's set-up kernels run on the views), and the entry
 // points of the kernels take the dtype.
 //
-// Several shapes (wafer_batch_create_mixed with more than one distinct nx, ny, nz).  The batch keeps a table of its distinct
-// geometries (`geoms`, each the one wafer_ctx_create builds for that shape; on the device too) and every member an index into it.
-// Storage is still one allocation per array kind, member m at element offset off[m] = the sum of the totals of the members
-// before it, every member with its own guard rows and planes.  The step tables are built over all active members at once
-// (wafer_batch_plan.h) and every entry carries its member's shape index, so a step or a fused pass is ONE launch whatever the
-// shapes; the kernels are the same templates instantiated with the geometry read from the device table (wafer_tu_batch_mixed.hip).
-// Observables, norm2 and normalise run on grids of (workgroup, member) as wide as the largest member needs, each member on the
-// partition a context of its shape gets (recorded in its WaferBatchMember).  A batch of one shape takes none of this: b->mixed is
-// false and every call runs what wafer_batch_create's batches run.  The state stores have no layout for several shapes yet, so the
-// excited-state calls are refused there (refuse_mixed).
+// Shapes and layout (wafer_batch_layout, wafer_batch_plan.h).  The batch keeps a table of its distinct geometries (`geoms`, each the
+// one wafer_ctx_create builds for that shape; on the device too) and every member an index into it (`shape_of`).  Storage is one
+// allocation per array kind, member m at element offset off[m] = the sum of the totals of the members before it, every member
+// with its own guard rows and planes.  The step tables are built over all active members at once (wafer_batch_plan.h) and every
+// entry carries its member's shape index, so a step or a fused pass is ONE launch whatever the shapes.  Observables, norm2 and
+// normalise run on grids of (workgroup, member) as wide as the largest launched member needs, each member on the partition a
+// context of its shape gets (recorded in its WaferBatchMember).
+// A batch of one shape (wafer_batch_create, or wafer_batch_create_mixed with equal shapes) is the case geoms.size() == 1 of all this:
+// off[m] == m * geoms[0].total, every member's partition is the same, and the widest is everyone's.  The one thing that differs is
+// where the kernels read the geometry from (with_geom, the one place that chooses): a kernel argument for one shape, the device
+// table for several -- the same kernel templates instantiated for either source (wafer_tu_batch.inc).  The state stores have no
+// layout for several shapes yet, so the excited-state calls are refused there (refuse_mixed).
+#include <memory>
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_batch.hip.h"
@@ -33,18 +35,19 @@
 struct wafer_batch {
     uint32_t n = 0;
     std::vector<wafer_params> P;
-    WaferGeom g;
     int device = 0, num_cus = 256;
     WaferTuning tune;
     hipStream_t s = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    size_t stride = 0;                        // elements per member in each array allocation (one shape)
-    // the distinct geometries, in order of first appearance; g is geoms[0].  mixed: more than one
+    // the layout (wafer_batch_layout): the distinct geometries in order of first appearance.  mixed: more than one
     std::vector<WaferGeom> geoms;
     std::vector<int> shape_of;                // member m's entry in geoms
-    std::vector<size_t> off;                  // member m's element offset in each array allocation (== m * stride for one shape)
+    std::vector<size_t> off;                  // member m's element offset in each array allocation
+    size_t cells = 0;                         // elements of each array allocation: every member's total, end to end
     WaferGeom *geoms_dev = nullptr;
     bool mixed = false;
+    const WaferGeom &g() const { return geoms[0]; }               // what every shape shares (R, G), and THE geometry of one shape
+    const WaferGeom &geom(uint32_t m) const { return geoms[shape_of[m]]; }
     std::string kernel_name = "wafer_k_batch_step";
     int dtype = WAFER_F64;                    // every member's (check_member)
     bool f32 = false;                         // float storage (f32 and f32fast)
@@ -55,27 +58,26 @@ struct wafer_batch {
     // device tables
     std::vector<WaferBatchMember> mem;
     WaferBatchMember *mem_dev = nullptr;
-    std::vector<WaferBatchBlock> blk;
-    WaferBatchBlock *blk_dev = nullptr;
-    size_t blk_cap = 0;
-    std::vector<uint8_t> blk_key;             // the active set the device block table was built for
-    // the fused pass (wafer_k_batch_stepk): its own table, for the same active set
-    std::vector<WaferBatchBlock> blkk;
-    WaferBatchBlock *blkk_dev = nullptr;
-    size_t blkk_cap = 0;
-    std::vector<uint8_t> blkk_key;
-    int blkk_K = 0;
+    // a workgroup table on the device, with the active set and the steps per pass it was built for
+    struct BlockTable {
+        std::vector<WaferBatchBlock> host;
+        WaferBatchBlock *dev = nullptr;
+        size_t cap = 0;
+        std::vector<uint8_t> key;
+        int K = 0;
+    };
+    BlockTable blk, blkk;                     // the one-step kernel's, and the fused pass's (wafer_k_batch_stepk) for the same active set
     int step_variant = -1;                    // wafer_batch_set_step_variant
     uint64_t n_fused_passes = 0, n_single_steps = 0;   // launches since creation (wafer_batch_diag_passes)
     int *act_dev = nullptr, *act_host = nullptr;
-    // observables: the single context's partition
-    int obs_ntx = 0, obs_nty = 0, obs_zchunk = 0, obs_nb = 0, swz = 0;
-    double *partials = nullptr;               // [member][4][obs_nb]
+    // observables: every member on the single context's partition of its shape (mem[].obs_*)
+    int swz = 0;
+    double *partials = nullptr;               // member m's [4][obs_nb] at mem[m].obs_off
     double *sums = nullptr, *sums_host = nullptr;   // [member][4]
     double *n2 = nullptr, *n2_host = nullptr;        // [member]
     uint64_t last_steps = 0;
     bool timing_valid = false;
-    // w_store: slot l of every member in one allocation with the member stride, made by the first push or load that needs it
+    // w_store: slot l of every member in one allocation laid out as the arrays are, made by the first push or load that needs it
     std::vector<void *> slots;
     std::vector<uint32_t> nst;                // states member m holds
     // excited states: norm2 at gs_scal[m * gs_stride], the overlap with state l at [m * gs_stride + 1 + l]; made at first use
@@ -141,7 +143,7 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk_dev, (void *)b->blkk_dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
                     (void *)b->gram_list_dev})
         if (p) (void)hipFree(p);
@@ -215,22 +217,25 @@ int upload_active(wafer_batch *b, const uint8_t *active, int *nact)
     return WAFER_OK;
 }
 
-// The step's workgroup table (wafer_batch_step_table, wafer_batch_plan.h) on the device, for this active set
-int build_blocks(wafer_batch *b, const uint8_t *active)
+// A workgroup table on the device for this active set: the one-step kernel's (K == 1: wafer_batch_step_table) or the fused pass's
+// (wafer_batch_fused_table, wafer_batch_plan.h).  Kept while the active set and K stay; an empty one too.
+int build_blocks(wafer_batch *b, wafer_batch::BlockTable &t, const uint8_t *active, int K)
 {
     std::vector<uint8_t> key(b->n);
     for (uint32_t m = 0; m < b->n; ++m) key[m] = (!active || active[m]) ? 1 : 0;
-    if (key == b->blk_key && b->blk_dev) return WAFER_OK;
-    b->blk = wafer_batch_step_table(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (key == t.key && K == t.K && t.dev) return WAFER_OK;
+    t.host = K > 1 ? wafer_batch_fused_table(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY)
+                   : wafer_batch_step_table(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, WAFER_BATCH_TX, WAFER_BATCH_TY);
     HIP_TRY(hipStreamSynchronize(b->s));
-    if (b->blk.size() > b->blk_cap) {
-        if (b->blk_dev) HIP_TRY(hipFree(b->blk_dev));
-        b->blk_dev = nullptr;
-        HIP_TRY(hipMalloc((void **)&b->blk_dev, sizeof(WaferBatchBlock) * b->blk.size()));
-        b->blk_cap = b->blk.size();
+    if (t.host.size() > t.cap || !t.dev) {
+        if (t.dev) HIP_TRY(hipFree(t.dev));
+        t.dev = nullptr;
+        t.cap = std::max<size_t>(t.host.size(), 1);
+        HIP_TRY(hipMalloc((void **)&t.dev, sizeof(WaferBatchBlock) * t.cap));
     }
-    if (!b->blk.empty()) HIP_TRY(hipMemcpy(b->blk_dev, b->blk.data(), sizeof(WaferBatchBlock) * b->blk.size(), hipMemcpyHostToDevice));
-    b->blk_key = key;
+    if (!t.host.empty()) HIP_TRY(hipMemcpy(t.dev, t.host.data(), sizeof(WaferBatchBlock) * t.host.size(), hipMemcpyHostToDevice));
+    t.key = key;
+    t.K = K;
     return WAFER_OK;
 }
 
@@ -239,7 +244,7 @@ int build_blocks(wafer_batch *b, const uint8_t *active)
 constexpr bool WAFER_BATCH_FUSED_BY_DEFAULT[4] = {false, false, false, false};
 int steps_per_pass(const wafer_batch *b)
 {
-    const int R = b->g.R;
+    const int R = b->g().R;
     const int K = R == 1 ? 3 : 2;
     const bool fused = b->step_variant < 0 ? WAFER_BATCH_FUSED_BY_DEFAULT[R] : b->step_variant == 1;
     if (!fused || wafer_batch_stepk_lds_bytes(b->dtype, R, K) == 0) return 1;
@@ -247,28 +252,14 @@ int steps_per_pass(const wafer_batch *b)
 }
 
 // a call's remainder of two steps is one pass where the two-step instantiation exists beside the K-step one
-bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->dtype, b->g.R, 2) != 0; }
+bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->dtype, b->g().R, 2) != 0; }
 
-// the fused pass's workgroup table (wafer_batch_fused_table) on the device, for this active set
-int build_blocks_fused(wafer_batch *b, const uint8_t *active, int K)
+// The one place that chooses where the kernels read the geometry from: launch(gs) with the batch's one geometry (a kernel
+// argument) or with its device table of several.  Every wafer_entry_batch_* entry point has an overload for either.
+template <typename F>
+hipError_t with_geom(const wafer_batch *b, F &&launch)
 {
-    std::vector<uint8_t> key(b->n);
-    for (uint32_t m = 0; m < b->n; ++m) key[m] = (!active || active[m]) ? 1 : 0;
-    if (key == b->blkk_key && K == b->blkk_K && b->blkk_dev) return WAFER_OK;
-    b->blkk = b->mixed ? wafer_batch_fused_table_mixed(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX,
-                                                       WAFER_BATCHK_TY)
-                       : wafer_batch_fused_table(b->g, key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY);
-    HIP_TRY(hipStreamSynchronize(b->s));
-    if (b->blkk.size() > b->blkk_cap || !b->blkk_dev) {
-        if (b->blkk_dev) HIP_TRY(hipFree(b->blkk_dev));
-        b->blkk_dev = nullptr;
-        b->blkk_cap = std::max<size_t>(b->blkk.size(), 1);
-        HIP_TRY(hipMalloc((void **)&b->blkk_dev, sizeof(WaferBatchBlock) * b->blkk_cap));
-    }
-    if (!b->blkk.empty()) HIP_TRY(hipMemcpy(b->blkk_dev, b->blkk.data(), sizeof(WaferBatchBlock) * b->blkk.size(), hipMemcpyHostToDevice));
-    b->blkk_key = key;
-    b->blkk_K = K;
-    return WAFER_OK;
+    return b->mixed ? launch(WaferBatchGeomTable{b->geoms_dev}) : launch(b->g());
 }
 
 // the four raw sums of the active members into sums_host[m * 4 ..]
@@ -281,12 +272,13 @@ int observables(wafer_batch *b, const uint8_t *active)
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
     RoctxRange range_("wafer_batch_observables");
-    int max_nb = 0;   // (several shapes: the grid is as wide as the largest launched member's partition)
+    int max_nb = 0;   // the grid is as wide as the largest launched member's partition
     for (int k = 0; k < nact; ++k) max_nb = std::max(max_nb, b->mem[b->act_host[k]].obs_nb);
-    const hipError_t e = b->mixed ? wafer_entry_batchm_observables(b->f32, b->g.R, b->geoms_dev, b->mem_dev, b->act_dev, nact, max_nb, b->swz,
-                                                                   b->partials, b->sums, b->s)
-                                  : wafer_entry_batch_observables(b->f32, b->g.R, b->g, b->mem_dev, b->act_dev, nact, b->obs_ntx, b->obs_nty,
-                                                                  b->obs_nb, b->obs_zchunk, b->swz, b->partials, b->sums, b->s);
+    const WaferBatchMember &m0 = b->mem[b->act_host[0]];   // (one shape: every member's partition)
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_observables(b->f32, b->g().R, gs, b->mem_dev, b->act_dev, nact, m0.obs_ntx, m0.obs_nty, m0.obs_zchunk, max_nb, b->swz,
+                                             b->partials, b->sums, b->s);
+    });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched observables launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(b->sums_host, b->sums, sizeof(double) * 4 * b->n, hipMemcpyDeviceToHost, b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
@@ -313,13 +305,14 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     if (!nact) return WAFER_OK;
     int max_tiles = 0, max_planes = 0;
     for (int k = 0; k < nact; ++k) {
-        const WaferGeom &g = b->geoms[b->shape_of[b->act_host[k]]];
+        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
         max_tiles = std::max(max_tiles, ((g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
         max_planes = std::max(max_planes, g.nzl);
     }
-    const hipError_t e = b->mixed ? wafer_entry_batchm_normalise(b->f32, b->geoms_dev, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, norm2_dev,
-                                                                 stride, b->s)
-                                  : wafer_entry_batch_normalise(b->f32, b->g, b->mem_dev, b->act_dev, nact, norm2_dev, stride, b->s);
+    const int ntx = (b->g().nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;   // (one shape: every member's tiles along x)
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_normalise(b->f32, gs, b->mem_dev, b->act_dev, nact, ntx, max_tiles, max_planes, norm2_dev, stride, b->s);
+    });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -328,7 +321,7 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
 // member m's state l as a logical pointer (plane 0, row 0), like the views' arrays
 void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
 {
-    return static_cast<char *>(b->slots[l]) + ((size_t)m * b->stride + (size_t)b->g.base_off) * b->esz;
+    return static_cast<char *>(b->slots[l]) + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
 }
 
 // slots [0, n) exist (zeros: frames, pads and guard zones of every member)
@@ -336,9 +329,9 @@ int ensure_slots(wafer_batch *b, uint32_t n)
 {
     while (b->slots.size() < n) {
         void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, b->stride * b->n * b->esz));
+        HIP_TRY(hipMalloc(&p, b->cells * b->esz));
         b->slots.push_back(p);
-        HIP_TRY(hipMemsetAsync(p, 0, b->stride * b->n * b->esz, b->s));
+        HIP_TRY(hipMemsetAsync(p, 0, b->cells * b->esz, b->s));
     }
     return WAFER_OK;
 }
@@ -370,7 +363,7 @@ int push_states(wafer_batch *b, const uint8_t *active)
     for (uint32_t m = 0; m < b->n; ++m) {
         if (active && !active[m]) continue;
         const wafer_ctx *c = b->views[m];
-        HIP_TRY(hipMemcpyAsync(alloc_base(c, slot_ptr(b, b->nst[m], m)), alloc_base(c, c->phi[c->cur]), b->stride * b->esz, hipMemcpyDeviceToDevice, b->s));
+        HIP_TRY(hipMemcpyAsync(alloc_base(c, slot_ptr(b, b->nst[m], m)), alloc_base(c, c->phi[c->cur]), (size_t)b->geom(m).total * b->esz, hipMemcpyDeviceToDevice, b->s));
         ++b->nst[m];
         mark_gram_stale(b, m);
     }
@@ -391,17 +384,26 @@ int ensure_gs(wafer_batch *b)
     return WAFER_OK;
 }
 
+// what the chain's and the one-pass form's kernel arguments (A) share: the one geometry, its 64 x 4 tiles, and the member stride of
+// the store slots (one shape: these calls are refused on several)
+template <typename A>
+A gs_args(const wafer_batch *b, int flip)
+{
+    A a;
+    a.g = b->g();
+    a.ntx = (a.g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    a.nty = (a.g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    a.flip = flip;
+    a.scal_stride = b->gs_stride;
+    a.mstride = a.g.total;
+    return a;
+}
+
 // one elementwise launch (+ its reduce into slot out_slot) over the members in act_dev; lower, dotwith: store slots, -1 none
 int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int lower, int dotwith, int out_slot)
 {
-    WaferBatchGsArgs a;
-    a.g = b->g;
-    a.ntx = (b->g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-    a.nty = (b->g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    a.flip = flip;
-    a.scal_stride = b->gs_stride;
+    WaferBatchGsArgs a = gs_args<WaferBatchGsArgs>(b, flip);
     a.coef_slot = coef_slot;
-    a.mstride = (long long)b->stride;
     a.lower = lower >= 0 ? slot_ptr(b, (uint32_t)lower, 0) : nullptr;
     a.dotwith = dotwith >= 0 ? slot_ptr(b, (uint32_t)dotwith, 0) : nullptr;
     const hipError_t e = wafer_entry_batch_gs(b->f32, mode, a, b->mem_dev, b->act_dev, nact, b->gs_scal, out_slot, b->gs_partials, b->s);
@@ -447,13 +449,7 @@ int ensure_onepass(wafer_batch *b)
 
 WaferBatchGsOneArgs onepass_args(const wafer_batch *b, int flip, uint32_t nslots)
 {
-    WaferBatchGsOneArgs a;
-    a.g = b->g;
-    a.ntx = (b->g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-    a.nty = (b->g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    a.flip = flip;
-    a.scal_stride = b->gs_stride;
-    a.mstride = (long long)b->stride;
+    WaferBatchGsOneArgs a = gs_args<WaferBatchGsOneArgs>(b, flip);
     for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? slot_ptr(b, l, 0) : nullptr;
     return a;
 }
@@ -518,28 +514,27 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
     const bool onepass = use_onepass(b, wnum);
     if (onepass) TRY(ensure_onepass(b));
     TRY(sync_members(b));
-    TRY(build_blocks(b, active));
+    TRY(build_blocks(b, b->blk, active, 1));
     const int K = wnum ? 1 : steps_per_pass(b);
     // excited steps compute in fp64 on every dtype, as a context's do: an f32fast batch takes the f32 step there
     const int step_dtype = (wnum && b->dtype == WAFER_F32_FAST) ? (int)WAFER_F32 : b->dtype;
     const bool have2 = have_two_step(b, K);
-    if (K > 1) TRY(build_blocks_fused(b, active, K));
+    if (K > 1) TRY(build_blocks(b, b->blkk, active, K));
     int nact = 0;
     if (wnum) TRY(upload_active(b, active, &nact));   // (the chain's member list; synchronises the stream, which a ground-state call must not)
     if (onepass && nact) TRY(refresh_gram(b, active));
     RoctxRange range_(wnum ? "wafer_batch_evolve_state" : "wafer_batch_evolve");
     HIP_TRY(hipEventRecord(b->ev_start, b->s));
     uint64_t launches = 0;
-    if (!b->blk.empty()) {   // (no active member: no workgroup)
+    if (!b->blk.host.empty()) {   // (no active member: no workgroup)
         uint64_t left = steps;
         while (left > 0) {   // no host synchronisation in here: every scalar stays on the device
             const int k = wafer_batch_next_pass(left, K, have2);
             const int flip = (int)(launches & 1);
-            const hipError_t e =
-                b->mixed ? (k > 1 ? wafer_entry_batchm_stepk(step_dtype, b->g.R, k, b->geoms_dev, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
-                                  : wafer_entry_batchm_step(step_dtype, b->g.R, b->geoms_dev, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s))
-                         : (k > 1 ? wafer_entry_batch_stepk(step_dtype, b->g.R, k, b->g, b->mem_dev, b->blkk_dev, (int)b->blkk.size(), flip, b->s)
-                                  : wafer_entry_batch_step(step_dtype, b->g.R, b->g, b->mem_dev, b->blk_dev, (int)b->blk.size(), flip, b->s));
+            const hipError_t e = with_geom(b, [&](const auto &gs) {
+                return k > 1 ? wafer_entry_batch_stepk(step_dtype, b->g().R, k, gs, b->mem_dev, b->blkk.dev, (int)b->blkk.host.size(), flip, b->s)
+                             : wafer_entry_batch_step(step_dtype, b->g().R, gs, b->mem_dev, b->blk.dev, (int)b->blk.host.size(), flip, b->s);
+            });
             if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
             ++launches;
             ++(k > 1 ? b->n_fused_passes : b->n_single_steps);
@@ -681,38 +676,108 @@ int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t s
     return WAFER_OK;
 }
 
-} // namespace
+// ---- creation --------------------------------------------------------------------------------------------------------------
+// Every member's partition record and the places of its partials.  Observables: the partition wafer_launch_observables_lds gives a
+// single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
+// (WaferLdsCfg::TX), and the z-chunk that follows from them -- with its [4][obs_nb] partials end to end (one shape: member m's at
+// m * 4 * obs_nb, as the single-shape kernels index them).  norm2: n2_nb workgroups, the partials end to end likewise.
+int init_partitions(wafer_batch *b)
+{
+    const int R = b->g().R;
+    const int NW = R <= 2 ? 8 : 4;
+    const int TX = b->f32 ? WaferLdsCfg<float, 1, 2>::TX : WaferLdsCfg<double, 1, 2>::TX, TY = 2 * NW;
+    const int ry = 2 * (NW / 4);
+    b->swz = wafer_lds_opts(b->tune).swz;
+    b->mem.resize(b->n);
+    size_t obs_total = 0, n2_total = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        WaferBatchMember &e = b->mem[m];
+        memset(&e, 0, sizeof e);
+        const WaferGeom &g = b->geom(m);
+        if (b->f32)
+            e.obs_zchunk = R == 1   ? wafer_lds_zchunk<float, 1>(b->tune, g, g.nzl, ry, b->num_cus)
+                           : R == 2 ? wafer_lds_zchunk<float, 2>(b->tune, g, g.nzl, ry, b->num_cus)
+                                    : wafer_lds_zchunk<float, 3>(b->tune, g, g.nzl, ry, b->num_cus);
+        else
+            e.obs_zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, ry, b->num_cus)
+                           : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, ry, b->num_cus)
+                                    : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, ry, b->num_cus);
+        e.shape = b->shape_of[m];
+        e.obs_ntx = (g.nx + TX - 1) / TX;
+        e.obs_nty = (g.ny + TY - 1) / TY;
+        e.obs_nb = e.obs_ntx * e.obs_nty * ((g.nzl + e.obs_zchunk - 1) / e.obs_zchunk);
+        e.n2_nb = b->f32 ? wafer_rownorm2_blocks(g, (int)b->esz, b->num_cus) : wafer_gs_blocks(g);
+        e.obs_off = (long long)obs_total;
+        e.n2_off = (long long)n2_total;
+        obs_total += 4 * (size_t)e.obs_nb;
+        n2_total += (size_t)e.n2_nb;
+    }
+    HIP_TRY(hipMalloc((void **)&b->partials, sizeof(double) * obs_total));
+    return WAFER_OK;
+}
 
-extern "C" {
+// The members' context views on their slices of the batch's arrays (b->alloc, b->view_scal), as wafer_ctx_create sets a context up,
+// and what the member records take from them: the array pointers, dt and the division plans.
+int init_views(wafer_batch *b)
+{
+    const int R = b->g().R;
+    b->views.reserve(b->n);
+    for (uint32_t m = 0; m < b->n; ++m) {
+        wafer_ctx *c = new wafer_ctx();
+        b->views.push_back(c);
+        const wafer_params &p = b->P[m];
+        const WaferGeom &g = b->geom(m);
+        c->P = p;
+        c->g = g;
+        c->f32 = b->f32;
+        c->f32_arith = p.dtype == WAFER_F32_FAST;
+        c->esz = b->esz;
+        c->num_cus = b->num_cus;
+        c->tune = b->tune;
+        c->bx = (g.px + 63) / 64;
+        c->by = (g.py + 3) / 4;
+        c->s_main = c->s_aux = b->s;
+        c->div_plan = wafer_divplan_make(wafer_stencil_den(R, p.dn, p.mass));
+        if (c->f32_arith) c->div_plan_f = wafer_divplan_make_f32((float)wafer_stencil_den(R, p.dn, p.mass));
+        if (p.flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = c->div_plan_f.checked = 0;
+        void **arr[4] = {&c->phi[0], &c->phi[1], &c->v, &c->potsub};
+        for (int k = 0; k < 4; ++k)
+            *arr[k] = static_cast<char *>(b->alloc[k]) + (b->off[m] + (size_t)g.base_off) * b->esz;
+        c->scal = b->view_scal + (size_t)m * SCAL_SLOTS;
+        c->scal_host = b->view_scal_host + (size_t)m * SCAL_SLOTS;
+        c->kernel_name = "wafer_k_batch_step";
+        WaferBatchMember &e = b->mem[m];
+        e.phi[0] = c->phi[0];
+        e.phi[1] = c->phi[1];
+        e.v = c->v;
+        e.potsub = c->potsub;
+        e.dt = p.dt;
+        e.den = c->div_plan.den;
+        e.zh = c->div_plan.zh;
+        e.zl = c->div_plan.zl;
+        e.den_f = (float)c->div_plan.den;   // (wafer_den<float> of a context's WaferStepArgs)
+        e.zh_f = c->div_plan_f.checked ? c->div_plan_f.zh : 0.f;
+        e.zl_f = c->div_plan_f.checked ? c->div_plan_f.zl : 0.f;
+    }
+    return WAFER_OK;
+}
 
 // wafer_batch_create (same_shape) and wafer_batch_create_mixed
-static int create_batch(const wafer_params *members, uint32_t n_members, bool same_shape, wafer_batch **out)
+int create_batch(const wafer_params *members, uint32_t n_members, bool same_shape, wafer_batch **out)
 {
     if (!members || !out) return fail(WAFER_ERR_INVALID, "null argument");
     if (n_members == 0) return fail(WAFER_ERR_INVALID, "a batch needs at least one member (n_members = 0)");
     for (uint32_t i = 0; i < n_members; ++i) TRY(check_member(&members[i], i, i ? &members[0] : nullptr, same_shape));
     const wafer_params &p0 = members[0];
     const int R = p0.central_difference;
-    const int G = p0.halo_depth ? (int)p0.halo_depth : R;
     const bool f32 = p0.dtype != WAFER_F64;
     const size_t esz = f32 ? 4 : 8;
-    // the distinct geometries in order of first appearance, each wafer_ctx_create's for that shape; members at the prefix sums of
-    // their totals (one shape: m * g.total)
-    std::vector<WaferGeom> geoms;
-    std::vector<int> shape_of(n_members);
-    std::vector<size_t> off(n_members);
-    size_t cells = 0, bytes = 0;
-    for (uint32_t m = 0; m < n_members; ++m) {
-        const wafer_params &p = members[m];
-        size_t k = 0;
-        while (k < geoms.size() && !(geoms[k].nx == (int)p.nx && geoms[k].ny == (int)p.ny && geoms[k].nz == (int)p.nz)) ++k;
-        if (k == geoms.size()) geoms.push_back(wafer_make_geom((int)p.nx, (int)p.ny, (int)p.nz, R, G, 0, (int)p.nz, (int)esz));
-        shape_of[m] = (int)k;
-        off[m] = cells;
-        if (__builtin_add_overflow(cells, (size_t)geoms[k].total, &cells) || __builtin_mul_overflow(cells, esz, &bytes))
-            return fail(WAFER_ERR_INVALID, "%u members of %zu padded cells up to member %u overflow the size of one allocation", n_members, cells, m);
-    }
-    const WaferGeom g = geoms[0];
+    std::vector<int> nxyz;
+    for (uint32_t m = 0; m < n_members; ++m) nxyz.insert(nxyz.end(), {(int)members[m].nx, (int)members[m].ny, (int)members[m].nz});
+    WaferBatchLayout L = wafer_batch_layout(nxyz.data(), n_members, R, p0.halo_depth ? (int)p0.halo_depth : R, esz);
+    if (L.overflow)
+        return fail(WAFER_ERR_INVALID, "%u members of %zu padded cells up to member %u overflow the size of one allocation", n_members, L.cells,
+                    (uint32_t)L.off.size() - 1);
 
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
@@ -722,157 +787,61 @@ static int create_batch(const wafer_params *members, uint32_t n_members, bool sa
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p0.device));
 
-    wafer_batch *b = new wafer_batch();
+    std::unique_ptr<wafer_batch, void (*)(wafer_batch *)> owner(new wafer_batch(), destroy);   // (a failure below frees what exists)
+    wafer_batch *b = owner.get();
     b->n = n_members;
     b->P.assign(members, members + n_members);
-    b->g = g;
     b->device = p0.device;
     b->num_cus = cus > 0 ? cus : 256;
     b->tune = wafer_tuning_from_env();
-    b->stride = (size_t)g.total;
-    b->mixed = geoms.size() > 1;
-    b->geoms = geoms;
-    b->shape_of = shape_of;
-    b->off = off;
+    b->geoms = std::move(L.geoms);
+    b->shape_of = std::move(L.shape_of);
+    b->off = std::move(L.off);
+    b->cells = L.cells;
+    b->mixed = b->geoms.size() > 1;
     b->dtype = (int)p0.dtype;
     b->f32 = f32;
     b->esz = esz;
     b->nst.assign(n_members, 0);
-    b->gs_nb = wafer_gs_blocks(g);
-    b->n2_nb = f32 ? wafer_rownorm2_blocks(g, (int)esz, b->num_cus) : 0;
+    b->gs_nb = wafer_gs_blocks(b->g());
+    b->n2_nb = f32 ? wafer_rownorm2_blocks(b->g(), (int)esz, b->num_cus) : 0;
     for (uint32_t m = 0; m < n_members; ++m) b->gs_stride = std::max(b->gs_stride, 1 + (int)members[m].max_states);
-#define HIP_TRYB(expr)                                                                               \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            const int rc_ = fail(WAFER_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-            destroy(b);                                                                              \
-            return rc_;                                                                              \
-        }                                                                                            \
-    } while (0)
-    HIP_TRYB(hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
-    HIP_TRYB(hipEventCreate(&b->ev_start));
-    HIP_TRYB(hipEventCreate(&b->ev_stop));
-    for (void *&a : b->alloc) {   // one allocation per array kind, zeros: frames, pads and guard zones of every member
-        HIP_TRYB(hipMalloc(&a, bytes));
-        HIP_TRYB(hipMemsetAsync(a, 0, bytes, b->s));
-    }
-    HIP_TRYB(hipMalloc((void **)&b->view_scal, sizeof(double) * SCAL_SLOTS * n_members));
-    HIP_TRYB(hipMemsetAsync(b->view_scal, 0, sizeof(double) * SCAL_SLOTS * n_members, b->s));
-    HIP_TRYB(hipHostMalloc((void **)&b->view_scal_host, sizeof(double) * SCAL_SLOTS * n_members, hipHostMallocDefault));
-
-    // observables: the partition wafer_launch_observables_lds gives a single context of this shape and storage type -- 16 bytes
-    // per lane, so tiles 128 wide on doubles and 256 wide on floats (WaferLdsCfg::TX), and the z-chunk that follows from them
-    // -- per shape; the batch's own fields are shape 0's (all a batch of one shape reads)
-    struct ObsPart {
-        int ntx, nty, zchunk, nb;
-    };
-    auto obs_partition = [&](const WaferGeom &g) {
-        ObsPart o;
-        const int NW = R <= 2 ? 8 : 4;
-        const int TX = f32 ? WaferLdsCfg<float, 1, 2>::TX : WaferLdsCfg<double, 1, 2>::TX, TY = 2 * NW;
-        const int ry = 2 * (NW / 4);
-        if (f32)
-            o.zchunk = R == 1   ? wafer_lds_zchunk<float, 1>(b->tune, g, g.nzl, ry, b->num_cus)
-                       : R == 2 ? wafer_lds_zchunk<float, 2>(b->tune, g, g.nzl, ry, b->num_cus)
-                                : wafer_lds_zchunk<float, 3>(b->tune, g, g.nzl, ry, b->num_cus);
-        else
-            o.zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, ry, b->num_cus)
-                       : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, ry, b->num_cus)
-                                : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, ry, b->num_cus);
-        o.ntx = (g.nx + TX - 1) / TX;
-        o.nty = (g.ny + TY - 1) / TY;
-        o.nb = o.ntx * o.nty * ((g.nzl + o.zchunk - 1) / o.zchunk);
-        return o;
-    };
-    {
-        const ObsPart o = obs_partition(g);
-        b->obs_zchunk = o.zchunk;
-        b->obs_ntx = o.ntx;
-        b->obs_nty = o.nty;
-        b->obs_nb = o.nb;
-        b->swz = wafer_lds_opts(b->tune).swz;
-    }
-    // the members' partition records and the places of their partials: [4][obs_nb] per member, end to end (one shape: member m's at
-    // m * 4 * obs_nb, as the single-shape kernels index them)
-    b->mem.resize(n_members);
-    size_t obs_total = 0, n2_total = 0;
-    for (uint32_t m = 0; m < n_members; ++m) {
-        WaferBatchMember &e = b->mem[m];
-        memset(&e, 0, sizeof e);
-        const WaferGeom &gm = b->geoms[shape_of[m]];
-        const ObsPart o = obs_partition(gm);
-        e.shape = shape_of[m];
-        e.obs_ntx = o.ntx;
-        e.obs_nty = o.nty;
-        e.obs_zchunk = o.zchunk;
-        e.obs_nb = o.nb;
-        e.n2_nb = f32 ? wafer_rownorm2_blocks(gm, (int)esz, b->num_cus) : wafer_gs_blocks(gm);
-        e.obs_off = (long long)obs_total;
-        e.n2_off = (long long)n2_total;
-        obs_total += 4 * (size_t)o.nb;
-        n2_total += (size_t)e.n2_nb;
-    }
-    HIP_TRYB(hipMalloc((void **)&b->partials, sizeof(double) * obs_total));
-    HIP_TRYB(hipMalloc((void **)&b->sums, sizeof(double) * 4 * n_members));
-    HIP_TRYB(hipHostMalloc((void **)&b->sums_host, sizeof(double) * 4 * n_members, hipHostMallocDefault));
-    HIP_TRYB(hipMalloc((void **)&b->n2, sizeof(double) * n_members));
-    HIP_TRYB(hipHostMalloc((void **)&b->n2_host, sizeof(double) * n_members, hipHostMallocDefault));
-    HIP_TRYB(hipMalloc((void **)&b->act_dev, sizeof(int) * n_members));
-    HIP_TRYB(hipHostMalloc((void **)&b->act_host, sizeof(int) * n_members, hipHostMallocDefault));
-    HIP_TRYB(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
-    HIP_TRYB(hipMalloc((void **)&b->geoms_dev, sizeof(WaferGeom) * b->geoms.size()));
-    HIP_TRYB(hipMemcpy(b->geoms_dev, b->geoms.data(), sizeof(WaferGeom) * b->geoms.size(), hipMemcpyHostToDevice));
     if (b->mixed) {
         static const char *const types[] = {"double,double", "float,double", "float,float"};
         char name[96];
         snprintf(name, sizeof name, "wafer_k_batch_step<%d,%s,WaferBatchGeomTable>", R, types[b->dtype]);
         b->kernel_name = name;
     }
-
-    b->views.reserve(n_members);
-    for (uint32_t m = 0; m < n_members; ++m) {
-        wafer_ctx *c = new wafer_ctx();
-        b->views.push_back(c);
-        const WaferGeom &g = b->geoms[shape_of[m]];   // (the member's own from here on)
-        c->P = members[m];
-        c->g = g;
-        c->f32 = f32;   // as wafer_ctx_create sets them
-        c->f32_arith = members[m].dtype == WAFER_F32_FAST;
-        c->esz = esz;
-        c->num_cus = b->num_cus;
-        c->tune = b->tune;
-        c->bx = (g.px + 63) / 64;
-        c->by = (g.py + 3) / 4;
-        c->s_main = c->s_aux = b->s;
-        c->div_plan = wafer_divplan_make(wafer_stencil_den(R, members[m].dn, members[m].mass));
-        if (c->f32_arith) c->div_plan_f = wafer_divplan_make_f32((float)wafer_stencil_den(R, members[m].dn, members[m].mass));
-        if (members[m].flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = c->div_plan_f.checked = 0;
-        void **arr[4] = {&c->phi[0], &c->phi[1], &c->v, &c->potsub};
-        for (int k = 0; k < 4; ++k)
-            *arr[k] = static_cast<char *>(b->alloc[k]) + (b->off[m] + (size_t)g.base_off) * esz;
-        c->scal = b->view_scal + (size_t)m * SCAL_SLOTS;
-        c->scal_host = b->view_scal_host + (size_t)m * SCAL_SLOTS;
-        c->kernel_name = "wafer_k_batch_step";
-        WaferBatchMember &e = b->mem[m];
-        e.phi[0] = c->phi[0];
-        e.phi[1] = c->phi[1];
-        e.v = c->v;
-        e.potsub = c->potsub;
-        e.dt = members[m].dt;
-        e.den = c->div_plan.den;
-        e.zh = c->div_plan.zh;
-        e.zl = c->div_plan.zl;
-        e.den_f = (float)c->div_plan.den;   // (wafer_den<float> of a context's WaferStepArgs)
-        e.zh_f = c->div_plan_f.checked ? c->div_plan_f.zh : 0.f;
-        e.zl_f = c->div_plan_f.checked ? c->div_plan_f.zl : 0.f;
+    HIP_TRY(hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&b->ev_start));
+    HIP_TRY(hipEventCreate(&b->ev_stop));
+    for (void *&a : b->alloc) {   // one allocation per array kind, zeros: frames, pads and guard zones of every member
+        HIP_TRY(hipMalloc(&a, b->cells * esz));
+        HIP_TRY(hipMemsetAsync(a, 0, b->cells * esz, b->s));
     }
-    HIP_TRYB(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * n_members, hipMemcpyHostToDevice));
-    HIP_TRYB(hipStreamSynchronize(b->s));
-#undef HIP_TRYB
-    *out = b;
+    HIP_TRY(hipMalloc((void **)&b->view_scal, sizeof(double) * SCAL_SLOTS * n_members));
+    HIP_TRY(hipMemsetAsync(b->view_scal, 0, sizeof(double) * SCAL_SLOTS * n_members, b->s));
+    HIP_TRY(hipHostMalloc((void **)&b->view_scal_host, sizeof(double) * SCAL_SLOTS * n_members, hipHostMallocDefault));
+    TRY(init_partitions(b));
+    HIP_TRY(hipMalloc((void **)&b->sums, sizeof(double) * 4 * n_members));
+    HIP_TRY(hipHostMalloc((void **)&b->sums_host, sizeof(double) * 4 * n_members, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&b->n2, sizeof(double) * n_members));
+    HIP_TRY(hipHostMalloc((void **)&b->n2_host, sizeof(double) * n_members, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&b->act_dev, sizeof(int) * n_members));
+    HIP_TRY(hipHostMalloc((void **)&b->act_host, sizeof(int) * n_members, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
+    HIP_TRY(hipMalloc((void **)&b->geoms_dev, sizeof(WaferGeom) * b->geoms.size()));
+    HIP_TRY(hipMemcpy(b->geoms_dev, b->geoms.data(), sizeof(WaferGeom) * b->geoms.size(), hipMemcpyHostToDevice));
+    TRY(init_views(b));
+    HIP_TRY(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * n_members, hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    *out = owner.release();
     return WAFER_OK;
 }
+
+} // namespace
+
+extern "C" {
 
 int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out)
 {
@@ -997,18 +966,14 @@ int wafer_batch_norm2(wafer_batch *b, double *out)
     TRY(sync_members(b));
     int nact = 0;
     TRY(upload_active(b, nullptr, &nact));
-    if (b->mixed) {   // every member on its own shape's partition: wafer_rownorm2_blocks (float storage) or wafer_gs_blocks (doubles)
-        int max_nb = 0;
-        for (uint32_t m = 0; m < b->n; ++m) max_nb = std::max(max_nb, b->mem[m].n2_nb);
-        const hipError_t e = wafer_entry_batchm_norm2(b->f32, b->geoms_dev, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, b->gs_stride, 0,
-                                                      b->gs_partials, b->s);
-        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
-    } else if (b->f32) {   // the partition of a context's wafer_norm2: the same double (fp64 keeps the batch's own partition)
-        const hipError_t e = wafer_entry_batch_rownorm2(b->g, b->mem_dev, b->act_dev, nact, b->n2_nb, b->gs_scal, b->gs_stride, 0, b->gs_partials, b->s);
-        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
-    } else {
-        TRY(gs_launch(b, WAFER_GS_NORM2, nact, 0, 0, -1, -1, 0));
-    }
+    // every member on its own shape's partition: a context's wafer_norm2 partition on float storage (wafer_rownorm2_blocks: the same
+    // double), the chain's on doubles (wafer_gs_blocks)
+    int max_nb = 0;
+    for (uint32_t m = 0; m < b->n; ++m) max_nb = std::max(max_nb, b->mem[m].n2_nb);
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_norm2(b->f32, gs, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, b->gs_stride, 0, b->gs_partials, b->s);
+    });
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(b->gs_host, b->gs_scal, sizeof(double) * (size_t)b->gs_stride * b->n, hipMemcpyDeviceToHost, b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
     for (uint32_t m = 0; m < b->n; ++m) out[m] = b->gs_host[(size_t)m * b->gs_stride];
@@ -1087,7 +1052,7 @@ int wafer_batch_clone_state_to_phi(wafer_batch *b, const uint8_t *active, uint32
     for (uint32_t m = 0; m < b->n; ++m) {
         if (active && !active[m]) continue;
         wafer_ctx *c = b->views[m];
-        HIP_TRY(hipMemcpyAsync(alloc_base(c, c->phi[c->cur]), alloc_base(c, slot_ptr(b, idx, m)), b->stride * b->esz, hipMemcpyDeviceToDevice, b->s));
+        HIP_TRY(hipMemcpyAsync(alloc_base(c, c->phi[c->cur]), alloc_base(c, slot_ptr(b, idx, m)), (size_t)b->geom(m).total * b->esz, hipMemcpyDeviceToDevice, b->s));
         c->have_phi = true;
         c->halo_valid = 0;
     }
@@ -1132,7 +1097,7 @@ int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n)
     static const char *const types_mixed[] = {",double,double,WaferBatchGeomTable", ",float,double,WaferBatchGeomTable",
                                               ",float,float,WaferBatchGeomTable"};   // several shapes: the geometry source after them
     const char *const *tn = b->mixed ? types_mixed : types;
-    const int R = b->g.R, K = steps_per_pass(b);
+    const int R = b->g().R, K = steps_per_pass(b);
     char kernel[96], tile[32];
     const char *remainder = "none";
     if (K > 1) {

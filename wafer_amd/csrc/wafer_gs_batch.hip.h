@@ -409,10 +409,6 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double
 // (NORM2, or dotwith given), the reduce into scal[member * scal_stride + out_slot].  f32: float storage.
 hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, const WaferBatchMember *mem, const int *act, int nact,
                                 double *scal, int out_slot, double *partials, hipStream_t s);
-// float storage: norm2 of the members in act into scal[member * scal_stride + out_slot] on the single context's partition (nb =
-// wafer_rownorm2_blocks workgroups per member; partials holds nb doubles per member of the batch)
-hipError_t wafer_entry_batch_rownorm2(const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, int nb, double *scal,
-                                      int scal_stride, int out_slot, double *partials, hipStream_t s);
 // the one-pass form: sums, reduce and apply (normalise: evolve; else orthogonalise) over the members in act.  1 <= nlow <= WAFER_MAX_LOW;
 // partials holds WAFER_GS_ONE_ROWS * wafer_gs_blocks doubles per member of the batch, gram WAFER_MAX_LOW^2.
 hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem,
@@ -421,7 +417,3 @@ hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, cons
 // WAFER_GRAM_PAIRS * wafer_gs_blocks doubles per member of the batch
 hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgs &a, const int *list, const int *cnt, int nlist, double *gram,
                                   double *partials, hipStream_t s);
-// a batch of several shapes (wafer_tu_batch_mixed.hip): norm2 of the members in act into scal[member * scal_stride + out_slot], each
-// on its own partition (float storage: wafer_k_batch_rownorm2, doubles: wafer_k_batch_gs<NORM2>); max_nb: the largest n2_nb among them
-hipError_t wafer_entry_batchm_norm2(bool f32, const WaferGeom *geoms, const WaferBatchMember *mem, const int *act, int nact, int max_nb,
-                                    double *scal, int scal_stride, int out_slot, double *partials, hipStream_t s);

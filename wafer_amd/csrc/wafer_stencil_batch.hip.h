@@ -462,27 +462,29 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, con
     *p = (T)wafer_div_invariant<double>((double)*p, coef);
 }
 
-// entry points (wafer_tu_batch.hip).  dtype: the batch's wafer_dtype as an int -- 0 f64, 1 f32 (float storage, fp64 arithmetic),
-// 2 f32fast (float storage, float arithmetic in the ground-state step).
-hipError_t wafer_entry_batch_step(int dtype, int R, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
-                                  int nblocks, int flip, hipStream_t s);
-// the fused pass of K steps; hipErrorInvalidValue where wafer_batch_stepk_lds_bytes(dtype, R, K) is 0 (no such instantiation)
-hipError_t wafer_entry_batch_stepk(int dtype, int R, int K, const WaferGeom &g, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
-                                   int nblocks, int flip, hipStream_t s);
+// entry points (wafer_tu_batch.inc), each once per geometry source GS: const WaferGeom & (a batch of one shape: wafer_tu_batch.hip)
+// and const WaferBatchGeomTable & (several: wafer_tu_batch_mixed.hip).  dtype: the batch's wafer_dtype as an int -- 0 f64, 1 f32
+// (float storage, fp64 arithmetic), 2 f32fast (float storage, float arithmetic in the ground-state step).  f32 is true for float
+// storage (dtype 1 and 2 alike: observables and normalise compute in fp64).
+// stepk: the fused pass of K steps; hipErrorInvalidValue where wafer_batch_stepk_lds_bytes(dtype, R, K) is 0 (no such instantiation).
+// observables, normalise: ntx, nty, zchunk are the partition of every launched member of a batch of one shape (several shapes: not
+// read, the kernels take each member's own from its record and geometry); max_*: the largest per-member count among the launched
+// members -- the grid's extent, and for one shape every member's count.
+// norm2 (wafer_batch_norm2; kernels: wafer_gs_batch.hip.h): norm2 of the members in act into scal[member * scal_stride + out_slot], each
+// on its own partition of WaferBatchMember::n2_nb workgroups -- float storage: wafer_k_batch_rownorm2 on a single context's wafer_norm2
+// partition, the same double; doubles: wafer_k_batch_gs<NORM2>.  partials holds every member's n2_nb doubles, end to end.
+#define WAFER_BATCH_ENTRIES(GS)                                                                                                                      \
+    hipError_t wafer_entry_batch_step(int dtype, int R, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks,      \
+                                      int flip, hipStream_t s);                                                                                      \
+    hipError_t wafer_entry_batch_stepk(int dtype, int R, int K, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks,           \
+                                       int nblocks, int flip, hipStream_t s);                                                                        \
+    hipError_t wafer_entry_batch_observables(bool f32, int R, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int nty, \
+                                             int zchunk, int max_nb, int swz, double *partials, double *out, hipStream_t s);                        \
+    hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int max_tiles,    \
+                                           int max_planes, const double *norm2, int n2_stride, hipStream_t s);                                      \
+    hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb, double *scal,     \
+                                       int scal_stride, int out_slot, double *partials, hipStream_t s);
+WAFER_BATCH_ENTRIES(WaferGeom)
+WAFER_BATCH_ENTRIES(WaferBatchGeomTable)
+#undef WAFER_BATCH_ENTRIES
 int wafer_batch_stepk_lds_bytes(int dtype, int R, int K);
-// f32 is true for float storage (dtype 1 and 2 alike: observables and normalise compute in fp64)
-hipError_t wafer_entry_batch_observables(bool f32, int R, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact,
-                                         int ntx, int nty, int nblocks, int zchunk, int swz, double *partials, double *out, hipStream_t s);
-hipError_t wafer_entry_batch_normalise(bool f32, const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact,
-                                       const double *norm2, int n2_stride, hipStream_t s);
-
-// the same for a batch of several shapes (wafer_tu_batch_mixed.hip): the geometries come from the device table `geoms`, the
-// partitions from the member records; max_*: the largest per-member count among the launched members (the grid's extent)
-hipError_t wafer_entry_batchm_step(int dtype, int R, const WaferGeom *geoms, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
-                                   int nblocks, int flip, hipStream_t s);
-hipError_t wafer_entry_batchm_stepk(int dtype, int R, int K, const WaferGeom *geoms, const WaferBatchMember *mem, const WaferBatchBlock *blocks,
-                                    int nblocks, int flip, hipStream_t s);
-hipError_t wafer_entry_batchm_observables(bool f32, int R, const WaferGeom *geoms, const WaferBatchMember *mem, const int *act, int nact,
-                                          int max_nb, int swz, double *partials, double *out, hipStream_t s);
-hipError_t wafer_entry_batchm_normalise(bool f32, const WaferGeom *geoms, const WaferBatchMember *mem, const int *act, int nact,
-                                        int max_tiles, int max_planes, const double *norm2, int n2_stride, hipStream_t s);

@@ -1,0 +1,150 @@
+// The launch layer of the batched ensemble kernels (wafer_stencil_batch.hip.h, wafer_gs_batch.hip.h), written once for both
+// geometry sources.  The including unit names its own as WAFER_TU_BATCH_GS: WaferGeom (wafer_tu_batch.hip: the one geometry of
+// a batch of one shape, a kernel argument) or WaferBatchGeomTable (wafer_tu_batch_mixed.hip: the device table of a batch of
+// several shapes), and gets the wafer_entry_batch_* overloads that take that type.  For each dtype -- 0 f64 <double, double>,
+// 1 f32 <float, double> (float storage, fp64 arithmetic), 2 f32fast <float, float> (float arithmetic in the ground-state step).
+#include <string.h>
+#include "wafer_gs_batch.hip.h"
+
+namespace {
+
+using GS = WAFER_TU_BATCH_GS;
+constexpr bool MIXED = wafer_batch_mixed<GS>;
+
+template <typename T, typename C>
+hipError_t launch_step(int R, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks, int flip, hipStream_t s)
+{
+    const dim3 grid((unsigned)nblocks), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    switch (R) {
+    case 1: hipLaunchKernelGGL((wafer_k_batch_step<1, T, C, GS>), grid, block, 0, s, gs, mem, blocks, flip); break;
+    case 2: hipLaunchKernelGGL((wafer_k_batch_step<2, T, C, GS>), grid, block, 0, s, gs, mem, blocks, flip); break;
+    case 3: hipLaunchKernelGGL((wafer_k_batch_step<3, T, C, GS>), grid, block, 0, s, gs, mem, blocks, flip); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// the instantiations of the fused pass (wafer_batch_stepk_lds_bytes), the same list for every dtype and geometry source:
+// ThreePoint 3 steps (and 2, for the remainder of a call), FivePoint 2 steps
+template <typename T, typename C>
+hipError_t launch_stepk(int R, int K, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks, int flip,
+                        hipStream_t s)
+{
+    const dim3 grid((unsigned)nblocks), block(256);
+    if (R == 1 && K == 3) hipLaunchKernelGGL((wafer_k_batch_stepk<1, 3, T, C, GS>), grid, block, 0, s, gs, mem, blocks, flip);
+    else if (R == 1 && K == 2) hipLaunchKernelGGL((wafer_k_batch_stepk<1, 2, T, C, GS>), grid, block, 0, s, gs, mem, blocks, flip);
+    else if (R == 2 && K == 2) hipLaunchKernelGGL((wafer_k_batch_stepk<2, 2, T, C, GS>), grid, block, 0, s, gs, mem, blocks, flip);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_observables(int R, const GS &gs, const WaferBatchMember *mem, const int *act, dim3 grid, int ntx, int nty, int zchunk,
+                              int swz, double *partials, hipStream_t s)
+{
+    // the waves per workgroup of wafer_launch_observables_lds: 8 (ThreePoint / FivePoint), 4 (SevenPoint)
+    switch (R) {
+    case 1: hipLaunchKernelGGL((wafer_k_batch_observables<1, 8, T, GS>), grid, dim3(512), 0, s, gs, mem, act, ntx, nty, zchunk, swz, partials); break;
+    case 2: hipLaunchKernelGGL((wafer_k_batch_observables<2, 8, T, GS>), grid, dim3(512), 0, s, gs, mem, act, ntx, nty, zchunk, swz, partials); break;
+    case 3: hipLaunchKernelGGL((wafer_k_batch_observables<3, 4, T, GS>), grid, dim3(256), 0, s, gs, mem, act, ntx, nty, zchunk, swz, partials); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// what the norm2 kernels take for each geometry source: the row walk's arguments over the whole slab, and the chain's arguments
+// with nothing but the geometry in them (the store fields are not read in NORM2 mode)
+WaferRowArgs row_args(const WaferGeom &g)
+{
+    WaferRowArgs ra;
+    ra.g = g;
+    ra.lz_lo = g.G;
+    ra.lz_hi = g.G + g.nzl;
+    return ra;
+}
+WaferBatchGeomTable row_args(const WaferBatchGeomTable &gt) { return gt; }
+
+WaferBatchGsArgs gs_norm2_args(const WaferGeom &g, int scal_stride)
+{
+    WaferBatchGsArgs a;
+    a.g = g;
+    a.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    a.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    a.flip = 0;
+    a.scal_stride = scal_stride;
+    a.coef_slot = 0;
+    a.mstride = g.total;
+    a.lower = a.dotwith = nullptr;
+    return a;
+}
+WaferBatchGsArgsMixed gs_norm2_args(const WaferBatchGeomTable &gt, int scal_stride)
+{
+    WaferBatchGsArgsMixed a;
+    memset(&a, 0, sizeof a);
+    a.geoms = gt.geoms;
+    a.scal_stride = scal_stride;
+    return a;
+}
+
+} // namespace
+
+hipError_t wafer_entry_batch_step(int dtype, int R, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks, int flip,
+                                  hipStream_t s)
+{
+    if (dtype == 0) return launch_step<double, double>(R, gs, mem, blocks, nblocks, flip, s);
+    if (dtype == 1) return launch_step<float, double>(R, gs, mem, blocks, nblocks, flip, s);
+    if (dtype == 2) return launch_step<float, float>(R, gs, mem, blocks, nblocks, flip, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t wafer_entry_batch_stepk(int dtype, int R, int K, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks,
+                                   int flip, hipStream_t s)
+{
+    if (dtype == 0) return launch_stepk<double, double>(R, K, gs, mem, blocks, nblocks, flip, s);
+    if (dtype == 1) return launch_stepk<float, double>(R, K, gs, mem, blocks, nblocks, flip, s);
+    if (dtype == 2) return launch_stepk<float, float>(R, K, gs, mem, blocks, nblocks, flip, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t wafer_entry_batch_observables(bool f32, int R, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int nty,
+                                         int zchunk, int max_nb, int swz, double *partials, double *out, hipStream_t s)
+{
+    if (MIXED) ntx = nty = zchunk = 0;   // (the kernel takes them from the member's record)
+    const dim3 grid((unsigned)max_nb, (unsigned)nact);
+    const hipError_t e = f32 ? launch_observables<float>(R, gs, mem, act, grid, ntx, nty, zchunk, swz, partials, s)
+                             : launch_observables<double>(R, gs, mem, act, grid, ntx, nty, zchunk, swz, partials, s);
+    if (e != hipSuccess) return e;
+    if constexpr (MIXED) hipLaunchKernelGGL(wafer_k_batch_reduce_mixed, dim3(4, (unsigned)nact), dim3(256), 0, s, partials, act, mem, out);
+    else hipLaunchKernelGGL(wafer_k_batch_reduce, dim3(4, (unsigned)nact), dim3(256), 0, s, partials, act, (long long)max_nb, out);
+    return hipGetLastError();
+}
+
+hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int max_tiles,
+                                       int max_planes, const double *norm2, int n2_stride, hipStream_t s)
+{
+    if (MIXED) ntx = 0;   // (the kernel forms it from the member's geometry)
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_normalise<float, GS>), grid, block, 0, s, gs, mem, act, ntx, norm2, n2_stride);
+    else hipLaunchKernelGGL((wafer_k_batch_normalise<double, GS>), grid, block, 0, s, gs, mem, act, ntx, norm2, n2_stride);
+    return hipGetLastError();
+}
+
+hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb, double *scal,
+                                   int scal_stride, int out_slot, double *partials, hipStream_t s)
+{
+    const dim3 grid((unsigned)max_nb, (unsigned)nact);
+    if (f32) {
+        const auto a = row_args(gs);
+        hipLaunchKernelGGL((wafer_k_batch_rownorm2<float, decltype(row_args(gs))>), grid, dim3(256), 0, s, a, mem, act, partials);
+    } else {
+        const auto a = gs_norm2_args(gs, scal_stride);
+        hipLaunchKernelGGL((wafer_k_batch_gs<WAFER_GS_NORM2, double, decltype(gs_norm2_args(gs, scal_stride))>), grid,
+                           dim3(WAFER_BATCH_TX, WAFER_BATCH_TY), 0, s, a, mem, act, (const double *)scal, partials);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if constexpr (MIXED)
+        hipLaunchKernelGGL(wafer_k_batch_gs_reduce_mixed, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
+    else hipLaunchKernelGGL(wafer_k_batch_gs_reduce, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, max_nb, scal, scal_stride, out_slot);
+    return hipGetLastError();
+}

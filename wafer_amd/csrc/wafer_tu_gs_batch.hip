@@ -27,20 +27,6 @@ hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, c
     return hipGetLastError();
 }
 
-hipError_t wafer_entry_batch_rownorm2(const WaferGeom &g, const WaferBatchMember *mem, const int *act, int nact, int nb, double *scal,
-                                      int scal_stride, int out_slot, double *partials, hipStream_t s)
-{
-    WaferRowArgs ra;
-    ra.g = g;
-    ra.lz_lo = g.G;
-    ra.lz_hi = g.G + g.nzl;
-    hipLaunchKernelGGL((wafer_k_batch_rownorm2<float>), dim3((unsigned)nb, (unsigned)nact), dim3(256), 0, s, ra, mem, act, partials);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wafer_k_batch_gs_reduce, dim3((unsigned)nact), dim3(256), 0, s, partials, act, nb, scal, scal_stride, out_slot);
-    return hipGetLastError();
-}
-
 template <int NLOW, typename T>
 static hipError_t launch_onepass(bool normalise, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem, const int *act, int nact, int nb,
                                  double *scal, const double *gram, double *partials, hipStream_t s)
