@@ -222,3 +222,72 @@ def test_layout(plan, R):
         assert lines[-1] == (sum(totals),)
         if shapes is UNIFORM:
             assert off == [m * totals[0] for m in range(len(shapes))]   # m * geoms[0].total
+
+
+# ---- members that share shapes: the list the GPU tests of tests/test_gpu_batch_mixed_shared.py run ----------------------------------
+from tests.test_gpu_batch_mixed_shared import SHAPE_LIST as SHARED, first_appearance, masks as shared_masks  # noqa: E402
+
+
+def step_chunks(s, layer, R, cus):
+    """wafer_batch_step_table's z-chunks of a member of shape s when the launch's layer is `layer`"""
+    nch = max(1, min((8 * cus + layer - 1) // layer, (s[2] + 7) // 8))
+    zchunk = (s[2] + nch - 1) // nch
+    return [(R + z0, min(R + z0 + zchunk, R + s[2])) for z0 in range(0, s[2], zchunk)]
+
+
+def fused_chunks(s, layer, R, K, cus):
+    """wafer_batch_fused_table's"""
+    nch = max(1, min((2 * max(cus, 1) + layer - 1) // layer, max(s[2] // max(4 * R * (K - 1), 1), 1)))
+    return [(R + i * s[2] // nch, R + (i + 1) * s[2] // nch) for i in range(nch)]
+
+
+@pytest.mark.parametrize("R", [1, 2, 3])
+def test_shared_shapes_keep_member_and_shape_indexing_apart(plan, R):
+    """The inputs of the GPU tests discriminate: with them the shape index is not the member index, a member's offset is not its
+    shape's, every table entry carries shape_of[its member], and under the masks that empty a shape the tables hold the active
+    members only, cut by the layer of the active members only."""
+    for shapes in (SHARED, SHARED[::-1]):
+        n = len(shapes)
+        table, shape_of = first_appearance(shapes)
+        assert 1 < len(table) < n and sum(1 for m in range(n) if shape_of[m] != m) > n // 2
+        _, members, lines = plan("layout", R, 1, 1, "1" * n, shapes)
+        assert [m[:3] for m in members] == list(shapes)
+        assert [m[3] for m in members] == shape_of                       # first-appearance order
+        off, totals = [l[0] for l in lines[:-1]], [l[1] for l in lines[:-1]]
+        assert off == [sum(totals[:m]) for m in range(n)]               # the prefix sum over MEMBERS
+        assert lines[-1] == (sum(totals),)
+        total_of_shape = {shape_of[m]: totals[m] for m in range(n)}
+        by_shape = [sum(total_of_shape[k] for k in range(shape_of[m])) for m in range(n)]   # ... which the one over the table is not
+        assert sum(1 for m in range(n) if off[m] != by_shape[m]) > n // 2, (off, by_shape)
+        assert len(set(off)) == n                                        # members of one shape lie apart
+    shapes, n = SHARED, len(SHARED)
+    _, shape_of = first_appearance(shapes)
+    every = {"all": [1] * n}
+    every.update(shared_masks(shapes))
+    seen_by_layer = set()   # the masks whose tables differ from the ones the layer of ALL members would give
+    for kind, K, tx, ty in (("step", 1, 64, 4), ("fused", 2, 64, 12), ("fused", 3, 64, 12)):
+        if kind == "fused" and K * R > 6:
+            continue
+        for (name, mask), cus in itertools.product(every.items(), (1, 4, 20, 32, 256)):
+            bits = "".join(str(a) for a in mask)
+            head, members, entries = plan(kind, R, K, cus, bits, shapes)
+            check_cover(head, members, entries, bits, R, K, fused=(kind == "fused"))
+            assert all(e[5] == shape_of[e[0]] for e in entries), (kind, name)            # shape == shape_of[entry.member]
+            assert any(e[5] != e[0] for e in entries), (kind, name)                        # ... and that is not the member
+            assert {e[0] for e in entries} == {m for m in range(n) if mask[m]}, (kind, name)   # no frozen member, every active one
+            tiles = lambda s: ((s[0] + tx - 1) // tx) * ((s[1] + ty - 1) // ty)   # noqa: E731
+            layer = sum(tiles(s) for s, a in zip(shapes, mask) if a)
+            layer_all = sum(tiles(s) for s in shapes)
+            for m in range(n):
+                if not mask[m]:
+                    continue
+                chunks = (lambda l: step_chunks(shapes[m], l, R, cus)) if kind == "step" else (lambda l: fused_chunks(shapes[m], l, R, K, cus))
+                z = sorted({(e[3], e[4]) for e in entries if e[0] == m})
+                assert z == chunks(layer), (kind, K, name, cus, m)       # the summed layer is the active members'
+                assert len([e for e in entries if e[0] == m]) == len(z) * tiles(shapes[m])
+                if chunks(layer) != chunks(layer_all):
+                    seen_by_layer.add(name)
+    # where an active member is thick enough to be cut at all, the active set's layer shows in its chunks: (130, 6, 5) alone -- mask
+    # (c) -- is one chunk under every layer, and so are mask (d)'s (260, 5, 4) and (8, 8, 8) except in the ThreePoint two-step pass
+    want = {k for k in every if k[:2] in (("a_", "b_", "d_") if R == 1 else ("a_", "b_"))}
+    assert want <= seen_by_layer, seen_by_layer
