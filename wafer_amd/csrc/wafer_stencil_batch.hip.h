@@ -336,10 +336,7 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(GS gs, cons
         zchunk = m.obs_zchunk;
     }
     int bid = blockIdx.x;
-    if (swz) {
-        const int n = nb, q = n >> 3, r = n & 7, k = bid & 7;
-        bid = k * q + min(k, r) + (bid >> 3);
-    }
+    if (swz) bid = wafer_xcd_tile(bid, nb);
     const int tx_i = bid % ntx;
     const int ty_i = (bid / ntx) % nty;
     const int tz_i = bid / (ntx * nty);

@@ -96,10 +96,7 @@ __global__ __launch_bounds__((WaferF2Cfg<T, R, NW2>::NT_)) void wafer_k_step2_fu
 
     const WaferGeom &g = a.g;
     int bid = blockIdx.x;
-    if (swz) {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, k = bid & 7;
-        bid = k * q + min(k, r) + (bid >> 3);
-    }
+    if (swz) bid = wafer_xcd_tile(bid, gridDim.x);
     int tx_i, ty_i, zs, ze;
     if (a.nsub > 1) { // mixed launch: long workgroups first (dispatched first), the last tiles as short ones
         int tile, sub = 0;

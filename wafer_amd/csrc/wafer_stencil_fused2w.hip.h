@@ -5,14 +5,11 @@
 //
 // The two-step kernel serves FivePoint with 4 main waves on a 128 x 8 tile + 2 halo-row waves + 1 halo-column wave: phi1 on 12 rows
 // per 8 stored, phi0 on 16, seven waves of which three idle through the second step -- 0.43 ms/step at 512^3, 4.0 TB/s of traffic,
-// half of the device's rate.  Here a workgroup is EIGHT waves on a 128 x 16 tile (fp64; 16 B of x per lane) and every wave owns two
-// rows of the tile at both levels plus ONE extra slot:
-//   wave 0   phi1 of row y0-1,  stages phi0 of row y0-3        wave 7   phi1 of row y0+16, stages row y0+18
-//   wave 1   phi1 of row y0-2,  stages phi0 of row y0-4        wave 6   phi1 of row y0+17, stages row y0+19
-//   waves 2..5   48 of the 192 phi0 halo-column cells each (4 columns per side x 24 rows), one per lane; phi1 on the inner two
-//                columns of rows y0-2 .. y0+17
-// so phi1 is computed on 20 rows per 16 stored and phi0 read on 24, every global access stays 128-byte aligned and the waves'
-// work is even.  z-queues in registers (five planes of phi0 and of phi1 per row slot), x / y neighbours through LDS: phi0 in two
+// half of the device's rate.  Here a workgroup is EIGHT waves on a 128 x 16 tile (fp64; 16 B of x per lane) in the layout of
+// wafer_tile_roles.hip.h (main rows, one extra slot per wave, the redirection of requests outside the work area), with these
+// particulars: every row wave carries phi1 on its halo row and stages one outer phi0 row (wave 0: y0-3, wave 1: y0-4, wave 6: y0+19,
+// wave 7: y0+18); the 192 phi0 halo-column cells (4 columns per side x 24 rows, 48 per wave) carry phi1 on the inner two columns of
+// rows y0-2 .. y0+17 -- so phi1 is computed on 20 rows per 16 stored and phi0 read on 24, and the waves' work is even.  z-queues in registers (five planes of phi0 and of phi1 per row slot), x / y neighbours through LDS: phi0 in two
 // buffers (the plane of level 1 and the one being staged), phi1 in a ring of three planes (level 2 reads the plane written two
 // iterations earlier).  One s_barrier per plane.
 //
@@ -31,6 +28,7 @@
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_fused2.hip.h"
 #include "wafer_storage.h"
+#include "wafer_tile_roles.hip.h"
 
 #define WAFER_W2_SETPRIO(n) __builtin_amdgcn_s_setprio(n)
 #ifndef WAFER_DIAG
@@ -46,13 +44,17 @@ struct WaferW2Cfg {
     static constexpr int HC0 = 2 * R, HC1 = R;            // halo columns per side of phi0 / phi1
     static constexpr int HX0 = ((HC0 + VEC - 1) / VEC) * VEC, HX1 = ((HC1 + VEC - 1) / VEC) * VEC;
     static constexpr int LP0 = TX + 2 * HX0, LP1 = TX + 2 * HX1;
-    static constexpr int ROWS0 = TY + 4 * R, ROWS1 = TY + 2 * R;
+    static constexpr int HALO = 2 * R;                     // halo rows per side of phi0
+    static constexpr int ROWS0 = TY + 2 * HALO, ROWS1 = TY + 2 * R;
     static constexpr int TILE0 = ROWS0 * LP0, TILE1 = ROWS1 * LP1;
     static constexpr int NB1 = R + 1;                      // planes in the phi1 ring
     static constexpr int NCOL = 2 * HC0 * ROWS0;           // phi0 halo-column cells per plane: 192
     static constexpr int HCW0 = 2, HCWN = 4, CPW = (NCOL + HCWN - 1) / HCWN;   // waves 2..5, 48 cells each, one per lane
     static_assert(CPW <= 64, "one halo-column cell per lane");
 };
+
+// the outer phi0 halo row a row wave stages
+#define WAFER_W2_OUTER_ROW_Y (wave == 0 ? y0 - 3 : wave == 1 ? y0 - 4 : wave == 6 ? y0 + TY + 3 : y0 + TY + 2)
 
 template <typename TS, typename C, bool VIR>
 __global__ __launch_bounds__((WaferW2Cfg<typename WaferF3Store<TS>::Q>::NT_)) void wafer_k_step2_wide(
@@ -65,22 +67,19 @@ __global__ __launch_bounds__((WaferW2Cfg<typename WaferF3Store<TS>::Q>::NT_)) vo
     using VT = typename WaferVec<T>::type;
     constexpr int R = 2, VEC = Cfg::VEC, RY = Cfg::RY, TX = Cfg::TX, TY = Cfg::TY;
     constexpr int HX0 = Cfg::HX0, HX1 = Cfg::HX1, LP0 = Cfg::LP0, LP1 = Cfg::LP1;
-    typedef ST __attribute__((ext_vector_type(VEC))) SVT;   // a lane's request: the same cells in the storage type
+    using Sto = WaferStored<ST, T, VEC>;
+    using SVT = typename Sto::SVT;                          // a lane's request: the same cells in the storage type
     typedef T __attribute__((ext_vector_type(2))) T2;       // the two cells beyond either end of a lane's cells, from LDS
     __shared__ __attribute__((aligned(16))) T lds0[2 * Cfg::TILE0];
     __shared__ __attribute__((aligned(16))) T lds1[Cfg::NB1 * Cfg::TILE1];
-    auto gload_raw = [](const ST *p) -> SVT { return *reinterpret_cast<const SVT *>(p); };
-    auto widen = [](const SVT &x) -> VT { return wafer_f3_widen<SVT, VT, VEC>(x); };
-    auto gload = [&](const ST *p) -> VT { return widen(gload_raw(p)); };
-    // a level's result as the storage type holds it (fp32 storage: rounded once per step, like a store and a load would)
-    auto as_stored = [](C x) -> T { return (T)(ST)x; };
+    constexpr typename Sto::Raw gload_raw{};
+    constexpr typename Sto::Widen widen{};
+    constexpr typename Sto::Load gload{};
 
     const WaferGeom &g = a.g;
     int bid = blockIdx.x + a.block0;
-    if (swz) {   // XCD-contiguous tile ranges (workgroup b runs on XCD b % 8; a round of a longer schedule starts at a multiple of 8)
-        const int n = a.nblocks_all > 0 ? a.nblocks_all : (int)gridDim.x, q = n >> 3, r = n & 7, k = bid & 7;
-        bid = k * q + min(k, r) + (bid >> 3);
-    }
+    // (XCD-contiguous tile ranges; a round of a longer schedule starts at a multiple of 8)
+    if (swz) bid = wafer_xcd_tile(bid, a.nblocks_all > 0 ? a.nblocks_all : (int)gridDim.x);
     const int tz_i = bid / (ntx * nty);
     const int tx_i = bid % ntx, ty_i = (bid / ntx) % nty;
     const int zs = a.lz_lo + tz_i * a.zchunk, ze = min(zs + a.zchunk, a.lz_hi);
@@ -90,7 +89,7 @@ __global__ __launch_bounds__((WaferW2Cfg<typename WaferF3Store<TS>::Q>::NT_)) vo
     const C dt = (C)a.dt;
     constexpr bool vir = VIR;
     const WaferDen<C> den = wafer_den<C>(a, vir);
-    const bool x_row = wave < 2 || wave >= 6;   // the extra slot is a halo row (else: halo-column cells)
+    const bool x_row = WAFER_TILE_ROW_WAVE;   // the extra slot is a halo row (else: halo-column cells)
 
     VT zero;
 #pragma unroll
@@ -100,58 +99,27 @@ __global__ __launch_bounds__((WaferW2Cfg<typename WaferF3Store<TS>::Q>::NT_)) vo
     for (int v = 0; v < VEC; ++v) szero[v] = ST(0);
     const int xl = lane * VEC, xi = x0 + xl;
 
-    // ---- main rows
-    int yrow[RY];
-    bool rowwk[RY];
-    long long rowoff[RY];
-#pragma unroll
-    for (int r = 0; r < RY; ++r) {
-        const int y = y0 + wave * RY + r;
-        yrow[r] = y;
-        rowwk[r] = y < g.ny;
-        rowoff[r] = (long long)(y + R) * g.pitch + g.xoff + R + xi;
-    }
-    // ---- the extra halo row (phi1 as well) and the outer row this wave stages (phi0 only)
-    const int xy = wave == 0 ? y0 - 1 : wave == 1 ? y0 - 2 : wave == 6 ? y0 + TY + 1 : y0 + TY;
-    const int oy = wave == 0 ? y0 - 3 : wave == 1 ? y0 - 4 : wave == 6 ? y0 + TY + 3 : y0 + TY + 2;
+    // ---- who owns what (wafer_tile_roles.hip.h; the lane's columns are folded into the rows' offsets)
+    WAFER_TILE_MAIN_ROWS(xi, )
+    // the extra halo row (phi1 as well) and the outer row this wave stages (phi0 only)
+    const int xy = WAFER_TILE_HALO_ROW_Y;
+    const int oy = WAFER_W2_OUTER_ROW_Y;
     const bool xwk = x_row && xy >= 0 && xy < g.ny;
-    // (a row above / below the work area -- frame and guard rows, zeros that no kernel writes -- is not fetched: the wave asks for
-    //  its own first row again and takes the zero the row stands for)
-    const bool xy_out = xy < 0 || xy >= g.ny, oy_out = oy < 0 || oy >= g.ny;
-    const long long xoff_row = xy_out ? rowoff[0] : (long long)(xy + R) * g.pitch + g.xoff + R + xi;
-    const long long orow_off = oy_out ? rowoff[0] : (long long)(oy + R) * g.pitch + g.xoff + R + xi;
-    const int xrow_lds0 = (xy - (y0 - 2 * R)) * LP0 + HX0 + xl, orow_lds = (oy - (y0 - 2 * R)) * LP0 + HX0 + xl;
-    // ---- the halo-column cell of this lane (waves 2..5): cell c: row c / 8 of the phi0 tile, k = c % 8: k < 4: column x0-1-k,
-    //      else column x0+TX+(k-4)
-    const int cidx = min((wave - Cfg::HCW0) * Cfg::CPW + lane, Cfg::NCOL - 1);
-    const int crow = cidx / (2 * Cfg::HC0), ck = cidx % (2 * Cfg::HC0);
-    const int ckk = ck < Cfg::HC0 ? ck : ck - Cfg::HC0;
-    const int clc = ck < Cfg::HC0 ? -1 - ckk : TX + ckk;
-    const int cxw = x0 + clc, cy = y0 - 2 * R + crow;
-    const bool c_ok = !x_row && lane < Cfg::CPW && (wave - Cfg::HCW0) * Cfg::CPW + lane < Cfg::NCOL;
-    const bool c_wk = cy >= 0 && cy < g.ny && cxw >= 0 && cxw < g.nx;
-    const bool c_l1 = c_ok && ckk < Cfg::HC1 && crow >= R && crow < Cfg::ROWS0 - R;
-    // (a cell left / right of the work area or above / below it: not fetched -- its 128-byte line holds nothing anybody else
-    //  reads -- the lane asks for the tile's own edge cell of that row and takes a zero)
-    const bool c_xout = cxw < 0 || cxw >= g.nx || cy < 0 || cy >= g.ny;
-    const long long c_off = (long long)((cy < 0 ? y0 : cy >= g.ny ? y0 + TY - 1 : cy) + R) * g.pitch + g.xoff + R +
-                            ((cxw < 0 || cxw >= g.nx) ? (ck < Cfg::HC0 ? x0 : x0 + TX - 1) : cxw);
-    const int c_lds0 = crow * LP0 + HX0 + clc, c_lds1 = (crow - R) * LP1 + HX1 + clc;
+    const bool xy_out = WAFER_TILE_ROW_OUTSIDE(xy), oy_out = WAFER_TILE_ROW_OUTSIDE(oy);
+    const long long xoff_row = WAFER_TILE_ROW_REQUEST(xy, xy_out, xi);
+    const long long orow_off = WAFER_TILE_ROW_REQUEST(oy, oy_out, xi);
+    const int xrow_lds0 = WAFER_TILE_LDS0_ROW(xy), orow_lds = WAFER_TILE_LDS0_ROW(oy);
+    WAFER_TILE_CELL_HEAD;
+    const bool c_l1 = WAFER_TILE_CELL_AT(1, R);   // phi1 on the inner two columns of rows y0-2 .. y0+17
+    WAFER_TILE_CELL_TAIL;
+    const int c_lds0 = WAFER_TILE_CELL_LDS0, c_lds1 = WAFER_TILE_CELL_LDS(1);
     // the extra slot's requests are the SAME instructions in every wave, the address chosen per lane (a halo row's vector, or
     // the vector that starts at the lane's halo-column cell: component 0 is the cell)
     const long long xslot_off = x_row ? xoff_row : c_off;
     const long long oslot_off = x_row ? orow_off : c_off;
 
-    auto work_plane = [&](int p) {
-        const int kg = g.z_begin + (p - g.G);
-        return kg >= 0 && kg < g.nz;
-    };
-    auto update_keep = [&](C w, C vv, C S, C &ca, C &cbdt) -> T {
-        C cb;
-        wafer_ab_from_v<C>(vv, dt, vir, ca, cb);
-        cbdt = cb * dt;
-        return as_stored(w * ca + wafer_div_invariant<C>(cbdt * S, den));
-    };
+    auto work_plane = [&](int p) { return wafer_work_plane(g, p); };
+    const WaferUpdateKeep<ST, T, C, VIR> update_keep{dt, den};
 
     // ---- state.  Main rows: phi0 planes z-2 .. z+2, phi1 planes z-4 .. z-1, V of planes z-2 .. z.
     //      Extra slot (component 0 only for a halo-column cell): phi0 planes z-2 .. z+2, V of plane z, the outer row of plane z+1.

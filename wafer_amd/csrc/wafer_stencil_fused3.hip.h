@@ -13,12 +13,11 @@
 // produced and stored.  phi1 and phi2 exist only in registers (own z-columns) and in two-slot LDS rings
 // (x / y neighbours).  One s_barrier per plane.
 //
-// Eight waves, two per SIMD, 241 VGPRs, no scratch.  Every wave owns two rows of the tile at all three levels plus ONE extra slot:
-//   wave 0   row y0-1   (phi1 and phi2)          wave 7   row y0+16  (phi1 and phi2)
-//   wave 1   row y0-2   (phi1), stages row y0-3  wave 6   row y0+17  (phi1), stages row y0+18
-//   waves 2..5   33 of the 132 phi0 halo-column cells each, one per lane (z-queues in component 0 of the extra slot's
-//                registers): phi1 on the inner two columns, phi2 on the innermost
-// so that every global access stays 128-byte aligned and tiles need no overlap.
+// Eight waves, two per SIMD, 241 VGPRs, no scratch, in the eight-wave tile layout of wafer_tile_roles.hip.h (main rows, one extra
+// slot per wave, the redirection of requests outside the work area), with these particulars: the halo rows of waves 0 and 7 carry
+// phi1 and phi2, those of waves 1 and 6 phi1 only; waves 1 and 6 also stage the outermost phi0 rows y0-3 / y0+18; the 132 phi0
+// halo-column cells (33 per wave; z-queues in component 0 of the extra slot's registers) carry phi1 on the inner two columns and phi2
+// on the innermost.
 //
 // a and b of a cell (potential.rs:104-110) are formed ONCE per pass, at level 1, and ride in registers to levels 2 and 3 as
 // a and b * dt (b enters the update only through that product): 29 + 16 + 16 fp64 instructions per cell and pass instead of
@@ -46,6 +45,7 @@
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_fused2.hip.h"
 #include "wafer_storage.h"
+#include "wafer_tile_roles.hip.h"
 
 template <typename T> struct WaferF3Vec : WaferVec<T> {};   // cells per lane: 16 bytes of x
 // Diagnostic builds (never timed as the product, never shipped): -DWAFER_DIAG=<bits>
@@ -92,13 +92,17 @@ struct WaferF3Cfg {
     static constexpr int HX1 = ((HC1 + VEC - 1) / VEC) * VEC;
     static constexpr int HX2 = ((HC2 + VEC - 1) / VEC) * VEC;
     static constexpr int LP0 = TX + 2 * HX0, LP1 = TX + 2 * HX1, LP2 = TX + 2 * HX2;
-    static constexpr int ROWS0 = TY + 6, ROWS1 = TY + 4, ROWS2 = TY + 2;
+    static constexpr int HALO = 3;                      // halo rows per side of phi0
+    static constexpr int ROWS0 = TY + 2 * HALO, ROWS1 = TY + 4, ROWS2 = TY + 2;
     static constexpr int TILE0 = ROWS0 * LP0, TILE1 = ROWS1 * LP1, TILE2 = ROWS2 * LP2;
     static constexpr int NCOL = 2 * HC0 * ROWS0;        // phi0 halo-column cells per plane
     static constexpr int HCW0 = 2, HCWN = 4;            // waves HCW0 .. HCW0 + HCWN - 1 take the halo-column cells,
     static constexpr int CPW = (NCOL + HCWN - 1) / HCWN; // one per lane: 33 each
     static_assert(CPW <= 64, "one halo-column cell per lane");
 };
+
+// the outermost phi0 halo row y0-3 is staged by wave 1, y0+18 by wave 6 (the other waves: never used)
+#define WAFER_F3_OUTER_ROW_Y (wave == 1 ? y0 - 3 : y0 + TY + 2)
 
 // One workgroup's assignment.  32 bytes, read with scalar loads.
 struct WaferF3Block {
@@ -230,18 +234,17 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
     using ST = typename WaferF3Store<TS>::S;  // the arrays in HBM
     constexpr bool WIDE = !std::is_same<ST, T>::value;
     using Cfg = WaferF3Cfg<T>;
+    using Sto = WaferStored<ST, T, WaferF3Vec<T>::N>;
     using VT = typename WaferF3Vec<T>::type;
-    typedef ST __attribute__((ext_vector_type(WaferF3Vec<T>::N))) SVT;   // a lane's request: the same cells, in the storage type
-    // global loads of a lane's vector / of one cell, widened to the register type
-    auto gload = [](const ST *p) -> VT { return wafer_f3_widen<SVT, VT, WaferF3Vec<T>::N>(*reinterpret_cast<const SVT *>(p)); };
-    auto gload_raw = [](const ST *p) -> SVT { return *reinterpret_cast<const SVT *>(p); };
+    using SVT = typename Sto::SVT;   // a lane's request: the same cells, in the storage type
+    // global loads of a lane's vector, widened to the register type (gload) or as they arrive
+    constexpr typename Sto::Load gload{};
+    constexpr typename Sto::Raw gload_raw{};
+    constexpr typename Sto::Widen widen{};
     // the result is streamed: nobody reads it before the next launch (the same box, 512^3 / 1024^3: 0.2150 -> 0.2067 / 1.98 -> 1.87
     // ms per step against plain stores; non-temporal LOADS of V or phi0 lose 4-12 %: the halo requests of the tiles next door want
     // those lines in the L2 -- profiles/r05_ab_f3_nontemporal.jsonl)
     auto gstore = [](ST *p, SVT v) { wafer_store_result(reinterpret_cast<SVT *>(p), v); };
-    auto widen = [](const SVT &x) -> VT { return wafer_f3_widen<SVT, VT, WaferF3Vec<T>::N>(x); };
-    // a level's result as the storage type holds it (fp32 storage: rounded once per step, like a store and a load would)
-    auto as_stored = [](C x) -> T { return (T)(ST)x; };
     constexpr int R = 1;
     constexpr int VEC = Cfg::VEC, RY = Cfg::RY, TX = Cfg::TX, TY = Cfg::TY;
     constexpr int HX0 = Cfg::HX0, HX1 = Cfg::HX1, HX2 = Cfg::HX2, LP0 = Cfg::LP0, LP1 = Cfg::LP1, LP2 = Cfg::LP2;
@@ -269,71 +272,36 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
     const C dt = (C)a.dt;
     constexpr bool vir = VIR;
     const WaferDen<C> den = wafer_den<C>(a, vir);
-    // the extra slot: a halo row (waves 0, 1, 6, 7) or halo-column cells (waves 2..5)
-    const bool x_row = wave < 2 || wave >= 6;
-    const bool x_l2 = wave == 0 || wave == 7;            // the halo row next to the tile: phi2 as well
-    const bool has_orow = wave == 1 || wave == 6;
+    // the extra slot: a halo row (waves 0, 1, 6, 7) or halo-column cells (waves 2..5) -- who owns what is wafer_tile_roles.hip.h's text
+    const bool x_row = WAFER_TILE_ROW_WAVE;
+    const bool x_l2 = WAFER_TILE_INNER_ROW_WAVE;   // the halo row next to the tile: phi2 as well
+    const bool has_orow = WAFER_TILE_OUTER_ROW_WAVE;
 
     VT zero;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) zero[v] = T(0);
     const int xl = lane * VEC, xi = x0 + xl;
-    const unsigned xlu = (unsigned)(lane * VEC);
+    const unsigned xlu = (unsigned)(lane * VEC);   // (the lane's columns are added to a row's offset at the request, unsigned)
 
-    // ---- main rows
-    int yrow[RY];
-    bool rowwk[RY];
-    long long rowoff[RY];
-#pragma unroll
-    for (int r = 0; r < RY; ++r) {
-        const int y = y0 + wave * RY + r;
-        yrow[r] = y;
-        rowwk[r] = y < g.ny;
-        rowoff[r] = (long long)(y + R) * g.pitch + g.xoff + R + x0;
-    }
+    WAFER_TILE_MAIN_ROWS(x0, )
     // the row V of work row y is read from (VS: the canonical one of y and its mirror image; rows outside the work area are never
-    // asked for -- their requests go to a row of the tile, below)
+    // asked for -- their requests go to a row of the tile)
     auto vrow = [&](int y) { return VS ? min(y, g.ny - 1 - y) : y; };
     long long vrowoff[RY];
 #pragma unroll
     for (int r = 0; r < RY; ++r) vrowoff[r] = VS ? (long long)(vrow(yrow[r]) + R) * g.pitch + g.xoff + R + x0 : rowoff[r];
-    // ---- the extra halo row
-    const int xy = wave == 0 ? y0 - 1 : wave == 1 ? y0 - 2 : wave == 6 ? y0 + TY + 1 : y0 + TY;
-    const bool xwk = x_row && xy >= 0 && xy < g.ny;
-    // (a halo row above / below the work area -- frame and guard rows, zeros -- is not fetched either: the wave requests its
-    //  own first row again and takes zeros)
-    const bool xy_out = xy < 0 || xy >= g.ny;
-    const long long xoff_row = xy_out ? rowoff[0] : (long long)(xy + R) * g.pitch + g.xoff + R + x0;
+    WAFER_TILE_HALO_ROW(x0);
     const long long xvoff_row = !VS ? xoff_row : xy_out ? vrowoff[0] : (long long)(vrow(xy) + R) * g.pitch + g.xoff + R + x0;
-    // ---- outermost phi0 halo rows y0-3 / y0+18 (plain vector loads staged through LDS)
-    const int oy = wave == 1 ? y0 - 3 : y0 + TY + 2;
-    const bool oy_out = oy < 0 || oy >= g.ny;
-    const long long orow_off = oy_out ? rowoff[0] : (long long)(oy + R) * g.pitch + g.xoff + R + x0;
-    const int orow_lds = (oy - (y0 - 3)) * LP0 + HX0 + xl;
-    // ---- halo-column cell of this lane (waves 2..5): cell c: row c / 6 of the phi0 tile, k = c % 6: k < 3: column x0-1-k,
-    //      else column x0+TX+(k-3)
-    const int cidx = min((wave - Cfg::HCW0) * Cfg::CPW + lane, Cfg::NCOL - 1);
-    const int crow = cidx / (2 * Cfg::HC0), ck = cidx % (2 * Cfg::HC0);
-    const int ckk = (ck < Cfg::HC0) ? ck : ck - Cfg::HC0;
-    const int clc = (ck < Cfg::HC0) ? (-1 - ckk) : (TX + ckk);
-    const int cxw = x0 + clc, cy = y0 - 3 + crow;
-    const bool c_ok = !x_row && lane < Cfg::CPW && (wave - Cfg::HCW0) * Cfg::CPW + lane < Cfg::NCOL;
-    const bool c_wk = cy >= 0 && cy < g.ny && cxw >= 0 && cxw < g.nx;
-    const bool c_l1 = c_ok && ckk < Cfg::HC1 && crow >= 1 && crow < Cfg::ROWS0 - 1;
-    const bool c_l2 = c_ok && ckk < Cfg::HC2 && crow >= 2 && crow < Cfg::ROWS0 - 2;
-    // a cell left or right of the work area (the Dirichlet frame column and the pad cells behind it: zeros that no kernel
-    // writes) is not fetched -- its 128-byte line holds nothing anybody else reads, so each such request was an HBM read of its
-    // own, 44 + 40 lines (phi0, V) per plane and row of tiles, 6 % of this kernel's reads at 512^3.  The lane requests the tile's
-    // own edge cell of that row instead (a line the row's owner requests in the same iteration) and phi0 becomes the zero it
-    // stands for; V of such a cell is never used (c_wk).  (Found with the halo-attribution runs of profiles/NOTES.md, round 3.
-    //  The same for a cell above / below the work area: the tile's own first / last row.)
-    const bool c_xout = cxw < 0 || cxw >= g.nx || cy < 0 || cy >= g.ny;
-    const long long c_off = (long long)((cy < 0 ? y0 : cy >= g.ny ? y0 + TY - 1 : cy) + R) * g.pitch + g.xoff + R +
-                            ((cxw < 0 || cxw >= g.nx) ? (ck < Cfg::HC0 ? x0 : x0 + TX - 1) : cxw);
-    const long long c_voff = !VS ? c_off
-                                 : (long long)(vrow(cy < 0 ? y0 : cy >= g.ny ? y0 + TY - 1 : cy) + R) * g.pitch + g.xoff + R +
-                                       ((cxw < 0 || cxw >= g.nx) ? (ck < Cfg::HC0 ? x0 : x0 + TX - 1) : cxw);
-    const int c_lds0 = crow * LP0 + HX0 + clc, c_lds1 = (crow - 1) * LP1 + HX1 + clc, c_lds2 = (crow - 2) * LP2 + HX2 + clc;
+    // the outermost phi0 halo rows (plain vector loads staged through LDS)
+    const int oy = WAFER_F3_OUTER_ROW_Y;
+    const bool oy_out = WAFER_TILE_ROW_OUTSIDE(oy);
+    const long long orow_off = WAFER_TILE_ROW_REQUEST(oy, oy_out, x0);
+    const int orow_lds = WAFER_TILE_LDS0_ROW(oy);
+    WAFER_TILE_CELL_HEAD;
+    const bool c_l1 = WAFER_TILE_CELL_AT(1, 1), c_l2 = WAFER_TILE_CELL_AT(2, 2);   // phi1 on the inner two columns, phi2 on the innermost
+    WAFER_TILE_CELL_TAIL;
+    const long long c_voff = !VS ? c_off : (long long)(vrow(WAFER_TILE_CELL_RY) + R) * g.pitch + g.xoff + R + WAFER_TILE_CELL_RX;
+    const int c_lds0 = WAFER_TILE_CELL_LDS0, c_lds1 = WAFER_TILE_CELL_LDS(1), c_lds2 = WAFER_TILE_CELL_LDS(2);
     // per-lane element offsets of the extra slot's requests inside a plane (see the prefetch at the top of the plane loop)
     const long long xslot_off = x_row ? xoff_row + (long long)xlu : c_off;
     const long long xslot_voff = !VS ? xslot_off : x_row ? xvoff_row + (long long)xlu : c_voff;
@@ -343,20 +311,9 @@ __device__ __forceinline__ void wafer_step3_body(const WaferStepArgs &a, const W
     static_assert(RY == 2, "pv_row");
     const long long orow_slot_off = has_orow ? orow_off + (long long)xlu : xslot_off;
 
-    auto work_plane = [&](int p) {
-        const int kg = g.z_begin + (p - g.G);
-        return kg >= 0 && kg < g.nz;
-    };
-    // level 1: a, b from V (potential.rs:104-110); what rides to levels 2 and 3 is a and the product b * dt -- b enters the
-    // update (grid.rs:580-589: w * a + b * dt * S / den, left to right) only through that product, which is the same number
-    // at every level
-    auto update_keep = [&](C w, C vv, C S, C &ca, C &cbdt) -> T {
-        C cb;
-        wafer_ab_from_v<C>(vv, dt, vir, ca, cb);
-        cbdt = cb * dt;
-        return as_stored(w * ca + wafer_div_invariant<C>(cbdt * S, den));
-    };
-    auto update_with = [&](C w, C ca, C cbdt, C S) -> T { return as_stored(w * ca + wafer_div_invariant<C>(cbdt * S, den)); };
+    auto work_plane = [&](int p) { return wafer_work_plane(g, p); };
+    const WaferUpdateKeep<ST, T, C, VIR> update_keep{dt, den};
+    const WaferUpdateWith<ST, T, C> update_with{den};
 
     // ---- state.  Main rows: three z-queues, V of the level-1 plane, a / b of the planes of levels 2 and 3.
     //      Extra slot (component 0 only for a halo-column cell): phi0 and phi1 queues, V, a / b of the level-2 plane.
@@ -610,15 +567,6 @@ __global__ __launch_bounds__((WaferF3Cfg<typename WaferF3Store<T>::Q>::NT_)) voi
 // ---- schedules (host) ---------------------------------------------------------------------------------------------
 #include <vector>
 
-// tiles in the order the XCD-aware map visits them: workgroup b runs on XCD b % 8 (observed, speed only), and each XCD
-// should work on one contiguous range of tiles so that neighbouring tiles' halo rows are in its L2.  Returns the tile
-// for dispatch slot b of n.
-static inline int wafer_f3_xcd_slot(int b, int n)
-{
-    const int q = n >> 3, r = n & 7, k = b & 7;
-    return k * q + (k < r ? k : r) + (b >> 3);
-}
-
 // Planes [lz_lo, lz_hi) of every tile, cut into chunks of `zchunk` planes, all marching up: the schedule of an
 // undecomposed grid (one workgroup per CU marching a long column) and of every unsplit pass.
 // fold (the VS instantiation's launches): the tile rows of a z-chunk are visited in the order 0, nty-1, 1, nty-2, ... (x fastest
@@ -633,7 +581,7 @@ static inline void wafer_f3_schedule_plain(std::vector<WaferF3Block> &out, int n
     const int nplanes = lz_hi - lz_lo, nch = (nplanes + zchunk - 1) / zchunk, n = ntx * nty * nch;
     out.resize((size_t)n);
     for (int b = 0; b < n; ++b) {
-        const int id = swz ? wafer_f3_xcd_slot(b, n) : b;     // x fastest, then y, then z-chunk
+        const int id = swz ? wafer_xcd_tile(b, n) : b;     // x fastest, then y, then z-chunk
         WaferF3Block k{};
         k.tile = id % (ntx * nty);
         if (fold) k.tile = wafer_f3_folded_row(k.tile / ntx, nty) * ntx + k.tile % ntx;
@@ -686,7 +634,7 @@ static inline void wafer_f3_schedule_halves(std::vector<WaferF3Block> &out, int 
     out.clear();
     auto push = [&](int half, int tile_, int zs, int ze) {
         WaferF3Block k{};
-        const int tile = (debug & 16) ? wafer_f3_xcd_slot(tile_, ntiles) : tile_;
+        const int tile = (debug & 16) ? wafer_xcd_tile(tile_, ntiles) : tile_;
         k.tile = tile; k.zs = zs; k.ze = ze;
         k.down = half == 0;
         k.wait_late = k.bump = -1;
@@ -748,7 +696,7 @@ static inline void wafer_f3_schedule_whole(std::vector<WaferF3Block> &out, int n
     const int first_side = down ? 1 : 0, last_side = down ? 0 : 1;
     for (int b = 0; b < n; ++b) {
         WaferF3Block k{};
-        k.tile = swz ? wafer_f3_xcd_slot(b, n) : b;
+        k.tile = swz ? wafer_xcd_tile(b, n) : b;
         k.zs = lo; k.ze = hi;
         k.down = (down ? 1 : 0) | ((need_wait[first_side] ? 1 + first_side : 0) << 8) | ((1 + first_side) << 16);
         k.wait_late = need_wait[last_side] ? last_side : -1;

@@ -19,6 +19,7 @@
 #include "wafer_geom.h"
 #include "wafer_stencil.hip.h"
 #include "wafer_setup.hip.h"
+#include "wafer_tile_roles.hip.h"
 
 template <typename T> struct WaferVec;
 template <> struct WaferVec<double> { static constexpr int N = 2; typedef double __attribute__((ext_vector_type(2))) type; };
@@ -211,10 +212,7 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_step_lds(WaferStepArgs a, int
     // (x, y, z-chunk) order, so neighbouring tiles -- which re-read each other's
     // halo rows -- share an L2.  Bijective for any grid size; speed only.
     int bid = blockIdx.x;
-    if (swz) {
-        const int n = gridDim.x, q = n >> 3, r = n & 7, k = bid & 7;
-        bid = k * q + min(k, r) + (bid >> 3);
-    }
+    if (swz) bid = wafer_xcd_tile(bid, gridDim.x);
     const int tx_i = bid % ntx;
     const int ty_i = (bid / ntx) % nty;
     const int tz_i = bid / (ntx * nty);

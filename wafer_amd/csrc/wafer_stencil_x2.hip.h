@@ -25,10 +25,9 @@
 // 2 * (2 + k) * 8 B for two one-step passes -- 16 / 24 / 32 B per update at k = 1 / 2 / 3 against 24 / 32 / 40.
 //
 // Structure: the three-step ground-state kernel's (wafer_stencil_fused3.hip.h) with one level less and a transform on load.
-// Eight waves on a 128 x (8 RY) tile marched up z; every wave owns RY rows at both levels plus ONE extra slot:
-//   wave 0   row y0-1   (x0 queue, Y1)           wave 7   row y0+TY   (x0 queue, Y1)
-//   wave 1   row y0-2   (x0 staged to LDS only)  wave 6   row y0+TY+1 (x0 staged to LDS only)
-//   waves 2..5   the 4 (TY + 4) x0 halo-column cells, one per lane: Y1 on the inner column
+// Eight waves on a 128 x (8 RY) tile marched up z, in the layout of wafer_tile_roles.hip.h (main rows, one extra slot per wave, the
+// redirection of requests outside the work area), with these particulars: the halo rows of waves 0 and 7 have an x0 queue and carry
+// Y1, those of waves 1 and 6 are x0 staged to LDS only; the 4 (TY + 4) x0 halo-column cells carry Y1 on the inner column.
 // a, b of a cell are formed once per pass (level 1) and ride to level 2 as a and b dt.
 // The sums of a plane are all taken when its Z is produced (Y1 of that plane is still in its z-queue), which is three
 // planes after l_j of that plane was loaded for the transform: the stored states' values at the lane's own cells wait in an
@@ -42,6 +41,7 @@
 #include "wafer_stencil_fused2.hip.h"
 #include "wafer_rowwalk.h"
 #include "wafer_storage.h"
+#include "wafer_tile_roles.hip.h"
 
 // the coefficient block the load transform reads (device memory, doubles):  x~ = w * W0 - sum_j m_j SB_j - sum_j l_j SC_j
 enum {
@@ -81,7 +81,8 @@ struct WaferX2Cfg {
     static constexpr int HC0 = 2, HC1 = 1;              // halo columns per side of x0 / Y1
     static constexpr int HX0 = 2, HX1 = 2;              // ... as kept in LDS (VEC aligned)
     static constexpr int LP0 = TX + 2 * HX0, LP1 = TX + 2 * HX1;
-    static constexpr int ROWS0 = TY + 4, ROWS1 = TY + 2;
+    static constexpr int HALO = 2;                      // halo rows per side of x0
+    static constexpr int ROWS0 = TY + 2 * HALO, ROWS1 = TY + 2;
     static constexpr int TILE0 = ROWS0 * LP0, TILE1 = ROWS1 * LP1;
     static constexpr int NCOL = 2 * HC0 * ROWS0;        // x0 halo-column cells per plane
     static constexpr int HCW0 = 2, HCWN = 4;            // waves HCW0 .. HCW0 + HCWN - 1 take them, one per lane
@@ -130,10 +131,11 @@ __global__ __launch_bounds__(512) void wafer_k_xstep2(WaferStepArgs a, int ntx, 
     typedef double C;
     using VT = typename WaferVec<double>::type;
     using ST = typename WaferF3Store<TS>::S;                       // the arrays in HBM
-    typedef ST __attribute__((ext_vector_type(2))) SVT;            // a lane's request
+    using Sto = WaferStored<ST, T, 2>;
+    using SVT = typename Sto::SVT;                                 // a lane's request
     [[maybe_unused]] constexpr bool WIDE = !std::is_same<ST, T>::value;
-    auto widen = [](const SVT &x) -> VT { return wafer_f3_widen<SVT, VT, 2>(x); };
-    auto as_stored = [](T x) -> T { return (T)(ST)x; };          // what the array will hold (fp32 storage: rounded once, like a store and a load)
+    constexpr typename Sto::Widen widen{};
+    constexpr typename Sto::AsStored as_stored{};                  // what the array will hold (fp32 storage: rounded once, like a store and a load)
 #define WAFER_X2_L(j) (static_cast<const ST *>(st.l[j]))
 #define WAFER_X2_M(j) (static_cast<const ST *>(st.m[j]))
     constexpr int R = 1;
@@ -160,10 +162,7 @@ __global__ __launch_bounds__(512) void wafer_k_xstep2(WaferStepArgs a, int ntx, 
 
     const WaferGeom &g = a.g;
     int bid = blockIdx.x;
-    if (swz) { // XCD-contiguous tile order (wafer_stencil_lds.hip.h)
-        const int n = gridDim.x, q = n >> 3, r = n & 7, k = bid & 7;
-        bid = k * q + min(k, r) + (bid >> 3);
-    }
+    if (swz) bid = wafer_xcd_tile(bid, gridDim.x);
     const int tx_i = bid % ntx, ty_i = (bid / ntx) % nty, tz_i = bid / (ntx * nty);
     const int zs = a.lz_lo + tz_i * a.zchunk;
     const int ze = min(zs + a.zchunk, a.lz_hi);
@@ -173,8 +172,8 @@ __global__ __launch_bounds__(512) void wafer_k_xstep2(WaferStepArgs a, int ntx, 
     const C dt = (C)a.dt;
     constexpr bool vir = VIR;
     const WaferDen<C> den = wafer_den<C>(a, vir);
-    const bool x_row = wave < 2 || wave >= 6;
-    const bool x_l1 = wave == 0 || wave == 7;            // the halo row next to the tile: Y1 as well
+    const bool x_row = WAFER_TILE_ROW_WAVE;
+    const bool x_l1 = WAFER_TILE_INNER_ROW_WAVE;   // the halo row next to the tile: Y1 as well
 
     WaferX2Coef<NL> kf;
     kf.w0 = coef[WAFER_X2_W0];
@@ -196,55 +195,23 @@ __global__ __launch_bounds__(512) void wafer_k_xstep2(WaferStepArgs a, int ntx, 
     SVT szero;
     szero[0] = szero[1] = ST(0);
     const int xl = lane * VEC, xi = x0 + xl;
-    const unsigned xlu = (unsigned)(lane * VEC);
+    const unsigned xlu = (unsigned)(lane * VEC);   // (the lane's columns are added to a row's offset at the request, unsigned)
 
-    // ---- main rows
-    int yrow[RY];
-    bool rowwk[RY];
-    long long rowoff[RY];
-    int qoff[RY];
-#pragma unroll
-    for (int r = 0; r < RY; ++r) {
-        const int y = y0 + wave * RY + r;
-        yrow[r] = y;
-        rowwk[r] = y < g.ny;
-        rowoff[r] = (long long)(y + R) * g.pitch + g.xoff + R + x0;
-        qoff[r] = (wave * RY + r) * TX + xl;
-    }
-    // ---- the extra halo row (requests of rows outside the work area are redirected to the wave's own first row and the
-    //      value replaced by the zero it stands for, as in the three-step kernel)
-    const int xy = wave == 0 ? y0 - 1 : wave == 1 ? y0 - 2 : wave == 6 ? y0 + TY + 1 : y0 + TY;
-    const bool xwk = x_row && xy >= 0 && xy < g.ny;
-    const bool xy_out = xy < 0 || xy >= g.ny;
-    const long long xoff_row = xy_out ? rowoff[0] : (long long)(xy + R) * g.pitch + g.xoff + R + x0;
-    // ---- halo-column cell of this lane (waves 2..5): cell c: row c / 4 of the x0 tile, k = c % 4: k < 2: column x0-1-k,
-    //      else column x0+TX+(k-2)
-    const int cidx = min((wave - Cfg::HCW0) * Cfg::CPW + lane, Cfg::NCOL - 1);
-    const int crow = cidx / (2 * Cfg::HC0), ck = cidx % (2 * Cfg::HC0);
-    const int ckk = (ck < Cfg::HC0) ? ck : ck - Cfg::HC0;
-    const int clc = (ck < Cfg::HC0) ? (-1 - ckk) : (TX + ckk);
-    const int cxw = x0 + clc, cy = y0 - 2 + crow;
-    const bool c_ok = !x_row && lane < Cfg::CPW && (wave - Cfg::HCW0) * Cfg::CPW + lane < Cfg::NCOL;
-    const bool c_wk = cy >= 0 && cy < g.ny && cxw >= 0 && cxw < g.nx;
-    const bool c_l1 = c_ok && ckk < Cfg::HC1 && crow >= 2 && crow < Cfg::ROWS0 - 2;   // rows y0 .. y0+TY-1: what level 2 reads
-    const bool c_xout = cxw < 0 || cxw >= g.nx || cy < 0 || cy >= g.ny;
-    const long long c_off = (long long)((cy < 0 ? y0 : cy >= g.ny ? y0 + TY - 1 : cy) + R) * g.pitch + g.xoff + R +
-                            ((cxw < 0 || cxw >= g.nx) ? (ck < Cfg::HC0 ? x0 : x0 + TX - 1) : cxw);
-    const int c_lds0 = crow * LP0 + HX0 + clc, c_lds1 = (crow - 1) * LP1 + HX1 + clc;
+    // ---- who owns what: wafer_tile_roles.hip.h's text (a request outside the work area is redirected and its value replaced by the
+    //      zero it stands for)
+    int qoff[RY];   // the lane's cells of a main row in a slot of the LDS queue
+    WAFER_TILE_MAIN_ROWS(x0, qoff[r] = (wave * RY + r) * TX + xl)
+    WAFER_TILE_HALO_ROW(x0);
+    WAFER_TILE_CELL_HEAD;
+    // Y1 on the inner column of rows y0 .. y0+TY-1 only: what level 2 reads (the LDS tile of Y1 starts one row above them)
+    const bool c_l1 = WAFER_TILE_CELL_AT(1, 2);
+    WAFER_TILE_CELL_TAIL;
+    const int c_lds0 = WAFER_TILE_CELL_LDS0, c_lds1 = WAFER_TILE_CELL_LDS(1);
 
-    auto work_plane = [&](int p) {
-        const int kg = g.z_begin + (p - g.G);
-        return kg >= 0 && kg < g.nz;
-    };
-    // level 1: a, b from V (potential.rs:104-110); what rides to level 2 is a and the product b * dt (grid.rs:580-589:
-    // w * a + b * dt * S / den, left to right)
-    auto update_keep = [&](C w, C vv, C S, C &ca, C &cbdt) -> T {
-        C cb;
-        wafer_ab_from_v<C>(vv, dt, vir, ca, cb);
-        cbdt = cb * dt;
-        return (T)(w * ca + wafer_div_invariant<C>(cbdt * S, den));
-    };
-    auto update_with = [&](C w, C ca, C cbdt, C S) -> T { return (T)(w * ca + wafer_div_invariant<C>(cbdt * S, den)); };
+    auto work_plane = [&](int p) { return wafer_work_plane(g, p); };
+    // (Y1 and Z stay in the register type here: Z is rounded to the storage type where its sums are taken)
+    const WaferUpdateKeep<T, T, C, VIR> update_keep{dt, den};
+    const WaferUpdateWith<T, T, C> update_with{den};
     // V of a cell: streamed (vv) or its closed form at the padded global index
     auto v_at = [&](C vv, int xw, int yw, int lzp) -> C {
         if constexpr (VG != 0) return (C)wafer_vgen_at<VG>(vgen, xw + R, yw + R, g.zp_of(lzp));
