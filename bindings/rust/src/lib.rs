@@ -246,6 +246,10 @@ extern "C" {
     pub fn wafer_batch_set_gs_variant(b: *mut wafer_batch, variant: c_int) -> c_int;
     pub fn wafer_batch_diag_gs(b: *mut wafer_batch, wnum: u32, buf: *mut c_char, n: usize) -> c_int;
     pub fn wafer_batch_diag_gs_steps(b: *mut wafer_batch, onepass: *mut u64, sequential: *mut u64) -> c_int;
+    /// `wafer_symmetrise` for every active member in one launch, member m with `constraints[m]` (n_members entries, WAFER_SYM_*)
+    pub fn wafer_batch_symmetrise(b: *mut wafer_batch, active: *const u8, constraints: *const c_int) -> c_int;
+    /// `wafer_set_potsub` for one member
+    pub fn wafer_batch_set_potsub(b: *mut wafer_batch, member: u32, kind: c_int, scalar: f64, potsub: *const f64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

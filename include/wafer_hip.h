@@ -499,6 +499,8 @@ int wafer_batch_set_potential_builtin(wafer_batch *b, uint32_t member, int poten
 int wafer_batch_set_potential_host(wafer_batch *b, uint32_t member, const double *v, int potsub_kind, double potsub_scalar,
                                    const double *potsub);
 int wafer_batch_set_initial_condition(wafer_batch *b, uint32_t member, int ic, uint64_t seed);
+/* wafer_set_potsub for one member (after its potential is set): a potential_sub override, potential.rs:113-131 */
+int wafer_batch_set_potsub(wafer_batch *b, uint32_t member, int kind, double scalar, const double *potsub);
 int wafer_batch_upload_phi(wafer_batch *b, uint32_t member, const double *phi);
 int wafer_batch_download_phi(wafer_batch *b, uint32_t member, double *phi);
 /* n_steps ground-state steps (0 takes one, as wafer_evolve) of the members with active[m] != 0 (active NULL: all) */
@@ -507,6 +509,13 @@ int wafer_batch_evolve(wafer_batch *b, const uint8_t *active, uint64_t n_steps);
 int wafer_batch_observables(wafer_batch *b, wafer_observables_t *out);
 /* normalise_wavefunction of the active members, member m by norm2[m] (n_members entries) */
 int wafer_batch_normalise(wafer_batch *b, const uint8_t *active, const double *norm2);
+/* wafer_symmetrise for every active member at once, member m with constraints[m] (n_members entries, WAFER_SYM_*): ONE launch for
+ * all members whose constraint is not WAFER_SYM_NOT_CONSTRAINED, each bit for bit what wafer_symmetrise gives a context, on batches
+ * of one shape and of several.  Members that are inactive or not constrained keep their buffer and their bits.  A constraint outside
+ * the enum on an active member: WAFER_ERR_INVALID; an active member without phi: WAFER_ERR_STATE; a constraint other than
+ * NotConstrained on a batch whose stencil is not SevenPoint: WAFER_ERR_INVALID with wafer_symmetrise's message.  Nothing has changed
+ * when it fails.  All constraints NotConstrained: succeeds on any stencil and launches nothing. */
+int wafer_batch_symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints);
 /* wafer_solve_state(ctx, 0, ...) for every member at once.  records: n_members * max_records_per_member rows, member m's at
  * m * max_records_per_member; n_records, finals, status: n_members entries.  status[m]: WAFER_OK (converged),
  * WAFER_ERR_MAX_STEP, or WAFER_ERR_STATE (non-finite energy; wafer_last_error names the first such member).  A member that

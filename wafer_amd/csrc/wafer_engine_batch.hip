@@ -70,6 +70,7 @@ struct wafer_batch {
     int step_variant = -1;                    // wafer_batch_set_step_variant
     uint64_t n_fused_passes = 0, n_single_steps = 0;   // launches since creation (wafer_batch_diag_passes)
     int *act_dev = nullptr, *act_host = nullptr;
+    int *sym_dev = nullptr, *sym_host = nullptr;      // [member]: the constraints of the last wafer_batch_symmetrise
     // observables: every member on the single context's partition of its shape (mem[].obs_*)
     int swz = 0;
     double *partials = nullptr;               // member m's [4][obs_nb] at mem[m].obs_off
@@ -143,11 +144,11 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->partials, (void *)b->sums,
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
                     (void *)b->gram_list_dev})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host})
+    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop})
         if (e) (void)hipEventDestroy(e);
@@ -315,6 +316,51 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
+}
+
+// config::symmetrise_wavefunction (config.rs:691-728) for every active member with a constraint, each with its own: the checks and
+// the message of wafer_symmetrise, then ONE launch from phi[cur] into the members' other buffers, whose views flip.  Needs no state
+// store: one shape or several.
+int symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
+{
+    std::vector<uint8_t> hit(b->n, 0);
+    bool any = false;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (constraints[m] < WAFER_SYM_NOT_CONSTRAINED || constraints[m] > WAFER_SYM_ANTISYM_ABOUT_Y)
+            return fail(WAFER_ERR_INVALID, "member %u: unknown symmetry constraint %d", m, constraints[m]);
+        if (!b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+        hit[m] = constraints[m] != WAFER_SYM_NOT_CONSTRAINED;
+        any = any || hit[m];
+    }
+    if (!any) return WAFER_OK;
+    if (b->g().R != 3)
+        return fail(WAFER_ERR_INVALID, "symmetry constraints index the SevenPoint frame (config.rs:702-725); "
+                                       "the reference runs out of bounds with central_difference ext %d", b->g().R);
+    HIP_TRY(hipSetDevice(b->device));
+    TRY(sync_members(b));
+    int nact = 0;
+    TRY(upload_active(b, hit.data(), &nact));   // (synchronises the stream: sym_host is not read by an earlier call's copy either)
+    for (uint32_t m = 0; m < b->n; ++m) b->sym_host[m] = hit[m] ? constraints[m] : 0;
+    HIP_TRY(hipMemcpyAsync(b->sym_dev, b->sym_host, sizeof(int) * b->n, hipMemcpyHostToDevice, b->s));
+    int max_tiles = 0, max_planes = 0;   // of the padded boxes: the kernel writes the frame's zeros too
+    for (int k = 0; k < nact; ++k) {
+        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
+        max_tiles = std::max(max_tiles, ((g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
+        max_planes = std::max(max_planes, g.lz);
+    }
+    const int ntx = (b->g().px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;   // (one shape: every member's tiles along x)
+    RoctxRange range_("wafer_batch_symmetrise");
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_symmetrise(b->f32, gs, b->mem_dev, b->act_dev, nact, b->sym_dev, ntx, max_tiles, max_planes, b->s);
+    });
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched symmetrise launch failed: %s", hipGetErrorString(e));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (!hit[m]) continue;
+        b->views[m]->cur ^= 1;
+        b->views[m]->halo_valid = 0;
+    }
+    return sync_members(b);
 }
 
 // ---- w_store ---------------------------------------------------------------------------------------------------------------
@@ -829,6 +875,8 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     HIP_TRY(hipHostMalloc((void **)&b->n2_host, sizeof(double) * n_members, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->act_dev, sizeof(int) * n_members));
     HIP_TRY(hipHostMalloc((void **)&b->act_host, sizeof(int) * n_members, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&b->sym_dev, sizeof(int) * n_members));
+    HIP_TRY(hipHostMalloc((void **)&b->sym_host, sizeof(int) * n_members, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
     HIP_TRY(hipMalloc((void **)&b->geoms_dev, sizeof(WaferGeom) * b->geoms.size()));
     HIP_TRY(hipMemcpy(b->geoms_dev, b->geoms.data(), sizeof(WaferGeom) * b->geoms.size(), hipMemcpyHostToDevice));
@@ -884,6 +932,18 @@ int wafer_batch_set_potential_host(wafer_batch *b, uint32_t member, const double
 {
     TRY(check_member_index(b, member));
     return wafer_set_potential_host(b->views[member], v, potsub_kind, potsub_scalar, potsub);
+}
+
+int wafer_batch_set_potsub(wafer_batch *b, uint32_t member, int kind, double scalar, const double *potsub)
+{
+    TRY(check_member_index(b, member));
+    return wafer_set_potsub(b->views[member], kind, scalar, potsub);
+}
+
+int wafer_batch_symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
+{
+    if (!b || !constraints) return fail(WAFER_ERR_INVALID, "null argument");
+    return symmetrise(b, active, constraints);
 }
 
 int wafer_batch_set_initial_condition(wafer_batch *b, uint32_t member, int ic, uint64_t seed)

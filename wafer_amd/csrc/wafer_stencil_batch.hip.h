@@ -23,6 +23,7 @@
 #include "wafer_batch_plan.h"
 #include "wafer_stencil.hip.h"
 #include "wafer_stencil_fused2.hip.h"
+#include "wafer_symmetry.hip.h"
 
 // one member of a batch, as the kernels read it (device table, one entry per member)
 struct WaferBatchMember {
@@ -459,6 +460,39 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, con
     *p = (T)wafer_div_invariant<double>((double)*p, coef);
 }
 
+// symmetrise_wavefunction (config.rs:691-728) of the members act[blockIdx.z], each with its own constraint sym[member] (WAFER_SYM_*,
+// never NotConstrained here: the host launches the constrained members only): wafer_k_symmetrise's arithmetic per cell
+// (wafer_symmetrise_cell, wafer_symmetry.hip.h) from the OLD values in phi[cur] into the member's other buffer; the host flips cur.
+// Block (64, 4) over a 64 x 4 tile of one plane (blockIdx.y) of the member's PADDED box -- px x py cells, all lz planes: the
+// context's grid.  The other buffer is scratch between steps, so the kernel writes the whole box: the new value inside the frame,
+// zero on it -- what a context gets from clearing the allocation first (the guard rows and planes and the row pads outside the box
+// are zeros from creation on and nothing writes them: DESIGN.md section 5).  The constraint is workgroup-uniform (a scalar load).
+// Several shapes: the grid has the largest tile and plane counts among the launched members, and a workgroup beyond its member's
+// own leaves as a whole before any load.
+template <typename T = double, typename GS = WaferGeom>
+static __global__ __launch_bounds__(256) void wafer_k_batch_symmetrise(GS gs, const WaferBatchMember *__restrict__ mem,
+                                                                       const int *__restrict__ act, const int *__restrict__ sym, int ntx)
+{
+    const int member = __builtin_amdgcn_readfirstlane(act[blockIdx.z]);
+    const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
+    if constexpr (wafer_batch_mixed<GS>) {
+        ntx = (g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+        if ((int)blockIdx.y >= g.lz || (int)blockIdx.x >= ntx * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
+    }
+    const int cons = __builtin_amdgcn_readfirstlane(sym[member]);
+    const int axis = cons <= 2 ? 0 : 1;                     // AboutZ, AntisymAboutZ | AboutY, AntisymAboutY
+    const double sign = (cons & 1) ? 1.0 : -1.0;            // the odd constraints are the symmetric ones
+    const int xp = (blockIdx.x % ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int yp = (blockIdx.x / ntx) * WAFER_BATCH_TY + threadIdx.y;
+    const int lzp = blockIdx.y;
+    if (xp >= g.px || yp >= g.py) return;
+    const int cur = m.cur & 1;
+    const T *__restrict__ in = static_cast<const T *>(m.phi[cur]);
+    T *__restrict__ out = static_cast<T *>(m.phi[cur ^ 1]);
+    out[g.at(lzp, yp, xp)] = wafer_symmetrise_inside(g, lzp, yp, xp) ? wafer_symmetrise_cell<T>(g, axis, sign, in, lzp, yp, xp) : T(0);
+}
+
 // entry points (wafer_tu_batch.inc), each once per geometry source GS: const WaferGeom & (a batch of one shape: wafer_tu_batch.hip)
 // and const WaferBatchGeomTable & (several: wafer_tu_batch_mixed.hip).  dtype: the batch's wafer_dtype as an int -- 0 f64, 1 f32
 // (float storage, fp64 arithmetic), 2 f32fast (float storage, float arithmetic in the ground-state step).  f32 is true for float
@@ -467,6 +501,8 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, con
 // observables, normalise: ntx, nty, zchunk are the partition of every launched member of a batch of one shape (several shapes: not
 // read, the kernels take each member's own from its record and geometry); max_*: the largest per-member count among the launched
 // members -- the grid's extent, and for one shape every member's count.
+// symmetrise: sym[member] is the member's WAFER_SYM_* constraint; ntx the tiles along x of the PADDED box of one shape; max_tiles and
+// max_planes count tiles and planes of the padded boxes (px x py, lz).
 // norm2 (wafer_batch_norm2; kernels: wafer_gs_batch.hip.h): norm2 of the members in act into scal[member * scal_stride + out_slot], each
 // on its own partition of WaferBatchMember::n2_nb workgroups -- float storage: wafer_k_batch_rownorm2 on a single context's wafer_norm2
 // partition, the same double; doubles: wafer_k_batch_gs<NORM2>.  partials holds every member's n2_nb doubles, end to end.
@@ -479,6 +515,8 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, con
                                              int zchunk, int max_nb, int swz, double *partials, double *out, hipStream_t s);                        \
     hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int max_tiles,    \
                                            int max_planes, const double *norm2, int n2_stride, hipStream_t s);                                      \
+    hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, const int *sym, int ntx,  \
+                                            int max_tiles, int max_planes, hipStream_t s);                                                           \
     hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb, double *scal,     \
                                        int scal_stride, int out_slot, double *partials, hipStream_t s);
 WAFER_BATCH_ENTRIES(WaferGeom)

@@ -129,6 +129,16 @@ hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchM
     return hipGetLastError();
 }
 
+hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, const int *sym, int ntx,
+                                        int max_tiles, int max_planes, hipStream_t s)
+{
+    if (MIXED) ntx = 0;   // (the kernel forms it from the member's geometry)
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_symmetrise<float, GS>), grid, block, 0, s, gs, mem, act, sym, ntx);
+    else hipLaunchKernelGGL((wafer_k_batch_symmetrise<double, GS>), grid, block, 0, s, gs, mem, act, sym, ntx);
+    return hipGetLastError();
+}
+
 hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb, double *scal,
                                    int scal_stride, int out_slot, double *partials, hipStream_t s)
 {

@@ -57,6 +57,7 @@ EXPORTS = [
     "wafer_batch_evolve_state", "wafer_batch_solve_state",
     "wafer_batch_set_gs_variant", "wafer_batch_diag_gs", "wafer_batch_diag_gs_steps",
     "wafer_batch_create_mixed", "wafer_batch_num_shapes",
+    "wafer_batch_symmetrise", "wafer_batch_set_potsub",
 ]
 
 
@@ -257,6 +258,8 @@ def load_library():
     L.wafer_batch_set_gs_variant.argtypes = [vp, C.c_int]
     L.wafer_batch_diag_gs.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
     L.wafer_batch_diag_gs_steps.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.wafer_batch_symmetrise.argtypes = [vp, u8p, C.POINTER(C.c_int)]
+    L.wafer_batch_set_potsub.argtypes = [vp, C.c_uint32, C.c_int, C.c_double, dp]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -695,7 +698,14 @@ class Batch:
     bits of a Context of its own Params on every dtype, in one launch per step or pass for all shapes together (num_shapes(),
     dispatch()["shapes"]).  With more than one distinct shape the calls that need the state stores (load_state, download_state,
     push_state, clear_states, clone_state_to_phi, orthogonalise, evolve with wnum > 0, solve_state, set_gs_variant(1)) raise
-    WaferError -1 with "mixed-shape" in the message; with one distinct shape the batch is a plain Batch in every call."""
+    WaferError -1 with "mixed-shape" in the message; with one distinct shape the batch is a plain Batch in every call.
+
+    symmetrise(constraints, active=None) applies constraints[m] (a name of SYMMETRY or its index, one per member) to every active
+    member in ONE launch, each member bit for bit what Context.symmetrise gives, on one shape and on several; members that are
+    inactive or "NotConstrained" keep their buffer and their bits.  SevenPoint only, like a Context, unless every constraint is
+    "NotConstrained".  set_potsub(i, kind, scalar, potsub) is Context.set_potsub for member i (a potential_sub override).
+    python -m wafer_amd.sweep drives whole wafer.yaml runs through batches with these calls: phases per state number, every run
+    with its own screen_update, tolerance and max_steps, one evolve for all running members between block boundaries."""
 
     def __init__(self, members: list, mixed_shapes: bool = False):
         self._L = load_library()
@@ -757,8 +767,24 @@ class Batch:
         self._check(self._L.wafer_batch_set_potential_host(
             self._h, i, _dp(v), potsub_kind, potsub_scalar, _dp(potsub) if potsub is not None else None))
 
+    def set_potsub(self, i: int, kind: int, scalar: float = 0.0, potsub: np.ndarray | None = None) -> None:
+        """override member i's pot_sub after its potential is set (Context.set_potsub: 0 none, 1 scalar, 2 array of the work shape)"""
+        i = self._member(i)
+        if potsub is not None:
+            assert potsub.shape == self.members[i].work_shape
+        self._check(self._L.wafer_batch_set_potsub(self._h, i, kind, scalar, _dp(potsub) if potsub is not None else None))
+
     def set_initial_condition(self, i: int, name: str, seed: int = 0) -> None:
         self._check(self._L.wafer_batch_set_initial_condition(self._h, i, INITIAL_CONDITIONS.index(name), seed))
+
+    def symmetrise(self, constraints, active=None) -> None:
+        """Context.symmetrise for every active member (None: all) in one launch, member m with constraints[m]: a name of SYMMETRY
+        or its index.  SevenPoint only unless every constraint is NotConstrained; the other members keep their bits."""
+        cons = [SYMMETRY.index(c) if isinstance(c, str) else int(c) for c in constraints]
+        if len(cons) != len(self.members):
+            raise ValueError("constraints must hold one entry per member")
+        a = self._mask(active)
+        self._check(self._L.wafer_batch_symmetrise(self._h, self._u8(a), (C.c_int * len(cons))(*cons)))
 
     def upload_phi(self, i: int, phi: np.ndarray) -> None:
         assert phi.shape == self.members[i].padded_shape

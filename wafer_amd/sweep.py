@@ -1,0 +1,391 @@
+"""Sweeps: many `wafer.yaml` runs as batches on one GPU -- a convergence study over N and dn, a scan over potentials or masses --
+every time step ONE launch for all runs of a batch that are still going (wafer_amd.Batch), instead of one process and one tiny
+context per run.
+
+    python -m wafer_amd.sweep -c a.yaml -c b.yaml ... [--output-dir DIR] [--input-dir DIR] [--max-batch N] [--seed S]
+                              [--progress] [--plan]
+
+Configuration reading and validation are the native driver's (`wafer-hip --check-config`, through wafer_amd.run.load_config), the
+input files, the directory names and the table are wafer_amd.run's, and every run computes what `wafer-hip` computes for its file:
+the loop of wafer_cli.cpp per run (observables, normalise, Gram-Schmidt, the symmetry constraint at the start and at every
+snapshot block, the convergence and max_steps tests), each run with its own tolerance, screen_update, snap_update, max_steps and dt.
+
+Grouping (plan_batches): runs are partitioned by (central_difference, dtype); within a partition the runs that need state stores
+(wavenum > 0 or wavemax > 0) are split by grid shape (a mixed-shape batch has no state stores), and the ground-state-only runs of
+all shapes share one mixed-shape batch.  Each group is cut in input order into batches of at most --max-batch members, which run
+one after another.
+
+Scheduling (run_phase): one phase per state number w = 0, 1, ...; in phase w the runs with wavenum <= w <= wavemax that have not
+failed take part.  A run is at a block boundary when its own step counter is a multiple of its screen_update.  Every batched call
+at a boundary -- normalise, orthogonalise, symmetrise, push_state -- covers all runs that are at a boundary at that moment, with an
+active mask; between boundaries one evolve advances ALL running runs by next_chunk steps, the distance to the nearest boundary of
+any of them.  A run that converges is pushed and sits out the rest of the phase; one that passes max_steps or whose energy is not
+finite has failed and takes no further part, and the others go on.
+
+Output: <output-dir>/<index:03d>_<project name>_<timestamp>/ per run with a copy of the config, table.txt (what wafer_amd.run prints
+for that run up to its "Simulation complete" line; every block's row with --progress), observables_N.json / .csv and, with
+save_wavefns, wavefunction_N.npy (wavefunction_N_partial.npy for a state that did not converge): the work area in the reference's
+axis order.  Stdout: one JSON line per run, then the elapsed time.  The exit code is 0 only if every run converged in every state
+it asked for.  Not in a sweep: script potentials, inputs of another resolution.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+from wafer_amd.run import load_config, measurement_row, observable_header, sanitize, staged_array, summary
+
+DEFAULT_MAX_BATCH = 64
+
+
+# ---- grouping -------------------------------------------------------------------------------------------------------------------
+def needs_states(cfg: dict) -> bool:
+    return cfg["wavenum"] > 0 or cfg["wavemax"] > 0
+
+
+def plan_batches(cfgs: list, max_batch: int = DEFAULT_MAX_BATCH) -> list:
+    """-> the batches in running order, each dict(members=[input indices], central_difference, dtype, needs_states, mixed_shapes,
+    shapes=[distinct (nx, ny, nz)]).  Groups appear in the order of their first member; every input index appears exactly once."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be >= 1")
+    groups: dict = {}
+    for i, c in enumerate(cfgs):
+        key = (c["central_difference"], c["dtype"])
+        key += ("states", c["nx"], c["ny"], c["nz"]) if needs_states(c) else ("ground",)
+        groups.setdefault(key, []).append(i)
+    out = []
+    for key, idx in groups.items():
+        for at in range(0, len(idx), max_batch):
+            members = idx[at:at + max_batch]
+            shapes = []
+            for i in members:
+                s = (cfgs[i]["nx"], cfgs[i]["ny"], cfgs[i]["nz"])
+                if s not in shapes:
+                    shapes.append(s)
+            out.append(dict(members=members, central_difference=key[0], dtype=key[1], needs_states=key[2] == "states",
+                            mixed_shapes=key[2] == "ground", shapes=[list(s) for s in shapes]))
+    return out
+
+
+def next_chunk(remaining) -> int:
+    """steps of the next evolve: the smallest distance (> 0) of any running run to its next block boundary"""
+    d = min(remaining)
+    if d < 1:
+        raise ValueError("a running member is at a boundary: it has to be handled before the next evolve")
+    return int(d)
+
+
+# ---- one run ----------------------------------------------------------------------------------------------------------------------
+class Run:
+    """one wafer.yaml in a batch: its configuration, its place (slot), its step counter and what it has printed so far"""
+
+    def __init__(self, index: int, cfg: dict, config_path: str | None = None, input_dir: str | None = None, out_dir: str | None = None):
+        self.index, self.cfg, self.config_path, self.input_dir, self.out_dir = index, cfg, config_path, input_dir, out_dir
+        self.slot = 0
+        self.batch = 0
+        self.lines: list = []        # table.txt, line by line
+        self.states: list = []       # per state: dict(state, status, steps, energy)
+        self.failed = False
+        self.boundaries: list = []   # the steps of this phase's block boundaries
+        # the phase's loop variables (grid.rs:122-125)
+        self.step, self.remaining, self.last_energy, self.cloned, self.running = 0, 0, sys.float_info.max, False, False
+
+    def say(self, text: str) -> None:
+        self.lines.append(text)
+
+    def path(self, name: str) -> str | None:
+        return None if self.out_dir is None else os.path.join(self.out_dir, name)
+
+    def write_table(self) -> None:
+        if self.out_dir is not None:
+            with open(self.path("table.txt"), "w") as f:
+                f.write("".join(l + "\n" for l in self.lines))
+
+    def save_phi(self, batch, name: str) -> None:
+        if self.out_dir is None:
+            return
+        e = self.cfg["central_difference"]
+        work = np.ascontiguousarray(batch.download_phi(self.slot)[e:-e, e:-e, e:-e])
+        tmp = self.path(name + ".tmp.npy")
+        np.save(tmp, work)
+        os.replace(tmp, self.path(name + ".npy"))
+
+    def takes_part(self, w: int) -> bool:
+        return not self.failed and self.cfg["wavenum"] <= w <= self.cfg["wavemax"]
+
+
+def _mask(runs, chosen) -> list:
+    on = {r.slot for r in chosen}
+    return [1 if r.slot in on else 0 for r in runs]
+
+
+def _norm_energy(o: dict) -> float:
+    return o["energy"] / o["norm2"] if o["norm2"] != 0.0 else math.nan
+
+
+def run_phase(batch, runs: list, w: int, progress: bool = False, push: bool = False, log=sys.stderr) -> None:
+    """State w of every run of `runs` (the batch's members in slot order) that takes part, from the starts already in the batch:
+    the loop of wafer_cli.cpp:666-753 per run, the batched calls shared as the module docstring says.  push: converged runs go to
+    their state stores (a batch that holds runs with excited states)."""
+    part = [r for r in runs if r.takes_part(w)]
+    for r in part:
+        r.step, r.remaining, r.last_energy, r.running, r.boundaries = 0, 0, sys.float_info.max, True, []
+        r.say(observable_header(w))
+    n = len(runs)
+
+    def finish(r, obs, converged, status):
+        r.running = False
+        r_norm = math.sqrt(obs["r2"] / obs["norm2"])
+        fin = dict(state=w, energy=obs["energy"] / obs["norm2"], binding_energy=(obs["energy"] - obs["v_infinity"]) / obs["norm2"],
+                   r=r_norm, l_r=r.cfg["nx"] / r_norm)
+        r.states.append(dict(state=w, status=status, steps=r.step, energy=fin["energy"]))
+        if converged:                                                     # output.rs:533-558
+            r.say(summary(fin))
+            if r.out_dir is not None:
+                with open(r.path(f"observables_{w}.json"), "w") as f:
+                    json.dump(fin, f, indent=2)
+                with open(r.path(f"observables_{w}.csv"), "w") as f:
+                    f.write("state,energy,binding_energy,r,l_r\n%d,%r,%r,%r,%r\n" % (w, fin["energy"], fin["binding_energy"], fin["r"], fin["l_r"]))
+                if r.cfg["snap_update"] is not None and os.path.exists(r.path(f"wavefunction_{w}_partial.npy")):
+                    os.remove(r.path(f"wavefunction_{w}_partial.npy"))
+        if r.cfg["save_wavefns"]:                                         # grid.rs:223-237: saved whether converged or not
+            r.save_phi(batch, f"wavefunction_{w}{'' if converged else '_partial'}")
+        if not converged:                                                 # grid.rs:243-245
+            print(f"run {r.index}: Error: MaxStep: maximum step limit reached for state {w}", file=log, flush=True)
+            r.failed = True
+        r.write_table()
+
+    while True:
+        running = [r for r in part if r.running]
+        if not running:
+            break
+        at = [r for r in running if r.remaining == 0]
+        if not at:                                                        # between boundaries: one evolve for every running run
+            d = next_chunk([r.remaining for r in running])
+            batch.evolve(d, active=_mask(runs, running), wnum=w)
+            for r in running:
+                r.step += d
+                r.remaining -= d
+            continue
+        for r in at:
+            r.boundaries.append(r.step)
+        obs = batch.observables()                                         # wafer_cli.cpp:671
+        finite = [r for r in at if math.isfinite(_norm_energy(obs[r.slot]))]
+        for r in at:
+            if r not in finite:
+                print(f"run {r.index}: Error: state {w}: energy is not finite at step {r.step}", file=log, flush=True)
+                r.running, r.failed = False, True
+                r.states.append(dict(state=w, status="NotFinite", steps=r.step, energy=None))
+                r.write_table()
+        at = finite
+        if not at:
+            continue
+        norm2s = [1.0] * n
+        for r in at:
+            norm2s[r.slot] = obs[r.slot]["norm2"]
+        batch.normalise(norm2s, active=_mask(runs, at))                   # :674
+        if w > 0:
+            batch.orthogonalise(w, active=_mask(runs, at))                # :675
+        clones = [r for r in at if r.cloned and r.step == 0]
+        if clones:                                                        # :676-692: a clone annihilated to exactly zero
+            n2 = batch.norm2()
+            for r in clones:
+                if not (n2[r.slot] > 0.0) or not math.isfinite(n2[r.slot]):
+                    print(f"run {r.index}: Warning: the clone of state {w - 1} was annihilated exactly by Gram-Schmidt; "
+                          f"starting state {w} from Gaussian noise instead.", file=log, flush=True)
+                    batch.set_initial_condition(r.slot, "Gaussian", seed=0x5EED + w)
+                    r.cloned, r.last_energy = False, sys.float_info.max
+                    r.boundaries.pop()
+                    at.remove(r)                                          # (it meets this boundary again, before any evolve)
+        snaps = [r for r in at if r.cfg["snap_update"] is not None and r.step % r.cfg["snap_update"] == 0]
+        if snaps:                                                         # :693-707
+            cons = ["NotConstrained"] * n
+            for r in snaps:
+                cons[r.slot] = r.cfg["init_symmetry"]
+            batch.symmetrise(cons, active=_mask(runs, snaps))             # grid.rs:138
+            for r in snaps:
+                r.save_phi(batch, f"wavefunction_{w}_partial")
+        done = []
+        for r in at:
+            o = obs[r.slot]
+            norm_energy = _norm_energy(o)
+            tau = r.step * r.cfg["dt"]
+            diff = abs(norm_energy - r.last_energy)                       # :708
+            if diff < r.cfg["tolerance"]:                                 # :710-714
+                r.say(measurement_row(tau, diff, o))
+                done.append(r)
+                continue
+            if progress:
+                r.say(measurement_row(tau, diff, o))
+            r.last_energy = norm_energy
+            if r.cfg["max_steps"] is not None and r.step > r.cfg["max_steps"]:   # :717
+                finish(r, o, False, "MaxStep")
+                continue
+            r.remaining = r.cfg["screen_update"]
+        for r in done:
+            finish(r, obs[r.slot], True, "Converged")
+        if push and done:
+            batch.push_state(active=_mask(runs, done))                    # grid.rs:241
+
+
+# ---- set-up ---------------------------------------------------------------------------------------------------------------------
+def _from_input(run: Run, stem: str, pad: int, shape, what: str):
+    a = staged_array(run.input_dir, stem, run.cfg["file_type"], pad, 0)
+    if a is not None and (a.dtype != np.float64 or tuple(a.shape) != tuple(shape)):
+        raise SystemExit(f"{run.config_path}: {what}: {stem} holds {tuple(a.shape)} {a.dtype}, this run needs {tuple(shape)} float64 "
+                         f"(the frame of {pad} cells included); resample it once with wafer-hip")
+    return a
+
+
+def set_up_member(batch, run: Run, par) -> None:
+    """potential, pot_sub override and the lower states from disk, as wafer_amd.run sets a context up"""
+    cfg, i, ext = run.cfg, run.slot, run.cfg["central_difference"]
+    if cfg["potential"] == "FromFile":                                    # potential.rs:80-86
+        v = _from_input(run, "potential", ext, par.padded_shape, "LoadPotential")
+        if v is None:
+            raise SystemExit(f"{run.config_path}: Error: LoadPotential: FileNotFound: {run.input_dir}/potential.*")
+        batch.set_potential_host(i, np.ascontiguousarray(v))
+    else:
+        batch.set_potential(i, cfg["potential"])
+    sub = staged_array(run.input_dir, "potential_sub", cfg["file_type"], 0, 0)   # potential.rs:113-131
+    if sub is not None:
+        variable = cfg["potential"] == "FullCornell"
+        if (sub.ndim == 0) == variable:
+            raise SystemExit(f"{run.config_path}: Error: WrongPotentialSubDims: potential_sub input file does not suit the potential type")
+        if sub.ndim == 0:
+            batch.set_potsub(i, 1, float(sub))
+        else:
+            if tuple(sub.shape) != par.work_shape:
+                raise SystemExit(f"{run.config_path}: potential_sub holds {tuple(sub.shape)}, the grid is {par.work_shape}; "
+                                 "resample it once with wafer-hip")
+            batch.set_potsub(i, 2, 0.0, np.ascontiguousarray(sub))
+    for w in range(cfg["wavenum"]):                                       # grid.rs:35-39: converged lower states from disk
+        st = _from_input(run, f"wavefunction_{w}", ext, par.padded_shape, f"LoadWavefunction({w})")
+        if st is None:
+            raise SystemExit(f"{run.config_path}: Error: LoadWavefunction({w}): FileNotFound: {run.input_dir}/wavefunction_{w}.*")
+        batch.load_state(i, w, np.ascontiguousarray(st))
+
+
+def start_phase(batch, runs: list, pars: list, w: int, seed: int) -> None:
+    """the start of state w for every run that takes part (grid.rs:60-100), then, for w = 0, one symmetrise with every run's
+    init_symmetry (config.rs:625)"""
+    part = [r for r in runs if r.takes_part(w)]
+    clones = []
+    for r in part:
+        ext, shape = r.cfg["central_difference"], pars[r.slot].padded_shape
+        r.cloned = False
+        start = _from_input(r, f"wavefunction_{w}", ext, shape, f"LoadWavefunction({w})")
+        if start is None:                                                 # input.rs:513-523
+            start = _from_input(r, f"wavefunction_{w}_partial", ext, shape, f"LoadWavefunction({w})")
+        if w > 0:
+            if start is not None:
+                batch.upload_phi(r.slot, np.ascontiguousarray(start))
+            else:                                                         # grid.rs:95
+                clones.append(r)
+                r.cloned = True
+        elif r.cfg["init_condition"] == "FromFile":
+            if start is None:
+                raise SystemExit(f"{r.config_path}: Error: SetInitialConditions: LoadWavefunction(0): FileNotFound: {r.input_dir}/wavefunction_0*.*")
+            batch.upload_phi(r.slot, np.ascontiguousarray(start))
+        else:                                                             # grid.rs:99, config.rs:577-627
+            batch.set_initial_condition(r.slot, r.cfg["init_condition"], seed=seed)
+    if clones:
+        batch.clone_state_to_phi(w - 1, active=_mask(runs, clones))
+    if w == 0 and part:
+        cons = ["NotConstrained"] * len(runs)
+        for r in part:
+            cons[r.slot] = r.cfg["init_symmetry"]
+        batch.symmetrise(cons, active=_mask(runs, part))
+
+
+def run_batch(plan: dict, runs: list, seed: int, progress: bool) -> tuple:
+    """one batch of the plan from creation to its last phase -> (fused passes, one-step launches)"""
+    import wafer_amd
+
+    pars = []
+    for slot, r in enumerate(runs):
+        r.slot = slot
+        c = r.cfg
+        pars.append(wafer_amd.Params(c["nx"], c["ny"], c["nz"], dn=c["dn"], dt=c["dt"], mass=c["mass"], sig=c["sig"],
+                                     central_difference=c["central_difference"], dtype=c["dtype"], max_states=c["wavemax"] + 1))
+    with wafer_amd.Batch(pars, mixed_shapes=plan["mixed_shapes"]) as batch:
+        for r in runs:
+            set_up_member(batch, r, pars[r.slot])
+        late = [r for r in runs if r.cfg["wavenum"] > 0]
+        if late:   # observables run over every member: a run that starts at a later state waits with its state 0 as phi
+            batch.clone_state_to_phi(0, active=_mask(runs, late))
+        for w in range(min(r.cfg["wavenum"] for r in runs), max(r.cfg["wavemax"] for r in runs) + 1):
+            start_phase(batch, runs, pars, w, seed)
+            run_phase(batch, runs, w, progress=progress, push=plan["needs_states"])
+        return batch.passes()
+
+
+# ---- command line ---------------------------------------------------------------------------------------------------------------
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m wafer_amd.sweep")
+    ap.add_argument("-c", "--config", action="append", required=True, help="a wafer.yaml; give it once per run")
+    ap.add_argument("--output-dir", default="./output")
+    ap.add_argument("--input-dir", default=None, help="one input directory for all runs (default: input/ next to each config file)")
+    ap.add_argument("--max-batch", type=int, default=DEFAULT_MAX_BATCH)
+    ap.add_argument("--seed", type=int, default=None, help="seed of Gaussian starts (default: the time)")
+    ap.add_argument("--progress", action="store_true", help="a table row per screen_update block in every table.txt")
+    ap.add_argument("--plan", action="store_true", help="print the grouping as JSON and exit; touches no GPU")
+    args = ap.parse_args(argv)
+    if args.max_batch < 1:
+        raise SystemExit("--max-batch must be >= 1")
+
+    cfgs = [load_config(p) for p in args.config]
+    for p, c in zip(args.config, cfgs):
+        if c["potential"] == "FromScript":
+            raise SystemExit(f"{p}: wafer_amd.sweep: script potentials are a single-GPU feature (wafer-hip -s); "
+                             "save the potential there and use potential: FromFile")
+        if c["init_symmetry"] != "NotConstrained" and c["central_difference"] != 3:
+            raise SystemExit(f"{p}: Error: init_symmetry {c['init_symmetry']} needs central_difference: SevenPoint "
+                             "(config.rs:702-725 indexes the 3-cell frame)")
+        if c["screen_update"] < 1:
+            raise SystemExit(f"{p}: a sweep needs screen_update >= 1")
+    plan = plan_batches(cfgs, args.max_batch)
+    if args.plan:
+        print(json.dumps(dict(configs=args.config, batches=plan)))
+        return 0
+
+    seed = int(time.time()) if args.seed is None else args.seed
+    print(f"seed of Gaussian starts: {seed}", file=sys.stderr, flush=True)
+    os.makedirs(args.output_dir, exist_ok=True)
+    stamp = time.strftime("%Y-%m-%d_%H:%M:%S")
+    runs = []
+    for i, (p, c) in enumerate(zip(args.config, cfgs)):
+        out_dir = os.path.join(args.output_dir, f"{i:03d}_{sanitize(c['project_name'])}_{stamp}")
+        os.makedirs(out_dir)
+        with open(p) as src, open(os.path.join(out_dir, os.path.basename(p)), "w") as dst:
+            dst.write(src.read())
+        runs.append(Run(i, c, p, args.input_dir or os.path.join(os.path.dirname(os.path.abspath(p)), "input"), out_dir))
+
+    t0 = time.perf_counter()
+    launches = []
+    for k, b in enumerate(plan):
+        members = [runs[i] for i in b["members"]]
+        for r in members:
+            r.batch = k
+        launches.append(run_batch(b, members, seed, args.progress))
+    ok = True
+    for r in runs:
+        asked = r.cfg["wavemax"] - r.cfg["wavenum"] + 1
+        converged = len(r.states) == asked and all(s["status"] == "Converged" for s in r.states)
+        ok = ok and converged
+        b = plan[r.batch]
+        print(json.dumps(dict(index=r.index, config=r.config_path, directory=r.out_dir, converged=converged, states=r.states, batch=r.batch,
+                              batch_members=b["members"], mixed_shapes=b["mixed_shapes"], fused_passes=launches[r.batch][0],
+                              single_steps=launches[r.batch][1])), flush=True)
+    print(f"Sweep complete. Elapsed time: {time.perf_counter() - t0:.3f} seconds.\nOutput directory: {args.output_dir}", flush=True)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
