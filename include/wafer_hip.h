@@ -248,10 +248,23 @@ int wafer_set_stencil_variant(wafer_ctx *ctx, int variant);
  * GB/s of read + written bytes.  MI355X_MICROARCH.md quotes ~6.3 TB/s for this pattern. */
 int wafer_diag_copy_bw(wafer_ctx *ctx, int iters, int unroll, int blocks_per_cu, double *gbps);
 
-/* Diagnostic: integer checksum (sum mod 2^64 of a hash of each cell's bits and its GLOBAL index) of the
- * work cells of global work planes [z_begin, z_begin + z_count) that this context owns.  Order
+/* Diagnostic: integer checksum of the current wavefunction's work cells on global work planes
+ * [z_begin, z_begin + z_count), a sum mod 2^64 of a hash of each cell's bits and its GLOBAL index.  Order
  * independent, so the checksums of the slabs of a decomposed run must equal those of the same plane
- * ranges of an undecomposed run whenever the bits agree: bench.py's N > 1 parity check. */
+ * ranges of an undecomposed run whenever the bits agree: bench.py's N > 1 parity check.
+ *
+ * The definition, all arithmetic in unsigned 64 bits (mod 2^64), so that any host can restate it
+ * (tests/checksum_model.py does, in numpy):
+ *   h(z):  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  return z ^ (z >> 31)
+ *   lin  = (k * ny + y) * nx + x        for the work cell (x, y, k): x in [0, nx), y in [0, ny), k the GLOBAL work plane
+ *   term = h(bits ^ h(lin + 0x9e3779b97f4a7c15))
+ *   *out = the sum of term over the cells counted
+ * bits: the 64 bits of the stored double (dtype f64); the 32 bits of the stored float, zero-extended to 64 (dtypes
+ * f32 and f32fast).  No bit is canonicalised: 0.0 and -0.0, and two NaNs of different payloads, give different terms.
+ * Cells counted: the work cells of the planes k that lie in the range AND are owned by this context
+ * (z_begin <= k < z_begin + z_count of its wafer_params).  Frame cells and ghost planes never count.  The range
+ * is clipped to the grid's planes [0, nz): what reaches past nz is ignored, and a range with z_count = 0
+ * or z_begin >= nz -- or one that misses the slab -- gives 0. */
 int wafer_diag_checksum(wafer_ctx *ctx, uint32_t z_begin, uint32_t z_count, uint64_t *out);
 
 /* Diagnostic: global padded planes [zp_begin, zp_begin + zp_count) of one device array in the reference's layout,

@@ -814,8 +814,6 @@ int wafer_diag_copy_bw(wafer_ctx *c, int iters, int unroll, int blocks_per_cu, d
     return WAFER_OK;
 }
 
-// position-dependent integer checksum of the work cells of global work planes [z_begin, z_begin + z_count)
-// that this context owns (wafer_k_checksum): equal for equal bits, whatever the decomposition
 int wafer_diag_x2_passes(wafer_ctx *c, uint64_t *out)
 {
     if (!c || !out) return fail(WAFER_ERR_INVALID, "null argument");
@@ -823,6 +821,9 @@ int wafer_diag_x2_passes(wafer_ctx *c, uint64_t *out)
     return WAFER_OK;
 }
 
+// position-dependent integer checksum of the work cells of global work planes [z_begin, z_begin + z_count)
+// that this context owns (wafer_k_checksum; the sum is defined in include/wafer_hip.h): equal for equal bits, whatever the
+// decomposition
 int wafer_diag_checksum(wafer_ctx *c, uint32_t z_begin, uint32_t z_count, uint64_t *out)
 {
     if (!c || !out) return fail(WAFER_ERR_INVALID, "null argument");
@@ -835,7 +836,10 @@ int wafer_diag_checksum(wafer_ctx *c, uint32_t z_begin, uint32_t z_count, uint64
     ra.g = c->g;
     ra.lz_lo = c->g.G;
     ra.lz_hi = c->g.G + c->g.nzl;
-    const int lo = (int)z_begin, hi = (int)std::min<uint64_t>((uint64_t)z_begin + z_count, (uint64_t)c->g.nz);
+    // both ends clipped to the grid in 64 bits: (int)z_begin of a z_begin >= 2^31 is a negative plane, and the kernel's own clip
+    // to the owned planes then let the whole slab through
+    const int lo = (int)std::min<uint64_t>((uint64_t)z_begin, (uint64_t)c->g.nz);
+    const int hi = (int)std::min<uint64_t>((uint64_t)z_begin + z_count, (uint64_t)c->g.nz);
     if (c->f32)
         hipLaunchKernelGGL((wafer_k_checksum<float>), dim3(c->num_cus * 8), dim3(256), 0, c->s_main, ra, as<float>(c->phi[c->cur]), lo, hi, d);
     else
