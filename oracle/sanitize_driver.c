@@ -49,6 +49,13 @@ static int run_case(int64_t nx, int64_t ny, int64_t nz, int ext, int potential)
     wo_evolve(&c, 0, a, b, phi, NULL, 3);
     wo_observables_t obs;
     wo_observables(&c, v, kind, scalar, kind == 2 ? potsub : NULL, phi, &obs);
+    /* the per-cell terms, into four arrays of exactly the work size; every pot_sub form on every grid */
+    double *cells[4] = {alloc(nw), alloc(nw), alloc(nw), alloc(nw)};
+    wo_observables_cells(&c, v, kind, scalar, kind == 2 ? potsub : NULL, phi, cells[0], cells[1], cells[2], cells[3]);
+    wo_observables_cells(&c, v, 0, 0.0, NULL, phi, cells[0], cells[1], cells[2], cells[3]);
+    wo_observables_cells(&c, v, 1, 0.75, NULL, phi, cells[0], cells[1], cells[2], cells[3]);
+    wo_observables_cells(&c, v, 2, 0.0, potsub, phi, cells[0], cells[1], cells[2], cells[3]);
+    for (int q = 0; q < 4; ++q) free(cells[q]);
     for (int wnum = 1; wnum <= 3; ++wnum) wo_evolve(&c, wnum, a, b, phi, (const double *const *)low, 2);
     if (ext == 3)
         for (int sym = 0; sym <= 4; ++sym) wo_symmetrise(&c, sym, phi);

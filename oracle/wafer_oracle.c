@@ -625,14 +625,61 @@ void wo_evolve(const wo_config *c, int wnum, const double *a, const double *b, d
     free(work);
 }
 
+/* The four per-cell terms of grid.rs:303-445 at work cell (i, j, k): the ONE text of the integrand.  wo_observables sums
+ * what this returns and wo_observables_cells stores it, so the arrays a test reads are the terms the sums are made of. */
+typedef struct {
+    double energy, norm2, v_infinity, r2;
+} wo_cell_terms;
+
+static inline wo_cell_terms observables_cell(wo_dims d, double den, const double *v, int potsub_kind,
+                                             double potsub_scalar, const double *potsub, const double *phi,
+                                             int64_t i, int64_t j, int64_t k)
+{
+    const size_t sy = (size_t)d.pz, sx = (size_t)d.py * (size_t)d.pz;
+    const size_t p = PIDX(d, i + d.e, j + d.e, k + d.e);
+    const double w = phi[p];
+    const double vv = v[p];
+    wo_cell_terms t;
+    /* :325-332: v*w*w - w*S/denominator */
+    t.energy = vv * w * w - w * stencil_sum(phi, p, sx, sy, (int)d.e, w) / den;
+    t.norm2 = w * w;       /* :407 */
+    if (potsub_kind == 2)  /* :410-418, unpadded array */
+        t.v_infinity = w * w * potsub[WIDX(d, i, j, k)];
+    else if (potsub_kind == 1) /* :419-424 */
+        t.v_infinity = w * w * potsub_scalar;
+    else
+        t.v_infinity = 0.;
+    /* :428-437: r2 from the WORK-AREA index */
+    t.r2 = w * w * wo_calculate_r2(i, j, k, d.nx, d.ny, d.nz);
+    return t;
+}
+
+/* the terms themselves, as four work-shaped arrays [nx][ny][nz] (v_infinity: zeros without a pot_sub) */
+void wo_observables_cells(const wo_config *c, const double *v, int potsub_kind, double potsub_scalar,
+                          const double *potsub, const double *phi, double *energy, double *norm2,
+                          double *v_infinity, double *r2)
+{
+    wo_dims d = dims_of(c);
+    const double den = stencil_denominator(c);
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < d.nx; ++i)
+        for (int64_t j = 0; j < d.ny; ++j)
+            for (int64_t k = 0; k < d.nz; ++k) {
+                const wo_cell_terms t = observables_cell(d, den, v, potsub_kind, potsub_scalar, potsub, phi, i, j, k);
+                const size_t q = WIDX(d, i, j, k);
+                energy[q] = t.energy;
+                norm2[q] = t.norm2;
+                v_infinity[q] = t.v_infinity;
+                r2[q] = t.r2;
+            }
+}
+
 /* grid.rs:303-445 */
 void wo_observables(const wo_config *c, const double *v, int potsub_kind, double potsub_scalar,
                     const double *potsub, const double *phi, wo_observables_t *out)
 {
     wo_dims d = dims_of(c);
     const double den = stencil_denominator(c);
-    const size_t sy = (size_t)d.pz, sx = (size_t)d.py * (size_t)d.pz;
-    const int ext = c->ext;
     long double *pe = (long double *)malloc(sizeof(long double) * 4 * (size_t)d.nx);
     long double *pn = pe + d.nx, *pv = pn + d.nx, *pr = pv + d.nx;
 #pragma omp parallel for schedule(static)
@@ -640,19 +687,11 @@ void wo_observables(const wo_config *c, const double *v, int potsub_kind, double
         long double se = 0.0L, sn = 0.0L, sv = 0.0L, sr = 0.0L;
         for (int64_t j = 0; j < d.ny; ++j)
             for (int64_t k = 0; k < d.nz; ++k) {
-                size_t p = PIDX(d, i + d.e, j + d.e, k + d.e);
-                double w = phi[p];
-                double vv = v[p];
-                /* :325-332: v*w*w - w*S/denominator */
-                double e = vv * w * w - w * stencil_sum(phi, p, sx, sy, ext, w) / den;
-                se += (long double)e;
-                sn += (long double)(w * w); /* :407 */
-                if (potsub_kind == 2)       /* :410-418, unpadded array */
-                    sv += (long double)(w * w * potsub[WIDX(d, i, j, k)]);
-                else if (potsub_kind == 1) /* :419-424 */
-                    sv += (long double)(w * w * potsub_scalar);
-                /* :428-437: r2 from the WORK-AREA index */
-                sr += (long double)(w * w * wo_calculate_r2(i, j, k, d.nx, d.ny, d.nz));
+                const wo_cell_terms t = observables_cell(d, den, v, potsub_kind, potsub_scalar, potsub, phi, i, j, k);
+                se += (long double)t.energy;
+                sn += (long double)t.norm2;
+                if (potsub_kind != 0) sv += (long double)t.v_infinity;
+                sr += (long double)t.r2;
             }
         pe[i] = se;
         pn[i] = sn;

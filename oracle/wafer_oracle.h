@@ -108,6 +108,11 @@ int wo_symmetrise(const wo_config *c, int kind, double *phi);
 /* grid.rs:303-445; potsub_kind/scalar/array as wo_potential_sub */
 void wo_observables(const wo_config *c, const double *v, int potsub_kind, double potsub_scalar,
                     const double *potsub, const double *phi, wo_observables_t *out);
+/* the per-cell terms whose sums wo_observables returns (it takes them from the same code): four work-shaped arrays
+ * [nx][ny][nz]; v_infinity is all zeros for potsub_kind 0 */
+void wo_observables_cells(const wo_config *c, const double *v, int potsub_kind, double potsub_scalar,
+                          const double *potsub, const double *phi, double *energy, double *norm2,
+                          double *v_infinity, double *r2);
 /* grid.rs:544-687, same pass structure (stencil into work, copy back, and for
  * wnum>0 norm2 / normalise / Gram-Schmidt every step). */
 void wo_evolve(const wo_config *c, int wnum, const double *a, const double *b, double *phi,

@@ -117,6 +117,8 @@ def _bind(L):
         L.wo_symmetrise.argtypes = [cp, C.c_int, dp]
         L.wo_observables.restype = None
         L.wo_observables.argtypes = [cp, dp, C.c_int, C.c_double, dp, dp, C.POINTER(_Obs)]
+        L.wo_observables_cells.restype = None
+        L.wo_observables_cells.argtypes = [cp, dp, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp]
         L.wo_evolve.restype = None
         L.wo_evolve.argtypes = [cp, C.c_int, dp, dp, dp, C.POINTER(dp), C.c_uint64]
         L.wo_stencil_step.restype = None
@@ -284,6 +286,16 @@ def observables(cfg: Config, v, phi, potsub=(0, 0.0, None)):
     lib().wo_observables(C.byref(c), _dp(v), kind, scalar, _dp(arr) if arr is not None else None,
                          _dp(phi), C.byref(o))
     return dict(energy=o.energy, norm2=o.norm2, v_infinity=o.v_infinity, r2=o.r2)
+
+
+def observables_cells(cfg: Config, v, phi, potsub=(0, 0.0, None)) -> dict:
+    """the per-cell terms wo_observables sums (one code for both): four arrays of the work shape"""
+    c = cfg.c()
+    kind, scalar, arr = potsub
+    out = {k: np.zeros(cfg.work_shape) for k in ("energy", "norm2", "v_infinity", "r2")}
+    lib().wo_observables_cells(C.byref(c), _dp(v), kind, scalar, _dp(arr) if arr is not None else None, _dp(phi),
+                               _dp(out["energy"]), _dp(out["norm2"]), _dp(out["v_infinity"]), _dp(out["r2"]))
+    return out
 
 
 def evolve(cfg: Config, wnum: int, a, b, phi, w_store, steps: int) -> None:
