@@ -205,6 +205,7 @@ extern "C" {
     pub fn wafer_batch_create(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
     /// as `wafer_batch_create`, but nx, ny, nz may differ from member to member (ground-state calls; see wafer_hip.h)
     pub fn wafer_batch_create_mixed(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
+    pub fn wafer_batch_create_mixed_states(members: *const wafer_params, n_members: u32, out: *mut *mut wafer_batch) -> c_int;
     /// number of distinct (nx, ny, nz) among the members
     pub fn wafer_batch_num_shapes(b: *mut wafer_batch, n_shapes: *mut u32) -> c_int;
     pub fn wafer_batch_destroy(b: *mut wafer_batch) -> c_int;

@@ -496,12 +496,32 @@ int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_ba
  *  - the calls that need the state stores return WAFER_ERR_INVALID with a message that contains "mixed-shape" and names the call,
  *    and change nothing: wafer_batch_load_state, _download_state, _push_state, _clear_states, _clone_state_to_phi, _orthogonalise,
  *    _evolve_state with wnum > 0, _solve_state with any wnum, and wafer_batch_set_gs_variant(b, 1).  (Excited states on several
- *    shapes are not built yet.)  wafer_batch_evolve_state(.., 0, ..) is wafer_batch_evolve, wafer_batch_num_states gives zeros,
- *    wafer_batch_diag_gs still answers.
+ *    shapes: create the batch with wafer_batch_create_mixed_states, below.)  wafer_batch_evolve_state(.., 0, ..) is
+ *    wafer_batch_evolve, wafer_batch_num_states gives zeros, wafer_batch_diag_gs still answers.
  *  - wafer_batch_diag_dispatch: kernel= names the instantiation actually launched, which reads its geometry from the batch's device
  *    table -- wafer_k_batch_step<R,T,C,WaferBatchGeomTable> / wafer_k_batch_stepk<R,K,T,C,WaferBatchGeomTable> -- and the line ends
  *    with " shapes=N".  wafer_batch_kernel_name gives that one-step instantiation's name. */
 int wafer_batch_create_mixed(const wafer_params *members, uint32_t n_members, wafer_batch **out);
+/* Mixed-shape batches WITH state stores (opt-in at creation).  Member rules, messages, layout and everything of the ground-state
+ * path are wafer_batch_create_mixed's; with one distinct shape the batch is a plain batch in every call and gives the same
+ * wafer_batch_diag_dispatch line.  With several shapes NO call is refused: wafer_batch_load_state, _download_state, _push_state,
+ * _clear_states, _clone_state_to_phi, _num_states, _orthogonalise, _norm2, _evolve_state with wnum > 0, _solve_state with any wnum
+ * and wafer_batch_set_gs_variant(b, 0 | 1 | -1) all work (wnum is one number per call; max_states stays per member).  A store slot
+ * is one allocation laid out as the arrays are.
+ *  - bits: a member's phi, stored states and norm2 after any of these calls are bit for bit what the same member gets in a batch
+ *    of ITS shape made by wafer_batch_create, under the same gs_variant, in the sequential and in the one-pass form, on every
+ *    dtype: its Gram-Schmidt partition (tiles of 64 x 4 work cells x 4 planes) and the order of its sums are fixed by its shape
+ *    alone.  So everything promised there holds here: WAFER_F64 within 1e-13 per cell of the oracle and of a wafer_ctx, norm2
+ *    rel 1e-12; no floating-point atomics; no host synchronisation between steps; frozen members and every stored state untouched
+ *    bit for bit; no dependence on B, the member's index, the other members' shapes or the active set.
+ *  - launches: one excited step is 1 + 2 (1 + wnum) + 1 launches for all members of all shapes, 4 under the one-pass form, the
+ *    Gram refresh one launch plus one reduce -- never one set per shape: the grid is (the largest launched member's workgroups,
+ *    launched members) and the workgroups beyond a smaller member's partition leave at once.
+ *  - wafer_batch_solve_state: per-member records, finals, statuses and pushes as in a batch of one shape; a short or a full
+ *    store is that member's status, not the call's.
+ *  - wafer_batch_diag_gs names the table-reading instantiations in kernels= (..,WaferBatchGsArgsMixed> /
+ *    ..,WaferBatchGsOneArgsMixed>) and ends with " shapes=N". */
+int wafer_batch_create_mixed_states(const wafer_params *members, uint32_t n_members, wafer_batch **out);
 /* number of distinct (nx, ny, nz) among the members */
 int wafer_batch_num_shapes(wafer_batch *b, uint32_t *n_shapes);
 int wafer_batch_destroy(wafer_batch *b);

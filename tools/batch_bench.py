@@ -24,7 +24,11 @@ call ran in each form ("gs_onepass_steps", "gs_sequential_steps").
 --mixed "64,50,37x50x23": one line per B instead -- the members cycle through these shapes (N is N x N x N) in ONE mixed-shape batch
 (Batch(members, mixed_shapes=True)), timed as above ("mixed_*"), and the same members run as one uniform batch per shape, one
 batch after another ("uniform": a row per shape; "uniform_sum_*": their times added).  "ratio_host" / "ratio_events": the uniform
-batches' summed time over the mixed batch's; "parity": every member's phi bit-identical in both."""
+batches' summed time over the mixed batch's; "parity": every member's phi bit-identical in both.
+With --wnum K (and --gs-variant V) the --mixed line times excited-state steps: the mixed batch is made with state stores
+(Batch(members, mixed_shapes=True, state_stores=True)), every member gets an orthonormal store of K states, both sides run
+evolve(steps, wnum=K) under the same gs variant; the same "ratio_*" and "parity" fields, plus "wnum", "gs_variant", the mixed batch's
+gs_dispatch line and the excited steps each form ran."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -144,20 +148,27 @@ def parse_shapes(text):
     return out
 
 
-def timed_batch(pars, steps, warmup, variant, mixed):
-    """-> (timings, [phi of every member]) of one batch of these members after warmup + steps ground-state steps"""
+def timed_batch(pars, steps, warmup, variant, mixed, wnum=0, gs_variant=-1, stores=None):
+    """-> (timings, [phi of every member]) of one batch of these members after warmup + steps steps (wnum > 0: excited-state steps
+    against stores[k], member k's orthonormal states; a mixed batch is then made with state stores)"""
     cells = sum(p.nx * p.ny * p.nz for p in pars)
-    with wafer_amd.Batch(pars, mixed_shapes=mixed) as b:
+    kind = dict(mixed_shapes=True, state_stores=True) if mixed and wnum else dict(mixed_shapes=mixed)
+    with wafer_amd.Batch(pars, **kind) as b:
         for k in range(len(pars)):
             b.set_potential(k, "Harmonic")
             b.set_initial_condition(k, "Gaussian")
+            for i in range(wnum):
+                b.load_state(k, i, stores[k][i])
         b.set_step_variant(variant)
         out = {"B": len(pars), "dispatch": b.dispatch(), "shapes": b.num_shapes()}
-        b.evolve(warmup)
+        if wnum:
+            b.set_gs_variant(gs_variant)
+            out["gs_dispatch"] = b.gs_dispatch(wnum)
+        b.evolve(warmup, wnum=wnum)
         b.last_evolve_ms()
-        p0 = b.passes()
+        p0, g0 = b.passes(), b.gs_steps()
         t0 = time.perf_counter()
-        b.evolve(steps)
+        b.evolve(steps, wnum=wnum)
         ms, st = b.last_evolve_ms()
         t = time.perf_counter() - t0
         out["host_us_per_step"] = 1e6 * t / steps
@@ -165,22 +176,30 @@ def timed_batch(pars, steps, warmup, variant, mixed):
         out["us_per_step"] = 1e3 * ms / st
         out["gups"] = cells * st / (ms * 1e-3) / 1e9
         out["fused_passes"], out["single_steps"] = [x - y for x, y in zip(b.passes(), p0)]
+        if wnum:
+            out["gs_onepass_steps"], out["gs_sequential_steps"] = [x - y for x, y in zip(b.gs_steps(), g0)]
         return out, [b.download_phi(k) for k in range(len(pars))]
 
 
-def mixed_row(shapes, B, steps, warmup, variant=-1, ext=1, dtype="f64"):
+def mixed_row(shapes, B, steps, warmup, variant=-1, ext=1, dtype="f64", wnum=0, gs_variant=-1):
     pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype)
             for k in range(B)]
     out = {"mixed": [list(s) for s in shapes], "B": B, "steps": steps, "warmup": warmup, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1],
            "dtype": dtype, "potential": "Harmonic", "variant": variant}
-    m, phis = timed_batch(pars, steps, warmup, variant, True)
+    stores = None
+    if wnum:
+        out["wnum"], out["gs_variant"] = wnum, gs_variant
+        per_shape = {s: [store(pars[shapes.index(s)], wnum, seed=j) for j in range(2)] for s in dict.fromkeys(shapes)}   # (two stores per shape, shared out)
+        stores = [per_shape[shapes[k % len(shapes)]][(k // len(shapes)) % 2] for k in range(B)]
+    m, phis = timed_batch(pars, steps, warmup, variant, True, wnum, gs_variant, stores)
     out.update({"mixed_" + k: v for k, v in m.items() if k != "B"})
     out["uniform"], parity = [], True
     for s in dict.fromkeys(shapes):   # one uniform batch per distinct shape, one after another
         idx = [k for k in range(B) if shapes[k % len(shapes)] == s]
         if not idx:
             continue
-        u, uphis = timed_batch([pars[k] for k in idx], steps, warmup, variant, False)
+        u, uphis = timed_batch([pars[k] for k in idx], steps, warmup, variant, False, wnum, gs_variant, stores and [stores[k] for k in idx])
+        u.pop("gs_dispatch", None)
         u["shape"] = list(s)
         u["dispatch"] = u["dispatch"]["kernel"]
         out["uniform"].append(u)
@@ -216,11 +235,12 @@ def main():
     ap.add_argument("--gs-variant", type=int, choices=[-1, 0, 1], default=-1,
                     help="Batch.set_gs_variant: -1 default dispatch, 0 the sequential chain, 1 the one-pass form (wnum <= 4)")
     ap.add_argument("--mixed", metavar="SHAPES", help='e.g. "64,50,37x50x23": the members cycle through these shapes in one mixed-shape batch, compared '
-                    "with one uniform batch per shape run one after another (ground state; --sizes, --wnum and --only-batch do not apply)")
+                    "with one uniform batch per shape run one after another (--wnum, --gs-variant: excited-state steps, the mixed batch with state stores; "
+                    "--sizes and --only-batch do not apply)")
     a = ap.parse_args()
     if a.mixed:
         for B in a.batch:
-            line = json.dumps(rounded(mixed_row(parse_shapes(a.mixed), B, a.steps, a.warmup, a.variant, a.ext, a.dtype)))
+            line = json.dumps(rounded(mixed_row(parse_shapes(a.mixed), B, a.steps, a.warmup, a.variant, a.ext, a.dtype, a.wnum, a.gs_variant)))
             print(line, flush=True)
             if a.out:
                 with open(a.out, "a") as f:

@@ -1,6 +1,7 @@
 // wafer_batch_plan.h -- the host-side plan of a batched ground-state evolve (wafer_engine_batch.hip): which passes a call of
 // `steps` steps launches, the workgroup table of the one-step kernel (wafer_k_batch_step) and the one of the fused K-step pass
-// (wafer_k_batch_stepk, wafer_stencil_batch.hip.h), and the batch's layout (its distinct shapes, every member's offset).
+// (wafer_k_batch_stepk, wafer_stencil_batch.hip.h), the batch's layout (its distinct shapes, every member's offset), and every
+// member's partition under the excited-state kernels with the places of its partials (wafer_batch_gs_partition).
 // Plain C++ with no HIP in it, so the host compiler and the sanitizers can run it (tests/test_batch_plan.py).
 #pragma once
 #include <stddef.h>
@@ -205,4 +206,39 @@ static inline WaferBatchLayout wafer_batch_layout(const int *nxyz, uint32_t n_me
         L.overflow = __builtin_add_overflow(L.cells, (size_t)L.geoms[k].total, &L.cells) || __builtin_mul_overflow(L.cells, esz, &bytes);
     }
     return L;
+}
+
+// ---- the Gram-Schmidt partition ----------------------------------------------------------------------------------------------
+// Workgroups of a member under the excited-state kernels (wafer_gs_batch.hip.h): tiles of tx x ty work cells (64 x 4), chunks of zc
+// planes (WAFER_GS_ZC).  Fixed by the shape alone.
+static inline int wafer_gs_blocks_of(const WaferGeom &g, int tx, int ty, int zc)
+{
+    return ((g.nx + tx - 1) / tx) * ((g.ny + ty - 1) / ty) * ((g.nzl + zc - 1) / zc);
+}
+
+// Every member's partition of the excited-state kernels and the places of its partials, one shape or several.  A kernel that
+// writes `rows` sums per workgroup (1: the chain; WAFER_GS_ONE_ROWS: the one-pass form's sums; WAFER_GRAM_PAIRS: the Gram kernel)
+// keeps member m's rows end to end from row_off(m, rows) on: row q, workgroup w at row_off(m, rows) + q * nb[m] + w.  first[m] is
+// the sum of nb over the members before m, so no two members' rows overlap whatever `rows`, and with one shape the layout is
+// the one the one-shape kernels index: row_off(m, rows) == m * rows * nb.
+struct WaferBatchGsPartition {
+    std::vector<int> nb;            // member m's workgroups: wafer_gs_blocks_of its shape
+    std::vector<long long> first;   // the workgroups of the members before it
+    long long blocks = 0;           // of all members
+    int max_nb = 0;                 // the widest member's
+    long long row_off(uint32_t m, int rows) const { return first[m] * rows; }
+    long long doubles(int rows) const { return blocks * rows; }   // the whole partials buffer of such a kernel
+};
+
+static inline WaferBatchGsPartition wafer_batch_gs_partition(const WaferGeom *geoms, const int *shape_of, uint32_t n_members, int tx, int ty, int zc)
+{
+    WaferBatchGsPartition P;
+    for (uint32_t m = 0; m < n_members; ++m) {
+        const int nb = wafer_gs_blocks_of(geoms[shape_of[m]], tx, ty, zc);
+        P.nb.push_back(nb);
+        P.first.push_back(P.blocks);
+        P.blocks += nb;
+        if (nb > P.max_nb) P.max_nb = nb;
+    }
+    return P;
 }

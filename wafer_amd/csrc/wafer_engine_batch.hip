@@ -24,8 +24,11 @@
 // A batch of one shape (wafer_batch_create, or wafer_batch_create_mixed with equal shapes) is the case geoms.size() == 1 of all this:
 // off[m] == m * geoms[0].total, every member's partition is the same, and the widest is everyone's.  The one thing that differs is
 // where the kernels read the geometry from (with_geom, the one place that chooses): a kernel argument for one shape, the device
-// table for several -- the same kernel templates instantiated for either source (wafer_tu_batch.inc).  The state stores have no
-// layout for several shapes yet, so the excited-state calls are refused there (refuse_mixed).
+// table for several -- the same kernel templates instantiated for either source (wafer_tu_batch.inc, wafer_tu_gs_batch.inc).
+// State stores on several shapes are opt-in at creation (wafer_batch_create_mixed_states: `mixed_states`): a slot is one allocation
+// laid out as the arrays are, and every member's Gram-Schmidt partition and the places of its partials come from
+// wafer_batch_gs_partition (wafer_batch_plan.h; `gsp`, and in its WaferBatchMember).  A batch of several shapes made by
+// wafer_batch_create_mixed refuses the excited-state calls as it always has (refuse_mixed).
 #include <memory>
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
@@ -46,6 +49,8 @@ struct wafer_batch {
     size_t cells = 0;                         // elements of each array allocation: every member's total, end to end
     WaferGeom *geoms_dev = nullptr;
     bool mixed = false;
+    bool mixed_states = false;                // several shapes WITH state stores (wafer_batch_create_mixed_states)
+    WaferBatchGsPartition gsp;                // every member's Gram-Schmidt partition (one shape: gs_nb workgroups each)
     const WaferGeom &g() const { return geoms[0]; }               // what every shape shares (R, G), and THE geometry of one shape
     const WaferGeom &geom(uint32_t m) const { return geoms[shape_of[m]]; }
     std::string kernel_name = "wafer_k_batch_step";
@@ -166,7 +171,7 @@ int check_member_index(const wafer_batch *b, uint32_t m)
 // the calls that need the state stores: not on a batch of several shapes; nothing has changed when this returns
 int refuse_mixed(const wafer_batch *b, const char *call)
 {
-    if (!b->mixed) return WAFER_OK;
+    if (!b->mixed || b->mixed_states) return WAFER_OK;
     return fail(WAFER_ERR_INVALID, "%s: not available on a mixed-shape batch (%zu distinct shapes): excited states need one shape per batch",
                 call, b->geoms.size());
 }
@@ -370,6 +375,10 @@ void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
     return static_cast<char *>(b->slots[l]) + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
 }
 
+// what the excited-state kernels take for slot l: member 0's logical pointer on one shape (they add member * mstride), the
+// allocation itself on several (they add WaferBatchMember::slot_off)
+const void *slot_arg(const wafer_batch *b, uint32_t l) { return b->mixed ? b->slots[l] : slot_ptr(b, l, 0); }
+
 // slots [0, n) exist (zeros: frames, pads and guard zones of every member)
 int ensure_slots(wafer_batch *b, uint32_t n)
 {
@@ -417,12 +426,21 @@ int push_states(wafer_batch *b, const uint8_t *active)
 }
 
 // ---- excited states --------------------------------------------------------------------------------------------------------
+// doubles of gs_partials under the sequential form
+size_t chain_partials_doubles(const wafer_batch *b)
+{
+    if (!b->mixed) return (size_t)std::max(b->gs_nb, b->n2_nb) * b->n;
+    const size_t n2 = (size_t)(b->mem[b->n - 1].n2_off + b->mem[b->n - 1].n2_nb);   // every member's own norm2 partition, end to end
+    // with state stores the chain's partition too: on float storage the two differ (the row walk's and the 64 x 4 x 4 tiles'), each
+    // with its own offsets from 0 (n2_off, gs_off), written and reduced by different calls in stream order
+    return b->mixed_states ? std::max(n2, (size_t)b->gsp.doubles(1)) : n2;
+}
+
 int ensure_gs(wafer_batch *b)
 {
     if (b->gs_scal) return WAFER_OK;
     const size_t nsc = (size_t)b->gs_stride * b->n;
-    size_t npart = (size_t)std::max(b->gs_nb, b->n2_nb) * b->n;
-    if (b->mixed) npart = (size_t)(b->mem[b->n - 1].n2_off + b->mem[b->n - 1].n2_nb);   // every member's own norm2 partition, end to end
+    const size_t npart = chain_partials_doubles(b);
     HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * npart));
     HIP_TRY(hipHostMalloc((void **)&b->gs_host, sizeof(double) * nsc, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->gs_scal, sizeof(double) * nsc));
@@ -430,13 +448,14 @@ int ensure_gs(wafer_batch *b)
     return WAFER_OK;
 }
 
-// what the chain's and the one-pass form's kernel arguments (A) share: the one geometry, its 64 x 4 tiles, and the member stride of
-// the store slots (one shape: these calls are refused on several)
+// what the chain's and the one-pass form's kernel arguments share.  One shape (A: WaferBatchGsArgs, WaferBatchGsOneArgs): the one
+// geometry, its 64 x 4 tiles, and the member stride of the store slots.  Several (the ...Mixed types): the device table; the rest
+// is in the member records.
 template <typename A>
-A gs_args(const wafer_batch *b, int flip)
+A gs_args(const wafer_batch *b, const WaferGeom &g, int flip)
 {
     A a;
-    a.g = b->g();
+    a.g = g;
     a.ntx = (a.g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
     a.nty = (a.g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
     a.flip = flip;
@@ -444,15 +463,38 @@ A gs_args(const wafer_batch *b, int flip)
     a.mstride = a.g.total;
     return a;
 }
+template <typename A>
+A gs_args(const wafer_batch *b, const WaferBatchGeomTable &gt, int flip)
+{
+    A a;
+    memset(&a, 0, sizeof a);
+    a.geoms = gt.geoms;
+    a.flip = flip;
+    a.scal_stride = b->gs_stride;
+    return a;
+}
+WaferBatchGsArgs chain_args(const wafer_batch *b, const WaferGeom &g, int flip) { return gs_args<WaferBatchGsArgs>(b, g, flip); }
+WaferBatchGsArgsMixed chain_args(const wafer_batch *b, const WaferBatchGeomTable &gt, int flip) { return gs_args<WaferBatchGsArgsMixed>(b, gt, flip); }
+
+// the grid's extent along x: the largest partition among the members in list (one shape: everyone's)
+int gs_max_nb(const wafer_batch *b, const int *list, int n)
+{
+    int nb = 0;
+    for (int k = 0; k < n; ++k) nb = std::max(nb, b->gsp.nb[list[k]]);
+    return nb;
+}
 
 // one elementwise launch (+ its reduce into slot out_slot) over the members in act_dev; lower, dotwith: store slots, -1 none
 int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int lower, int dotwith, int out_slot)
 {
-    WaferBatchGsArgs a = gs_args<WaferBatchGsArgs>(b, flip);
-    a.coef_slot = coef_slot;
-    a.lower = lower >= 0 ? slot_ptr(b, (uint32_t)lower, 0) : nullptr;
-    a.dotwith = dotwith >= 0 ? slot_ptr(b, (uint32_t)dotwith, 0) : nullptr;
-    const hipError_t e = wafer_entry_batch_gs(b->f32, mode, a, b->mem_dev, b->act_dev, nact, b->gs_scal, out_slot, b->gs_partials, b->s);
+    const int max_nb = gs_max_nb(b, b->act_host, nact);
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        auto a = chain_args(b, gs, flip);
+        a.coef_slot = coef_slot;
+        a.lower = lower >= 0 ? slot_arg(b, (uint32_t)lower) : nullptr;
+        a.dotwith = dotwith >= 0 ? slot_arg(b, (uint32_t)dotwith) : nullptr;
+        return wafer_entry_batch_gs(b->f32, mode, a, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, out_slot, b->gs_partials, b->s);
+    });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram-Schmidt launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -464,6 +506,8 @@ bool use_onepass(const wafer_batch *b, uint32_t wnum) { return b->gs_variant == 
 // bytes of gs_partials under the one-pass form: WAFER_GS_ONE_ROWS rows per member (or the float norm2's partition, if wider)
 size_t onepass_partials_bytes(const wafer_batch *b)
 {
+    if (b->mixed)   // every member's own rows end to end; the row walk's partials (float storage) lie in the same buffer from 0 on
+        return sizeof(double) * std::max((size_t)b->gsp.doubles(WAFER_GS_ONE_ROWS), (size_t)(b->mem[b->n - 1].n2_off + b->mem[b->n - 1].n2_nb));
     return sizeof(double) * std::max((size_t)WAFER_GS_ONE_ROWS * (size_t)b->gs_nb, (size_t)b->n2_nb) * b->n;
 }
 
@@ -485,7 +529,7 @@ int ensure_onepass(wafer_batch *b)
         HIP_TRY(hipMalloc((void **)&b->gram, sizeof(double) * WAFER_MAX_LOW * WAFER_MAX_LOW * b->n));
         HIP_TRY(hipMemsetAsync(b->gram, 0, sizeof(double) * WAFER_MAX_LOW * WAFER_MAX_LOW * b->n, b->s));
     }
-    if (!b->gram_partials) HIP_TRY(hipMalloc((void **)&b->gram_partials, sizeof(double) * WAFER_GRAM_PAIRS * (size_t)b->gs_nb * b->n));
+    if (!b->gram_partials) HIP_TRY(hipMalloc((void **)&b->gram_partials, sizeof(double) * (size_t)b->gsp.doubles(WAFER_GRAM_PAIRS)));
     if (!b->gram_list_dev) HIP_TRY(hipMalloc((void **)&b->gram_list_dev, sizeof(int) * 2 * b->n));
     if (!b->gram_list_host) HIP_TRY(hipHostMalloc((void **)&b->gram_list_host, sizeof(int) * 2 * b->n, hipHostMallocDefault));
     b->gram_stale.assign(b->n, 1);
@@ -493,11 +537,19 @@ int ensure_onepass(wafer_batch *b)
     return WAFER_OK;
 }
 
-WaferBatchGsOneArgs onepass_args(const wafer_batch *b, int flip, uint32_t nslots)
+template <typename A>
+A with_slots(const wafer_batch *b, A a, uint32_t nslots)
 {
-    WaferBatchGsOneArgs a = gs_args<WaferBatchGsOneArgs>(b, flip);
-    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? slot_ptr(b, l, 0) : nullptr;
+    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? slot_arg(b, l) : nullptr;
     return a;
+}
+WaferBatchGsOneArgs onepass_args(const wafer_batch *b, const WaferGeom &g, int flip, uint32_t nslots)
+{
+    return with_slots(b, gs_args<WaferBatchGsOneArgs>(b, g, flip), nslots);
+}
+WaferBatchGsOneArgsMixed onepass_args(const wafer_batch *b, const WaferBatchGeomTable &gt, int flip, uint32_t nslots)
+{
+    return with_slots(b, gs_args<WaferBatchGsOneArgsMixed>(b, gt, flip), nslots);
 }
 
 // the Gram matrices of the active members whose stores changed since they were formed: one launch and its reduce, in stream
@@ -517,8 +569,11 @@ int refresh_gram(wafer_batch *b, const uint8_t *active)
     if (!nlist) return WAFER_OK;
     for (int k = 0; k < nlist; ++k) b->gram_list_host[nlist + k] = (int)std::min<uint32_t>(b->nst[b->gram_list_host[k]], WAFER_MAX_LOW);
     HIP_TRY(hipMemcpyAsync(b->gram_list_dev, b->gram_list_host, sizeof(int) * 2 * nlist, hipMemcpyHostToDevice, b->s));
-    const hipError_t e = wafer_entry_batch_gram(b->f32, nl, onepass_args(b, 0, (uint32_t)nl), b->gram_list_dev, b->gram_list_dev + nlist, nlist, b->gram,
-                                                b->gram_partials, b->s);
+    const int max_nb = gs_max_nb(b, b->gram_list_host, nlist);
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_gram(b->f32, nl, onepass_args(b, gs, 0, (uint32_t)nl), b->mem_dev, b->gram_list_dev, b->gram_list_dev + nlist, nlist,
+                                      max_nb, b->gram, b->gram_partials, b->s);
+    });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram matrix launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -526,8 +581,11 @@ int refresh_gram(wafer_batch *b, const uint8_t *active)
 // sums, reduce, apply on phi[cur ^ flip] of the members in act_dev: the step's tail (normalise_first) or orthogonalise alone
 int gs_onepass(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_first)
 {
-    const hipError_t e = wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, onepass_args(b, flip, wnum), b->mem_dev, b->act_dev, nact,
-                                                      b->gs_scal, b->gram, b->gs_partials, b->s);
+    const int max_nb = gs_max_nb(b, b->act_host, nact);
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, onepass_args(b, gs, flip, wnum), b->mem_dev, b->act_dev, nact, max_nb,
+                                            b->gs_scal, b->gram, b->gs_partials, b->s);
+    });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched one-pass Gram-Schmidt launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
 }
@@ -735,6 +793,7 @@ int init_partitions(wafer_batch *b)
     const int ry = 2 * (NW / 4);
     b->swz = wafer_lds_opts(b->tune).swz;
     b->mem.resize(b->n);
+    b->gsp = wafer_batch_gs_partition(b->geoms.data(), b->shape_of.data(), b->n, WAFER_BATCH_TX, WAFER_BATCH_TY, WAFER_GS_ZC);
     size_t obs_total = 0, n2_total = 0;
     for (uint32_t m = 0; m < b->n; ++m) {
         WaferBatchMember &e = b->mem[m];
@@ -755,6 +814,9 @@ int init_partitions(wafer_batch *b)
         e.n2_nb = b->f32 ? wafer_rownorm2_blocks(g, (int)b->esz, b->num_cus) : wafer_gs_blocks(g);
         e.obs_off = (long long)obs_total;
         e.n2_off = (long long)n2_total;
+        e.gs_nb = b->gsp.nb[m];
+        e.gs_off = b->gsp.first[m];
+        e.slot_off = (long long)b->off[m] + g.base_off;
         obs_total += 4 * (size_t)e.obs_nb;
         n2_total += (size_t)e.n2_nb;
     }
@@ -808,8 +870,8 @@ int init_views(wafer_batch *b)
     return WAFER_OK;
 }
 
-// wafer_batch_create (same_shape) and wafer_batch_create_mixed
-int create_batch(const wafer_params *members, uint32_t n_members, bool same_shape, wafer_batch **out)
+// wafer_batch_create (same_shape), wafer_batch_create_mixed, and wafer_batch_create_mixed_states (states: state stores on several shapes)
+int create_batch(const wafer_params *members, uint32_t n_members, bool same_shape, bool states, wafer_batch **out)
 {
     if (!members || !out) return fail(WAFER_ERR_INVALID, "null argument");
     if (n_members == 0) return fail(WAFER_ERR_INVALID, "a batch needs at least one member (n_members = 0)");
@@ -845,6 +907,7 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     b->off = std::move(L.off);
     b->cells = L.cells;
     b->mixed = b->geoms.size() > 1;
+    b->mixed_states = b->mixed && states;   // (one distinct shape: a plain batch in every call)
     b->dtype = (int)p0.dtype;
     b->f32 = f32;
     b->esz = esz;
@@ -893,12 +956,17 @@ extern "C" {
 
 int wafer_batch_create(const wafer_params *members, uint32_t n_members, wafer_batch **out)
 {
-    return create_batch(members, n_members, true, out);
+    return create_batch(members, n_members, true, false, out);
 }
 
 int wafer_batch_create_mixed(const wafer_params *members, uint32_t n_members, wafer_batch **out)
 {
-    return create_batch(members, n_members, false, out);
+    return create_batch(members, n_members, false, false, out);
+}
+
+int wafer_batch_create_mixed_states(const wafer_params *members, uint32_t n_members, wafer_batch **out)
+{
+    return create_batch(members, n_members, false, true, out);
 }
 
 int wafer_batch_num_shapes(wafer_batch *b, uint32_t *n_shapes)
@@ -1198,23 +1266,27 @@ int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n)
     const char *T = b->f32 ? "float" : "double";
     // what the one-pass form allocated on first use: the Gram matrices, their partials, the member lists, and the growth of gs_partials
     const size_t onepass_bytes = !b->onepass_ready ? 0
-        : sizeof(double) * (WAFER_MAX_LOW * WAFER_MAX_LOW + WAFER_GRAM_PAIRS * (size_t)b->gs_nb) * b->n + sizeof(int) * 2 * b->n +
-              onepass_partials_bytes(b) - sizeof(double) * (size_t)std::max(b->gs_nb, b->n2_nb) * b->n;
-    char kernels[256];
+        : sizeof(double) * (WAFER_MAX_LOW * WAFER_MAX_LOW * (size_t)b->n + (size_t)b->gsp.doubles(WAFER_GRAM_PAIRS)) + sizeof(int) * 2 * b->n +
+              onepass_partials_bytes(b) - sizeof(double) * chain_partials_doubles(b);
+    char kernels[320];
+    char Tm[40], Tc[40];   // the kernels' type lists: several shapes name the table-reading instantiations
+    snprintf(Tm, sizeof Tm, "%s%s", T, b->mixed_states ? ",WaferBatchGsOneArgsMixed" : "");
+    snprintf(Tc, sizeof Tc, "%s%s", T, b->mixed_states ? ",WaferBatchGsArgsMixed" : "");
     int launches = 1;
     const bool onepass = use_onepass(b, wnum);
     if (onepass) {
         launches = 4;
-        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs_sums<%u,%s>+wafer_k_batch_gs_reduce_sums+wafer_k_batch_gs_apply<%u,%s,true>",
-                 wnum, T, wnum, T);
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs_sums<%u,%s>+wafer_k_batch_gs_reduce_sums%s+wafer_k_batch_gs_apply<%u,%s,true%s>",
+                 wnum, Tm, b->mixed_states ? "<false,true>" : "", wnum, T, b->mixed_states ? ",WaferBatchGsOneArgsMixed" : "");
     } else if (wnum) {
         launches = 1 + 2 * (1 + (int)wnum) + 1;
-        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs<NORM2|SCALE|AXPY,%s>+wafer_k_batch_gs_reduce", T);
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs<NORM2|SCALE|AXPY,%s>+wafer_k_batch_gs_reduce%s", Tc, b->mixed_states ? "_mixed" : "");
     } else {
         snprintf(kernels, sizeof kernels, "wafer_k_batch_step");
     }
-    snprintf(buf, n, "wnum=%u form=%s launches_per_step=%d kernels=%s variant=%d dtype=%s onepass_bytes=%zu", wnum, onepass ? "onepass" : "sequential",
-             launches, kernels, b->gs_variant, dtypes[b->dtype], onepass_bytes);
+    const int len = snprintf(buf, n, "wnum=%u form=%s launches_per_step=%d kernels=%s variant=%d dtype=%s onepass_bytes=%zu", wnum,
+                             onepass ? "onepass" : "sequential", launches, kernels, b->gs_variant, dtypes[b->dtype], onepass_bytes);
+    if (b->mixed_states && len > 0 && (size_t)len < n) snprintf(buf + len, n - (size_t)len, " shapes=%zu", b->geoms.size());
     return WAFER_OK;
 }
 

@@ -43,23 +43,53 @@ struct WaferBatchGsArgs {
     const void *dotwith;        // DOT, SCALE, AXPY: the state whose overlap with the resulting phi is summed; null: none
 };
 
-// A batch of several shapes (wafer_batch_norm2 on doubles is the one call that gets here: the excited-state calls are refused):
-// the geometry comes from the device table, the tile counts from it, the member's workgroup count and the place of its partials
-// from its record (WaferBatchMember::n2_nb, n2_off); a.g, a.ntx, a.nty and a.mstride are not read.
+// A batch of several shapes (wafer_batch_norm2 on doubles, and every excited-state call of a batch made by
+// wafer_batch_create_mixed_states): the geometry comes from the device table, the tile counts from it, the member's workgroup
+// count, the place of its partials and its place in a store slot from its record (WaferBatchMember::gs_nb, gs_off, slot_off);
+// a.g, a.ntx, a.nty and a.mstride are not read, and lower / dotwith are the slot's ALLOCATION, not member 0's logical pointer.
 struct WaferBatchGsArgsMixed : WaferBatchGsArgs {
     const WaferGeom *geoms;
 };
-__device__ __forceinline__ const WaferGeom &wafer_gs_geom(const WaferBatchGsArgs &a, int) { return a.g; }
-__device__ __forceinline__ WaferGeom wafer_gs_geom(const WaferBatchGsArgsMixed &a, int shape)
-{
-    return a.geoms[__builtin_amdgcn_readfirstlane(shape)];
-}
 
 // workgroups per member
-static inline int wafer_gs_blocks(const WaferGeom &g)
+static inline int wafer_gs_blocks(const WaferGeom &g) { return wafer_gs_blocks_of(g, WAFER_BATCH_TX, WAFER_BATCH_TY, WAFER_GS_ZC); }
+
+// What a workgroup of these kernels works on, for either argument type A (one text below).  One shape: the tile counts and the
+// member stride are kernel arguments, every member has gridDim.x workgroups and `rows` rows of that many partials from
+// member * rows * gridDim.x on.  Several shapes (A has `geoms`): the tile counts follow from the member's geometry, its place in a
+// slot, its workgroup count and the start of its partials from its record.  A partial of row q lies at p0 + q * nb + blockIdx.x.
+struct WaferBatchGsOneArgs;   // (the one-pass form's arguments, below)
+template <typename A> inline constexpr bool wafer_gs_mixed = !std::is_same_v<A, WaferBatchGsArgs> && !std::is_same_v<A, WaferBatchGsOneArgs>;
+template <typename A>
+__device__ __forceinline__ decltype(auto) wafer_gs_geom(const A &a, int shape)
 {
-    const int ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX, nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    return ntx * nty * ((g.nzl + WAFER_GS_ZC - 1) / WAFER_GS_ZC);
+    if constexpr (wafer_gs_mixed<A>) return WaferGeom(a.geoms[__builtin_amdgcn_readfirstlane(shape)]);   // scalar loads, once, before any loop
+    else return (a.g);
+}
+struct WaferGsPart {
+    int ntx, nty, nb;
+    long long moff;   // the member's element offset from the slot pointers of the arguments
+    size_t p0;
+};
+// false: the workgroup lies beyond its member's partition and leaves as a whole (before any barrier)
+template <typename A>
+__device__ __forceinline__ bool wafer_gs_part(const A &a, const WaferGeom &g, const WaferBatchMember &m, int member, int rows, WaferGsPart &w)
+{
+    if constexpr (wafer_gs_mixed<A>) {
+        if ((int)blockIdx.x >= m.gs_nb) return false;
+        w.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+        w.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+        w.nb = m.gs_nb;
+        w.moff = m.slot_off;
+        w.p0 = (size_t)m.gs_off * rows;
+    } else {
+        w.ntx = a.ntx;
+        w.nty = a.nty;
+        w.nb = gridDim.x;
+        w.moff = (long long)member * a.mstride;
+        w.p0 = (size_t)member * rows * gridDim.x;
+    }
+    return true;
 }
 
 // Block (64, 4), grid (wafer_gs_blocks, active members).
@@ -68,25 +98,20 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs(A a, const WaferBatchMem
                                                         const int *__restrict__ act, const double *__restrict__ scal,
                                                         double *__restrict__ partials)
 {
-    constexpr bool MIXED = std::is_same_v<A, WaferBatchGsArgsMixed>;
-    static_assert(!MIXED || MODE == WAFER_GS_NORM2, "the state stores of a batch of several shapes have no layout yet");
     __shared__ double red[4];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
     const WaferGeom &g = wafer_gs_geom(a, m.shape);
-    if constexpr (MIXED) {   // the member's own partition; a workgroup beyond it leaves as a whole
-        if ((int)blockIdx.x >= m.n2_nb) return;
-        a.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-        a.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    }
+    WaferGsPart wg;
+    if (!wafer_gs_part(a, g, m, member, 1, wg)) return;
     T *__restrict__ phi = static_cast<T *>(m.phi[(m.cur ^ a.flip) & 1]);
-    const long long moff = (long long)member * a.mstride;
+    const long long moff = wg.moff;
     const T *__restrict__ lower = (MODE == WAFER_GS_AXPY) ? static_cast<const T *>(a.lower) + moff : nullptr;
     const T *__restrict__ dotw = (MODE != WAFER_GS_NORM2 && a.dotwith) ? static_cast<const T *>(a.dotwith) + moff : nullptr;
     const int bid = blockIdx.x;
-    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
-    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
-    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    const int i = (bid % wg.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / wg.ntx) % wg.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (wg.ntx * wg.nty)) * WAFER_GS_ZC;
     const int tid = threadIdx.y * WAFER_BATCH_TX + threadIdx.x;
     double coef = 0.0;
     if (MODE == WAFER_GS_SCALE) coef = sqrt(scal[(size_t)member * a.scal_stride + a.coef_slot]);
@@ -119,11 +144,7 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs(A a, const WaferBatchMem
     }
     if (MODE == WAFER_GS_NORM2 || a.dotwith) {   // (uniform: a kernel argument)
         const double s = wafer_block_sum<4>(acc, red, tid);
-        if constexpr (MIXED) {
-            if (tid == 0) partials[(size_t)m.n2_off + blockIdx.x] = s;
-        } else {
-            if (tid == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
-        }
+        if (tid == 0) partials[wg.p0 + blockIdx.x] = s;
     }
 }
 
@@ -138,14 +159,17 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce(const doub
     if (threadIdx.x == 0) scal[(size_t)member * scal_stride + out_slot] = s;
 }
 
-// several shapes: the member's own n2_nb partials, at its own offset
-static __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_mixed(const double *__restrict__ partials, const int *__restrict__ act,
-                                                                            const WaferBatchMember *__restrict__ mem, double *__restrict__ scal,
-                                                                            int scal_stride, int out_slot)
+// several shapes: the member's own partials, at its own offset -- ROWWALK: the n2_nb of the row-walk norm2 (float storage) at
+// n2_off; else the gs_nb of wafer_k_batch_gs at gs_off (on doubles the two partitions are one)
+template <bool ROWWALK>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_mixed(const double *__restrict__ partials, const int *__restrict__ act,
+                                                                     const WaferBatchMember *__restrict__ mem, double *__restrict__ scal,
+                                                                     int scal_stride, int out_slot)
 {
     __shared__ double sh[256];
     const int member = act[blockIdx.x];
-    const double s = wafer_batch_reduce_tree(partials + mem[member].n2_off, mem[member].n2_nb, sh);
+    const double s = ROWWALK ? wafer_batch_reduce_tree(partials + mem[member].n2_off, mem[member].n2_nb, sh)
+                             : wafer_batch_reduce_tree(partials + mem[member].gs_off, mem[member].gs_nb, sh);
     if (threadIdx.x == 0) scal[(size_t)member * scal_stride + out_slot] = s;
 }
 
@@ -236,24 +260,31 @@ struct WaferBatchGsOneArgs {
     const void *low[WAFER_MAX_LOW];     // store slot j (member 0's logical pointer, of the storage type)
 };
 
+// several shapes: as WaferBatchGsArgsMixed -- a.g, a.ntx, a.nty, a.mstride are not read, low[] are the slots' ALLOCATIONS
+struct WaferBatchGsOneArgsMixed : WaferBatchGsOneArgs {
+    const WaferGeom *geoms;
+};
+
 #define WAFER_GS_ONE_ROWS (1 + WAFER_MAX_LOW)                        // partial rows per member of the sums kernel
 #define WAFER_GRAM_PAIRS (WAFER_MAX_LOW * (WAFER_MAX_LOW - 1) / 2)   // partial rows per member of the Gram kernel
 
 // Block (64, 4), grid (wafer_gs_blocks, active members).  All loads of a lane before the arithmetic: 4 planes x (1 + NLOW) arrays.
-template <int NLOW, typename T>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
+template <int NLOW, typename T, typename A = WaferBatchGsOneArgs>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(A a, const WaferBatchMember *__restrict__ mem,
                                                              const int *__restrict__ act, double *__restrict__ partials)
 {
     __shared__ double red[4];
-    const WaferGeom &g = a.g;
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    WaferGsPart wg;
+    if (!wafer_gs_part(a, g, m, member, WAFER_GS_ONE_ROWS, wg)) return;
     const T *__restrict__ phi = static_cast<const T *>(m.phi[(m.cur ^ a.flip) & 1]);
-    const long long moff = (long long)member * a.mstride;
+    const long long moff = wg.moff;
     const int bid = blockIdx.x;
-    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
-    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
-    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    const int i = (bid % wg.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / wg.ntx) % wg.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (wg.ntx * wg.nty)) * WAFER_GS_ZC;
     const int tid = threadIdx.y * WAFER_BATCH_TX + threadIdx.x;
     double acc[1 + NLOW];
 #pragma unroll
@@ -280,21 +311,23 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(WaferBatchGsOneArgs
 #pragma unroll
     for (int q = 0; q <= NLOW; ++q) {
         const double s = wafer_block_sum<4>(acc[q], red, tid);
-        if (tid == 0) partials[((size_t)member * WAFER_GS_ONE_ROWS + q) * gridDim.x + blockIdx.x] = s;
+        if (tid == 0) partials[wg.p0 + (size_t)q * wg.nb + blockIdx.x] = s;
     }
 }
 
 // Block (64, 4), grid (wafer_gs_blocks, active members).  NORMALISE = false (wafer_batch_orthogonalise): no division, norm = 1.
-template <int NLOW, typename T, bool NORMALISE>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
+template <int NLOW, typename T, bool NORMALISE, typename A = WaferBatchGsOneArgs>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(A a, const WaferBatchMember *__restrict__ mem,
                                                               const int *__restrict__ act, const double *__restrict__ scal,
                                                               const double *__restrict__ gram)
 {
-    const WaferGeom &g = a.g;
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    WaferGsPart wg;
+    if (!wafer_gs_part(a, g, m, member, 0, wg)) return;
     T *__restrict__ phi = static_cast<T *>(m.phi[(m.cur ^ a.flip) & 1]);
-    const long long moff = (long long)member * a.mstride;
+    const long long moff = wg.moff;
     const double *__restrict__ sc = scal + (size_t)member * a.scal_stride;
     const double *__restrict__ gm = gram + (size_t)member * (WAFER_MAX_LOW * WAFER_MAX_LOW);
     const double norm = NORMALISE ? sqrt(sc[0]) : 1.0;
@@ -307,9 +340,9 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(WaferBatchGsOneArg
         sj[jj] = s;
     }
     const int bid = blockIdx.x;
-    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
-    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
-    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    const int i = (bid % wg.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / wg.ntx) % wg.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (wg.ntx * wg.nty)) * WAFER_GS_ZC;
     if (i >= g.nx || j >= g.ny) return;
     const long long col = (long long)(j + g.R) * g.pitch + g.xoff + (i + g.R);
     double w[WAFER_GS_ZC], l[NLOW][WAFER_GS_ZC];
@@ -334,20 +367,23 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(WaferBatchGsOneArg
 
 // G_ji = sum l_j l_i, i < j < cnt[blockIdx.y] <= NL, of the members in list: every stored state read once, all pairs formed.
 // Partial row q = j (j - 1) / 2 + i at partials[(member * WAFER_GRAM_PAIRS + q) * nb + workgroup]; rows with j >= the member's
-// count come out zero.  Block (64, 4), grid (wafer_gs_blocks, listed members).
-template <int NL, typename T>
-__global__ __launch_bounds__(256) void wafer_k_batch_gram(WaferBatchGsOneArgs a, const int *__restrict__ list, const int *__restrict__ cnt,
-                                                          double *__restrict__ partials)
+// count come out zero.  Block (64, 4), grid (wafer_gs_blocks, listed members).  mem: the member table (read on several shapes only).
+template <int NL, typename T, typename A = WaferBatchGsOneArgs>
+__global__ __launch_bounds__(256) void wafer_k_batch_gram(A a, const WaferBatchMember *__restrict__ mem, const int *__restrict__ list,
+                                                          const int *__restrict__ cnt, double *__restrict__ partials)
 {
     __shared__ double red[4];
     constexpr int NP = NL * (NL - 1) / 2;
-    const WaferGeom &g = a.g;
     const int member = list[blockIdx.y], count = cnt[blockIdx.y];
-    const long long moff = (long long)member * a.mstride;
+    const WaferBatchMember &m = mem[member];
+    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    WaferGsPart wg;
+    if (!wafer_gs_part(a, g, m, member, WAFER_GRAM_PAIRS, wg)) return;
+    const long long moff = wg.moff;
     const int bid = blockIdx.x;
-    const int i = (bid % a.ntx) * WAFER_BATCH_TX + threadIdx.x;
-    const int j = ((bid / a.ntx) % a.nty) * WAFER_BATCH_TY + threadIdx.y;
-    const int z0 = g.G + (bid / (a.ntx * a.nty)) * WAFER_GS_ZC;
+    const int i = (bid % wg.ntx) * WAFER_BATCH_TX + threadIdx.x;
+    const int j = ((bid / wg.ntx) % wg.nty) * WAFER_BATCH_TY + threadIdx.y;
+    const int z0 = g.G + (bid / (wg.ntx * wg.nty)) * WAFER_GS_ZC;
     const int tid = threadIdx.y * WAFER_BATCH_TX + threadIdx.x;
     double acc[NP];
 #pragma unroll
@@ -372,20 +408,23 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gram(WaferBatchGsOneArgs a,
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         const double s = wafer_block_sum<4>(acc[q], red, tid);
-        if (tid == 0) partials[((size_t)member * WAFER_GRAM_PAIRS + q) * gridDim.x + blockIdx.x] = s;
+        if (tid == 0) partials[wg.p0 + (size_t)q * wg.nb + blockIdx.x] = s;
     }
 }
 
 // wafer_k_reduce for every listed member and partial row at once: block (slot, q) sums the n partials of row q of member
 // act[slot] in wafer_k_reduce's order.  GRAM = false: `rows` = WAFER_GS_ONE_ROWS, into out[member * out_stride + q] (the scalars);
 // GRAM = true: `rows` = WAFER_GRAM_PAIRS, row q = j (j - 1) / 2 + i into out[member * out_stride + j * WAFER_MAX_LOW + i].
-template <bool GRAM>
+// MIXED (several shapes): n is not read; the member's gs_nb partials per row, its rows from gs_off * rows on (mem: the member table).
+template <bool GRAM, bool MIXED = false>
 __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double *__restrict__ partials, const int *__restrict__ act, int n,
-                                                                    int rows, double *__restrict__ out, int out_stride)
+                                                                    int rows, double *__restrict__ out, int out_stride,
+                                                                    const WaferBatchMember *__restrict__ mem)
 {
     __shared__ double sh[256];
     const int member = act[blockIdx.x], q = blockIdx.y;
-    const double *p = partials + ((size_t)member * rows + q) * n;
+    if constexpr (MIXED) n = mem[member].gs_nb;
+    const double *p = MIXED ? partials + (size_t)mem[member].gs_off * rows + (size_t)q * n : partials + ((size_t)member * rows + q) * n;
     double s = 0.0;
     for (int r = threadIdx.x; r < n; r += 256) s += p[r];
     sh[threadIdx.x] = s;
@@ -407,13 +446,21 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double
 
 // entry points (wafer_tu_gs_batch.hip).  One elementwise launch of `mode` over the active members and, where it sums
 // (NORM2, or dotwith given), the reduce into scal[member * scal_stride + out_slot].  f32: float storage.
-hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, const WaferBatchMember *mem, const int *act, int nact,
+// Each entry point once per argument type: one shape (wafer_tu_gs_batch.hip; max_nb == wafer_gs_blocks of the one geometry) and
+// several (the ...Mixed arguments, wafer_tu_gs_batch_mixed.hip; max_nb: the largest gs_nb among the launched members, the grid's extent).
+hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, const WaferBatchMember *mem, const int *act, int nact, int max_nb,
+                                double *scal, int out_slot, double *partials, hipStream_t s);
+hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgsMixed &a, const WaferBatchMember *mem, const int *act, int nact, int max_nb,
                                 double *scal, int out_slot, double *partials, hipStream_t s);
 // the one-pass form: sums, reduce and apply (normalise: evolve; else orthogonalise) over the members in act.  1 <= nlow <= WAFER_MAX_LOW;
 // partials holds WAFER_GS_ONE_ROWS * wafer_gs_blocks doubles per member of the batch, gram WAFER_MAX_LOW^2.
 hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem,
-                                        const int *act, int nact, double *scal, const double *gram, double *partials, hipStream_t s);
+                                        const int *act, int nact, int max_nb, double *scal, const double *gram, double *partials, hipStream_t s);
+hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const WaferBatchGsOneArgsMixed &a, const WaferBatchMember *mem,
+                                        const int *act, int nact, int max_nb, double *scal, const double *gram, double *partials, hipStream_t s);
 // the Gram matrices of the nlist members in list (cnt: states of each, 2 <= cnt <= nl <= WAFER_MAX_LOW) into gram; partials holds
 // WAFER_GRAM_PAIRS * wafer_gs_blocks doubles per member of the batch
-hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgs &a, const int *list, const int *cnt, int nlist, double *gram,
-                                  double *partials, hipStream_t s);
+hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem, const int *list, const int *cnt,
+                                  int nlist, int max_nb, double *gram, double *partials, hipStream_t s);
+hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgsMixed &a, const WaferBatchMember *mem, const int *list, const int *cnt,
+                                  int nlist, int max_nb, double *gram, double *partials, hipStream_t s);

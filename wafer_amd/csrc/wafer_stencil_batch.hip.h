@@ -43,6 +43,10 @@ struct WaferBatchMember {
     int n2_nb;               // workgroups of its wafer_batch_norm2 (wafer_rownorm2_blocks on float storage, wafer_gs_blocks on doubles)
     long long obs_off;       // where its [4][obs_nb] partials begin in the observables' partials buffer (doubles)
     long long n2_off;        // where its n2_nb partials begin in the norm2 partials buffer
+    // the excited-state kernels' partition of its shape (wafer_batch_gs_partition, wafer_batch_plan.h) and its place in a store slot
+    int gs_nb;               // its workgroups: wafer_gs_blocks of its shape (float storage: not n2_nb, which is the row walk's there)
+    long long gs_off;        // the workgroups of the members before it: its `rows` rows of gs_nb partials begin at gs_off * rows
+    long long slot_off;      // its logical origin (plane 0, row 0) in a store slot's allocation, in elements
 };
 
 // Where a kernel takes its geometry from (the template parameter GS of the kernels below).  WaferGeom: the batch's one geometry, a

@@ -153,8 +153,9 @@ hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMembe
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if constexpr (MIXED)
-        hipLaunchKernelGGL(wafer_k_batch_gs_reduce_mixed, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
-    else hipLaunchKernelGGL(wafer_k_batch_gs_reduce, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, max_nb, scal, scal_stride, out_slot);
+    if constexpr (MIXED) {
+        if (f32) hipLaunchKernelGGL(wafer_k_batch_gs_reduce_mixed<true>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
+        else hipLaunchKernelGGL(wafer_k_batch_gs_reduce_mixed<false>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
+    } else hipLaunchKernelGGL(wafer_k_batch_gs_reduce, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, max_nb, scal, scal_stride, out_slot);
     return hipGetLastError();
 }

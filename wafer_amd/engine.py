@@ -56,7 +56,7 @@ EXPORTS = [
     "wafer_batch_clear_states", "wafer_batch_clone_state_to_phi", "wafer_batch_orthogonalise", "wafer_batch_norm2",
     "wafer_batch_evolve_state", "wafer_batch_solve_state",
     "wafer_batch_set_gs_variant", "wafer_batch_diag_gs", "wafer_batch_diag_gs_steps",
-    "wafer_batch_create_mixed", "wafer_batch_num_shapes",
+    "wafer_batch_create_mixed", "wafer_batch_create_mixed_states", "wafer_batch_num_shapes",
     "wafer_batch_symmetrise", "wafer_batch_set_potsub",
 ]
 
@@ -224,6 +224,7 @@ def load_library():
     u8p = C.POINTER(C.c_uint8)
     L.wafer_batch_create.argtypes = [C.POINTER(_Params), C.c_uint32, C.POINTER(vp)]
     L.wafer_batch_create_mixed.argtypes = [C.POINTER(_Params), C.c_uint32, C.POINTER(vp)]
+    L.wafer_batch_create_mixed_states.argtypes = [C.POINTER(_Params), C.c_uint32, C.POINTER(vp)]
     L.wafer_batch_num_shapes.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.wafer_batch_destroy.argtypes = [vp]
     L.wafer_batch_size.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -699,6 +700,10 @@ class Batch:
     dispatch()["shapes"]).  With more than one distinct shape the calls that need the state stores (load_state, download_state,
     push_state, clear_states, clone_state_to_phi, orthogonalise, evolve with wnum > 0, solve_state, set_gs_variant(1)) raise
     WaferError -1 with "mixed-shape" in the message; with one distinct shape the batch is a plain Batch in every call.
+    mixed_shapes=True, state_stores=True (wafer_batch_create_mixed_states) lifts that: every state-store and excited-state call
+    works on several shapes, in the same number of launches per step for all shapes together, and gives each member bit for bit
+    what it gets in a Batch of its own shape under the same gs variant, on every dtype (gs_dispatch(wnum)["shapes"]).
+    state_stores=True without mixed_shapes=True is a ValueError: a Batch of one shape always has its stores.
 
     symmetrise(constraints, active=None) applies constraints[m] (a name of SYMMETRY or its index, one per member) to every active
     member in ONE launch, each member bit for bit what Context.symmetrise gives, on one shape and on several; members that are
@@ -707,12 +712,16 @@ class Batch:
     python -m wafer_amd.sweep drives whole wafer.yaml runs through batches with these calls: phases per state number, every run
     with its own screen_update, tolerance and max_steps, one evolve for all running members between block boundaries."""
 
-    def __init__(self, members: list, mixed_shapes: bool = False):
+    def __init__(self, members: list, mixed_shapes: bool = False, state_stores: bool = False):
+        if state_stores and not mixed_shapes:
+            raise ValueError("state_stores=True goes with mixed_shapes=True (a Batch of one shape always has state stores)")
         self._L = load_library()
         self.members = list(members)
         self._h = C.c_void_p()
         arr = (_Params * max(1, len(self.members)))(*[m.c() for m in self.members])
-        create = self._L.wafer_batch_create_mixed if mixed_shapes else self._L.wafer_batch_create
+        create = self._L.wafer_batch_create
+        if mixed_shapes:
+            create = self._L.wafer_batch_create_mixed_states if state_stores else self._L.wafer_batch_create_mixed
         self._check(create(arr, len(self.members), C.byref(self._h)))
 
     def _check(self, rc: int) -> None:
@@ -952,12 +961,14 @@ class Batch:
         self._check(self._L.wafer_batch_set_gs_variant(self._h, int(variant)))
 
     def gs_dispatch(self, wnum: int) -> dict:
-        """what an excited step with `wnum` would launch: wnum, form, launches_per_step, kernels, variant, dtype, onepass_bytes"""
+        """what an excited step with `wnum` would launch: wnum, form, launches_per_step, kernels, variant, dtype, onepass_bytes and,
+        on a batch of several shapes with state stores, shapes (their number)"""
         buf = C.create_string_buffer(768)
         self._check(self._L.wafer_batch_diag_gs(self._h, int(wnum), buf, len(buf)))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split())
-        for k in ("wnum", "launches_per_step", "variant", "onepass_bytes"):
-            d[k] = int(d[k])
+        for k in ("wnum", "launches_per_step", "variant", "onepass_bytes", "shapes"):
+            if k in d:
+                d[k] = int(d[k])
         return d
 
     def gs_steps(self) -> tuple:

@@ -3,7 +3,7 @@ every time step ONE launch for all runs of a batch that are still going (wafer_a
 context per run.
 
     python -m wafer_amd.sweep -c a.yaml -c b.yaml ... [--output-dir DIR] [--input-dir DIR] [--max-batch N] [--seed S]
-                              [--progress] [--plan]
+                              [--progress] [--plan] [--mix-states]
 
 Configuration reading and validation are the native driver's (`wafer-hip --check-config`, through wafer_amd.run.load_config), the
 input files, the directory names and the table are wafer_amd.run's, and every run computes what `wafer-hip` computes for its file:
@@ -11,9 +11,11 @@ the loop of wafer_cli.cpp per run (observables, normalise, Gram-Schmidt, the sym
 snapshot block, the convergence and max_steps tests), each run with its own tolerance, screen_update, snap_update, max_steps and dt.
 
 Grouping (plan_batches): runs are partitioned by (central_difference, dtype); within a partition the runs that need state stores
-(wavenum > 0 or wavemax > 0) are split by grid shape (a mixed-shape batch has no state stores), and the ground-state-only runs of
-all shapes share one mixed-shape batch.  Each group is cut in input order into batches of at most --max-batch members, which run
-one after another.
+(wavenum > 0 or wavemax > 0) are split by grid shape, and the ground-state-only runs of all shapes share one mixed-shape batch.
+With --mix-states the state runs of a partition form ONE group of all shapes instead: a mixed-shape batch with state stores
+(wafer_amd.Batch(members, mixed_shapes=True, state_stores=True)), every run with the bits it has in a batch of its own shape.  It is
+opt-in: the default grouping is unchanged.  Each group is cut in input order into batches of at most --max-batch members, which
+run one after another.
 
 Scheduling (run_phase): one phase per state number w = 0, 1, ...; in phase w the runs with wavenum <= w <= wavemax that have not
 failed take part.  A run is at a block boundary when its own step counter is a multiple of its screen_update.  Every batched call
@@ -49,15 +51,20 @@ def needs_states(cfg: dict) -> bool:
     return cfg["wavenum"] > 0 or cfg["wavemax"] > 0
 
 
-def plan_batches(cfgs: list, max_batch: int = DEFAULT_MAX_BATCH) -> list:
+def plan_batches(cfgs: list, max_batch: int = DEFAULT_MAX_BATCH, mix_states: bool = False) -> list:
     """-> the batches in running order, each dict(members=[input indices], central_difference, dtype, needs_states, mixed_shapes,
-    shapes=[distinct (nx, ny, nz)]).  Groups appear in the order of their first member; every input index appears exactly once."""
+    shapes=[distinct (nx, ny, nz)]).  Groups appear in the order of their first member; every input index appears exactly once.
+    mix_states: the state runs of a (stencil, dtype) partition are one group whatever their shapes (needs_states and mixed_shapes
+    both True: a mixed-shape batch with state stores) instead of one group per shape."""
     if max_batch < 1:
         raise ValueError("max_batch must be >= 1")
     groups: dict = {}
     for i, c in enumerate(cfgs):
         key = (c["central_difference"], c["dtype"])
-        key += ("states", c["nx"], c["ny"], c["nz"]) if needs_states(c) else ("ground",)
+        if not needs_states(c):
+            key += ("ground",)
+        else:
+            key += ("states",) if mix_states else ("states", c["nx"], c["ny"], c["nz"])
         groups.setdefault(key, []).append(i)
     out = []
     for key, idx in groups.items():
@@ -69,7 +76,7 @@ def plan_batches(cfgs: list, max_batch: int = DEFAULT_MAX_BATCH) -> list:
                 if s not in shapes:
                     shapes.append(s)
             out.append(dict(members=members, central_difference=key[0], dtype=key[1], needs_states=key[2] == "states",
-                            mixed_shapes=key[2] == "ground", shapes=[list(s) for s in shapes]))
+                            mixed_shapes=key[2] == "ground" or len(key) == 3, shapes=[list(s) for s in shapes]))
     return out
 
 
@@ -314,7 +321,9 @@ def run_batch(plan: dict, runs: list, seed: int, progress: bool) -> tuple:
         c = r.cfg
         pars.append(wafer_amd.Params(c["nx"], c["ny"], c["nz"], dn=c["dn"], dt=c["dt"], mass=c["mass"], sig=c["sig"],
                                      central_difference=c["central_difference"], dtype=c["dtype"], max_states=c["wavemax"] + 1))
-    with wafer_amd.Batch(pars, mixed_shapes=plan["mixed_shapes"]) as batch:
+    # (a state group of plan_batches(mix_states=True): the mixed-shape batch that has state stores)
+    kind = dict(mixed_shapes=True, state_stores=True) if plan["needs_states"] and plan["mixed_shapes"] else dict(mixed_shapes=plan["mixed_shapes"])
+    with wafer_amd.Batch(pars, **kind) as batch:
         for r in runs:
             set_up_member(batch, r, pars[r.slot])
         late = [r for r in runs if r.cfg["wavenum"] > 0]
@@ -336,6 +345,8 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=None, help="seed of Gaussian starts (default: the time)")
     ap.add_argument("--progress", action="store_true", help="a table row per screen_update block in every table.txt")
     ap.add_argument("--plan", action="store_true", help="print the grouping as JSON and exit; touches no GPU")
+    ap.add_argument("--mix-states", action="store_true",
+                    help="runs with excited states share one mixed-shape batch per (stencil, dtype) instead of one batch per grid shape")
     args = ap.parse_args(argv)
     if args.max_batch < 1:
         raise SystemExit("--max-batch must be >= 1")
@@ -350,7 +361,7 @@ def main(argv=None) -> int:
                              "(config.rs:702-725 indexes the 3-cell frame)")
         if c["screen_update"] < 1:
             raise SystemExit(f"{p}: a sweep needs screen_update >= 1")
-    plan = plan_batches(cfgs, args.max_batch)
+    plan = plan_batches(cfgs, args.max_batch, mix_states=args.mix_states)
     if args.plan:
         print(json.dumps(dict(configs=args.config, batches=plan)))
         return 0
