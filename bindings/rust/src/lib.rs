@@ -86,6 +86,14 @@ pub struct wafer_div_plan_f32_t {
 /// wafer_params.flags
 pub const WAFER_FLAG_SKIP_DT_CHECK: u32 = 1;
 pub const WAFER_FLAG_UNPLANNED_DIV: u32 = 2;
+/// `target` / `src_kind` of `wafer_batch_resample(_member)`
+pub const WAFER_RESAMPLE_PHI: c_int = 0;
+pub const WAFER_RESAMPLE_POTENTIAL: c_int = 1;
+pub const WAFER_RESAMPLE_POTSUB: c_int = 2;
+pub const WAFER_RESAMPLE_STATE: c_int = 3;
+/// `basis` of `wafer_batch_resample(_member)`: the member's padded size, or its work size
+pub const WAFER_BASIS_PADDED: c_int = 0;
+pub const WAFER_BASIS_WORK: c_int = 1;
 
 /// wafer_peer_info (peer stores, wafer_set_overlap mode 3): what a rank publishes to its z-neighbours
 #[repr(C)]
@@ -251,6 +259,12 @@ extern "C" {
     pub fn wafer_batch_symmetrise(b: *mut wafer_batch, active: *const u8, constraints: *const c_int) -> c_int;
     /// `wafer_set_potsub` for one member
     pub fn wafer_batch_set_potsub(b: *mut wafer_batch, member: u32, kind: c_int, scalar: f64, potsub: *const f64) -> c_int;
+    /// one host source (an unpadded `[sx][sy][sz]` array) resampled onto `target` (WAFER_RESAMPLE_*) of every active member in one launch
+    pub fn wafer_batch_resample(b: *mut wafer_batch, active: *const u8, target: c_int, idx: u32, src: *const f64, sx: u32, sy: u32, sz: u32, basis: c_int) -> c_int;
+    /// the same from the work cells of `src_member`'s phi (`src_kind` PHI) or stored state `src_idx` (STATE)
+    pub fn wafer_batch_resample_member(b: *mut wafer_batch, active: *const u8, target: c_int, idx: u32, src_member: u32, src_kind: c_int, src_idx: u32, basis: c_int) -> c_int;
+    /// HIP-event time of the last resample call's upload, transpose and launch
+    pub fn wafer_batch_last_resample_ms(b: *mut wafer_batch, ms: *mut f32) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

@@ -549,6 +549,32 @@ int wafer_batch_normalise(wafer_batch *b, const uint8_t *active, const double *n
  * NotConstrained on a batch whose stencil is not SevenPoint: WAFER_ERR_INVALID with wafer_symmetrise's message.  Nothing has changed
  * when it fails.  All constraints NotConstrained: succeeds on any stencil and launches nothing. */
 int wafer_batch_symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints);
+/* Resampling in a batch: ONE source trilinearly resampled (input::trilerp_resize, input.rs:667-716) onto an array of every active
+ * member (active NULL: all) in one launch, whatever the members' shapes -- each member bit for bit what the context entry
+ * (wafer_upload_phi_resampled, wafer_set_potential_resampled, wafer_set_potsub_resampled) gives a context of its wafer_params, with
+ * that entry's bookkeeping; WAFER_RESAMPLE_STATE writes stored state idx under wafer_batch_load_state's rules (idx <= the member's
+ * count, capacity, the count grows where idx equals it; a mixed-shape batch needs its state stores).  Every element of a target that
+ * is not a work cell is zero afterwards; members not listed are not touched.
+ * basis: where the sample positions come from -- linspace(0, s - 1, basis size) per axis, the first n of them used.
+ * WAFER_RESAMPLE_POTSUB needs the member's potential and WAFER_BASIS_WORK.
+ * All checks for all listed members run before anything is uploaded or launched: a refused call changes nothing.
+ * (A WAFER_ERR_HIP failure is not a refusal: behind the launch the listed arrays are written, and for WAFER_RESAMPLE_POTENTIAL the
+ * per-member bookkeeping stops at the member whose range check failed; set the potential again.)
+ * WAFER_ERR_INVALID: sx, sy or sz below 2, an unknown target / src_kind / basis, src_member out of range, a member source that is
+ * itself a listed target in the same buffer (its phi onto its phi, its state l onto its state l).  WAFER_ERR_STATE: a member source
+ * without phi or without state src_idx, and what the per-member rules above refuse.  An empty active set: WAFER_OK. */
+enum { WAFER_RESAMPLE_PHI = 0, WAFER_RESAMPLE_POTENTIAL = 1, WAFER_RESAMPLE_POTSUB = 2, WAFER_RESAMPLE_STATE = 3 };
+enum { WAFER_BASIS_PADDED = 0,   /* the member's padded size: input::fill_data's production call */
+       WAFER_BASIS_WORK   = 1 }; /* the member's (nx, ny, nz): fill_sub_data, and the reference's unit test */
+/* one host source, an UNPADDED [sx][sy][sz] array, onto `target` of every active member (NULL: all) */
+int wafer_batch_resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx,
+                         const double *src, uint32_t sx, uint32_t sy, uint32_t sz, int basis);
+/* the same with the work cells of src_member's phi (src_kind PHI) or stored state src_idx (STATE) as the source */
+int wafer_batch_resample_member(wafer_batch *b, const uint8_t *active, int target, uint32_t idx,
+                                uint32_t src_member, int src_kind, uint32_t src_idx, int basis);
+/* device time of the last wafer_batch_resample / _resample_member that launched: HIP events around its upload, transpose and the
+ * one launch (not the per-member bookkeeping of WAFER_RESAMPLE_POTENTIAL behind it); WAFER_ERR_STATE before the first */
+int wafer_batch_last_resample_ms(wafer_batch *b, float *ms);
 /* wafer_solve_state(ctx, 0, ...) for every member at once.  records: n_members * max_records_per_member rows, member m's at
  * m * max_records_per_member; n_records, finals, status: n_members entries.  status[m]: WAFER_OK (converged),
  * WAFER_ERR_MAX_STEP, or WAFER_ERR_STATE (non-finite energy; wafer_last_error names the first such member).  A member that

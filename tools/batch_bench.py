@@ -28,7 +28,16 @@ batches' summed time over the mixed batch's; "parity": every member's phi bit-id
 With --wnum K (and --gs-variant V) the --mixed line times excited-state steps: the mixed batch is made with state stores
 (Batch(members, mixed_shapes=True, state_stores=True)), every member gets an orthonormal store of K states, both sides run
 evolve(steps, wnum=K) under the same gs variant; the same "ratio_*" and "parity" fields, plus "wnum", "gs_variant", the mixed batch's
-gs_dispatch line and the excited steps each form ran."""
+gs_dispatch line and the excited steps each form ran.
+--resample SX: a mode of its own -- one SX^3 source (seeded random) onto the potential of every member.  One line per B: the members are
+--sizes' first size, or cycle through --mixed's shapes in one mixed-shape batch.  "batch_host_ms": host clock around
+Batch.resample_potential(source) (one upload, one transpose, one launch, then every member's potential bookkeeping; the call returns
+when it is done), "batch_events_ms": HIP events around the upload, transpose and launch alone (Batch.last_resample_ms), "ctx_host_ms":
+host clock around B Contexts each calling set_potential_resampled(source) one after another -- what a user does without the batched
+call.  --reps repetitions after one warm-up, every one listed; "ratio_host": ctx over batch, per repetition.  "parity": phi of the
+first and the last member after Batch.resample_phi(source) bit-identical to a Context's upload_phi_resampled.
+The lines are appended to profiles/batch_resample_rows.jsonl unless --out names another file.
+--resample-contexts-only times the contexts alone (it runs on a tree without the batched call) and writes "ctx_host_ms" only."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -212,6 +221,46 @@ def mixed_row(shapes, B, steps, warmup, variant=-1, ext=1, dtype="f64", wnum=0, 
     return out
 
 
+def resample_row(shapes, B, sx, reps, ext=1, dtype="f64", contexts_only=False):
+    pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype)
+            for k in range(B)]
+    src = np.random.default_rng(sx).standard_normal((sx, sx, sx))
+    out = {"mode": "resample", "target": "potential", "source": [sx, sx, sx], "shapes": [list(s) for s in shapes], "B": B, "reps": reps,
+           "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype, "basis": "padded"}
+    ctxs = [wafer_amd.Context(p) for p in pars]
+    try:
+        for c in ctxs:   # warm-up
+            c.set_potential_resampled(src)
+        out["ctx_host_ms"] = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for c in ctxs:
+                c.set_potential_resampled(src)   # (returns when the device has finished: it reads V's range back)
+            out["ctx_host_ms"].append(1e3 * (time.perf_counter() - t0))
+        if contexts_only:
+            return out
+        with wafer_amd.Batch(pars, mixed_shapes=len(set(shapes)) > 1) as b:
+            b.resample_potential(src)   # warm-up: the scratch is made here
+            out["batch_host_ms"], out["batch_events_ms"] = [], []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                b.resample_potential(src)
+                out["batch_host_ms"].append(1e3 * (time.perf_counter() - t0))
+                out["batch_events_ms"].append(b.last_resample_ms())
+            b.resample_phi(src)
+            parity = True
+            for k in sorted({0, B - 1}):
+                ctxs[k].upload_phi_resampled(src)
+                parity = parity and bool(np.array_equal(ctxs[k].download_phi().view(np.int64), b.download_phi(k).view(np.int64)))
+            out["parity"] = parity
+            out["shapes_in_batch"] = b.num_shapes()
+        out["ratio_host"] = [c / h for c, h in zip(out["ctx_host_ms"], out["batch_host_ms"])]
+    finally:
+        for c in ctxs:
+            c.close()
+    return out
+
+
 def rounded(d):
     if isinstance(d, dict):
         return {k: rounded(v) for k, v in d.items()}
@@ -237,7 +286,22 @@ def main():
     ap.add_argument("--mixed", metavar="SHAPES", help='e.g. "64,50,37x50x23": the members cycle through these shapes in one mixed-shape batch, compared '
                     "with one uniform batch per shape run one after another (--wnum, --gs-variant: excited-state steps, the mixed batch with state stores; "
                     "--sizes and --only-batch do not apply)")
+    ap.add_argument("--resample", type=int, metavar="SX", help="time Batch.resample_potential of one SX^3 source onto every member against B contexts "
+                    "calling set_potential_resampled (a mode of its own: --steps, --warmup, --wnum and the variants do not apply)")
+    ap.add_argument("--reps", type=int, default=3, help="--resample: timed repetitions after one warm-up (default 3)")
+    ap.add_argument("--resample-contexts-only", action="store_true", help="--resample: the contexts alone")
     a = ap.parse_args()
+    if a.resample:
+        if not a.out:   # this mode's rows have a place of their own
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_resample_rows.jsonl")
+        shapes = parse_shapes(a.mixed) if a.mixed else [(a.sizes[0],) * 3]
+        for B in a.batch:
+            line = json.dumps(rounded(resample_row(shapes, B, a.resample, a.reps, a.ext, a.dtype, a.resample_contexts_only)))
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+        return
     if a.mixed:
         for B in a.batch:
             line = json.dumps(rounded(mixed_row(parse_shapes(a.mixed), B, a.steps, a.warmup, a.variant, a.ext, a.dtype, a.wnum, a.gs_variant)))

@@ -34,6 +34,7 @@
 #include "wafer_stencil_lds.hip.h"
 #include "wafer_stencil_batch.hip.h"
 #include "wafer_gs_batch.hip.h"
+#include "wafer_resample_batch.hip.h"
 
 struct wafer_batch {
     uint32_t n = 0;
@@ -99,6 +100,11 @@ struct wafer_batch {
     double *gram_partials = nullptr;          // [member][WAFER_GRAM_PAIRS][gs_nb]
     int *gram_list_dev = nullptr, *gram_list_host = nullptr;   // the members to recompute, then their state counts: 2 n ints
     std::vector<uint8_t> gram_stale;          // member m's store changed since its Gram matrix was formed
+    // wafer_batch_resample: a host source as uploaded ([sx][sy][sz]) and, behind it, transposed to x-fastest; grown on demand
+    double *rs_scratch = nullptr;
+    size_t rs_cap = 0;                        // doubles
+    hipEvent_t rs_start = nullptr, rs_stop = nullptr;   // around the last call's upload, transpose and launch (wafer_batch_last_resample_ms)
+    bool rs_timing_valid = false;
 };
 
 namespace {
@@ -151,11 +157,11 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
-                    (void *)b->gram_list_dev})
+                    (void *)b->gram_list_dev, (void *)b->rs_scratch})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {b->ev_start, b->ev_stop})
+    for (hipEvent_t e : {b->ev_start, b->ev_stop, b->rs_start, b->rs_stop})
         if (e) (void)hipEventDestroy(e);
     if (b->s) (void)hipStreamDestroy(b->s);
     delete b;
@@ -780,6 +786,162 @@ int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t s
     return WAFER_OK;
 }
 
+// ---- resampling --------------------------------------------------------------------------------------------------------------
+// the resample scratch holds at least `doubles` doubles: grown on demand, never per call, freed with the batch
+int ensure_scratch(wafer_batch *b, size_t doubles)
+{
+    if (doubles <= b->rs_cap) return WAFER_OK;
+    HIP_TRY(hipStreamSynchronize(b->s));   // no launch in flight reads the scratch that goes back
+    if (b->rs_scratch) HIP_TRY(hipFree(b->rs_scratch));
+    b->rs_scratch = nullptr;
+    b->rs_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->rs_scratch, sizeof(double) * doubles));
+    b->rs_cap = doubles;
+    return WAFER_OK;
+}
+
+// A host source on the device, x-fastest (wafer_resample_batch.hip.h): one upload into the batch's scratch and one transpose behind
+// it, in stream order -- a later call reuses the scratch behind this call's launch.
+int stage_host_source(wafer_batch *b, const double *src, int sx, int sy, int sz, WaferResampleSource *out)
+{
+    const size_t n = (size_t)sx * sy * sz;
+    TRY(ensure_scratch(b, 2 * n));
+    double *raw = b->rs_scratch, *xfast = b->rs_scratch + n;
+    HIP_TRY(hipMemcpyAsync(raw, src, sizeof(double) * n, hipMemcpyHostToDevice, b->s));
+    WaferXposeArgs a;
+    memset(&a, 0, sizeof a);
+    a.g.pitch = sx;                            // a dense [sz][sy][sx] box: only WaferGeom::at is read
+    a.g.plane = (long long)sx * sy;
+    a.sx = sx; a.sy = sy; a.sz = sz;
+    const dim3 grid((unsigned)((sx + 31) / 32), (unsigned)sy, (unsigned)((sz + 31) / 32)), block(32, 8);
+    hipLaunchKernelGGL((wafer_k_transpose<double, true>), grid, block, 0, b->s, a, raw, xfast);
+    HIP_TRY(hipGetLastError());
+    out->base = xfast;
+    out->off0 = 0;
+    out->pitch = sx;
+    out->plane = (long long)sx * sy;
+    out->sx = sx; out->sy = sy; out->sz = sz;
+    return WAFER_OK;
+}
+
+// wafer_batch_resample (host != nullptr) and wafer_batch_resample_member: every check for every listed member, then one launch,
+// then per member the bookkeeping of the context entry (wafer_upload_phi_resampled, wafer_set_potential_resampled,
+// wafer_set_potsub_resampled) or of wafer_batch_load_state.
+// A REFUSED call (WAFER_ERR_INVALID, WAFER_ERR_STATE) has changed nothing.  A HIP error (WAFER_ERR_HIP) is another matter, as for a
+// context: before the launch it leaves every target as it was; behind it the arrays of all listed members are written, and for a
+// potential the per-member bookkeeping stops at the member whose refresh_ab / check_v_range failed -- the listed members after it
+// hold the new V without have_pot, with v_ysym off (the safe answer), until the potential is set again.
+int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, const double *host, uint32_t sx, uint32_t sy, uint32_t sz,
+             uint32_t src_member, int src_kind, uint32_t src_idx, int basis)
+{
+    if (target < WAFER_RESAMPLE_PHI || target > WAFER_RESAMPLE_STATE) return fail(WAFER_ERR_INVALID, "unknown resample target %d", target);
+    if (basis != WAFER_BASIS_PADDED && basis != WAFER_BASIS_WORK) return fail(WAFER_ERR_INVALID, "unknown resample basis %d", basis);
+    if (target == WAFER_RESAMPLE_POTSUB && basis != WAFER_BASIS_WORK)
+        return fail(WAFER_ERR_INVALID, "pot_sub is resampled with the work size as basis (input.rs:472): WAFER_BASIS_WORK");
+    if (!host) {
+        if (src_member >= b->n) return fail(WAFER_ERR_INVALID, "source member %u out of range (the batch has %u)", src_member, b->n);
+        if (src_kind != WAFER_RESAMPLE_PHI && src_kind != WAFER_RESAMPLE_STATE)
+            return fail(WAFER_ERR_INVALID, "a member source is its phi (WAFER_RESAMPLE_PHI) or a stored state (WAFER_RESAMPLE_STATE), not %d", src_kind);
+        const WaferGeom &sg = b->geom(src_member);
+        sx = (uint32_t)sg.nx; sy = (uint32_t)sg.ny; sz = (uint32_t)sg.nz;
+    }
+    if (sx < 2 || sy < 2 || sz < 2) return fail(WAFER_ERR_INVALID, "resampling needs at least 2 points per axis");
+    if (sx > 0x7fffffffu || sy > 0x7fffffffu || sz > 0x7fffffffu) return fail(WAFER_ERR_INVALID, "source size out of range");
+    if (target == WAFER_RESAMPLE_STATE || (!host && src_kind == WAFER_RESAMPLE_STATE)) TRY(refuse_mixed(b, "wafer_batch_resample (stored states)"));
+    if (!host) {
+        if (src_kind == WAFER_RESAMPLE_PHI && !b->views[src_member]->have_phi) return fail(WAFER_ERR_STATE, "source member %u: phi not set", src_member);
+        if (src_kind == WAFER_RESAMPLE_STATE && src_idx >= b->nst[src_member]) return fail(WAFER_ERR_STATE, "source member %u: no state %u", src_member, src_idx);
+    }
+    int nlisted = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        ++nlisted;
+        if (!host && m == src_member && target == src_kind && (target == WAFER_RESAMPLE_PHI || idx == src_idx))
+            return fail(WAFER_ERR_INVALID, "member %u is the source and a target in the same buffer", m);
+        if (target == WAFER_RESAMPLE_POTSUB && !b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: set the potential first", m);
+        if (target == WAFER_RESAMPLE_STATE) {
+            if (idx > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: states must be loaded in order", m);
+            if (idx == b->nst[m]) TRY(check_capacity(b, m));
+        }
+    }
+    if (!nlisted) return WAFER_OK;
+
+    HIP_TRY(hipSetDevice(b->device));
+    if (target == WAFER_RESAMPLE_STATE) TRY(ensure_slots(b, idx + 1));
+    b->rs_timing_valid = false;   // (a call that fails below leaves no half-recorded pair behind)
+    if (host) TRY(ensure_scratch(b, 2 * (size_t)sx * sy * sz));   // (before the events: growing it synchronises, frees and allocates)
+    HIP_TRY(hipEventRecord(b->rs_start, b->s));
+    WaferResampleSource src;
+    if (host) {
+        TRY(stage_host_source(b, host, (int)sx, (int)sy, (int)sz, &src));
+    } else {
+        const WaferGeom &sg = b->geom(src_member);
+        const wafer_ctx *sc = b->views[src_member];
+        src.base = src_kind == WAFER_RESAMPLE_PHI ? sc->phi[sc->cur] : slot_ptr(b, src_idx, src_member);
+        src.off0 = sg.at(sg.G, sg.R, sg.R);
+        src.pitch = sg.pitch;
+        src.plane = sg.plane;
+        src.sx = sg.nx; src.sy = sg.ny; src.sz = sg.nz;
+    }
+    TRY(sync_members(b));   // (the kernel reads cur)
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    // From here on the targets are written.  V is about to change: check_v_range re-establishes the flag (cleared behind the last
+    // step that can fail before the launch, so that a call that launched nothing leaves it as it was).
+    if (target == WAFER_RESAMPLE_POTENTIAL)
+        for (uint32_t m = 0; m < b->n; ++m)
+            if (!active || active[m]) b->views[m]->v_ysym = false;
+    int max_tiles = 0, max_planes = 0;   // of the padded boxes: the kernel writes the frame's zeros too
+    for (int k = 0; k < nact; ++k) {
+        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
+        max_tiles = std::max(max_tiles, ((g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
+        max_planes = std::max(max_planes, g.lz);
+    }
+    const int ntx = (b->g().px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;   // (one shape: every member's tiles along x)
+    void *dst0 = target == WAFER_RESAMPLE_PHI ? b->alloc[0] : target == WAFER_RESAMPLE_POTENTIAL ? b->alloc[2]
+               : target == WAFER_RESAMPLE_POTSUB ? b->alloc[3] : b->slots[idx];
+    void *dst1 = target == WAFER_RESAMPLE_PHI ? b->alloc[1] : dst0;
+    {
+        RoctxRange range_("wafer_batch_resample");
+        const hipError_t e = with_geom(b, [&](const auto &gs) {
+            return wafer_entry_batch_trilerp(b->f32, !host && b->f32, gs, b->mem_dev, b->act_dev, nact, ntx, max_tiles, max_planes, src, dst0, dst1,
+                                             target == WAFER_RESAMPLE_PHI, basis, b->s);
+        });
+        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched resample launch failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(hipEventRecord(b->rs_stop, b->s));
+    b->rs_timing_valid = true;
+    if (host) HIP_TRY(hipStreamSynchronize(b->s));   // the caller's array has been read
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        wafer_ctx *c = b->views[m];
+        switch (target) {
+        case WAFER_RESAMPLE_PHI:
+            c->have_phi = true;
+            c->halo_valid = c->g.G;   // ghost planes were interpolated from the same source
+            break;
+        case WAFER_RESAMPLE_POTENTIAL:
+            TRY(refresh_ab(c));
+            c->vgen_type = 0;
+            c->potsub_kind = WAFER_POTSUB_NONE;   // potential.rs:357-358: FromFile has no pot_sub of its own
+            c->potsub_scalar = 0.0;
+            c->have_pot = true;
+            c->x2_ready = 0;
+            TRY(check_v_range(c));
+            break;
+        case WAFER_RESAMPLE_POTSUB:
+            c->potsub_kind = WAFER_POTSUB_ARRAY;
+            c->potsub_scalar = 0.0;
+            break;
+        default:
+            if (idx == b->nst[m]) ++b->nst[m];
+            mark_gram_stale(b, m);
+            break;
+        }
+    }
+    return WAFER_OK;
+}
+
 // ---- creation --------------------------------------------------------------------------------------------------------------
 // Every member's partition record and the places of its partials.  Observables: the partition wafer_launch_observables_lds gives a
 // single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
@@ -924,6 +1086,8 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     HIP_TRY(hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&b->ev_start));
     HIP_TRY(hipEventCreate(&b->ev_stop));
+    HIP_TRY(hipEventCreate(&b->rs_start));
+    HIP_TRY(hipEventCreate(&b->rs_stop));
     for (void *&a : b->alloc) {   // one allocation per array kind, zeros: frames, pads and guard zones of every member
         HIP_TRY(hipMalloc(&a, b->cells * esz));
         HIP_TRY(hipMemsetAsync(a, 0, b->cells * esz, b->s));
@@ -1006,6 +1170,20 @@ int wafer_batch_set_potsub(wafer_batch *b, uint32_t member, int kind, double sca
 {
     TRY(check_member_index(b, member));
     return wafer_set_potsub(b->views[member], kind, scalar, potsub);
+}
+
+int wafer_batch_resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, const double *src, uint32_t sx, uint32_t sy,
+                         uint32_t sz, int basis)
+{
+    if (!b || !src) return fail(WAFER_ERR_INVALID, "null argument");
+    return resample(b, active, target, idx, src, sx, sy, sz, 0, 0, 0, basis);
+}
+
+int wafer_batch_resample_member(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, uint32_t src_member, int src_kind,
+                                uint32_t src_idx, int basis)
+{
+    if (!b) return fail(WAFER_ERR_INVALID, "null batch");
+    return resample(b, active, target, idx, nullptr, 0, 0, 0, src_member, src_kind, src_idx, basis);
 }
 
 int wafer_batch_symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
@@ -1194,6 +1372,15 @@ int wafer_batch_last_evolve_ms(wafer_batch *b, float *ms, uint64_t *steps)
     HIP_TRY(hipEventSynchronize(b->ev_stop));
     HIP_TRY(hipEventElapsedTime(ms, b->ev_start, b->ev_stop));
     *steps = b->last_steps;
+    return WAFER_OK;
+}
+
+int wafer_batch_last_resample_ms(wafer_batch *b, float *ms)
+{
+    if (!b || !ms) return fail(WAFER_ERR_INVALID, "null argument");
+    if (!b->rs_timing_valid) return fail(WAFER_ERR_STATE, "no wafer_batch_resample has run");
+    HIP_TRY(hipEventSynchronize(b->rs_stop));
+    HIP_TRY(hipEventElapsedTime(ms, b->rs_start, b->rs_stop));
     return WAFER_OK;
 }
 

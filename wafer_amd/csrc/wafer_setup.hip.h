@@ -327,6 +327,35 @@ __device__ __forceinline__ void wafer_bracket(int n, double look, int *lo, int *
     }
 }
 
+// One target cell: the value at work cell (i, j, k) of a target whose sample positions are linspace(0, s - 1, b) per axis, from a
+// source of (sx, sy, sz) points read through at(x, y, z) -> double.  The linspace step, the bracket, the three weights and the
+// seven c0 * (1 - d) + c1 * d in the reference's order (input.rs:683-712); the ONE statement of this arithmetic, shared by
+// wafer_k_trilerp below and wafer_k_batch_trilerp (wafer_resample_batch.hip.h), whose sources differ only in layout.
+template <typename At>
+__device__ __forceinline__ double wafer_trilerp_cell(int sx, int sy, int sz, int bx, int by, int bz, int i, int j, int k, At at)
+{
+    const int nx = sx - 1, ny = sy - 1, nz = sz - 1;
+    const double stx = bx > 1 ? ((double)nx - 0.) / (double)(bx - 1) : 0.;
+    const double sty = by > 1 ? ((double)ny - 0.) / (double)(by - 1) : 0.;
+    const double stz = bz > 1 ? ((double)nz - 0.) / (double)(bz - 1) : 0.;
+    const double xl = 0. + stx * (double)i, yl = 0. + sty * (double)j, zl = 0. + stz * (double)k;
+    int x0, x1, y0, y1, z0, z1;
+    wafer_bracket(nx, xl, &x0, &x1);
+    wafer_bracket(ny, yl, &y0, &y1);
+    wafer_bracket(nz, zl, &z0, &z1);
+    const double xd = (xl - (double)x0) / ((double)x1 - (double)x0);
+    const double yd = (yl - (double)y0) / ((double)y1 - (double)y0);
+    const double zd = (zl - (double)z0) / ((double)z1 - (double)z0);
+    auto op = [](double c0, double c1, double d) { return c0 * (1. - d) + c1 * d; };
+    const double c00 = op(at(x0, y0, z0), at(x1, y0, z0), xd);
+    const double c01 = op(at(x0, y0, z1), at(x1, y0, z1), xd);
+    const double c10 = op(at(x0, y1, z0), at(x1, y1, z0), xd);
+    const double c11 = op(at(x0, y1, z1), at(x1, y1, z1), xd);
+    const double c0 = op(c00, c10, yd);
+    const double c1 = op(c01, c11, yd);
+    return op(c0, c1, zd);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void wafer_k_trilerp(WaferResampleArgs a, const double *__restrict__ src,
                                                        T *__restrict__ dst)
@@ -337,27 +366,8 @@ __global__ __launch_bounds__(256) void wafer_k_trilerp(WaferResampleArgs a, cons
     const int lzp = blockIdx.z;                 // every local plane, ghost planes included
     const int k = g.z_begin + (lzp - g.G);      // global work-z
     if (i >= g.nx || j >= g.ny || k < 0 || k >= g.nz) return;
-    const int nx = a.sx - 1, ny = a.sy - 1, nz = a.sz - 1;
-    const double stx = a.bx > 1 ? ((double)nx - 0.) / (double)(a.bx - 1) : 0.;
-    const double sty = a.by > 1 ? ((double)ny - 0.) / (double)(a.by - 1) : 0.;
-    const double stz = a.bz > 1 ? ((double)nz - 0.) / (double)(a.bz - 1) : 0.;
-    const double xl = 0. + stx * (double)i, yl = 0. + sty * (double)j, zl = 0. + stz * (double)k;
-    int x0, x1, y0, y1, z0, z1;
-    wafer_bracket(nx, xl, &x0, &x1);
-    wafer_bracket(ny, yl, &y0, &y1);
-    wafer_bracket(nz, zl, &z0, &z1);
-    const double xd = (xl - (double)x0) / ((double)x1 - (double)x0);
-    const double yd = (yl - (double)y0) / ((double)y1 - (double)y0);
-    const double zd = (zl - (double)z0) / ((double)z1 - (double)z0);
     auto at = [&](int x, int y, int z) { return src[((size_t)x * a.sy + y) * (size_t)a.sz + z]; };
-    auto op = [](double c0, double c1, double d) { return c0 * (1. - d) + c1 * d; };
-    const double c00 = op(at(x0, y0, z0), at(x1, y0, z0), xd);
-    const double c01 = op(at(x0, y0, z1), at(x1, y0, z1), xd);
-    const double c10 = op(at(x0, y1, z0), at(x1, y1, z0), xd);
-    const double c11 = op(at(x0, y1, z1), at(x1, y1, z1), xd);
-    const double c0 = op(c00, c10, yd);
-    const double c1 = op(c01, c11, yd);
-    dst[g.at(lzp, j + g.R, i + g.R)] = (T)op(c0, c1, zd);
+    dst[g.at(lzp, j + g.R, i + g.R)] = (T)wafer_trilerp_cell(a.sx, a.sy, a.sz, a.bx, a.by, a.bz, i, j, k, at);
 }
 
 // Is V its own mirror image in y?  ORs 1 into *out when V[x, y, z] and V[x, ny-1-y, z] differ in any BIT on a work cell of any local

@@ -5,6 +5,7 @@
 // 1 f32 <float, double> (float storage, fp64 arithmetic), 2 f32fast <float, float> (float arithmetic in the ground-state step).
 #include <string.h>
 #include "wafer_gs_batch.hip.h"
+#include "wafer_resample_batch.hip.h"
 
 namespace {
 
@@ -136,6 +137,19 @@ hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatch
     const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
     if (f32) hipLaunchKernelGGL((wafer_k_batch_symmetrise<float, GS>), grid, block, 0, s, gs, mem, act, sym, ntx);
     else hipLaunchKernelGGL((wafer_k_batch_symmetrise<double, GS>), grid, block, 0, s, gs, mem, act, sym, ntx);
+    return hipGetLastError();
+}
+
+hipError_t wafer_entry_batch_trilerp(bool f32, bool src_f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx,
+                                     int max_tiles, int max_planes, const WaferResampleSource &src, void *dst0, void *dst1, int by_cur, int basis,
+                                     hipStream_t s)
+{
+    if (MIXED) ntx = 0;   // (the kernel forms it from the member's geometry)
+    if (src_f32 && !f32) return hipErrorInvalidValue;   // (a member source has the batch's storage type)
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (!f32) hipLaunchKernelGGL((wafer_k_batch_trilerp<double, double, GS>), grid, block, 0, s, gs, mem, act, ntx, src, dst0, dst1, by_cur, basis);
+    else if (src_f32) hipLaunchKernelGGL((wafer_k_batch_trilerp<float, float, GS>), grid, block, 0, s, gs, mem, act, ntx, src, dst0, dst1, by_cur, basis);
+    else hipLaunchKernelGGL((wafer_k_batch_trilerp<float, double, GS>), grid, block, 0, s, gs, mem, act, ntx, src, dst0, dst1, by_cur, basis);
     return hipGetLastError();
 }
 

@@ -32,6 +32,8 @@ WAFER_ERR_INVALID = -1
 WAFER_ERR_HIP = -2
 WAFER_ERR_STATE = -4
 WAFER_ERR_MAX_STEP = -5
+RESAMPLE_PHI, RESAMPLE_POTENTIAL, RESAMPLE_POTSUB, RESAMPLE_STATE = 0, 1, 2, 3   # wafer_batch_resample's target / src_kind
+RESAMPLE_BASIS = ("padded", "work")                                              # WAFER_BASIS_*
 FLAG_SKIP_DT_CHECK = 1
 FLAG_UNPLANNED_DIV = 2
 
@@ -58,6 +60,7 @@ EXPORTS = [
     "wafer_batch_set_gs_variant", "wafer_batch_diag_gs", "wafer_batch_diag_gs_steps",
     "wafer_batch_create_mixed", "wafer_batch_create_mixed_states", "wafer_batch_num_shapes",
     "wafer_batch_symmetrise", "wafer_batch_set_potsub",
+    "wafer_batch_resample", "wafer_batch_resample_member", "wafer_batch_last_resample_ms",
 ]
 
 
@@ -261,6 +264,9 @@ def load_library():
     L.wafer_batch_diag_gs_steps.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.wafer_batch_symmetrise.argtypes = [vp, u8p, C.POINTER(C.c_int)]
     L.wafer_batch_set_potsub.argtypes = [vp, C.c_uint32, C.c_int, C.c_double, dp]
+    L.wafer_batch_resample.argtypes = [vp, u8p, C.c_int, C.c_uint32, dp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
+    L.wafer_batch_resample_member.argtypes = [vp, u8p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int]
+    L.wafer_batch_last_resample_ms.argtypes = [vp, C.POINTER(C.c_float)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -709,6 +715,12 @@ class Batch:
     member in ONE launch, each member bit for bit what Context.symmetrise gives, on one shape and on several; members that are
     inactive or "NotConstrained" keep their buffer and their bits.  SevenPoint only, like a Context, unless every constraint is
     "NotConstrained".  set_potsub(i, kind, scalar, potsub) is Context.set_potsub for member i (a potential_sub override).
+    resample_phi / resample_potential / resample_potsub / resample_state(idx, ...) set an array of every active member from ONE source
+    of any resolution in one launch (wafer_k_batch_trilerp): a numpy array, uploaded once, or ("member", m) / ("state", m, l), the work
+    cells of member m's phi or stored state l on the device -- a coarse member's result as the start of a finer one.  Each member gets
+    bit for bit what Context.upload_phi_resampled / set_potential_resampled / set_potsub_resampled give a Context of its Params
+    (basis "padded": the reference's production call; "work": its nx, ny, nz), with that call's bookkeeping; resample_state follows
+    load_state's rules.  A refused call changes nothing.
     python -m wafer_amd.sweep drives whole wafer.yaml runs through batches with these calls: phases per state number, every run
     with its own screen_update, tolerance and max_steps, one evolve for all running members between block boundaries."""
 
@@ -794,6 +806,50 @@ class Batch:
             raise ValueError("constraints must hold one entry per member")
         a = self._mask(active)
         self._check(self._L.wafer_batch_symmetrise(self._h, self._u8(a), (C.c_int * len(cons))(*cons)))
+
+    # -- resampling: one source onto many members in one launch ---------------------------------
+    def _resample(self, target: int, idx: int, src, active, basis) -> None:
+        """src: an unpadded 3-d numpy array, ("member", m): the work cells of member m's phi, or ("state", m, l): of its stored state l"""
+        a = self._mask(active)
+        if basis not in RESAMPLE_BASIS:
+            raise ValueError("basis must be one of %s" % (RESAMPLE_BASIS,))
+        basis = RESAMPLE_BASIS.index(basis)
+        if isinstance(src, tuple):
+            if len(src) == 2 and src[0] == "member":
+                kind, m, l = RESAMPLE_PHI, src[1], 0
+            elif len(src) == 3 and src[0] == "state":
+                kind, m, l = RESAMPLE_STATE, src[1], src[2]
+            else:
+                raise ValueError('a member source is ("member", m) or ("state", m, l)')
+            self._check(self._L.wafer_batch_resample_member(self._h, self._u8(a), target, idx, self._member(m), kind, int(l), basis))
+            return
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        if src.ndim != 3:
+            raise ValueError("the source must be a 3-d array")
+        self._check(self._L.wafer_batch_resample(self._h, self._u8(a), target, idx, _dp(src), *src.shape, basis))
+
+    def resample_phi(self, src, active=None, basis: str = "padded") -> None:
+        """Context.upload_phi_resampled(src) for every active member (None: all) in ONE launch from one source, each member bit for
+        bit what its Context gets; basis "padded" (the reference's production call) or "work" (the member's nx, ny, nz)"""
+        self._resample(RESAMPLE_PHI, 0, src, active, basis)
+
+    def resample_potential(self, src, active=None, basis: str = "padded") -> None:
+        """Context.set_potential_resampled(src) for every active member in one launch"""
+        self._resample(RESAMPLE_POTENTIAL, 0, src, active, basis)
+
+    def resample_potsub(self, src, active=None, basis: str = "work") -> None:
+        """Context.set_potsub_resampled(src) for every active member in one launch (after their potentials; basis "work" only)"""
+        self._resample(RESAMPLE_POTSUB, 0, src, active, basis)
+
+    def resample_state(self, idx: int, src, active=None, basis: str = "padded") -> None:
+        """stored state idx of every active member from one source, under load_state's rules (idx <= the member's count)"""
+        self._resample(RESAMPLE_STATE, int(idx), src, active, basis)
+
+    def last_resample_ms(self) -> float:
+        """HIP-event time of the last resample_* call's upload, transpose and launch, in milliseconds"""
+        ms = C.c_float(0)
+        self._check(self._L.wafer_batch_last_resample_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def upload_phi(self, i: int, phi: np.ndarray) -> None:
         assert phi.shape == self.members[i].padded_shape

@@ -294,9 +294,10 @@ def main(argv=None) -> int:
             if sub.ndim == 0:
                 ctx.set_potsub(1, float(sub))
             else:
-                if tuple(sub.shape) != par.work_shape:
-                    raise SystemExit(f"potential_sub holds {tuple(sub.shape)}, the grid is {par.work_shape}; resample it once with wafer-hip")
-                ctx.set_potsub(2, 0.0, sub)
+                if tuple(sub.shape) != par.work_shape:                   # input.rs:453-478: fill_sub_data resamples it
+                    ctx.set_potsub_resampled(np.ascontiguousarray(sub, dtype=np.float64))
+                else:
+                    ctx.set_potsub(2, 0.0, sub)
             say("Potential_sub loaded from disk", file=sys.stderr)
             del sub
         for w in range(cfg["wavenum"]):                                  # grid.rs:35-39: converged lower states from disk

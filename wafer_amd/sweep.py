@@ -28,7 +28,16 @@ Output: <output-dir>/<index:03d>_<project name>_<timestamp>/ per run with a copy
 for that run up to its "Simulation complete" line; every block's row with --progress), observables_N.json / .csv and, with
 save_wavefns, wavefunction_N.npy (wavefunction_N_partial.npy for a state that did not converge): the work area in the reference's
 axis order.  Stdout: one JSON line per run, then the elapsed time.  The exit code is 0 only if every run converged in every state
-it asked for.  Not in a sweep: script potentials, inputs of another resolution.
+it asked for.  Not in a sweep: script potentials.
+
+Inputs (plan_inputs, set_up_batch): `potential` (FromFile), a `potential_sub` array, `wavefunction_N` (lower states and starts) and
+`wavefunction_N_partial` may have another resolution than the run.  A file of the run's own size is copied; anything else is
+trilinearly resampled on the device as `wafer-hip` resamples it (basis: the padded size; for potential_sub the work size), and the
+runs of one batch that name the same file (real path and modification time) for the same role are set by ONE Batch.resample_* call
+with their mask -- with --input-dir, one upload and one launch per file however many runs read it.  The five text / binary formats
+are staged without a frame (pad 0); a ready-made `<stem>.npy` counts as framed for a run whose padded size it has and as plain data
+for every other run.  --plan lists the groups under "inputs" without converting or writing anything: the shape of a .npy or .csv is
+read from the file, for the other formats "shape", "copy" and "resample" are null.
 """
 from __future__ import annotations
 
@@ -41,7 +50,7 @@ import time
 
 import numpy as np
 
-from wafer_amd.run import load_config, measurement_row, observable_header, sanitize, staged_array, summary
+from wafer_amd.run import find_input, load_config, measurement_row, observable_header, sanitize, staged_array, summary
 
 DEFAULT_MAX_BATCH = 64
 
@@ -242,66 +251,195 @@ def run_phase(batch, runs: list, w: int, progress: bool = False, push: bool = Fa
 
 
 # ---- set-up ---------------------------------------------------------------------------------------------------------------------
-def _from_input(run: Run, stem: str, pad: int, shape, what: str):
-    a = staged_array(run.input_dir, stem, run.cfg["file_type"], pad, 0)
-    if a is not None and (a.dtype != np.float64 or tuple(a.shape) != tuple(shape)):
-        raise SystemExit(f"{run.config_path}: {what}: {stem} holds {tuple(a.shape)} {a.dtype}, this run needs {tuple(shape)} float64 "
-                         f"(the frame of {pad} cells included); resample it once with wafer-hip")
-    return a
+def input_file(input_dir: str, stem: str, file_type: str):
+    """the file a run reads for `stem` (a ready-made <stem>.npy first, as staged_array takes it) -> (real path, mtime) or None"""
+    ready = os.path.join(input_dir, stem + ".npy")
+    path = ready if os.path.exists(ready) else find_input(input_dir, stem, file_type)
+    if path is None:
+        return None
+    path = os.path.realpath(path)
+    return path, os.path.getmtime(path)
 
 
-def set_up_member(batch, run: Run, par) -> None:
-    """potential, pot_sub override and the lower states from disk, as wafer_amd.run sets a context up"""
-    cfg, i, ext = run.cfg, run.slot, run.cfg["central_difference"]
-    if cfg["potential"] == "FromFile":                                    # potential.rs:80-86
-        v = _from_input(run, "potential", ext, par.padded_shape, "LoadPotential")
-        if v is None:
-            raise SystemExit(f"{run.config_path}: Error: LoadPotential: FileNotFound: {run.input_dir}/potential.*")
-        batch.set_potential_host(i, np.ascontiguousarray(v))
-    else:
-        batch.set_potential(i, cfg["potential"])
-    sub = staged_array(run.input_dir, "potential_sub", cfg["file_type"], 0, 0)   # potential.rs:113-131
-    if sub is not None:
-        variable = cfg["potential"] == "FullCornell"
-        if (sub.ndim == 0) == variable:
-            raise SystemExit(f"{run.config_path}: Error: WrongPotentialSubDims: potential_sub input file does not suit the potential type")
-        if sub.ndim == 0:
-            batch.set_potsub(i, 1, float(sub))
+def _shapes(cfg: dict) -> tuple:
+    e, work = cfg["central_difference"], (cfg["nx"], cfg["ny"], cfg["nz"])
+    return work, tuple(n + 2 * e for n in work)
+
+
+def _load(run: Run, stem: str) -> np.ndarray:
+    """the array of stem.* without a frame (a ready-made .npy as it is)"""
+    return staged_array(run.input_dir, stem, run.cfg["file_type"], 0, 0)
+
+
+def peek_shape(path: str):
+    """the shape of an input file without converting it (what --plan may do: no driver binary, nothing written): a .npy from its header,
+    a .csv (i,j,k,data rows in C order, output.rs:148-165) from its last row; None for the formats that have to be parsed whole"""
+    if path.endswith(".npy"):
+        return list(np.load(path, mmap_mode="r").shape)
+    if path.endswith(".csv"):
+        with open(path, "rb") as f:
+            f.seek(0, os.SEEK_END)
+            f.seek(max(0, f.tell() - 4096))
+            rows = [l for l in f.read().decode(errors="replace").splitlines() if l.strip()]
+        try:
+            cells = rows[-1].split(",")
+            return [int(c) + 1 for c in cells[:-1]] if len(cells) == 4 else ([] if len(cells) == 1 else None)
+        except (IndexError, ValueError):
+            return None
+    return None
+
+
+def how_to_set(cfg: dict, role: str, path: str, shape) -> str:
+    """"framed": a ready-made .npy of the run's padded size, used as it is; "copy": the run's own work size (a scalar too);
+    "resample": anything else"""
+    work, padded = _shapes(cfg)
+    shape = tuple(shape)
+    if role != "potential_sub" and path.endswith(".npy") and shape == padded:
+        return "framed"
+    return "copy" if shape == work or shape == () else "resample"
+
+
+def _starts(cfg: dict, w: int) -> bool:
+    """does state w of this run start from a file if there is one?  (grid.rs:60-100)"""
+    return cfg["wavenum"] <= w <= cfg["wavemax"] and (w > 0 or cfg["init_condition"] == "FromFile")
+
+
+def plan_inputs(runs: list, load=_load, roles=None) -> list:
+    """The input files of the runs of ONE batch, grouped: -> [dict(role, state, stem, path, mtime, shape, members, copy, resample)] in
+    the order potential, potential_sub, state (lower states from disk, by number), start (by number), then first appearance.  Two runs
+    share a group when they read the same file -- the same real path and modification time -- for the same role and state number.
+    members: the runs' input indices; copy: those of them whose own size the file has (set per member, as before), resample: the rest
+    (set by one Batch.resample_* call).  Touches no GPU.  load(run, stem) -> array reads a file, once per group; the array stays in
+    the group as "array" for apply_inputs.  load=None only looks (--plan): the shape comes from peek_shape, and where that cannot tell
+    without converting the file, shape, copy and resample are None.
+    roles: only these (start_phase asks for one phase's starts)."""
+    wanted = []
+    for r in runs:
+        c = r.cfg
+        if c["potential"] == "FromFile":
+            wanted.append((0, "potential", 0, "potential", r))
+        wanted.append((1, "potential_sub", 0, "potential_sub", r))
+        for w in range(c["wavenum"]):
+            wanted.append((2, "state", w, f"wavefunction_{w}", r))
+        for w in range(c["wavenum"], c["wavemax"] + 1):
+            if _starts(c, w):
+                stem = f"wavefunction_{w}"
+                if input_file(r.input_dir, stem, c["file_type"]) is None:     # input.rs:513-523
+                    stem += "_partial"
+                wanted.append((3, "start", w, stem, r))
+    groups: dict = {}
+    for order, role, w, stem, r in sorted(wanted, key=lambda t: (t[0], t[2])):
+        if roles is not None and (role, w) not in roles:
+            continue
+        f = input_file(r.input_dir, stem, r.cfg["file_type"])
+        if f is None:
+            continue
+        key = (role, w) + f
+        g = groups.get(key)
+        if g is None:
+            g = groups[key] = dict(role=role, state=w, stem=stem, path=f[0], mtime=f[1], members=[], copy=[], resample=[])
+            if load is None:
+                g["shape"] = peek_shape(f[0])
+                if g["shape"] is None:
+                    g["copy"] = g["resample"] = None
+            else:
+                g["array"] = load(r, stem)
+                g["shape"] = list(np.shape(g["array"]))
+        g["members"].append(r.index)
+        if g["shape"] is not None:
+            g["resample" if how_to_set(r.cfg, role, g["path"], g["shape"]) == "resample" else "copy"].append(r.index)
+    return list(groups.values())
+
+
+def _framed(run: Run, role: str, path: str, a: np.ndarray) -> np.ndarray:
+    """a copied array in the run's zero frame (a ready-made framed .npy as it is)"""
+    if how_to_set(run.cfg, role, path, a.shape) == "framed":
+        return np.ascontiguousarray(a, dtype=np.float64)
+    e = run.cfg["central_difference"]
+    out = np.zeros(_shapes(run.cfg)[1])
+    out[e:-e, e:-e, e:-e] = a
+    return out
+
+
+def apply_inputs(batch, runs: list, groups: list, load=_load) -> None:
+    """the groups of plan_inputs onto the batch: the copies per member, the rest of a group in one resample call with its mask"""
+    by_index = {r.index: r for r in runs}
+    for g in groups:
+        first = by_index[g["members"][0]]
+        a = g["array"] if "array" in g else load(first, g["stem"])       # (read once, by plan_inputs)
+        role, w = g["role"], g["state"]
+        if role == "potential_sub":                                       # potential.rs:113-131
+            for i in g["members"]:
+                r = by_index[i]
+                if (a.ndim == 0) == (r.cfg["potential"] == "FullCornell"):
+                    raise SystemExit(f"{r.config_path}: Error: WrongPotentialSubDims: potential_sub input file does not suit the potential type")
+            for i in g["copy"]:
+                if a.ndim == 0:
+                    batch.set_potsub(by_index[i].slot, 1, float(a))
+                else:
+                    batch.set_potsub(by_index[i].slot, 2, 0.0, np.ascontiguousarray(a, dtype=np.float64))
         else:
-            if tuple(sub.shape) != par.work_shape:
-                raise SystemExit(f"{run.config_path}: potential_sub holds {tuple(sub.shape)}, the grid is {par.work_shape}; "
-                                 "resample it once with wafer-hip")
-            batch.set_potsub(i, 2, 0.0, np.ascontiguousarray(sub))
-    for w in range(cfg["wavenum"]):                                       # grid.rs:35-39: converged lower states from disk
-        st = _from_input(run, f"wavefunction_{w}", ext, par.padded_shape, f"LoadWavefunction({w})")
-        if st is None:
-            raise SystemExit(f"{run.config_path}: Error: LoadWavefunction({w}): FileNotFound: {run.input_dir}/wavefunction_{w}.*")
-        batch.load_state(i, w, np.ascontiguousarray(st))
+            if a.ndim != 3:
+                raise SystemExit(f"{first.config_path}: {g['path']} holds {a.ndim} dimensions, not 3")
+            for i in g["copy"]:
+                r = by_index[i]
+                full = _framed(r, role, g["path"], a)
+                if role == "potential":
+                    batch.set_potential_host(r.slot, full)
+                elif role == "state":
+                    batch.load_state(r.slot, w, full)
+                else:
+                    batch.upload_phi(r.slot, full)
+        if g["resample"]:
+            src = np.ascontiguousarray(a, dtype=np.float64)
+            mask = _mask(runs, [by_index[i] for i in g["resample"]])
+            if role == "potential":
+                batch.resample_potential(src, active=mask, basis="padded")
+            elif role == "potential_sub":
+                batch.resample_potsub(src, active=mask, basis="work")     # input.rs:472
+            elif role == "state":
+                batch.resample_state(w, src, active=mask, basis="padded")
+            else:
+                batch.resample_phi(src, active=mask, basis="padded")
 
 
-def start_phase(batch, runs: list, pars: list, w: int, seed: int) -> None:
+def set_up_batch(batch, runs: list, load=_load) -> None:
+    """potentials, pot_sub overrides and the lower states from disk for every run of the batch, as wafer_amd.run sets a context up:
+    built-in potentials per member, everything that comes from a file through plan_inputs' groups"""
+    for r in runs:
+        c = r.cfg
+        if c["potential"] == "FromFile":                                  # potential.rs:80-86
+            if input_file(r.input_dir, "potential", c["file_type"]) is None:
+                raise SystemExit(f"{r.config_path}: Error: LoadPotential: FileNotFound: {r.input_dir}/potential.*")
+        else:
+            batch.set_potential(r.slot, c["potential"])
+        for w in range(c["wavenum"]):                                     # grid.rs:35-39: converged lower states from disk
+            if input_file(r.input_dir, f"wavefunction_{w}", c["file_type"]) is None:
+                raise SystemExit(f"{r.config_path}: Error: LoadWavefunction({w}): FileNotFound: {r.input_dir}/wavefunction_{w}.*")
+    roles = {("potential", 0), ("potential_sub", 0)} | {("state", w) for r in runs for w in range(r.cfg["wavenum"])}
+    groups = plan_inputs(runs, load, roles=roles)                          # (the starts are read by start_phase, phase by phase)
+    apply_inputs(batch, runs, groups, load)
+
+
+def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load) -> None:
     """the start of state w for every run that takes part (grid.rs:60-100), then, for w = 0, one symmetrise with every run's
     init_symmetry (config.rs:625)"""
     part = [r for r in runs if r.takes_part(w)]
+    groups = plan_inputs(part, load, roles={("start", w)})
+    from_file = {i for g in groups for i in g["members"]}
     clones = []
     for r in part:
-        ext, shape = r.cfg["central_difference"], pars[r.slot].padded_shape
         r.cloned = False
-        start = _from_input(r, f"wavefunction_{w}", ext, shape, f"LoadWavefunction({w})")
-        if start is None:                                                 # input.rs:513-523
-            start = _from_input(r, f"wavefunction_{w}_partial", ext, shape, f"LoadWavefunction({w})")
-        if w > 0:
-            if start is not None:
-                batch.upload_phi(r.slot, np.ascontiguousarray(start))
-            else:                                                         # grid.rs:95
-                clones.append(r)
-                r.cloned = True
+        if r.index in from_file:
+            continue
+        if w > 0:                                                         # grid.rs:95
+            clones.append(r)
+            r.cloned = True
         elif r.cfg["init_condition"] == "FromFile":
-            if start is None:
-                raise SystemExit(f"{r.config_path}: Error: SetInitialConditions: LoadWavefunction(0): FileNotFound: {r.input_dir}/wavefunction_0*.*")
-            batch.upload_phi(r.slot, np.ascontiguousarray(start))
+            raise SystemExit(f"{r.config_path}: Error: SetInitialConditions: LoadWavefunction(0): FileNotFound: {r.input_dir}/wavefunction_0*.*")
         else:                                                             # grid.rs:99, config.rs:577-627
             batch.set_initial_condition(r.slot, r.cfg["init_condition"], seed=seed)
+    apply_inputs(batch, runs, groups, load)
     if clones:
         batch.clone_state_to_phi(w - 1, active=_mask(runs, clones))
     if w == 0 and part:
@@ -324,8 +462,7 @@ def run_batch(plan: dict, runs: list, seed: int, progress: bool) -> tuple:
     # (a state group of plan_batches(mix_states=True): the mixed-shape batch that has state stores)
     kind = dict(mixed_shapes=True, state_stores=True) if plan["needs_states"] and plan["mixed_shapes"] else dict(mixed_shapes=plan["mixed_shapes"])
     with wafer_amd.Batch(pars, **kind) as batch:
-        for r in runs:
-            set_up_member(batch, r, pars[r.slot])
+        set_up_batch(batch, runs)
         late = [r for r in runs if r.cfg["wavenum"] > 0]
         if late:   # observables run over every member: a run that starts at a later state waits with its state 0 as phi
             batch.clone_state_to_phi(0, active=_mask(runs, late))
@@ -363,7 +500,14 @@ def main(argv=None) -> int:
             raise SystemExit(f"{p}: a sweep needs screen_update >= 1")
     plan = plan_batches(cfgs, args.max_batch, mix_states=args.mix_states)
     if args.plan:
-        print(json.dumps(dict(configs=args.config, batches=plan)))
+        inputs = []
+        for k, b in enumerate(plan):
+            members = [Run(i, cfgs[i], args.config[i], args.input_dir or os.path.join(os.path.dirname(os.path.abspath(args.config[i])), "input"))
+                       for i in b["members"]]
+            for g in plan_inputs(members, load=None):                     # (looks only: converts nothing, writes nothing)
+                inputs.append(dict(batch=k, role=g["role"], state=g["state"], path=g["path"], shape=g["shape"], members=g["members"],
+                                   copy=g["copy"], resample=g["resample"]))
+        print(json.dumps(dict(configs=args.config, batches=plan, inputs=inputs)))
         return 0
 
     seed = int(time.time()) if args.seed is None else args.seed
