@@ -519,8 +519,9 @@ int wafer_batch_create_mixed(const wafer_params *members, uint32_t n_members, wa
  *    launched members) and the workgroups beyond a smaller member's partition leave at once.
  *  - wafer_batch_solve_state: per-member records, finals, statuses and pushes as in a batch of one shape; a short or a full
  *    store is that member's status, not the call's.
- *  - wafer_batch_diag_gs names the table-reading instantiations in kernels= (..,WaferBatchGsArgsMixed> /
- *    ..,WaferBatchGsOneArgsMixed>) and ends with " shapes=N". */
+ *  - wafer_batch_diag_gs names the table-reading instantiations in kernels= (wafer_k_batch_gs<..,WaferBatchGeomTable>,
+ *    wafer_k_batch_gs_sums<..,WaferBatchGeomTable>, wafer_k_batch_gs_apply<..,WaferBatchGeomTable>; the reduces are the same
+ *    kernels for every batch) and ends with " shapes=N". */
 int wafer_batch_create_mixed_states(const wafer_params *members, uint32_t n_members, wafer_batch **out);
 /* number of distinct (nx, ny, nz) among the members */
 int wafer_batch_num_shapes(wafer_batch *b, uint32_t *n_shapes);

@@ -88,7 +88,8 @@ def test_partition(partition, shapes, kind, R):
         for q in range(rows):
             for w in (0, b - 1):
                 assert owner.setdefault(off + q * b + w, (m, q, w)) == (m, q, w)
-    if len(set(shapes)) == 1:   # one shape: the layout the one-shape kernels index, member * rows * nb
+    if len(set(shapes)) == 1:   # one shape: the records hold the closed forms a one-shape batch used to index by, member * rows * nb
+        assert [m[1] for m in members] == [m * nb[0] for m in range(n)] and doubles == rows * n * nb[0]
         assert [m[2] for m in members] == [m * rows * nb[0] for m in range(n)]
         assert all(off + q * nb[0] == (m * rows + q) * nb[0] for m, (_, _, off) in enumerate(members) for q in range(rows))
 

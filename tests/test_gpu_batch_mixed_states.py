@@ -435,18 +435,27 @@ def test_unchanged_contracts_and_dispatch(wa, wo):
         assert b.gs_dispatch(wnum) == u.gs_dispatch(wnum)   # (onepass_bytes too: the same allocations)
         for g, w in zip(snapshot(b, wnum), snapshot(u, wnum)):
             same(g, w, "one shape")
+        one_kernels = {}   # the one-shape kernels= fields, (gs variant, wnum): what the several-shape lines below must differ from
+        for variant in (0, 1):
+            u.set_gs_variant(variant)
+            for w in (1, 2, 3, 4):
+                one_kernels[variant, w] = u.gs_dispatch(w)["kernels"]
+                assert "WaferBatchGeomTable" not in one_kernels[variant, w]
     # several shapes: the table-reading instantiations, the launch counts, shapes=6
     with make_batch(wa, wo, ALL, ext, wnum) as b:
         for w in (1, 2, 3):
             d = b.gs_dispatch(w)
             assert d["form"] == "sequential" and d["launches_per_step"] == 1 + 2 * (1 + w) + 1 and d["shapes"] == 6, d
-            assert "WaferBatchGsArgsMixed>" in d["kernels"] and "wafer_k_batch_gs_reduce_mixed" in d["kernels"], d
+            assert "wafer_k_batch_gs<NORM2|SCALE|AXPY,double,WaferBatchGeomTable>" in d["kernels"], d
+            assert d["kernels"].endswith("+wafer_k_batch_gs_reduce") and d["kernels"] != one_kernels[0, w], d
         assert b.gs_dispatch(0)["launches_per_step"] == 1 and b.gs_dispatch(0)["shapes"] == 6
         b.set_gs_variant(1)
         for w in (1, 2, 3, 4):
             d = b.gs_dispatch(w)
             assert d["form"] == "onepass" and d["launches_per_step"] == 4 and d["shapes"] == 6 and d["onepass_bytes"] == 0, d
-            assert "WaferBatchGsOneArgsMixed>" in d["kernels"], d
+            assert "wafer_k_batch_gs_sums<%d,double,WaferBatchGeomTable>" % w in d["kernels"], d
+            assert "wafer_k_batch_gs_apply<%d,double,true,WaferBatchGeomTable>" % w in d["kernels"], d
+            assert "+wafer_k_batch_gs_reduce_sums+" in d["kernels"] and d["kernels"] != one_kernels[1, w], d
         b.evolve(1, wnum=wnum)
         assert b.gs_dispatch(wnum)["onepass_bytes"] > 0
         b.set_gs_variant(-1)

@@ -18,16 +18,16 @@
 // one wafer_ctx_create builds for that shape; on the device too) and every member an index into it (`shape_of`).  Storage is one
 // allocation per array kind, member m at element offset off[m] = the sum of the totals of the members before it, every member
 // with its own guard rows and planes.  The step tables are built over all active members at once (wafer_batch_plan.h) and every
-// entry carries its member's shape index, so a step or a fused pass is ONE launch whatever the shapes.  Observables, norm2 and
-// normalise run on grids of (workgroup, member) as wide as the largest launched member needs, each member on the partition a
-// context of its shape gets (recorded in its WaferBatchMember).
+// entry carries its member's shape index, so a step or a fused pass is ONE launch whatever the shapes.  Every other kernel runs on
+// a grid of (workgroup, member) as wide as the largest launched member needs and takes what depends on the member -- its partition,
+// its workgroup count, the places of its partials, its origin in a store slot -- from its WaferBatchMember record (init_partitions).
 // A batch of one shape (wafer_batch_create, or wafer_batch_create_mixed with equal shapes) is the case geoms.size() == 1 of all this:
 // off[m] == m * geoms[0].total, every member's partition is the same, and the widest is everyone's.  The one thing that differs is
 // where the kernels read the geometry from (with_geom, the one place that chooses): a kernel argument for one shape, the device
 // table for several -- the same kernel templates instantiated for either source (wafer_tu_batch.inc, wafer_tu_gs_batch.inc).
-// State stores on several shapes are opt-in at creation (wafer_batch_create_mixed_states: `mixed_states`): a slot is one allocation
-// laid out as the arrays are, and every member's Gram-Schmidt partition and the places of its partials come from
-// wafer_batch_gs_partition (wafer_batch_plan.h; `gsp`, and in its WaferBatchMember).  A batch of several shapes made by
+// State stores: a slot is one allocation laid out as the arrays are, and every member's Gram-Schmidt partition and the places of
+// its partials come from wafer_batch_gs_partition (wafer_batch_plan.h; `gsp`, and in its WaferBatchMember).  On several shapes they
+// are opt-in at creation (wafer_batch_create_mixed_states: `mixed_states`); a batch of several shapes made by
 // wafer_batch_create_mixed refuses the excited-state calls as it always has (refuse_mixed).
 #include <memory>
 #include "wafer_engine.h"
@@ -51,7 +51,8 @@ struct wafer_batch {
     WaferGeom *geoms_dev = nullptr;
     bool mixed = false;
     bool mixed_states = false;                // several shapes WITH state stores (wafer_batch_create_mixed_states)
-    WaferBatchGsPartition gsp;                // every member's Gram-Schmidt partition (one shape: gs_nb workgroups each)
+    WaferBatchGsPartition gsp;                // every member's Gram-Schmidt partition and the places of its partials
+    size_t n2_doubles = 0;                    // every member's wafer_batch_norm2 partials (mem[].n2_nb), end to end
     const WaferGeom &g() const { return geoms[0]; }               // what every shape shares (R, G), and THE geometry of one shape
     const WaferGeom &geom(uint32_t m) const { return geoms[shape_of[m]]; }
     std::string kernel_name = "wafer_k_batch_step";
@@ -88,16 +89,15 @@ struct wafer_batch {
     std::vector<void *> slots;
     std::vector<uint32_t> nst;                // states member m holds
     // excited states: norm2 at gs_scal[m * gs_stride], the overlap with state l at [m * gs_stride + 1 + l]; made at first use
-    int gs_nb = 0, gs_stride = 0;
-    int n2_nb = 0;                            // float storage: workgroups per member of wafer_batch_norm2 (a context's wafer_norm2 partition)
-    double *gs_partials = nullptr;            // [member][gs_nb]
+    int gs_stride = 0;
+    double *gs_partials = nullptr;            // member m's rows at gsp.row_off(m, rows); wafer_batch_norm2's at mem[m].n2_off (partials_doubles)
     double *gs_scal = nullptr, *gs_host = nullptr;
     // the one-pass form (wafer_batch_set_gs_variant); everything below is made by its first use (ensure_onepass)
     int gs_variant = -1;
     uint64_t n_onepass = 0, n_sequential = 0;   // excited steps and orthogonalise calls in each form (wafer_batch_diag_gs_steps)
     bool onepass_ready = false;               // gs_partials holds WAFER_GS_ONE_ROWS rows per member, the Gram storage exists
     double *gram = nullptr;                   // [member][WAFER_MAX_LOW^2]: G_ji = <state j | state i>, i < j
-    double *gram_partials = nullptr;          // [member][WAFER_GRAM_PAIRS][gs_nb]
+    double *gram_partials = nullptr;          // member m's [WAFER_GRAM_PAIRS][gsp.nb[m]] at gsp.row_off(m, WAFER_GRAM_PAIRS)
     int *gram_list_dev = nullptr, *gram_list_host = nullptr;   // the members to recompute, then their state counts: 2 n ints
     std::vector<uint8_t> gram_stale;          // member m's store changed since its Gram matrix was formed
     // wafer_batch_resample: a host source as uploaded ([sx][sy][sz]) and, behind it, transposed to x-fastest; grown on demand
@@ -274,6 +274,20 @@ hipError_t with_geom(const wafer_batch *b, F &&launch)
     return b->mixed ? launch(WaferBatchGeomTable{b->geoms_dev}) : launch(b->g());
 }
 
+// The grid of the kernels that run one 64 x 4 tile of one plane per workgroup (normalise, symmetrise, resample): the largest tile
+// and plane counts among the members in act_host -- of their work boxes, or (padded) of their padded boxes, frame and ghost planes
+// included.
+void max_tiles_planes(const wafer_batch *b, int nact, bool padded, int *max_tiles, int *max_planes)
+{
+    *max_tiles = *max_planes = 0;
+    for (int k = 0; k < nact; ++k) {
+        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
+        const int x = padded ? g.px : g.nx, y = padded ? g.py : g.ny;
+        *max_tiles = std::max(*max_tiles, ((x + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((y + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
+        *max_planes = std::max(*max_planes, padded ? g.lz : g.nzl);
+    }
+}
+
 // the four raw sums of the active members into sums_host[m * 4 ..]
 int observables(wafer_batch *b, const uint8_t *active)
 {
@@ -286,10 +300,8 @@ int observables(wafer_batch *b, const uint8_t *active)
     RoctxRange range_("wafer_batch_observables");
     int max_nb = 0;   // the grid is as wide as the largest launched member's partition
     for (int k = 0; k < nact; ++k) max_nb = std::max(max_nb, b->mem[b->act_host[k]].obs_nb);
-    const WaferBatchMember &m0 = b->mem[b->act_host[0]];   // (one shape: every member's partition)
     const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_observables(b->f32, b->g().R, gs, b->mem_dev, b->act_dev, nact, m0.obs_ntx, m0.obs_nty, m0.obs_zchunk, max_nb, b->swz,
-                                             b->partials, b->sums, b->s);
+        return wafer_entry_batch_observables(b->f32, b->g().R, gs, b->mem_dev, b->act_dev, nact, max_nb, b->swz, b->partials, b->sums, b->s);
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched observables launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(b->sums_host, b->sums, sizeof(double) * 4 * b->n, hipMemcpyDeviceToHost, b->s));
@@ -315,15 +327,10 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     int nact = 0;
     TRY(upload_active(b, active, &nact));
     if (!nact) return WAFER_OK;
-    int max_tiles = 0, max_planes = 0;
-    for (int k = 0; k < nact; ++k) {
-        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
-        max_tiles = std::max(max_tiles, ((g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
-        max_planes = std::max(max_planes, g.nzl);
-    }
-    const int ntx = (b->g().nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;   // (one shape: every member's tiles along x)
+    int max_tiles, max_planes;
+    max_tiles_planes(b, nact, false, &max_tiles, &max_planes);
     const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_normalise(b->f32, gs, b->mem_dev, b->act_dev, nact, ntx, max_tiles, max_planes, norm2_dev, stride, b->s);
+        return wafer_entry_batch_normalise(b->f32, gs, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, norm2_dev, stride, b->s);
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
@@ -354,16 +361,11 @@ int symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
     TRY(upload_active(b, hit.data(), &nact));   // (synchronises the stream: sym_host is not read by an earlier call's copy either)
     for (uint32_t m = 0; m < b->n; ++m) b->sym_host[m] = hit[m] ? constraints[m] : 0;
     HIP_TRY(hipMemcpyAsync(b->sym_dev, b->sym_host, sizeof(int) * b->n, hipMemcpyHostToDevice, b->s));
-    int max_tiles = 0, max_planes = 0;   // of the padded boxes: the kernel writes the frame's zeros too
-    for (int k = 0; k < nact; ++k) {
-        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
-        max_tiles = std::max(max_tiles, ((g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
-        max_planes = std::max(max_planes, g.lz);
-    }
-    const int ntx = (b->g().px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;   // (one shape: every member's tiles along x)
+    int max_tiles, max_planes;   // of the padded boxes: the kernel writes the frame's zeros too
+    max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
     RoctxRange range_("wafer_batch_symmetrise");
     const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_symmetrise(b->f32, gs, b->mem_dev, b->act_dev, nact, b->sym_dev, ntx, max_tiles, max_planes, b->s);
+        return wafer_entry_batch_symmetrise(b->f32, gs, b->mem_dev, b->act_dev, nact, b->sym_dev, max_tiles, max_planes, b->s);
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched symmetrise launch failed: %s", hipGetErrorString(e));
     for (uint32_t m = 0; m < b->n; ++m) {
@@ -380,10 +382,6 @@ void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
 {
     return static_cast<char *>(b->slots[l]) + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
 }
-
-// what the excited-state kernels take for slot l: member 0's logical pointer on one shape (they add member * mstride), the
-// allocation itself on several (they add WaferBatchMember::slot_off)
-const void *slot_arg(const wafer_batch *b, uint32_t l) { return b->mixed ? b->slots[l] : slot_ptr(b, l, 0); }
 
 // slots [0, n) exist (zeros: frames, pads and guard zones of every member)
 int ensure_slots(wafer_batch *b, uint32_t n)
@@ -432,55 +430,23 @@ int push_states(wafer_batch *b, const uint8_t *active)
 }
 
 // ---- excited states --------------------------------------------------------------------------------------------------------
-// doubles of gs_partials under the sequential form
-size_t chain_partials_doubles(const wafer_batch *b)
-{
-    if (!b->mixed) return (size_t)std::max(b->gs_nb, b->n2_nb) * b->n;
-    const size_t n2 = (size_t)(b->mem[b->n - 1].n2_off + b->mem[b->n - 1].n2_nb);   // every member's own norm2 partition, end to end
-    // with state stores the chain's partition too: on float storage the two differ (the row walk's and the 64 x 4 x 4 tiles'), each
-    // with its own offsets from 0 (n2_off, gs_off), written and reduced by different calls in stream order
-    return b->mixed_states ? std::max(n2, (size_t)b->gsp.doubles(1)) : n2;
-}
+// Doubles of gs_partials for kernels that write `rows` sums per workgroup (1: the sequential form; WAFER_GS_ONE_ROWS: the one-pass
+// form's sums): every member's rows end to end (gsp), or every member's wafer_batch_norm2 partition end to end if that is longer --
+// on float storage the two differ (the row walk's and the 64 x 4 x 4 tiles'), each with its own offsets from 0 (n2_off, gs_off),
+// written and reduced by different calls in stream order.
+size_t partials_doubles(const wafer_batch *b, int rows) { return std::max((size_t)b->gsp.doubles(rows), b->n2_doubles); }
 
 int ensure_gs(wafer_batch *b)
 {
     if (b->gs_scal) return WAFER_OK;
     const size_t nsc = (size_t)b->gs_stride * b->n;
-    const size_t npart = chain_partials_doubles(b);
+    const size_t npart = partials_doubles(b, 1);
     HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * npart));
     HIP_TRY(hipHostMalloc((void **)&b->gs_host, sizeof(double) * nsc, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->gs_scal, sizeof(double) * nsc));
     HIP_TRY(hipMemsetAsync(b->gs_scal, 0, sizeof(double) * nsc, b->s));
     return WAFER_OK;
 }
-
-// what the chain's and the one-pass form's kernel arguments share.  One shape (A: WaferBatchGsArgs, WaferBatchGsOneArgs): the one
-// geometry, its 64 x 4 tiles, and the member stride of the store slots.  Several (the ...Mixed types): the device table; the rest
-// is in the member records.
-template <typename A>
-A gs_args(const wafer_batch *b, const WaferGeom &g, int flip)
-{
-    A a;
-    a.g = g;
-    a.ntx = (a.g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-    a.nty = (a.g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    a.flip = flip;
-    a.scal_stride = b->gs_stride;
-    a.mstride = a.g.total;
-    return a;
-}
-template <typename A>
-A gs_args(const wafer_batch *b, const WaferBatchGeomTable &gt, int flip)
-{
-    A a;
-    memset(&a, 0, sizeof a);
-    a.geoms = gt.geoms;
-    a.flip = flip;
-    a.scal_stride = b->gs_stride;
-    return a;
-}
-WaferBatchGsArgs chain_args(const wafer_batch *b, const WaferGeom &g, int flip) { return gs_args<WaferBatchGsArgs>(b, g, flip); }
-WaferBatchGsArgsMixed chain_args(const wafer_batch *b, const WaferBatchGeomTable &gt, int flip) { return gs_args<WaferBatchGsArgsMixed>(b, gt, flip); }
 
 // the grid's extent along x: the largest partition among the members in list (one shape: everyone's)
 int gs_max_nb(const wafer_batch *b, const int *list, int n)
@@ -495,11 +461,8 @@ int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int l
 {
     const int max_nb = gs_max_nb(b, b->act_host, nact);
     const hipError_t e = with_geom(b, [&](const auto &gs) {
-        auto a = chain_args(b, gs, flip);
-        a.coef_slot = coef_slot;
-        a.lower = lower >= 0 ? slot_arg(b, (uint32_t)lower) : nullptr;
-        a.dotwith = dotwith >= 0 ? slot_arg(b, (uint32_t)dotwith) : nullptr;
-        return wafer_entry_batch_gs(b->f32, mode, a, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, out_slot, b->gs_partials, b->s);
+        const WaferBatchGsArgs a{flip, b->gs_stride, coef_slot, lower >= 0 ? b->slots[lower] : nullptr, dotwith >= 0 ? b->slots[dotwith] : nullptr};
+        return wafer_entry_batch_gs(b->f32, mode, gs, a, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, out_slot, b->gs_partials, b->s);
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram-Schmidt launch failed: %s", hipGetErrorString(e));
     return WAFER_OK;
@@ -509,21 +472,13 @@ int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int l
 // the launch path's predicate: which form a call with this wnum takes
 bool use_onepass(const wafer_batch *b, uint32_t wnum) { return b->gs_variant == 1 && wnum >= 1 && wnum <= WAFER_MAX_LOW; }
 
-// bytes of gs_partials under the one-pass form: WAFER_GS_ONE_ROWS rows per member (or the float norm2's partition, if wider)
-size_t onepass_partials_bytes(const wafer_batch *b)
-{
-    if (b->mixed)   // every member's own rows end to end; the row walk's partials (float storage) lie in the same buffer from 0 on
-        return sizeof(double) * std::max((size_t)b->gsp.doubles(WAFER_GS_ONE_ROWS), (size_t)(b->mem[b->n - 1].n2_off + b->mem[b->n - 1].n2_nb));
-    return sizeof(double) * std::max((size_t)WAFER_GS_ONE_ROWS * (size_t)b->gs_nb, (size_t)b->n2_nb) * b->n;
-}
-
 // gs_partials grown to the sums kernel's rows, and the Gram storage; every member's matrix is stale
 int ensure_onepass(wafer_batch *b)
 {
     if (b->onepass_ready) return WAFER_OK;
     TRY(ensure_gs(b));
     double *wider = nullptr;   // (the new buffer first: a failed allocation leaves the sequential form's partials in place)
-    HIP_TRY(hipMalloc((void **)&wider, onepass_partials_bytes(b)));
+    HIP_TRY(hipMalloc((void **)&wider, sizeof(double) * partials_doubles(b, WAFER_GS_ONE_ROWS)));
     const hipError_t e = hipStreamSynchronize(b->s);   // no launch in flight writes the partials that go back
     if (e != hipSuccess) {
         (void)hipFree(wider);
@@ -543,19 +498,14 @@ int ensure_onepass(wafer_batch *b)
     return WAFER_OK;
 }
 
-template <typename A>
-A with_slots(const wafer_batch *b, A a, uint32_t nslots)
+// the one-pass kernels' arguments: the allocations of store slots [0, nslots)
+WaferBatchGsOneArgs onepass_args(const wafer_batch *b, int flip, uint32_t nslots)
 {
-    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? slot_arg(b, l) : nullptr;
+    WaferBatchGsOneArgs a;
+    a.flip = flip;
+    a.scal_stride = b->gs_stride;
+    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? b->slots[l] : nullptr;
     return a;
-}
-WaferBatchGsOneArgs onepass_args(const wafer_batch *b, const WaferGeom &g, int flip, uint32_t nslots)
-{
-    return with_slots(b, gs_args<WaferBatchGsOneArgs>(b, g, flip), nslots);
-}
-WaferBatchGsOneArgsMixed onepass_args(const wafer_batch *b, const WaferBatchGeomTable &gt, int flip, uint32_t nslots)
-{
-    return with_slots(b, gs_args<WaferBatchGsOneArgsMixed>(b, gt, flip), nslots);
 }
 
 // the Gram matrices of the active members whose stores changed since they were formed: one launch and its reduce, in stream
@@ -577,7 +527,7 @@ int refresh_gram(wafer_batch *b, const uint8_t *active)
     HIP_TRY(hipMemcpyAsync(b->gram_list_dev, b->gram_list_host, sizeof(int) * 2 * nlist, hipMemcpyHostToDevice, b->s));
     const int max_nb = gs_max_nb(b, b->gram_list_host, nlist);
     const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_gram(b->f32, nl, onepass_args(b, gs, 0, (uint32_t)nl), b->mem_dev, b->gram_list_dev, b->gram_list_dev + nlist, nlist,
+        return wafer_entry_batch_gram(b->f32, nl, gs, onepass_args(b, 0, (uint32_t)nl), b->mem_dev, b->gram_list_dev, b->gram_list_dev + nlist, nlist,
                                       max_nb, b->gram, b->gram_partials, b->s);
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram matrix launch failed: %s", hipGetErrorString(e));
@@ -589,7 +539,7 @@ int gs_onepass(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise
 {
     const int max_nb = gs_max_nb(b, b->act_host, nact);
     const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, onepass_args(b, gs, flip, wnum), b->mem_dev, b->act_dev, nact, max_nb,
+        return wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, gs, onepass_args(b, flip, wnum), b->mem_dev, b->act_dev, nact, max_nb,
                                             b->gs_scal, b->gram, b->gs_partials, b->s);
     });
     if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched one-pass Gram-Schmidt launch failed: %s", hipGetErrorString(e));
@@ -891,20 +841,15 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
     if (target == WAFER_RESAMPLE_POTENTIAL)
         for (uint32_t m = 0; m < b->n; ++m)
             if (!active || active[m]) b->views[m]->v_ysym = false;
-    int max_tiles = 0, max_planes = 0;   // of the padded boxes: the kernel writes the frame's zeros too
-    for (int k = 0; k < nact; ++k) {
-        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
-        max_tiles = std::max(max_tiles, ((g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
-        max_planes = std::max(max_planes, g.lz);
-    }
-    const int ntx = (b->g().px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;   // (one shape: every member's tiles along x)
+    int max_tiles, max_planes;   // of the padded boxes: the kernel writes the frame's zeros too
+    max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
     void *dst0 = target == WAFER_RESAMPLE_PHI ? b->alloc[0] : target == WAFER_RESAMPLE_POTENTIAL ? b->alloc[2]
                : target == WAFER_RESAMPLE_POTSUB ? b->alloc[3] : b->slots[idx];
     void *dst1 = target == WAFER_RESAMPLE_PHI ? b->alloc[1] : dst0;
     {
         RoctxRange range_("wafer_batch_resample");
         const hipError_t e = with_geom(b, [&](const auto &gs) {
-            return wafer_entry_batch_trilerp(b->f32, !host && b->f32, gs, b->mem_dev, b->act_dev, nact, ntx, max_tiles, max_planes, src, dst0, dst1,
+            return wafer_entry_batch_trilerp(b->f32, !host && b->f32, gs, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, src, dst0, dst1,
                                              target == WAFER_RESAMPLE_PHI, basis, b->s);
         });
         if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched resample launch failed: %s", hipGetErrorString(e));
@@ -946,7 +891,7 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
 // Every member's partition record and the places of its partials.  Observables: the partition wafer_launch_observables_lds gives a
 // single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
 // (WaferLdsCfg::TX), and the z-chunk that follows from them -- with its [4][obs_nb] partials end to end (one shape: member m's at
-// m * 4 * obs_nb, as the single-shape kernels index them).  norm2: n2_nb workgroups, the partials end to end likewise.
+// m * 4 * obs_nb).  norm2: n2_nb workgroups, the partials end to end likewise.  The kernels read all of it from the records.
 int init_partitions(wafer_batch *b)
 {
     const int R = b->g().R;
@@ -956,7 +901,7 @@ int init_partitions(wafer_batch *b)
     b->swz = wafer_lds_opts(b->tune).swz;
     b->mem.resize(b->n);
     b->gsp = wafer_batch_gs_partition(b->geoms.data(), b->shape_of.data(), b->n, WAFER_BATCH_TX, WAFER_BATCH_TY, WAFER_GS_ZC);
-    size_t obs_total = 0, n2_total = 0;
+    size_t obs_total = 0;
     for (uint32_t m = 0; m < b->n; ++m) {
         WaferBatchMember &e = b->mem[m];
         memset(&e, 0, sizeof e);
@@ -975,12 +920,12 @@ int init_partitions(wafer_batch *b)
         e.obs_nb = e.obs_ntx * e.obs_nty * ((g.nzl + e.obs_zchunk - 1) / e.obs_zchunk);
         e.n2_nb = b->f32 ? wafer_rownorm2_blocks(g, (int)b->esz, b->num_cus) : wafer_gs_blocks(g);
         e.obs_off = (long long)obs_total;
-        e.n2_off = (long long)n2_total;
+        e.n2_off = (long long)b->n2_doubles;
         e.gs_nb = b->gsp.nb[m];
         e.gs_off = b->gsp.first[m];
         e.slot_off = (long long)b->off[m] + g.base_off;
         obs_total += 4 * (size_t)e.obs_nb;
-        n2_total += (size_t)e.n2_nb;
+        b->n2_doubles += (size_t)e.n2_nb;
     }
     HIP_TRY(hipMalloc((void **)&b->partials, sizeof(double) * obs_total));
     return WAFER_OK;
@@ -1074,8 +1019,6 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     b->f32 = f32;
     b->esz = esz;
     b->nst.assign(n_members, 0);
-    b->gs_nb = wafer_gs_blocks(b->g());
-    b->n2_nb = f32 ? wafer_rownorm2_blocks(b->g(), (int)esz, b->num_cus) : 0;
     for (uint32_t m = 0; m < n_members; ++m) b->gs_stride = std::max(b->gs_stride, 1 + (int)members[m].max_states);
     if (b->mixed) {
         static const char *const types[] = {"double,double", "float,double", "float,float"};
@@ -1454,20 +1397,18 @@ int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n)
     // what the one-pass form allocated on first use: the Gram matrices, their partials, the member lists, and the growth of gs_partials
     const size_t onepass_bytes = !b->onepass_ready ? 0
         : sizeof(double) * (WAFER_MAX_LOW * WAFER_MAX_LOW * (size_t)b->n + (size_t)b->gsp.doubles(WAFER_GRAM_PAIRS)) + sizeof(int) * 2 * b->n +
-              onepass_partials_bytes(b) - sizeof(double) * chain_partials_doubles(b);
+              sizeof(double) * (partials_doubles(b, WAFER_GS_ONE_ROWS) - partials_doubles(b, 1));
     char kernels[320];
-    char Tm[40], Tc[40];   // the kernels' type lists: several shapes name the table-reading instantiations
-    snprintf(Tm, sizeof Tm, "%s%s", T, b->mixed_states ? ",WaferBatchGsOneArgsMixed" : "");
-    snprintf(Tc, sizeof Tc, "%s%s", T, b->mixed_states ? ",WaferBatchGsArgsMixed" : "");
+    const char *GS = b->mixed_states ? ",WaferBatchGeomTable" : "";   // several shapes name the table-reading instantiations
     int launches = 1;
     const bool onepass = use_onepass(b, wnum);
     if (onepass) {
         launches = 4;
-        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs_sums<%u,%s>+wafer_k_batch_gs_reduce_sums%s+wafer_k_batch_gs_apply<%u,%s,true%s>",
-                 wnum, Tm, b->mixed_states ? "<false,true>" : "", wnum, T, b->mixed_states ? ",WaferBatchGsOneArgsMixed" : "");
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs_sums<%u,%s%s>+wafer_k_batch_gs_reduce_sums+wafer_k_batch_gs_apply<%u,%s,true%s>",
+                 wnum, T, GS, wnum, T, GS);
     } else if (wnum) {
         launches = 1 + 2 * (1 + (int)wnum) + 1;
-        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs<NORM2|SCALE|AXPY,%s>+wafer_k_batch_gs_reduce%s", Tc, b->mixed_states ? "_mixed" : "");
+        snprintf(kernels, sizeof kernels, "wafer_k_batch_step+wafer_k_batch_gs<NORM2|SCALE|AXPY,%s%s>+wafer_k_batch_gs_reduce", T, GS);
     } else {
         snprintf(kernels, sizeof kernels, "wafer_k_batch_step");
     }

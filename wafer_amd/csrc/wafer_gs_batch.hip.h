@@ -10,10 +10,15 @@
 //   wafer_k_batch_gs<AXPY>                               phi -= lower_{wnum-1} s_{wnum-1}
 // 1 + 2 (1 + wnum) + 1 launches, whatever the number of members.
 //
-// Determinism and independence: the partition of a member is fixed by the geometry alone -- tiles of 64 x 4 work cells, chunks
-// of WAFER_GS_ZC planes, one partial per workgroup at partials[member * nb + workgroup] -- and the reduce sums a member's nb
-// partials in wafer_k_reduce's order.  The grid is (nb, active members): which other members run, how many there are and where
-// the member sits in the batch change blockIdx.y and nothing a sum sees.  No floating-point atomics.
+// Determinism and independence: the partition of a member is fixed by its geometry alone -- tiles of 64 x 4 work cells, chunks
+// of WAFER_GS_ZC planes, gs_nb workgroups, one partial per workgroup at partials[gs_off + workgroup] (one shape: gs_off ==
+// member * gs_nb) -- and the reduce sums a member's gs_nb partials in wafer_k_reduce's order.  The grid is (the largest gs_nb
+// among the launched members, active members): which other members run, how many there are and where the member sits in the
+// batch change blockIdx.y and nothing a sum sees.  No floating-point atomics.
+//
+// One shape or several: the kernels take the geometry source GS first (wafer_batch_geom, wafer_stencil_batch.hip.h -- the one
+// place the two instantiations differ) and everything that depends on the member from its WaferBatchMember record: gs_nb, gs_off,
+// and slot_off, its logical origin in a store slot's allocation.  The slot pointers in the arguments are the ALLOCATIONS.
 //
 // Work cells only: frame cells are zero in phi and in every stored state, so the reference's whole-padded-array sums agree.
 // Per cell the arithmetic is the single context's (wafer_k_row_op): x / sqrt(norm2) by wafer_div_invariant, x - l * s unfused.
@@ -33,78 +38,63 @@
 enum { WAFER_GS_NORM2 = 0, WAFER_GS_DOT = 1, WAFER_GS_SCALE = 2, WAFER_GS_AXPY = 3 };
 
 struct WaferBatchGsArgs {
-    WaferGeom g;
-    int ntx, nty;               // tiles of 64 x 4 work cells per plane
     int flip;                   // the wavefunction of member m is phi[m.cur ^ flip]
     int scal_stride;            // doubles per member in scal
     int coef_slot;              // SCALE: norm2 at scal[member * scal_stride + coef_slot]; AXPY: the overlap with `lower`
-    long long mstride;          // elements per member in a store slot's allocation
-    const void *lower;          // AXPY: the state to project out (member 0's logical pointer, of the storage type), else unused
-    const void *dotwith;        // DOT, SCALE, AXPY: the state whose overlap with the resulting phi is summed; null: none
-};
-
-// A batch of several shapes (wafer_batch_norm2 on doubles, and every excited-state call of a batch made by
-// wafer_batch_create_mixed_states): the geometry comes from the device table, the tile counts from it, the member's workgroup
-// count, the place of its partials and its place in a store slot from its record (WaferBatchMember::gs_nb, gs_off, slot_off);
-// a.g, a.ntx, a.nty and a.mstride are not read, and lower / dotwith are the slot's ALLOCATION, not member 0's logical pointer.
-struct WaferBatchGsArgsMixed : WaferBatchGsArgs {
-    const WaferGeom *geoms;
+    const void *lower;          // AXPY: the store slot to project out (its allocation, of the storage type), else unused
+    const void *dotwith;        // DOT, SCALE, AXPY: the store slot whose overlap with the resulting phi is summed; null: none
 };
 
 // workgroups per member
 static inline int wafer_gs_blocks(const WaferGeom &g) { return wafer_gs_blocks_of(g, WAFER_BATCH_TX, WAFER_BATCH_TY, WAFER_GS_ZC); }
 
-// What a workgroup of these kernels works on, for either argument type A (one text below).  One shape: the tile counts and the
-// member stride are kernel arguments, every member has gridDim.x workgroups and `rows` rows of that many partials from
-// member * rows * gridDim.x on.  Several shapes (A has `geoms`): the tile counts follow from the member's geometry, its place in a
-// slot, its workgroup count and the start of its partials from its record.  A partial of row q lies at p0 + q * nb + blockIdx.x.
-struct WaferBatchGsOneArgs;   // (the one-pass form's arguments, below)
-template <typename A> inline constexpr bool wafer_gs_mixed = !std::is_same_v<A, WaferBatchGsArgs> && !std::is_same_v<A, WaferBatchGsOneArgs>;
-template <typename A>
-__device__ __forceinline__ decltype(auto) wafer_gs_geom(const A &a, int shape)
-{
-    if constexpr (wafer_gs_mixed<A>) return WaferGeom(a.geoms[__builtin_amdgcn_readfirstlane(shape)]);   // scalar loads, once, before any loop
-    else return (a.g);
-}
+// What a workgroup of these kernels works on: the tile counts of its member's geometry and, from the member's record, its
+// workgroup count, its place in a store slot and the start of its `rows` rows of partials (wafer_batch_gs_partition,
+// wafer_batch_plan.h).  A partial of row q lies at p0 + q * nb + blockIdx.x.
 struct WaferGsPart {
     int ntx, nty, nb;
     long long moff;   // the member's element offset from the slot pointers of the arguments
     size_t p0;
 };
-// false: the workgroup lies beyond its member's partition and leaves as a whole (before any barrier)
-template <typename A>
-__device__ __forceinline__ bool wafer_gs_part(const A &a, const WaferGeom &g, const WaferBatchMember &m, int member, int rows, WaferGsPart &w)
+// A workgroup beyond its member's partition (blockIdx.x >= nb, on a grid as wide as a larger member needs) has its z-chunk past
+// the member's last plane -- nb == ntx * nty * ceil(nzl / WAFER_GS_ZC), wafer_gs_blocks_of -- so the plane predicate `in` of the
+// kernels below is false for each of its planes: it loads and stores no cell.  The summing kernels send it away as a whole with
+// wafer_gs_beyond BEHIND that body: before the barrier of the block sum, and before it could write a partial outside its
+// member's rows.  Not at the top: a test of the record's gs_nb there put the act -> record loads and a branch in front of
+// everything else the prologue does (the geometry's loads, the tile divisions), two more dependent scalar round trips per
+// workgroup, measured as +1 % per excited step of a one-shape batch of 32 x 64^3 ("One member addressing").
+__device__ __forceinline__ void wafer_gs_part(const WaferGeom &g, const WaferBatchMember &m, int rows, WaferGsPart &w)
 {
-    if constexpr (wafer_gs_mixed<A>) {
-        if ((int)blockIdx.x >= m.gs_nb) return false;
-        w.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-        w.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-        w.nb = m.gs_nb;
-        w.moff = m.slot_off;
-        w.p0 = (size_t)m.gs_off * rows;
-    } else {
-        w.ntx = a.ntx;
-        w.nty = a.nty;
-        w.nb = gridDim.x;
-        w.moff = (long long)member * a.mstride;
-        w.p0 = (size_t)member * rows * gridDim.x;
-    }
-    return true;
+    w.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    w.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
+    w.nb = m.gs_nb;
+    w.moff = m.slot_off;
+    w.p0 = (size_t)m.gs_off * rows;
+}
+__device__ __forceinline__ bool wafer_gs_beyond(const WaferGsPart &w) { return (int)blockIdx.x >= w.nb; }
+
+// The wavefunction of member m at step parity `flip`, phi[(cur ^ flip) & 1]: both pointers are loaded beside cur and one is
+// selected, where a load indexed by cur would be one more dependent scalar round trip in front of the workgroup's first vector load.
+template <typename T>
+__device__ __forceinline__ T *wafer_gs_phi(const WaferBatchMember &m, int flip)
+{
+    void *const p0 = m.phi[0], *const p1 = m.phi[1];
+    return static_cast<T *>(((m.cur ^ flip) & 1) ? p1 : p0);
 }
 
-// Block (64, 4), grid (wafer_gs_blocks, active members).
-template <int MODE, typename T = double, typename A = WaferBatchGsArgs>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs(A a, const WaferBatchMember *__restrict__ mem,
+// Block (64, 4), grid (the largest gs_nb among the launched members, active members).
+template <int MODE, typename T = double, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs(GS gs, WaferBatchGsArgs a, const WaferBatchMember *__restrict__ mem,
                                                         const int *__restrict__ act, const double *__restrict__ scal,
                                                         double *__restrict__ partials)
 {
     __shared__ double red[4];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
-    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
     WaferGsPart wg;
-    if (!wafer_gs_part(a, g, m, member, 1, wg)) return;
-    T *__restrict__ phi = static_cast<T *>(m.phi[(m.cur ^ a.flip) & 1]);
+    wafer_gs_part(g, m, 1, wg);
+    T *__restrict__ phi = wafer_gs_phi<T>(m, a.flip);
     const long long moff = wg.moff;
     const T *__restrict__ lower = (MODE == WAFER_GS_AXPY) ? static_cast<const T *>(a.lower) + moff : nullptr;
     const T *__restrict__ dotw = (MODE != WAFER_GS_NORM2 && a.dotwith) ? static_cast<const T *>(a.dotwith) + moff : nullptr;
@@ -142,29 +132,20 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs(A a, const WaferBatchMem
             else acc += d[k] * x;                                                   // grid.rs:482-487
         }
     }
+    if (wafer_gs_beyond(wg)) return;
     if (MODE == WAFER_GS_NORM2 || a.dotwith) {   // (uniform: a kernel argument)
         const double s = wafer_block_sum<4>(acc, red, tid);
         if (tid == 0) partials[wg.p0 + blockIdx.x] = s;
     }
 }
 
-// wafer_k_reduce for every active member at once: block `slot` sums the n partials of member act[slot] in wafer_k_reduce's
-// order into scal[member * scal_stride + out_slot].
-static __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce(const double *__restrict__ partials, const int *__restrict__ act,
-                                                                      int n, double *__restrict__ scal, int scal_stride, int out_slot)
-{
-    __shared__ double sh[256];
-    const int member = act[blockIdx.x];
-    const double s = wafer_batch_reduce_tree(partials + (size_t)member * n, n, sh);
-    if (threadIdx.x == 0) scal[(size_t)member * scal_stride + out_slot] = s;
-}
-
-// several shapes: the member's own partials, at its own offset -- ROWWALK: the n2_nb of the row-walk norm2 (float storage) at
-// n2_off; else the gs_nb of wafer_k_batch_gs at gs_off (on doubles the two partitions are one)
+// wafer_k_reduce for every active member at once: block `slot` sums the partials of member act[slot] in wafer_k_reduce's order
+// into scal[member * scal_stride + out_slot] -- the member's own partials, at its own offset.  ROWWALK: the n2_nb of the row-walk
+// norm2 (float storage) at n2_off; else the gs_nb of wafer_k_batch_gs at gs_off (on doubles the two partitions are one).
 template <bool ROWWALK>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_mixed(const double *__restrict__ partials, const int *__restrict__ act,
-                                                                     const WaferBatchMember *__restrict__ mem, double *__restrict__ scal,
-                                                                     int scal_stride, int out_slot)
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce(const double *__restrict__ partials, const int *__restrict__ act,
+                                                               const WaferBatchMember *__restrict__ mem, double *__restrict__ scal,
+                                                               int scal_stride, int out_slot)
 {
     __shared__ double sh[256];
     const int member = act[blockIdx.x];
@@ -174,11 +155,12 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_mixed(const doubl
 }
 
 // wafer_batch_norm2 on float storage: get_norm_squared on the partition of a single context's wafer_norm2 -- wafer_k_row_op<T, double, 0>
-// (wafer_elementwise.hip.h) on the row walk, four waves per workgroup, 16 bytes per lane, gridDim.x = wafer_rownorm2_blocks workgroups
-// per member, each lane adding the squares of its cells in the same order, the same wafer_block_sum, one partial per workgroup at
-// partials[member * gridDim.x + workgroup]; wafer_k_batch_gs_reduce then sums them in wafer_k_reduce's order.  So the double is
-// the one wafer_norm2 returns for a context of that dtype.  The partition follows the shape, the element size and the device's CU
-// count: nothing of the batch (B, index, active set).  Grid (wafer_rownorm2_blocks, members), block 256.
+// (wafer_elementwise.hip.h) on the row walk over the whole slab (local planes [G, G + nzl)), four waves per workgroup, 16 bytes per
+// lane, the walk dealt over the member's own n2_nb = wafer_rownorm2_blocks workgroups, each lane adding the squares of its cells in
+// the same order, the same wafer_block_sum, one partial per workgroup at partials[n2_off + workgroup] (one shape: n2_off ==
+// member * n2_nb); wafer_k_batch_gs_reduce<true> then sums them in wafer_k_reduce's order.  So the double is the one wafer_norm2
+// returns for a context of that dtype.  The partition follows the shape, the element size and the device's CU count: nothing of
+// the batch (B, index, active set).  Grid (the largest n2_nb among the launched members, members), block 256.
 static inline int wafer_rownorm2_blocks(const WaferGeom &g, int esz, int num_cus)   // launch_row_op's grid (wafer_engine_schedules.hip)
 {
     const long long segs = (long long)g.nzl * g.ny * ((g.nx + 1024 / esz - 1) / (1024 / esz));
@@ -186,32 +168,19 @@ static inline int wafer_rownorm2_blocks(const WaferGeom &g, int esz, int num_cus
     return (int)(nb > 1 ? nb : 1);
 }
 
-// Several shapes (A = WaferBatchGeomTable): the walk is dealt over the member's own n2_nb workgroups (wafer_rownorm2_blocks of ITS
-// shape), gridDim.x is the largest among the launched members, and the partials lie at partials[n2_off + workgroup].
-__device__ __forceinline__ const WaferGeom &wafer_row_geom(const WaferRowArgs &a, int) { return a.g; }
-__device__ __forceinline__ WaferGeom wafer_row_geom(const WaferBatchGeomTable &a, int shape) { return wafer_batch_geom(a, shape); }
-
-template <typename T, typename A = WaferRowArgs>
-__global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(A a, const WaferBatchMember *__restrict__ mem,
+template <typename T, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(GS gs, const WaferBatchMember *__restrict__ mem,
                                                               const int *__restrict__ act, double *__restrict__ partials)
 {
     using VT = typename WaferRowVec<T>::type;
     constexpr int VEC = WaferRowVec<T>::N;
-    constexpr bool MIXED = std::is_same_v<A, WaferBatchGeomTable>;
     __shared__ double red[4];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
-    const WaferGeom &g = wafer_row_geom(a, m.shape);
-    int nb = gridDim.x, lz_lo, lz_hi;
-    if constexpr (MIXED) {
-        nb = m.n2_nb;
-        if ((int)blockIdx.x >= nb) return;
-        lz_lo = g.G;
-        lz_hi = g.G + g.nzl;
-    } else {
-        lz_lo = a.lz_lo;
-        lz_hi = a.lz_hi;
-    }
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
+    const int nb = m.n2_nb;
+    if ((int)blockIdx.x >= nb) return;
+    const int lz_lo = g.G, lz_hi = g.G + g.nzl;
     const T *__restrict__ phi = static_cast<const T *>(m.phi[m.cur]);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nsegx = (g.nx + 64 * VEC - 1) / (64 * VEC);
@@ -228,11 +197,7 @@ __global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(A a, const WaferBa
     }
     WAFER_ROW_WALK_END(g)
     const double s = wafer_block_sum<4>(acc, red, threadIdx.x);
-    if constexpr (MIXED) {
-        if (threadIdx.x == 0) partials[(size_t)m.n2_off + blockIdx.x] = s;
-    } else {
-        if (threadIdx.x == 0) partials[(size_t)member * gridDim.x + blockIdx.x] = s;
-    }
+    if (threadIdx.x == 0) partials[(size_t)m.n2_off + blockIdx.x] = s;
 }
 
 // ---- the one-pass form (wafer_batch_set_gs_variant(b, 1), wnum <= WAFER_MAX_LOW) ---------------------------------------------------
@@ -244,42 +209,34 @@ __global__ __launch_bounds__(256) void wafer_k_batch_rownorm2(A a, const WaferBa
 //   wafer_k_batch_gs_apply<NLOW>            norm = sqrt(scal[0]), s_j = t_j / norm - sum_{i<j} s_i G_ji (every thread, identically),
 //                                           x = phi' / norm, x = x - l_j s_j (j = 0 .. NLOW-1, unfused), one store
 // Bytes per cell on doubles: 24 (step) + 8 (1 + wnum) (sums) + 8 (2 + wnum) (apply), against 48 + 32 wnum of the chain.
-// The partition is the chain's (tiles of 64 x 4 work cells x WAFER_GS_ZC planes, grid (wafer_gs_blocks, active members)), a
-// partial lies at partials[(member * (1 + WAFER_MAX_LOW) + q) * nb + workgroup], and a member's Gram matrix at
+// The partition is the chain's (tiles of 64 x 4 work cells x WAFER_GS_ZC planes, gs_nb workgroups per member), a partial of row
+// q lies at partials[gs_off * (1 + WAFER_MAX_LOW) + q * gs_nb + workgroup], and a member's Gram matrix at
 // gram[member * WAFER_MAX_LOW^2 + j * WAFER_MAX_LOW + i] (i < j) is summed over the same partition (wafer_k_batch_gram): nothing a
 // sum sees depends on B, the member's index or the active set.  No floating-point atomics.
 // Float storage: every operand widened, every operation fp64; phi is rounded to float ONCE per step after the step kernel's own
 // store -- at the apply kernel's store -- where the chain rounds it 1 + wnum times.  Not the chain's bits on any dtype: the
 // overlaps are formed by the recurrence instead of on the projected phi (rel ~1e-16 on the scalars).
 struct WaferBatchGsOneArgs {
-    WaferGeom g;
-    int ntx, nty;                       // tiles of 64 x 4 work cells per plane
     int flip;                           // the wavefunction of member m is phi[m.cur ^ flip]
     int scal_stride;                    // doubles per member in scal
-    long long mstride;                  // elements per member in a store slot's allocation
-    const void *low[WAFER_MAX_LOW];     // store slot j (member 0's logical pointer, of the storage type)
-};
-
-// several shapes: as WaferBatchGsArgsMixed -- a.g, a.ntx, a.nty, a.mstride are not read, low[] are the slots' ALLOCATIONS
-struct WaferBatchGsOneArgsMixed : WaferBatchGsOneArgs {
-    const WaferGeom *geoms;
+    const void *low[WAFER_MAX_LOW];     // store slot j (its allocation, of the storage type)
 };
 
 #define WAFER_GS_ONE_ROWS (1 + WAFER_MAX_LOW)                        // partial rows per member of the sums kernel
 #define WAFER_GRAM_PAIRS (WAFER_MAX_LOW * (WAFER_MAX_LOW - 1) / 2)   // partial rows per member of the Gram kernel
 
-// Block (64, 4), grid (wafer_gs_blocks, active members).  All loads of a lane before the arithmetic: 4 planes x (1 + NLOW) arrays.
-template <int NLOW, typename T, typename A = WaferBatchGsOneArgs>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(A a, const WaferBatchMember *__restrict__ mem,
+// Block (64, 4), grid (largest gs_nb, active members).  All loads of a lane before the arithmetic: 4 planes x (1 + NLOW) arrays.
+template <int NLOW, typename T, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(GS gs, WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
                                                              const int *__restrict__ act, double *__restrict__ partials)
 {
     __shared__ double red[4];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
-    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
     WaferGsPart wg;
-    if (!wafer_gs_part(a, g, m, member, WAFER_GS_ONE_ROWS, wg)) return;
-    const T *__restrict__ phi = static_cast<const T *>(m.phi[(m.cur ^ a.flip) & 1]);
+    wafer_gs_part(g, m, WAFER_GS_ONE_ROWS, wg);
+    const T *__restrict__ phi = wafer_gs_phi<T>(m, a.flip);
     const long long moff = wg.moff;
     const int bid = blockIdx.x;
     const int i = (bid % wg.ntx) * WAFER_BATCH_TX + threadIdx.x;
@@ -308,6 +265,7 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(A a, const WaferBat
             for (int s = 0; s < NLOW; ++s) acc[1 + s] += l[s][k] * w[k];   // grid.rs:482-487 on the un-normalised phi'
         }
     }
+    if (wafer_gs_beyond(wg)) return;
 #pragma unroll
     for (int q = 0; q <= NLOW; ++q) {
         const double s = wafer_block_sum<4>(acc[q], red, tid);
@@ -315,18 +273,18 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_sums(A a, const WaferBat
     }
 }
 
-// Block (64, 4), grid (wafer_gs_blocks, active members).  NORMALISE = false (wafer_batch_orthogonalise): no division, norm = 1.
-template <int NLOW, typename T, bool NORMALISE, typename A = WaferBatchGsOneArgs>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(A a, const WaferBatchMember *__restrict__ mem,
+// Block (64, 4), grid (largest gs_nb, active members).  NORMALISE = false (wafer_batch_orthogonalise): no division, norm = 1.
+template <int NLOW, typename T, bool NORMALISE, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(GS gs, WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
                                                               const int *__restrict__ act, const double *__restrict__ scal,
                                                               const double *__restrict__ gram)
 {
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
-    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
     WaferGsPart wg;
-    if (!wafer_gs_part(a, g, m, member, 0, wg)) return;
-    T *__restrict__ phi = static_cast<T *>(m.phi[(m.cur ^ a.flip) & 1]);
+    wafer_gs_part(g, m, 0, wg);   // (no sum, no barrier: a workgroup beyond the member's partition falls through the `in` predicates)
+    T *__restrict__ phi = wafer_gs_phi<T>(m, a.flip);
     const long long moff = wg.moff;
     const double *__restrict__ sc = scal + (size_t)member * a.scal_stride;
     const double *__restrict__ gm = gram + (size_t)member * (WAFER_MAX_LOW * WAFER_MAX_LOW);
@@ -366,19 +324,20 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_apply(A a, const WaferBa
 }
 
 // G_ji = sum l_j l_i, i < j < cnt[blockIdx.y] <= NL, of the members in list: every stored state read once, all pairs formed.
-// Partial row q = j (j - 1) / 2 + i at partials[(member * WAFER_GRAM_PAIRS + q) * nb + workgroup]; rows with j >= the member's
-// count come out zero.  Block (64, 4), grid (wafer_gs_blocks, listed members).  mem: the member table (read on several shapes only).
-template <int NL, typename T, typename A = WaferBatchGsOneArgs>
-__global__ __launch_bounds__(256) void wafer_k_batch_gram(A a, const WaferBatchMember *__restrict__ mem, const int *__restrict__ list,
-                                                          const int *__restrict__ cnt, double *__restrict__ partials)
+// Partial row q = j (j - 1) / 2 + i at partials[gs_off * WAFER_GRAM_PAIRS + q * gs_nb + workgroup]; rows with j >= the member's
+// count come out zero.  Block (64, 4), grid (largest gs_nb, listed members).
+template <int NL, typename T, typename GS = WaferGeom>
+__global__ __launch_bounds__(256) void wafer_k_batch_gram(GS gs, WaferBatchGsOneArgs a, const WaferBatchMember *__restrict__ mem,
+                                                          const int *__restrict__ list, const int *__restrict__ cnt,
+                                                          double *__restrict__ partials)
 {
     __shared__ double red[4];
     constexpr int NP = NL * (NL - 1) / 2;
     const int member = list[blockIdx.y], count = cnt[blockIdx.y];
     const WaferBatchMember &m = mem[member];
-    const WaferGeom &g = wafer_gs_geom(a, m.shape);
+    const WaferGeom &g = wafer_batch_geom(gs, m.shape);
     WaferGsPart wg;
-    if (!wafer_gs_part(a, g, m, member, WAFER_GRAM_PAIRS, wg)) return;
+    wafer_gs_part(g, m, WAFER_GRAM_PAIRS, wg);
     const long long moff = wg.moff;
     const int bid = blockIdx.x;
     const int i = (bid % wg.ntx) * WAFER_BATCH_TX + threadIdx.x;
@@ -405,6 +364,7 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gram(A a, const WaferBatchM
 #pragma unroll
                 for (int ii = 0; ii < jj; ++ii) acc[jj * (jj - 1) / 2 + ii] += l[jj][k] * l[ii][k];
     }
+    if (wafer_gs_beyond(wg)) return;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         const double s = wafer_block_sum<4>(acc[q], red, tid);
@@ -412,19 +372,19 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gram(A a, const WaferBatchM
     }
 }
 
-// wafer_k_reduce for every listed member and partial row at once: block (slot, q) sums the n partials of row q of member
-// act[slot] in wafer_k_reduce's order.  GRAM = false: `rows` = WAFER_GS_ONE_ROWS, into out[member * out_stride + q] (the scalars);
-// GRAM = true: `rows` = WAFER_GRAM_PAIRS, row q = j (j - 1) / 2 + i into out[member * out_stride + j * WAFER_MAX_LOW + i].
-// MIXED (several shapes): n is not read; the member's gs_nb partials per row, its rows from gs_off * rows on (mem: the member table).
-template <bool GRAM, bool MIXED = false>
-__global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double *__restrict__ partials, const int *__restrict__ act, int n,
+// wafer_k_reduce for every listed member and partial row at once: block (slot, q) sums the gs_nb partials of row q of member
+// act[slot], its rows from gs_off * rows on, in wafer_k_reduce's order.  GRAM = false: `rows` = WAFER_GS_ONE_ROWS, into
+// out[member * out_stride + q] (the scalars); GRAM = true: `rows` = WAFER_GRAM_PAIRS, row q = j (j - 1) / 2 + i into
+// out[member * out_stride + j * WAFER_MAX_LOW + i].
+template <bool GRAM>
+__global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double *__restrict__ partials, const int *__restrict__ act,
                                                                     int rows, double *__restrict__ out, int out_stride,
                                                                     const WaferBatchMember *__restrict__ mem)
 {
     __shared__ double sh[256];
     const int member = act[blockIdx.x], q = blockIdx.y;
-    if constexpr (MIXED) n = mem[member].gs_nb;
-    const double *p = MIXED ? partials + (size_t)mem[member].gs_off * rows + (size_t)q * n : partials + ((size_t)member * rows + q) * n;
+    const int n = mem[member].gs_nb;
+    const double *p = partials + (size_t)mem[member].gs_off * rows + (size_t)q * n;
     double s = 0.0;
     for (int r = threadIdx.x; r < n; r += 256) s += p[r];
     sh[threadIdx.x] = s;
@@ -444,23 +404,23 @@ __global__ __launch_bounds__(256) void wafer_k_batch_gs_reduce_sums(const double
     out[(size_t)member * out_stride + slot] = sh[0];
 }
 
-// entry points (wafer_tu_gs_batch.hip).  One elementwise launch of `mode` over the active members and, where it sums
-// (NORM2, or dotwith given), the reduce into scal[member * scal_stride + out_slot].  f32: float storage.
-// Each entry point once per argument type: one shape (wafer_tu_gs_batch.hip; max_nb == wafer_gs_blocks of the one geometry) and
-// several (the ...Mixed arguments, wafer_tu_gs_batch_mixed.hip; max_nb: the largest gs_nb among the launched members, the grid's extent).
-hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgs &a, const WaferBatchMember *mem, const int *act, int nact, int max_nb,
-                                double *scal, int out_slot, double *partials, hipStream_t s);
-hipError_t wafer_entry_batch_gs(bool f32, int mode, const WaferBatchGsArgsMixed &a, const WaferBatchMember *mem, const int *act, int nact, int max_nb,
-                                double *scal, int out_slot, double *partials, hipStream_t s);
-// the one-pass form: sums, reduce and apply (normalise: evolve; else orthogonalise) over the members in act.  1 <= nlow <= WAFER_MAX_LOW;
-// partials holds WAFER_GS_ONE_ROWS * wafer_gs_blocks doubles per member of the batch, gram WAFER_MAX_LOW^2.
-hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem,
-                                        const int *act, int nact, int max_nb, double *scal, const double *gram, double *partials, hipStream_t s);
-hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const WaferBatchGsOneArgsMixed &a, const WaferBatchMember *mem,
-                                        const int *act, int nact, int max_nb, double *scal, const double *gram, double *partials, hipStream_t s);
-// the Gram matrices of the nlist members in list (cnt: states of each, 2 <= cnt <= nl <= WAFER_MAX_LOW) into gram; partials holds
-// WAFER_GRAM_PAIRS * wafer_gs_blocks doubles per member of the batch
-hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem, const int *list, const int *cnt,
-                                  int nlist, int max_nb, double *gram, double *partials, hipStream_t s);
-hipError_t wafer_entry_batch_gram(bool f32, int nl, const WaferBatchGsOneArgsMixed &a, const WaferBatchMember *mem, const int *list, const int *cnt,
-                                  int nlist, int max_nb, double *gram, double *partials, hipStream_t s);
+// entry points (wafer_tu_gs_batch.inc), each once per geometry source GS like WAFER_BATCH_ENTRIES (wafer_tu_gs_batch.hip: WaferGeom,
+// wafer_tu_gs_batch_mixed.hip: WaferBatchGeomTable).  f32: float storage.  max_nb: the largest gs_nb among the launched members,
+// the grid's extent.
+// gs: one elementwise launch of `mode` over the active members and, where it sums (NORM2, or dotwith given), the reduce into
+// scal[member * scal_stride + out_slot].
+// gs_onepass: sums, reduce and apply (normalise: evolve; else orthogonalise) over the members in act.  1 <= nlow <= WAFER_MAX_LOW;
+// partials holds WAFER_GS_ONE_ROWS * gs_nb doubles per member of the batch, gram WAFER_MAX_LOW^2.
+// gram: the Gram matrices of the nlist members in list (cnt: states of each, 2 <= cnt <= nl <= WAFER_MAX_LOW) into gram; partials
+// holds WAFER_GRAM_PAIRS * gs_nb doubles per member of the batch.
+#define WAFER_BATCH_GS_ENTRIES(GS)                                                                                                                   \
+    hipError_t wafer_entry_batch_gs(bool f32, int mode, const GS &gs, const WaferBatchGsArgs &a, const WaferBatchMember *mem, const int *act,        \
+                                    int nact, int max_nb, double *scal, int out_slot, double *partials, hipStream_t s);                              \
+    hipError_t wafer_entry_batch_gs_onepass(bool f32, int nlow, bool normalise, const GS &gs, const WaferBatchGsOneArgs &a,                         \
+                                            const WaferBatchMember *mem, const int *act, int nact, int max_nb, double *scal, const double *gram,    \
+                                            double *partials, hipStream_t s);                                                                        \
+    hipError_t wafer_entry_batch_gram(bool f32, int nl, const GS &gs, const WaferBatchGsOneArgs &a, const WaferBatchMember *mem, const int *list,   \
+                                      const int *cnt, int nlist, int max_nb, double *gram, double *partials, hipStream_t s);
+WAFER_BATCH_GS_ENTRIES(WaferGeom)
+WAFER_BATCH_GS_ENTRIES(WaferBatchGeomTable)
+#undef WAFER_BATCH_GS_ENTRIES

@@ -33,20 +33,18 @@ struct WaferResampleSource {
 // left non-zero (wafer_k_potential and the uploads write it whole).
 // The target array: dst0 (an allocation laid out as the batch's arrays are; the member's origin is WaferBatchMember::slot_off),
 // or, with by_cur, dst1 for a member whose current phi buffer is 1.  basis: WAFER_BASIS_PADDED (0) the padded size, WAFER_BASIS_WORK
-// (1) the work size.  Several shapes: the grid has the largest tile and plane counts among the launched members, and a workgroup
-// beyond its member's own leaves as a whole before any load.  No LDS, no scratch.
+// (1) the work size.  The grid has the largest tile and plane counts among the launched members, and a workgroup beyond its
+// member's own leaves as a whole before any load.  No LDS, no scratch.
 template <typename T = double, typename S = double, typename GS = WaferGeom>
 static __global__ __launch_bounds__(256) void wafer_k_batch_trilerp(GS gs, const WaferBatchMember *__restrict__ mem,
-                                                                    const int *__restrict__ act, int ntx, WaferResampleSource src,
+                                                                    const int *__restrict__ act, WaferResampleSource src,
                                                                     void *dst0, void *dst1, int by_cur, int basis)
 {
     const int member = __builtin_amdgcn_readfirstlane(act[blockIdx.z]);
     const WaferBatchMember &m = mem[member];
     const WaferGeom &g = wafer_batch_geom(gs, m.shape);
-    if constexpr (wafer_batch_mixed<GS>) {
-        ntx = (g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-        if ((int)blockIdx.y >= g.lz || (int)blockIdx.x >= ntx * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
-    }
+    const int ntx = (g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    if ((int)blockIdx.y >= g.lz || (int)blockIdx.x >= ntx * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
     const int xp = (blockIdx.x % ntx) * WAFER_BATCH_TX + threadIdx.x;
     const int yp = (blockIdx.x / ntx) * WAFER_BATCH_TY + threadIdx.y;
     const int lzp = blockIdx.y;
@@ -64,10 +62,10 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_trilerp(GS gs, const
 }
 
 // entry points (wafer_tu_batch.inc), once per geometry source.  f32: float storage; src_f32: the source holds floats (a member of
-// a float batch; a host source is always double).  ntx: the tiles along x of the padded box of one shape; max_tiles and max_planes
-// count tiles and planes of the padded boxes of the launched members.
+// a float batch; a host source is always double).  max_tiles and max_planes count tiles and planes of the padded boxes of the
+// launched members.
 #define WAFER_BATCH_RESAMPLE_ENTRY(GS)                                                                                                              \
-    hipError_t wafer_entry_batch_trilerp(bool f32, bool src_f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx,      \
+    hipError_t wafer_entry_batch_trilerp(bool f32, bool src_f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact,               \
                                          int max_tiles, int max_planes, const WaferResampleSource &src, void *dst0, void *dst1, int by_cur,         \
                                          int basis, hipStream_t s);
 WAFER_BATCH_RESAMPLE_ENTRY(WaferGeom)

@@ -37,8 +37,9 @@ struct WaferBatchMember {
     int short_forms;         // v_in_range && the plan is checked (WaferStepArgs::v_in_range of a single context)
     int potsub_kind;
     int cur;                 // which phi buffer holds the wavefunction
-    // read by the kernels of a batch of several shapes only (WaferBatchGeomTable below)
-    int shape;               // the member's entry in the batch's table of distinct geometries
+    // what depends on the member beside its arrays, for every batch, one shape or several: the kernels below take a member's
+    // partition, its workgroup count, the place of its partials and its place in a store slot from here and from nowhere else
+    int shape;               // the member's entry in the batch's table of distinct geometries (one shape: 0, not read -- wafer_batch_geom)
     int obs_ntx, obs_nty, obs_zchunk, obs_nb;   // its observables partition: a single context's of that shape
     int n2_nb;               // workgroups of its wafer_batch_norm2 (wafer_rownorm2_blocks on float storage, wafer_gs_blocks on doubles)
     long long obs_off;       // where its [4][obs_nb] partials begin in the observables' partials buffer (doubles)
@@ -53,7 +54,11 @@ struct WaferBatchMember {
 // kernel argument -- a batch of one shape.  WaferBatchGeomTable: the batch's table of distinct geometries in device memory,
 // indexed by the workgroup's shape index -- a batch of several shapes.  The index is workgroup-uniform (it comes from the
 // workgroup's table entry or its member record), so the copy below is scalar loads into SGPRs, made once before any loop.
-// Everything after that copy is one text for both.
+// Everything after that copy is one text for both: this function is the ONLY place where the two instantiations of a batched
+// kernel differ.  Whatever depends on the member comes from its WaferBatchMember record; gridDim.x is the grid's extent (the
+// largest count among the launched members), and a workgroup at or beyond its member's own count leaves as a whole before any
+// load or barrier -- which never happens on one shape, where every member's count is the extent.  (The excited-state kernels place
+// that exit behind a body whose plane predicate already keeps such a workgroup from touching a cell: wafer_gs_part.)
 struct WaferBatchGeomTable {
     const WaferGeom *geoms;
 };
@@ -62,7 +67,6 @@ __device__ __forceinline__ WaferGeom wafer_batch_geom(const WaferBatchGeomTable 
 {
     return t.geoms[__builtin_amdgcn_readfirstlane(shape)];
 }
-template <typename GS> inline constexpr bool wafer_batch_mixed = !std::is_same_v<GS, WaferGeom>;
 
 // the member's division by c dn^2 m in the arithmetic type C (wafer_den of a single context's WaferStepArgs)
 template <typename C>
@@ -315,31 +319,24 @@ __global__ __launch_bounds__(256) void wafer_k_batch_stepk(GS gs, const WaferBat
 
 // compute_observables (grid.rs:303-445) for the members act[blockIdx.y], on the partition of the single context's observables
 // launch (wafer_launch_observables_lds: NW waves x RY = 2 rows x VEC cells per lane -- 16 bytes of the storage type T: 2 doubles,
-// 4 floats -- so tiles of 64 VEC x 2 NW, i.e. 128 x 2 NW (fp64) or 256 x 2 NW (float storage), z-chunks of `zchunk` planes,
-// gridDim.x workgroups per member, swizzled as wafer_k_step_lds swizzles them).  Float values are widened; every product and sum
-// is fp64, as in the context's kernel (its C is double for every dtype).  partials[(member * 4 + q) *
-// gridDim.x + workgroup]: the four sums energy, norm2, pot_sub, r2.
-// Several shapes (GS = WaferBatchGeomTable): the partition is the member's own (WaferBatchMember::obs_*: ntx, nty, zchunk and nb
-// workgroups, what a context of ITS shape gets), gridDim.x is the largest nb among the launched members, a workgroup beyond its
-// member's nb leaves as a whole before any load or barrier, and the partials lie at partials[obs_off + q * nb + workgroup].
+// 4 floats -- so tiles of 64 VEC x 2 NW, i.e. 128 x 2 NW (fp64) or 256 x 2 NW (float storage), z-chunks of obs_zchunk planes,
+// swizzled as wafer_k_step_lds swizzles them).  Float values are widened; every product and sum is fp64, as in the context's
+// kernel (its C is double for every dtype).
+// The partition is the member's own (WaferBatchMember::obs_*: ntx, nty, zchunk and nb workgroups, what a context of ITS shape
+// gets), gridDim.x is the largest nb among the launched members, and the four sums energy, norm2, pot_sub, r2 of a workgroup lie
+// at partials[obs_off + q * nb + workgroup] (one shape: obs_off == member * 4 * nb).
 template <int R, int NW, typename T = double, typename GS = WaferGeom>
 __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(GS gs, const WaferBatchMember *__restrict__ mem,
-                                                                     const int *__restrict__ act, int ntx, int nty, int zchunk,
-                                                                     int swz, double *__restrict__ partials)
+                                                                     const int *__restrict__ act, int swz, double *__restrict__ partials)
 {
     constexpr int VEC = 16 / (int)sizeof(T), RY = 2, TX = 64 * VEC, TY = NW * RY;
     __shared__ double red[NW];
     const int member = act[blockIdx.y];
     const WaferBatchMember &m = mem[member];
     const WaferGeom &g = wafer_batch_geom(gs, m.shape);
-    int nb = gridDim.x;   // workgroups of this member
-    if constexpr (wafer_batch_mixed<GS>) {
-        nb = m.obs_nb;
-        if ((int)blockIdx.x >= nb) return;
-        ntx = m.obs_ntx;
-        nty = m.obs_nty;
-        zchunk = m.obs_zchunk;
-    }
+    const int nb = m.obs_nb;   // workgroups of this member
+    if ((int)blockIdx.x >= nb) return;
+    const int ntx = m.obs_ntx, nty = m.obs_nty, zchunk = m.obs_zchunk;
     int bid = blockIdx.x;
     if (swz) bid = wafer_xcd_tile(bid, nb);
     const int tx_i = bid % ntx;
@@ -394,16 +391,12 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_observables(GS gs, cons
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const double s = wafer_block_sum<NW>(sums[q], red, tid);
-        if constexpr (wafer_batch_mixed<GS>) {
-            if (tid == 0) partials[(size_t)m.obs_off + (size_t)q * nb + blockIdx.x] = s;
-        } else {
-            if (tid == 0) partials[((size_t)member * 4 + q) * gridDim.x + blockIdx.x] = s;
-        }
+        if (tid == 0) partials[(size_t)m.obs_off + (size_t)q * nb + blockIdx.x] = s;
     }
 }
 
-// wafer_k_reduce for every active member at once: block (q, slot) sums the n partials of quantity q of member act[slot] in
-// wafer_k_reduce's order into out[member * 4 + q].
+// wafer_k_reduce for every active member at once: block (q, slot) sums the obs_nb partials of quantity q of member act[slot],
+// from its obs_off on, in wafer_k_reduce's order into out[member * 4 + q].
 // wafer_k_reduce's order over the n doubles at p, by one workgroup of 256 threads: the sum, valid in thread 0
 template <typename I>
 __device__ __forceinline__ double wafer_batch_reduce_tree(const double *__restrict__ p, I n, double *sh)
@@ -421,17 +414,7 @@ __device__ __forceinline__ double wafer_batch_reduce_tree(const double *__restri
 }
 
 static __global__ __launch_bounds__(256) void wafer_k_batch_reduce(const double *__restrict__ partials, const int *__restrict__ act,
-                                                                   long long n, double *__restrict__ out)
-{
-    __shared__ double sh[256];
-    const int member = act[blockIdx.y];
-    const double s = wafer_batch_reduce_tree(partials + ((size_t)member * 4 + blockIdx.x) * n, n, sh);
-    if (threadIdx.x == 0) out[(size_t)member * 4 + blockIdx.x] = s;
-}
-
-// several shapes: the member's own nb partials per quantity, at its own offset
-static __global__ __launch_bounds__(256) void wafer_k_batch_reduce_mixed(const double *__restrict__ partials, const int *__restrict__ act,
-                                                                         const WaferBatchMember *__restrict__ mem, double *__restrict__ out)
+                                                                   const WaferBatchMember *__restrict__ mem, double *__restrict__ out)
 {
     __shared__ double sh[256];
     const int member = act[blockIdx.y];
@@ -442,20 +425,18 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_reduce_mixed(const d
 
 // normalise_wavefunction (grid.rs:465-468) of the members act[blockIdx.z]: phi /= sqrt(norm2[member * n2_stride]), the
 // expression of wafer_k_row_op<2> (the quotient in fp64, rounded to the storage type).  Block (64, 4) over a 64 x 4 tile of one
-// work plane (blockIdx.y).  Several shapes: the grid has the largest tile and plane counts among the launched members, and a
-// workgroup beyond its member's own leaves as a whole.
+// work plane (blockIdx.y).  The grid has the largest tile and plane counts among the launched members, and a workgroup beyond its
+// member's own leaves as a whole.
 template <typename T = double, typename GS = WaferGeom>
 static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, const WaferBatchMember *__restrict__ mem,
-                                                                      const int *__restrict__ act, int ntx,
+                                                                      const int *__restrict__ act,
                                                                       const double *__restrict__ norm2, int n2_stride)
 {
     const int member = act[blockIdx.z];
     const WaferBatchMember &m = mem[member];
     const WaferGeom &g = wafer_batch_geom(gs, m.shape);
-    if constexpr (wafer_batch_mixed<GS>) {
-        ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-        if ((int)blockIdx.y >= g.nzl || (int)blockIdx.x >= ntx * ((g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
-    }
+    const int ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    if ((int)blockIdx.y >= g.nzl || (int)blockIdx.x >= ntx * ((g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
     const int i = (blockIdx.x % ntx) * WAFER_BATCH_TX + threadIdx.x;
     const int j = (blockIdx.x / ntx) * WAFER_BATCH_TY + threadIdx.y;
     if (i >= g.nx || j >= g.ny) return;
@@ -471,19 +452,17 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_normalise(GS gs, con
 // context's grid.  The other buffer is scratch between steps, so the kernel writes the whole box: the new value inside the frame,
 // zero on it -- what a context gets from clearing the allocation first (the guard rows and planes and the row pads outside the box
 // are zeros from creation on and nothing writes them: DESIGN.md section 5).  The constraint is workgroup-uniform (a scalar load).
-// Several shapes: the grid has the largest tile and plane counts among the launched members, and a workgroup beyond its member's
-// own leaves as a whole before any load.
+// The grid has the largest tile and plane counts among the launched members, and a workgroup beyond its member's own leaves as a
+// whole before any load.
 template <typename T = double, typename GS = WaferGeom>
 static __global__ __launch_bounds__(256) void wafer_k_batch_symmetrise(GS gs, const WaferBatchMember *__restrict__ mem,
-                                                                       const int *__restrict__ act, const int *__restrict__ sym, int ntx)
+                                                                       const int *__restrict__ act, const int *__restrict__ sym)
 {
     const int member = __builtin_amdgcn_readfirstlane(act[blockIdx.z]);
     const WaferBatchMember &m = mem[member];
     const WaferGeom &g = wafer_batch_geom(gs, m.shape);
-    if constexpr (wafer_batch_mixed<GS>) {
-        ntx = (g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-        if ((int)blockIdx.y >= g.lz || (int)blockIdx.x >= ntx * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
-    }
+    const int ntx = (g.px + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
+    if ((int)blockIdx.y >= g.lz || (int)blockIdx.x >= ntx * ((g.py + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY)) return;
     const int cons = __builtin_amdgcn_readfirstlane(sym[member]);
     const int axis = cons <= 2 ? 0 : 1;                     // AboutZ, AntisymAboutZ | AboutY, AntisymAboutY
     const double sign = (cons & 1) ? 1.0 : -1.0;            // the odd constraints are the symmetric ones
@@ -502,11 +481,10 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_symmetrise(GS gs, co
 // (float storage, fp64 arithmetic), 2 f32fast (float storage, float arithmetic in the ground-state step).  f32 is true for float
 // storage (dtype 1 and 2 alike: observables and normalise compute in fp64).
 // stepk: the fused pass of K steps; hipErrorInvalidValue where wafer_batch_stepk_lds_bytes(dtype, R, K) is 0 (no such instantiation).
-// observables, normalise: ntx, nty, zchunk are the partition of every launched member of a batch of one shape (several shapes: not
-// read, the kernels take each member's own from its record and geometry); max_*: the largest per-member count among the launched
-// members -- the grid's extent, and for one shape every member's count.
-// symmetrise: sym[member] is the member's WAFER_SYM_* constraint; ntx the tiles along x of the PADDED box of one shape; max_tiles and
-// max_planes count tiles and planes of the padded boxes (px x py, lz).
+// observables, normalise: max_*: the largest per-member count among the launched members -- the grid's extent, and for one shape
+// every member's count.
+// symmetrise: sym[member] is the member's WAFER_SYM_* constraint; max_tiles and max_planes count tiles and planes of the padded
+// boxes (px x py, lz).
 // norm2 (wafer_batch_norm2; kernels: wafer_gs_batch.hip.h): norm2 of the members in act into scal[member * scal_stride + out_slot], each
 // on its own partition of WaferBatchMember::n2_nb workgroups -- float storage: wafer_k_batch_rownorm2 on a single context's wafer_norm2
 // partition, the same double; doubles: wafer_k_batch_gs<NORM2>.  partials holds every member's n2_nb doubles, end to end.
@@ -515,11 +493,11 @@ static __global__ __launch_bounds__(256) void wafer_k_batch_symmetrise(GS gs, co
                                       int flip, hipStream_t s);                                                                                      \
     hipError_t wafer_entry_batch_stepk(int dtype, int R, int K, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks,           \
                                        int nblocks, int flip, hipStream_t s);                                                                        \
-    hipError_t wafer_entry_batch_observables(bool f32, int R, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int nty, \
-                                             int zchunk, int max_nb, int swz, double *partials, double *out, hipStream_t s);                        \
-    hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int max_tiles,    \
+    hipError_t wafer_entry_batch_observables(bool f32, int R, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb,         \
+                                             int swz, double *partials, double *out, hipStream_t s);                                                \
+    hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_tiles,             \
                                            int max_planes, const double *norm2, int n2_stride, hipStream_t s);                                      \
-    hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, const int *sym, int ntx,  \
+    hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, const int *sym,           \
                                             int max_tiles, int max_planes, hipStream_t s);                                                           \
     hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb, double *scal,     \
                                        int scal_stride, int out_slot, double *partials, hipStream_t s);

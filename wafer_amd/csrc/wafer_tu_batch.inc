@@ -3,14 +3,12 @@
 // a batch of one shape, a kernel argument) or WaferBatchGeomTable (wafer_tu_batch_mixed.hip: the device table of a batch of
 // several shapes), and gets the wafer_entry_batch_* overloads that take that type.  For each dtype -- 0 f64 <double, double>,
 // 1 f32 <float, double> (float storage, fp64 arithmetic), 2 f32fast <float, float> (float arithmetic in the ground-state step).
-#include <string.h>
 #include "wafer_gs_batch.hip.h"
 #include "wafer_resample_batch.hip.h"
 
 namespace {
 
 using GS = WAFER_TU_BATCH_GS;
-constexpr bool MIXED = wafer_batch_mixed<GS>;
 
 template <typename T, typename C>
 hipError_t launch_step(int R, const GS &gs, const WaferBatchMember *mem, const WaferBatchBlock *blocks, int nblocks, int flip, hipStream_t s)
@@ -40,51 +38,17 @@ hipError_t launch_stepk(int R, int K, const GS &gs, const WaferBatchMember *mem,
 }
 
 template <typename T>
-hipError_t launch_observables(int R, const GS &gs, const WaferBatchMember *mem, const int *act, dim3 grid, int ntx, int nty, int zchunk,
-                              int swz, double *partials, hipStream_t s)
+hipError_t launch_observables(int R, const GS &gs, const WaferBatchMember *mem, const int *act, dim3 grid, int swz, double *partials,
+                              hipStream_t s)
 {
     // the waves per workgroup of wafer_launch_observables_lds: 8 (ThreePoint / FivePoint), 4 (SevenPoint)
     switch (R) {
-    case 1: hipLaunchKernelGGL((wafer_k_batch_observables<1, 8, T, GS>), grid, dim3(512), 0, s, gs, mem, act, ntx, nty, zchunk, swz, partials); break;
-    case 2: hipLaunchKernelGGL((wafer_k_batch_observables<2, 8, T, GS>), grid, dim3(512), 0, s, gs, mem, act, ntx, nty, zchunk, swz, partials); break;
-    case 3: hipLaunchKernelGGL((wafer_k_batch_observables<3, 4, T, GS>), grid, dim3(256), 0, s, gs, mem, act, ntx, nty, zchunk, swz, partials); break;
+    case 1: hipLaunchKernelGGL((wafer_k_batch_observables<1, 8, T, GS>), grid, dim3(512), 0, s, gs, mem, act, swz, partials); break;
+    case 2: hipLaunchKernelGGL((wafer_k_batch_observables<2, 8, T, GS>), grid, dim3(512), 0, s, gs, mem, act, swz, partials); break;
+    case 3: hipLaunchKernelGGL((wafer_k_batch_observables<3, 4, T, GS>), grid, dim3(256), 0, s, gs, mem, act, swz, partials); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
-}
-
-// what the norm2 kernels take for each geometry source: the row walk's arguments over the whole slab, and the chain's arguments
-// with nothing but the geometry in them (the store fields are not read in NORM2 mode)
-WaferRowArgs row_args(const WaferGeom &g)
-{
-    WaferRowArgs ra;
-    ra.g = g;
-    ra.lz_lo = g.G;
-    ra.lz_hi = g.G + g.nzl;
-    return ra;
-}
-WaferBatchGeomTable row_args(const WaferBatchGeomTable &gt) { return gt; }
-
-WaferBatchGsArgs gs_norm2_args(const WaferGeom &g, int scal_stride)
-{
-    WaferBatchGsArgs a;
-    a.g = g;
-    a.ntx = (g.nx + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX;
-    a.nty = (g.ny + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY;
-    a.flip = 0;
-    a.scal_stride = scal_stride;
-    a.coef_slot = 0;
-    a.mstride = g.total;
-    a.lower = a.dotwith = nullptr;
-    return a;
-}
-WaferBatchGsArgsMixed gs_norm2_args(const WaferBatchGeomTable &gt, int scal_stride)
-{
-    WaferBatchGsArgsMixed a;
-    memset(&a, 0, sizeof a);
-    a.geoms = gt.geoms;
-    a.scal_stride = scal_stride;
-    return a;
 }
 
 } // namespace
@@ -107,49 +71,44 @@ hipError_t wafer_entry_batch_stepk(int dtype, int R, int K, const GS &gs, const 
     return hipErrorInvalidValue;
 }
 
-hipError_t wafer_entry_batch_observables(bool f32, int R, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int nty,
-                                         int zchunk, int max_nb, int swz, double *partials, double *out, hipStream_t s)
+hipError_t wafer_entry_batch_observables(bool f32, int R, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_nb, int swz,
+                                         double *partials, double *out, hipStream_t s)
 {
-    if (MIXED) ntx = nty = zchunk = 0;   // (the kernel takes them from the member's record)
     const dim3 grid((unsigned)max_nb, (unsigned)nact);
-    const hipError_t e = f32 ? launch_observables<float>(R, gs, mem, act, grid, ntx, nty, zchunk, swz, partials, s)
-                             : launch_observables<double>(R, gs, mem, act, grid, ntx, nty, zchunk, swz, partials, s);
+    const hipError_t e = f32 ? launch_observables<float>(R, gs, mem, act, grid, swz, partials, s)
+                             : launch_observables<double>(R, gs, mem, act, grid, swz, partials, s);
     if (e != hipSuccess) return e;
-    if constexpr (MIXED) hipLaunchKernelGGL(wafer_k_batch_reduce_mixed, dim3(4, (unsigned)nact), dim3(256), 0, s, partials, act, mem, out);
-    else hipLaunchKernelGGL(wafer_k_batch_reduce, dim3(4, (unsigned)nact), dim3(256), 0, s, partials, act, (long long)max_nb, out);
+    hipLaunchKernelGGL(wafer_k_batch_reduce, dim3(4, (unsigned)nact), dim3(256), 0, s, partials, act, mem, out);
     return hipGetLastError();
 }
 
-hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx, int max_tiles,
+hipError_t wafer_entry_batch_normalise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_tiles,
                                        int max_planes, const double *norm2, int n2_stride, hipStream_t s)
 {
-    if (MIXED) ntx = 0;   // (the kernel forms it from the member's geometry)
     const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
-    if (f32) hipLaunchKernelGGL((wafer_k_batch_normalise<float, GS>), grid, block, 0, s, gs, mem, act, ntx, norm2, n2_stride);
-    else hipLaunchKernelGGL((wafer_k_batch_normalise<double, GS>), grid, block, 0, s, gs, mem, act, ntx, norm2, n2_stride);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_normalise<float, GS>), grid, block, 0, s, gs, mem, act, norm2, n2_stride);
+    else hipLaunchKernelGGL((wafer_k_batch_normalise<double, GS>), grid, block, 0, s, gs, mem, act, norm2, n2_stride);
     return hipGetLastError();
 }
 
-hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, const int *sym, int ntx,
+hipError_t wafer_entry_batch_symmetrise(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, const int *sym,
                                         int max_tiles, int max_planes, hipStream_t s)
 {
-    if (MIXED) ntx = 0;   // (the kernel forms it from the member's geometry)
     const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
-    if (f32) hipLaunchKernelGGL((wafer_k_batch_symmetrise<float, GS>), grid, block, 0, s, gs, mem, act, sym, ntx);
-    else hipLaunchKernelGGL((wafer_k_batch_symmetrise<double, GS>), grid, block, 0, s, gs, mem, act, sym, ntx);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_symmetrise<float, GS>), grid, block, 0, s, gs, mem, act, sym);
+    else hipLaunchKernelGGL((wafer_k_batch_symmetrise<double, GS>), grid, block, 0, s, gs, mem, act, sym);
     return hipGetLastError();
 }
 
-hipError_t wafer_entry_batch_trilerp(bool f32, bool src_f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int ntx,
+hipError_t wafer_entry_batch_trilerp(bool f32, bool src_f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact,
                                      int max_tiles, int max_planes, const WaferResampleSource &src, void *dst0, void *dst1, int by_cur, int basis,
                                      hipStream_t s)
 {
-    if (MIXED) ntx = 0;   // (the kernel forms it from the member's geometry)
     if (src_f32 && !f32) return hipErrorInvalidValue;   // (a member source has the batch's storage type)
     const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
-    if (!f32) hipLaunchKernelGGL((wafer_k_batch_trilerp<double, double, GS>), grid, block, 0, s, gs, mem, act, ntx, src, dst0, dst1, by_cur, basis);
-    else if (src_f32) hipLaunchKernelGGL((wafer_k_batch_trilerp<float, float, GS>), grid, block, 0, s, gs, mem, act, ntx, src, dst0, dst1, by_cur, basis);
-    else hipLaunchKernelGGL((wafer_k_batch_trilerp<float, double, GS>), grid, block, 0, s, gs, mem, act, ntx, src, dst0, dst1, by_cur, basis);
+    if (!f32) hipLaunchKernelGGL((wafer_k_batch_trilerp<double, double, GS>), grid, block, 0, s, gs, mem, act, src, dst0, dst1, by_cur, basis);
+    else if (src_f32) hipLaunchKernelGGL((wafer_k_batch_trilerp<float, float, GS>), grid, block, 0, s, gs, mem, act, src, dst0, dst1, by_cur, basis);
+    else hipLaunchKernelGGL((wafer_k_batch_trilerp<float, double, GS>), grid, block, 0, s, gs, mem, act, src, dst0, dst1, by_cur, basis);
     return hipGetLastError();
 }
 
@@ -158,18 +117,15 @@ hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMembe
 {
     const dim3 grid((unsigned)max_nb, (unsigned)nact);
     if (f32) {
-        const auto a = row_args(gs);
-        hipLaunchKernelGGL((wafer_k_batch_rownorm2<float, decltype(row_args(gs))>), grid, dim3(256), 0, s, a, mem, act, partials);
-    } else {
-        const auto a = gs_norm2_args(gs, scal_stride);
-        hipLaunchKernelGGL((wafer_k_batch_gs<WAFER_GS_NORM2, double, decltype(gs_norm2_args(gs, scal_stride))>), grid,
-                           dim3(WAFER_BATCH_TX, WAFER_BATCH_TY), 0, s, a, mem, act, (const double *)scal, partials);
+        hipLaunchKernelGGL((wafer_k_batch_rownorm2<float, GS>), grid, dim3(256), 0, s, gs, mem, act, partials);
+    } else {   // the chain's NORM2 mode reads no store slot
+        const WaferBatchGsArgs a{0, scal_stride, 0, nullptr, nullptr};
+        hipLaunchKernelGGL((wafer_k_batch_gs<WAFER_GS_NORM2, double, GS>), grid, dim3(WAFER_BATCH_TX, WAFER_BATCH_TY), 0, s, gs, a, mem, act,
+                           (const double *)scal, partials);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if constexpr (MIXED) {
-        if (f32) hipLaunchKernelGGL(wafer_k_batch_gs_reduce_mixed<true>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
-        else hipLaunchKernelGGL(wafer_k_batch_gs_reduce_mixed<false>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
-    } else hipLaunchKernelGGL(wafer_k_batch_gs_reduce, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, max_nb, scal, scal_stride, out_slot);
+    if (f32) hipLaunchKernelGGL(wafer_k_batch_gs_reduce<true>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
+    else hipLaunchKernelGGL(wafer_k_batch_gs_reduce<false>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
     return hipGetLastError();
 }
