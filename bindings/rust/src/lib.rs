@@ -265,6 +265,14 @@ extern "C" {
     pub fn wafer_batch_resample_member(b: *mut wafer_batch, active: *const u8, target: c_int, idx: u32, src_member: u32, src_kind: c_int, src_idx: u32, basis: c_int) -> c_int;
     /// HIP-event time of the last resample call's upload, transpose and launch
     pub fn wafer_batch_last_resample_ms(b: *mut wafer_batch, ms: *mut f32) -> c_int;
+    /// set-up of every listed member (`active[m] != 0`, null: all) in one launch each; `potentials` / `ics` / `seeds`: `n_members` entries
+    pub fn wafer_batch_set_potentials_builtin(b: *mut wafer_batch, active: *const u8, potentials: *const c_int) -> c_int;
+    pub fn wafer_batch_set_initial_conditions(b: *mut wafer_batch, active: *const u8, ics: *const c_int, seeds: *const u64) -> c_int;
+    /// `wafer_download_array` / `wafer_get_potsub` of one member
+    pub fn wafer_batch_download_array(b: *mut wafer_batch, member: u32, array_id: c_int, out: *mut f64) -> c_int;
+    pub fn wafer_batch_get_potsub(b: *mut wafer_batch, member: u32, kind: *mut c_int, scalar: *mut f64) -> c_int;
+    pub fn wafer_batch_diag_member(b: *mut wafer_batch, member: u32, buf: *mut c_char, n: usize) -> c_int;
+    pub fn wafer_batch_diag_setup_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

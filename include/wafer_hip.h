@@ -533,6 +533,30 @@ int wafer_batch_set_potential_builtin(wafer_batch *b, uint32_t member, int poten
 int wafer_batch_set_potential_host(wafer_batch *b, uint32_t member, const double *v, int potsub_kind, double potsub_scalar,
                                    const double *potsub);
 int wafer_batch_set_initial_condition(wafer_batch *b, uint32_t member, int ic, uint64_t seed);
+/* Set-up of many members at once.  The members with active[m] != 0 (NULL: all) are LISTED; potentials / ics / seeds have n_members
+ * entries (WAFER_POT_*, WAFER_IC_*; seeds NULL: 0 for all), those of members not listed are not read.  Every listed member ends bit for
+ * bit as after wafer_batch_set_potential_builtin / wafer_batch_set_initial_condition on that member -- V (a, b where they exist), pot_sub
+ * kind, scalar and array, phi, and every flag -- on batches of one shape and of several, on every dtype; members not listed keep
+ * every bit.  The per-cell arithmetic is the context kernels' own (wafer_setup_batch.hip.h).
+ * Launches, whatever n_members and the shapes: potentials -- one that generates V, one for the pot_sub arrays if and only if a listed
+ * member is FullCornell, one range check, one read-back (a context pays two check launches, two read-backs and a synchronisation per
+ * member); initial conditions -- one launch, no read-back.  wafer_batch_diag_setup_counts counts them.
+ * All checks for all listed members run before anything is uploaded or launched, and a refused call changes nothing: a value outside
+ * its enum on a listed member is WAFER_ERR_INVALID, FromFile / FromScript WAFER_ERR_NOT_AVAILABLE with the context entry's message,
+ * each naming the member.  No listed member: WAFER_OK, nothing launched.  (WAFER_ERR_HIP behind the launch: V of the listed members
+ * is written and every one of them has v_ysym and v_in_range off -- the safe answers -- until its potential is set again.) */
+int wafer_batch_set_potentials_builtin(wafer_batch *b, const uint8_t *active, const int *potentials);
+int wafer_batch_set_initial_conditions(wafer_batch *b, const uint8_t *active, const int *ics, const uint64_t *seeds);
+/* wafer_download_array / wafer_get_potsub of one member: the arrays it evolves in (WAFER_ARRAY_*: V, a, b padded; pot_sub unpadded) */
+int wafer_batch_download_array(wafer_batch *b, uint32_t member, int array_id, double *out);
+int wafer_batch_get_potsub(wafer_batch *b, uint32_t member, int *kind, double *scalar);
+/* one line of key=value pairs from the member's own host record -- member= have_pot= have_phi= potsub_kind= v_in_range= v_ysym=
+ * short_forms= cur= states= -- launches nothing */
+int wafer_batch_diag_member(wafer_batch *b, uint32_t member, char *buf, size_t n);
+/* launches and read-backs of the batched set-up paths since creation: wafer_batch_set_potentials_builtin,
+ * wafer_batch_set_initial_conditions, and the one range check behind a wafer_batch_resample(_member) onto WAFER_RESAMPLE_POTENTIAL
+ * (its resampling launch is not counted) */
+int wafer_batch_diag_setup_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
 /* wafer_set_potsub for one member (after its potential is set): a potential_sub override, potential.rs:113-131 */
 int wafer_batch_set_potsub(wafer_batch *b, uint32_t member, int kind, double scalar, const double *potsub);
 int wafer_batch_upload_phi(wafer_batch *b, uint32_t member, const double *phi);
@@ -559,8 +583,9 @@ int wafer_batch_symmetrise(wafer_batch *b, const uint8_t *active, const int *con
  * basis: where the sample positions come from -- linspace(0, s - 1, basis size) per axis, the first n of them used.
  * WAFER_RESAMPLE_POTSUB needs the member's potential and WAFER_BASIS_WORK.
  * All checks for all listed members run before anything is uploaded or launched: a refused call changes nothing.
- * (A WAFER_ERR_HIP failure is not a refusal: behind the launch the listed arrays are written, and for WAFER_RESAMPLE_POTENTIAL the
- * per-member bookkeeping stops at the member whose range check failed; set the potential again.)
+ * WAFER_RESAMPLE_POTENTIAL ends in ONE range check for all listed members (one launch, one read-back), not one per member.
+ * (A WAFER_ERR_HIP failure is not a refusal: behind the launch the listed arrays are written, and for WAFER_RESAMPLE_POTENTIAL a
+ * failed range check leaves every listed member with v_ysym and v_in_range off, the safe answers; set the potential again.)
  * WAFER_ERR_INVALID: sx, sy or sz below 2, an unknown target / src_kind / basis, src_member out of range, a member source that is
  * itself a listed target in the same buffer (its phi onto its phi, its state l onto its state l).  WAFER_ERR_STATE: a member source
  * without phi or without state src_idx, and what the per-member rules above refuse.  An empty active set: WAFER_OK. */

@@ -37,7 +37,15 @@ host clock around B Contexts each calling set_potential_resampled(source) one af
 call.  --reps repetitions after one warm-up, every one listed; "ratio_host": ctx over batch, per repetition.  "parity": phi of the
 first and the last member after Batch.resample_phi(source) bit-identical to a Context's upload_phi_resampled.
 The lines are appended to profiles/batch_resample_rows.jsonl unless --out names another file.
---resample-contexts-only times the contexts alone (it runs on a tree without the batched call) and writes "ctx_host_ms" only."""
+--resample-contexts-only times the contexts alone (it runs on a tree without the batched call) and writes "ctx_host_ms" only.
+--setup B: a mode of its own -- B members (--sizes' first size, or cycling through --mixed's shapes) set up from nothing: "batched_ms":
+host clock around Batch.set_initial_conditions + Batch.set_potentials (one launch each, one range check and one read-back; the call
+returns when the device has finished), "per_member_ms": around the loops of set_initial_condition and set_potential over the members
+of the same batch -- the code path a batch has without the batched calls, unchanged.  Both write the same potentials (Harmonic, Coulomb,
+SimpleCornell, Cube in turn) and starts (Boolean, Gaussian, Constant, Coulomb).  The parts are listed too ("*_potentials_ms",
+"*_starts_ms": the starts alone do not wait for the device).  --reps repetitions after one warm-up of each, every one listed; "ratio":
+per_member over batched, per repetition; "parity": V and phi of the first and the last member bit-identical after either; "setup_counts":
+the launches and read-backs one batched repetition adds.  Appended to profiles/batch_setup_rows.jsonl unless --out names another file."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -261,6 +269,62 @@ def resample_row(shapes, B, sx, reps, ext=1, dtype="f64", contexts_only=False):
     return out
 
 
+SETUP_POTENTIALS = ["Harmonic", "Coulomb", "SimpleCornell", "Cube"]
+SETUP_STARTS = ["Boolean", "Gaussian", "Constant", "Coulomb"]
+
+
+def setup_row(shapes, B, reps, ext=1, dtype="f64"):
+    pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype)
+            for k in range(B)]
+    pots = [SETUP_POTENTIALS[k % 4] for k in range(B)]
+    starts = [SETUP_STARTS[k % 4] for k in range(B)]
+    seeds = [100 + k for k in range(B)]
+    out = {"mode": "setup", "shapes": [list(s) for s in shapes], "B": B, "reps": reps, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1],
+           "dtype": dtype, "potentials": SETUP_POTENTIALS, "starts": SETUP_STARTS}
+    keys = ("batched_ms", "batched_starts_ms", "batched_potentials_ms", "per_member_ms", "per_member_starts_ms", "per_member_potentials_ms")
+    for k in keys:
+        out[k] = []
+
+    def batched(b):
+        t0 = time.perf_counter()
+        b.set_initial_conditions(starts, seeds=seeds)
+        t1 = time.perf_counter()
+        b.set_potentials(pots)   # (its read-back waits for the stream: the starts have been written too)
+        t2 = time.perf_counter()
+        return 1e3 * (t2 - t0), 1e3 * (t1 - t0), 1e3 * (t2 - t1)
+
+    def per_member(b):
+        t0 = time.perf_counter()
+        for k in range(B):
+            b.set_initial_condition(k, starts[k], seed=seeds[k])
+        t1 = time.perf_counter()
+        for k in range(B):
+            b.set_potential(k, pots[k])   # (each reads V's range back: the last one waits for everything)
+        t2 = time.perf_counter()
+        return 1e3 * (t2 - t0), 1e3 * (t1 - t0), 1e3 * (t2 - t1)
+
+    def bits(b):
+        return [x.view(np.int64) for k in sorted({0, B - 1}) for x in (b.download_array(k, "v"), b.download_phi(k))]
+
+    with wafer_amd.Batch(pars, mixed_shapes=len(set(shapes)) > 1) as b:
+        batched(b)       # warm-up of each
+        per_member(b)
+        for _ in range(reps):   # (nothing but the timed calls in here: a download allocates and frees its staging buffer)
+            for key, val in zip(keys[:3], batched(b)):
+                out[key].append(val)
+            for key, val in zip(keys[3:], per_member(b)):
+                out[key].append(val)
+        c0 = b.setup_counts()
+        batched(b)
+        out["setup_counts"] = [x - y for x, y in zip(b.setup_counts(), c0)]
+        got = bits(b)
+        per_member(b)
+        out["parity"] = all(np.array_equal(x, y) for x, y in zip(got, bits(b)))
+        out["shapes_in_batch"] = b.num_shapes()
+    out["ratio"] = [p / q for p, q in zip(out["per_member_ms"], out["batched_ms"])]
+    return out
+
+
 def rounded(d):
     if isinstance(d, dict):
         return {k: rounded(v) for k, v in d.items()}
@@ -290,7 +354,18 @@ def main():
                     "calling set_potential_resampled (a mode of its own: --steps, --warmup, --wnum and the variants do not apply)")
     ap.add_argument("--reps", type=int, default=3, help="--resample: timed repetitions after one warm-up (default 3)")
     ap.add_argument("--resample-contexts-only", action="store_true", help="--resample: the contexts alone")
+    ap.add_argument("--setup", type=int, metavar="B", help="time Batch.set_initial_conditions + set_potentials on B members against the loops of "
+                    "per-member calls on the same batch (a mode of its own; --reps, --sizes or --mixed, --ext, --dtype apply)")
     a = ap.parse_args()
+    if a.setup:
+        if not a.out:
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_setup_rows.jsonl")
+        shapes = parse_shapes(a.mixed) if a.mixed else [(a.sizes[0],) * 3]
+        line = json.dumps(rounded(setup_row(shapes, a.setup, a.reps, a.ext, a.dtype)))
+        print(line, flush=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+        return
     if a.resample:
         if not a.out:   # this mode's rows have a place of their own
             a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_resample_rows.jsonl")

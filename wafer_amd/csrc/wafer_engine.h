@@ -237,6 +237,11 @@ int download_padded(wafer_ctx *c, double *host, void *dev);
 int ensure_ab(wafer_ctx *c);
 int refresh_ab(wafer_ctx *c);
 int check_v_range(wafer_ctx *c);
+// the four FullCornell host constants of a WaferPotArgs (mu_t, alphas_2pit, xi_coef, xi_fac), as wafer_set_potential_builtin forms them
+void pot_host_constants(double out[4]);
+// what wafer_set_potential_builtin records once V (and FullCornell's pot_sub array) of `potential` is written: pot_sub kind and
+// scalar, have_pot, x2_ready, vgen_type.  The range check comes after it.
+void builtin_potential_set(wafer_ctx *c, int potential);
 // ---- wafer_engine_schedules.hip
 enum { X2_SUM_SLOT = 18 };   // scal[18 .. 18 + 1 + 2k): the sums of a two-step pass
 enum { V_YSYM_SLOT = SCAL_SLOTS - 1 };   // scal[31]: the word wafer_k_v_ysym ORs into (check_v_range); no pass reaches it: wnum + 2 <= SCAL_SLOTS, the x2 sums end at 24

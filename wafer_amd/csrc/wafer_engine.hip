@@ -136,6 +136,40 @@ int check_v_range(wafer_ctx *c)
     return WAFER_OK;
 }
 
+// t = 1, xi = 0 (potential.rs:252-253)
+void pot_host_constants(double out[4])
+{
+    const double t = 1.0, xi = 0.0;
+    out[0] = host_mu(t);
+    out[1] = host_alphas(2. * WAFER_PI * t);
+    out[2] = 0.07 * std::pow(xi, 0.2);
+    out[3] = std::pow(1. + xi, -0.29);
+}
+
+void builtin_potential_set(wafer_ctx *c, int potential)
+{
+    // pot_sub: potential.rs:134-153 with 326-363
+    c->potsub_kind = WAFER_POTSUB_NONE;
+    c->potsub_scalar = 0.0;
+    if (potential == WAFER_POT_FULLCORNELL) {
+        c->potsub_kind = WAFER_POTSUB_ARRAY;
+    } else {
+        double s = 0.0;
+        if (potential == WAFER_POT_ELIPTICALCOULOMB) s = 1. / c->P.dn;   // potential.rs:359
+        if (potential == WAFER_POT_SIMPLECORNELL) s = 4.0 * c->P.mass;   // potential.rs:360
+        if (s > 0.0) { // potential.rs:148-152
+            c->potsub_kind = WAFER_POTSUB_SCALAR;
+            c->potsub_scalar = s;
+        }
+    }
+    c->have_pot = true;
+    c->x2_ready = 0;   // M_j = A l_j follows V
+    // the excited-state kernels can evaluate these instead of reading V (wafer_k_step_lds, VG)
+    c->vgen_type = (potential == WAFER_POT_COULOMB || potential == WAFER_POT_COMPLEXCOULOMB) ? WAFER_POT_COULOMB
+                   : (potential == WAFER_POT_HARMONIC || potential == WAFER_POT_COMPLEXHARMONIC) ? WAFER_POT_HARMONIC
+                   : (potential == WAFER_POT_SIMPLECORNELL) ? WAFER_POT_SIMPLECORNELL : 0;
+}
+
 } // namespace wafer_eng
 
 // ---------------------------------------------------------------------------
@@ -408,11 +442,12 @@ static WaferPotArgs pot_args(wafer_ctx *c, int type)
     a.g = c->g;
     a.type = type;
     a.dn = c->P.dn; a.dt = c->P.dt; a.mass = c->P.mass; a.sig = c->P.sig;
-    const double t = 1.0, xi = 0.0; // potential.rs:252-253
-    a.mu_t = host_mu(t);
-    a.alphas_2pit = host_alphas(2. * WAFER_PI * t);
-    a.xi_coef = 0.07 * std::pow(xi, 0.2);
-    a.xi_fac = std::pow(1. + xi, -0.29);
+    double k[4];
+    pot_host_constants(k);
+    a.mu_t = k[0];
+    a.alphas_2pit = k[1];
+    a.xi_coef = k[2];
+    a.xi_fac = k[3];
     return a;
 }
 
@@ -450,22 +485,8 @@ int wafer_set_potential_builtin(wafer_ctx *c, int potential)
         else
             hipLaunchKernelGGL((wafer_k_potsub_fullcornell<double>), g2, block, 0, c->s_main, a, as<double>(c->potsub));
         HIP_TRY(hipGetLastError());
-        c->potsub_kind = WAFER_POTSUB_ARRAY;
-    } else {
-        double s = 0.0;
-        if (potential == WAFER_POT_ELIPTICALCOULOMB) s = 1. / c->P.dn;   // potential.rs:359
-        if (potential == WAFER_POT_SIMPLECORNELL) s = 4.0 * c->P.mass;   // potential.rs:360
-        if (s > 0.0) { // potential.rs:148-152
-            c->potsub_kind = WAFER_POTSUB_SCALAR;
-            c->potsub_scalar = s;
-        }
     }
-    c->have_pot = true;
-    c->x2_ready = 0;   // M_j = A l_j follows V
-    // the excited-state kernels can evaluate these instead of reading V (wafer_k_step_lds, VG)
-    c->vgen_type = (potential == WAFER_POT_COULOMB || potential == WAFER_POT_COMPLEXCOULOMB) ? WAFER_POT_COULOMB
-                   : (potential == WAFER_POT_HARMONIC || potential == WAFER_POT_COMPLEXHARMONIC) ? WAFER_POT_HARMONIC
-                   : (potential == WAFER_POT_SIMPLECORNELL) ? WAFER_POT_SIMPLECORNELL : 0;
+    builtin_potential_set(c, potential);
     return check_v_range(c);
 }
 

@@ -7,7 +7,11 @@
 //
 // Each member is also a context VIEW: a wafer_ctx whose arrays are the member's slices of the batch's allocations and whose
 // stream is the batch's.  Potentials, initial conditions, uploads and downloads go through the context entry points on that
-// view, so a member is set up by the very code that sets up a single context.  The views own nothing.
+// view, so a member is set up by the very code that sets up a single context.  The views own nothing but the a, b arrays that
+// wafer_batch_download_array may have made (ensure_ab), which go back with the batch.
+// Set-up of many members at once (set_potentials, set_initial_conditions: wafer_setup_batch.hip.h) writes the same cells with the same
+// per-cell functions in one launch for all listed members, and every batched writer of V -- those and resample -- ends in ONE range
+// check for all listed members (check_v_listed) instead of a context's check_v_range per member.
 //
 // One dtype per batch (member 0's): f64, f32 (float arrays, fp64 arithmetic) or f32fast (float arrays, float arithmetic in the
 // ground-state step).  Every array and store slot is allocated in the element size `esz`, the geometry is the one a context of
@@ -35,6 +39,7 @@
 #include "wafer_stencil_batch.hip.h"
 #include "wafer_gs_batch.hip.h"
 #include "wafer_resample_batch.hip.h"
+#include "wafer_setup_batch.hip.h"
 
 struct wafer_batch {
     uint32_t n = 0;
@@ -105,6 +110,11 @@ struct wafer_batch {
     size_t rs_cap = 0;                        // doubles
     hipEvent_t rs_start = nullptr, rs_stop = nullptr;   // around the last call's upload, transpose and launch (wafer_batch_last_resample_ms)
     bool rs_timing_valid = false;
+    // batched set-up (wafer_setup_batch.hip.h): one record per listed member, and the range check's three words per listed member --
+    // on the device, their start values (~0, 0, 0) and the read-back, pinned; all n entries long, made at creation
+    WaferBatchSetupRec *setup_dev = nullptr, *setup_host = nullptr;
+    unsigned long long *vchk_dev = nullptr, *vchk_init = nullptr, *vchk_host = nullptr;
+    uint64_t n_setup_launches = 0, n_setup_readbacks = 0;   // of the batched set-up paths since creation (wafer_batch_diag_setup_counts)
 };
 
 namespace {
@@ -150,16 +160,21 @@ void destroy(wafer_batch *b)
 {
     (void)hipSetDevice(b->device);
     if (b->s) (void)hipStreamSynchronize(b->s);
-    for (wafer_ctx *v : b->views) delete v;   // views borrow every array and the stream
+    for (wafer_ctx *v : b->views) {   // views borrow every array and the stream, except a and b (ensure_ab)
+        for (void *p : {v->a, v->b})
+            if (p) (void)hipFree(alloc_base(v, p));
+        delete v;
+    }
     for (void *p : b->alloc)
         if (p) (void)hipFree(p);
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
-                    (void *)b->gram_list_dev, (void *)b->rs_scratch})
+                    (void *)b->gram_list_dev, (void *)b->rs_scratch, (void *)b->setup_dev, (void *)b->vchk_dev})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host})
+    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host, (void *)b->setup_host,
+                    (void *)b->vchk_init, (void *)b->vchk_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop, b->rs_start, b->rs_stop})
         if (e) (void)hipEventDestroy(e);
@@ -736,6 +751,60 @@ int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t s
     return WAFER_OK;
 }
 
+// ---- the range check of many members at once -----------------------------------------------------------------------------------
+// the safe answers for the members in act_host, whose V was written but could not be checked: no mirrored reads, the long forms
+void v_unknown(wafer_batch *b, int nact)
+{
+    for (int k = 0; k < nact; ++k) {
+        wafer_ctx *c = b->views[b->act_host[k]];
+        c->v_ysym = c->v_in_range = false;
+        for (int &a : c->x2_agreed) a = -1;
+    }
+    (void)sync_members(b);
+}
+
+// check_v_range (wafer_engine.hip) for the members in act_host / act_dev, whose V has just been written and whose v_ysym the writer
+// cleared before its first store: the words' start values in one copy, ONE launch (wafer_k_batch_v_check), one read-back and one
+// stream synchronisation, then per member the context's bookkeeping -- v_in_range by the same predicate, v_ysym, x2_agreed -- and the
+// device member table as the views stand now.  A HIP error leaves every one of them with both flags off (v_unknown).
+int check_v_listed(wafer_batch *b, int nact)
+{
+    const size_t bytes = sizeof(unsigned long long) * 3 * (size_t)nact;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(b->vchk_dev, b->vchk_init, bytes, hipMemcpyHostToDevice, b->s));
+        int max_tiles = 0, max_planes = 0;
+        for (int k = 0; k < nact; ++k) {
+            const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
+            max_tiles = std::max(max_tiles, wafer_v_check_tiles(g, (int)b->esz));
+            max_planes = std::max(max_planes, g.lz);
+        }
+        const hipError_t e = with_geom(b, [&](const auto &gs) {
+            return wafer_entry_batch_v_check(b->f32, gs, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, b->vchk_dev, b->s);
+        });
+        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched range check launch failed: %s", hipGetErrorString(e));
+        ++b->n_setup_launches;
+        HIP_TRY(hipMemcpyAsync(b->vchk_host, b->vchk_dev, bytes, hipMemcpyDeviceToHost, b->s));
+        HIP_TRY(hipStreamSynchronize(b->s));
+        ++b->n_setup_readbacks;
+        return WAFER_OK;
+    };
+    const int rc = run();
+    if (rc != WAFER_OK) {
+        v_unknown(b, nact);
+        return rc;
+    }
+    for (int k = 0; k < nact; ++k) {
+        wafer_ctx *c = b->views[b->act_host[k]];
+        double lo, hi;
+        memcpy(&lo, &b->vchk_host[3 * k], 8);
+        memcpy(&hi, &b->vchk_host[3 * k + 1], 8);
+        c->v_in_range = (lo > 0x1p-400) && (hi < 0x1p400);   // a NaN anywhere makes hi a NaN: false
+        c->v_ysym = b->vchk_host[3 * k + 2] == 0;
+        for (int &a : c->x2_agreed) a = -1;
+    }
+    return sync_members(b);
+}
+
 // ---- resampling --------------------------------------------------------------------------------------------------------------
 // the resample scratch holds at least `doubles` doubles: grown on demand, never per call, freed with the batch
 int ensure_scratch(wafer_batch *b, size_t doubles)
@@ -779,8 +848,9 @@ int stage_host_source(wafer_batch *b, const double *src, int sx, int sy, int sz,
 // wafer_set_potsub_resampled) or of wafer_batch_load_state.
 // A REFUSED call (WAFER_ERR_INVALID, WAFER_ERR_STATE) has changed nothing.  A HIP error (WAFER_ERR_HIP) is another matter, as for a
 // context: before the launch it leaves every target as it was; behind it the arrays of all listed members are written, and for a
-// potential the per-member bookkeeping stops at the member whose refresh_ab / check_v_range failed -- the listed members after it
-// hold the new V without have_pot, with v_ysym off (the safe answer), until the potential is set again.
+// potential a failure of refresh_ab or of the one range check for all listed members (check_v_listed) leaves EVERY listed member
+// with v_ysym and v_in_range off -- the safe answers: no mirrored reads, the long arithmetic forms -- until the potential is set
+// again; the a, b arrays and the have_pot bookkeeping stop at the member whose refresh_ab failed.
 int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, const double *host, uint32_t sx, uint32_t sy, uint32_t sz,
              uint32_t src_member, int src_kind, uint32_t src_idx, int basis)
 {
@@ -836,7 +906,7 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
     TRY(sync_members(b));   // (the kernel reads cur)
     int nact = 0;
     TRY(upload_active(b, active, &nact));
-    // From here on the targets are written.  V is about to change: check_v_range re-establishes the flag (cleared behind the last
+    // From here on the targets are written.  V is about to change: check_v_listed re-establishes the flag (cleared behind the last
     // step that can fail before the launch, so that a call that launched nothing leaves it as it was).
     if (target == WAFER_RESAMPLE_POTENTIAL)
         for (uint32_t m = 0; m < b->n; ++m)
@@ -865,15 +935,19 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
             c->have_phi = true;
             c->halo_valid = c->g.G;   // ghost planes were interpolated from the same source
             break;
-        case WAFER_RESAMPLE_POTENTIAL:
-            TRY(refresh_ab(c));
+        case WAFER_RESAMPLE_POTENTIAL: {
+            const int rc = refresh_ab(c);
+            if (rc != WAFER_OK) {
+                v_unknown(b, nact);
+                return rc;
+            }
             c->vgen_type = 0;
             c->potsub_kind = WAFER_POTSUB_NONE;   // potential.rs:357-358: FromFile has no pot_sub of its own
             c->potsub_scalar = 0.0;
             c->have_pot = true;
             c->x2_ready = 0;
-            TRY(check_v_range(c));
             break;
+        }
         case WAFER_RESAMPLE_POTSUB:
             c->potsub_kind = WAFER_POTSUB_ARRAY;
             c->potsub_scalar = 0.0;
@@ -883,6 +957,104 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
             mark_gram_stale(b, m);
             break;
         }
+    }
+    if (target == WAFER_RESAMPLE_POTENTIAL) return check_v_listed(b, nact);   // one launch and one read-back for all of them
+    return WAFER_OK;
+}
+
+// ---- set-up of many members at once ------------------------------------------------------------------------------------------
+// one record per member in act_host (upload_active has synchronised the stream: setup_host is not read by an earlier call's copy)
+int upload_setup(wafer_batch *b, int nact, const int *kinds, const uint64_t *seeds)
+{
+    double k[4];
+    pot_host_constants(k);
+    for (int i = 0; i < nact; ++i) {
+        const int m = b->act_host[i];
+        const wafer_ctx *c = b->views[m];
+        WaferBatchSetupRec &r = b->setup_host[i];
+        r.member = m;
+        r.kind = kinds[m];
+        r.seed = seeds ? seeds[m] : 0;
+        r.dn = c->P.dn; r.dt = c->P.dt; r.mass = c->P.mass; r.sig = c->P.sig;
+        r.mu_t = k[0]; r.alphas_2pit = k[1]; r.xi_coef = k[2]; r.xi_fac = k[3];
+        r.pa = c->a;
+        r.pb = c->b;
+    }
+    HIP_TRY(hipMemcpyAsync(b->setup_dev, b->setup_host, sizeof(WaferBatchSetupRec) * nact, hipMemcpyHostToDevice, b->s));
+    return WAFER_OK;
+}
+
+// wafer_set_potential_builtin for every listed member: every check first, then one launch for V (a, b), one for the pot_sub arrays
+// if a listed member is FullCornell, the context's bookkeeping per member, and the one range check.
+int set_potentials(wafer_batch *b, const uint8_t *active, const int *potentials)
+{
+    int nlisted = 0;
+    bool fullcornell = false;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        const int pot = potentials[m];
+        if (pot < 0 || pot > WAFER_POT_FROMSCRIPT) return fail(WAFER_ERR_INVALID, "member %u: unknown potential %d", m, pot);
+        if (pot == WAFER_POT_FROMFILE || pot == WAFER_POT_FROMSCRIPT)
+            return fail(WAFER_ERR_NOT_AVAILABLE, "member %u: PotentialNotAvailable: FromFile/FromScript need wafer_set_potential_host", m);
+        fullcornell = fullcornell || pot == WAFER_POT_FULLCORNELL;
+        ++nlisted;
+    }
+    if (!nlisted) return WAFER_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    TRY(upload_setup(b, nact, potentials, nullptr));
+    for (int k = 0; k < nact; ++k) b->views[b->act_host[k]]->v_ysym = false;   // V is about to change: check_v_listed re-establishes it
+    int max_tiles, max_planes;
+    max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
+    RoctxRange range_("wafer_batch_set_potentials");
+    hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_potential(b->f32, gs, b->mem_dev, b->setup_dev, nact, max_tiles, max_planes, b->s);
+    });
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched potential launch failed: %s", hipGetErrorString(e));
+    ++b->n_setup_launches;
+    if (fullcornell) {
+        e = with_geom(b, [&](const auto &gs) {
+            return wafer_entry_batch_potsub_fullcornell(b->f32, gs, b->mem_dev, b->setup_dev, nact, max_tiles, max_planes, b->s);
+        });
+        if (e != hipSuccess) {
+            v_unknown(b, nact);
+            return fail(WAFER_ERR_HIP, "batched pot_sub launch failed: %s", hipGetErrorString(e));
+        }
+        ++b->n_setup_launches;
+    }
+    for (int k = 0; k < nact; ++k) builtin_potential_set(b->views[b->act_host[k]], potentials[b->act_host[k]]);
+    return check_v_listed(b, nact);
+}
+
+// wafer_set_initial_condition for every listed member: every check first, then one launch into the members' phi[cur]
+int set_initial_conditions(wafer_batch *b, const uint8_t *active, const int *ics, const uint64_t *seeds)
+{
+    int nlisted = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (ics[m] == WAFER_IC_FROMFILE) return fail(WAFER_ERR_NOT_AVAILABLE, "member %u: FromFile: use wafer_upload_phi", m);
+        if (ics[m] < WAFER_IC_GAUSSIAN || ics[m] > WAFER_IC_BOOLEAN) return fail(WAFER_ERR_INVALID, "member %u: unknown initial condition %d", m, ics[m]);
+        ++nlisted;
+    }
+    if (!nlisted) return WAFER_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    TRY(sync_members(b));   // (the kernel reads cur)
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));
+    TRY(upload_setup(b, nact, ics, seeds));
+    int max_tiles, max_planes;
+    max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
+    RoctxRange range_("wafer_batch_set_initial_conditions");
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_initial_condition(b->f32, gs, b->mem_dev, b->setup_dev, nact, max_tiles, max_planes, b->s);
+    });
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched initial condition launch failed: %s", hipGetErrorString(e));
+    ++b->n_setup_launches;
+    for (int k = 0; k < nact; ++k) {
+        wafer_ctx *c = b->views[b->act_host[k]];
+        c->have_phi = true;
+        c->halo_valid = c->g.G;   // every ghost plane was generated from global indices
     }
     return WAFER_OK;
 }
@@ -1048,6 +1220,15 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     HIP_TRY(hipMalloc((void **)&b->sym_dev, sizeof(int) * n_members));
     HIP_TRY(hipHostMalloc((void **)&b->sym_host, sizeof(int) * n_members, hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
+    HIP_TRY(hipMalloc((void **)&b->setup_dev, sizeof(WaferBatchSetupRec) * n_members));
+    HIP_TRY(hipHostMalloc((void **)&b->setup_host, sizeof(WaferBatchSetupRec) * n_members, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&b->vchk_dev, sizeof(unsigned long long) * 3 * n_members));
+    HIP_TRY(hipHostMalloc((void **)&b->vchk_init, sizeof(unsigned long long) * 3 * n_members, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **)&b->vchk_host, sizeof(unsigned long long) * 3 * n_members, hipHostMallocDefault));
+    for (uint32_t m = 0; m < n_members; ++m) {
+        b->vchk_init[3 * m] = ~0ull;
+        b->vchk_init[3 * m + 1] = b->vchk_init[3 * m + 2] = 0ull;
+    }
     HIP_TRY(hipMalloc((void **)&b->geoms_dev, sizeof(WaferGeom) * b->geoms.size()));
     HIP_TRY(hipMemcpy(b->geoms_dev, b->geoms.data(), sizeof(WaferGeom) * b->geoms.size(), hipMemcpyHostToDevice));
     TRY(init_views(b));
@@ -1139,6 +1320,48 @@ int wafer_batch_set_initial_condition(wafer_batch *b, uint32_t member, int ic, u
 {
     TRY(check_member_index(b, member));
     return wafer_set_initial_condition(b->views[member], ic, seed);
+}
+
+int wafer_batch_set_potentials_builtin(wafer_batch *b, const uint8_t *active, const int *potentials)
+{
+    if (!b || !potentials) return fail(WAFER_ERR_INVALID, "null argument");
+    return set_potentials(b, active, potentials);
+}
+
+int wafer_batch_set_initial_conditions(wafer_batch *b, const uint8_t *active, const int *ics, const uint64_t *seeds)
+{
+    if (!b || !ics) return fail(WAFER_ERR_INVALID, "null argument");
+    return set_initial_conditions(b, active, ics, seeds);
+}
+
+int wafer_batch_download_array(wafer_batch *b, uint32_t member, int array_id, double *out)
+{
+    TRY(check_member_index(b, member));
+    return wafer_download_array(b->views[member], array_id, out);
+}
+
+int wafer_batch_get_potsub(wafer_batch *b, uint32_t member, int *kind, double *scalar)
+{
+    TRY(check_member_index(b, member));
+    return wafer_get_potsub(b->views[member], kind, scalar);
+}
+
+int wafer_batch_diag_member(wafer_batch *b, uint32_t member, char *buf, size_t n)
+{
+    TRY(check_member_index(b, member));
+    if (!buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
+    const wafer_ctx *c = b->views[member];
+    snprintf(buf, n, "member=%u have_pot=%d have_phi=%d potsub_kind=%d v_in_range=%d v_ysym=%d short_forms=%d cur=%d states=%u", member,
+             (int)c->have_pot, (int)c->have_phi, c->potsub_kind, (int)c->v_in_range, (int)c->v_ysym, short_forms(c) ? 1 : 0, c->cur, b->nst[member]);
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_setup_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks)
+{
+    if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
+    *launches = b->n_setup_launches;
+    *readbacks = b->n_setup_readbacks;
+    return WAFER_OK;
 }
 
 int wafer_batch_upload_phi(wafer_batch *b, uint32_t member, const double *phi)

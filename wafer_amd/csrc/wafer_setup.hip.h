@@ -113,17 +113,15 @@ __device__ __forceinline__ double wafer_potential_at(const WaferPotArgs &a, int 
     }
 }
 
-// potential::generate (potential.rs:46-62) + ancillary arrays (potential.rs:101-110)
-// over every padded cell of the slab (ghost planes included).
-// grid (ceil(px/64), ceil(py/4), lz), block (64,4).
+// One padded cell (lzp, yp, xp) of potential::generate (potential.rs:46-62) + the ancillary arrays (potential.rs:101-110): V, and a, b
+// where they exist.  Cells outside the padded box or the global grid are left alone.  The ONE statement of this, shared by
+// wafer_k_potential below and wafer_k_batch_potential (wafer_setup_batch.hip.h), which differ only in where a.g and the scalars
+// come from.
 template <typename T>
-__global__ __launch_bounds__(256) void wafer_k_potential(WaferPotArgs a, T *__restrict__ v,
-                                                         T *__restrict__ pa, T *__restrict__ pb)
+__device__ __forceinline__ void wafer_potential_cell(const WaferPotArgs &a, int lzp, int yp, int xp, T *__restrict__ v,
+                                                     T *__restrict__ pa, T *__restrict__ pb)
 {
     const WaferGeom &g = a.g;
-    const int xp = blockIdx.x * 64 + threadIdx.x;
-    const int yp = blockIdx.y * 4 + threadIdx.y;
-    const int lzp = blockIdx.z;
     const int zp = g.zp_of(lzp);
     if (xp >= g.px || yp >= g.py || zp < 0 || zp >= g.pzg) return;
     const double vv = wafer_potential_at(a, xp, yp, zp);
@@ -135,6 +133,18 @@ __global__ __launch_bounds__(256) void wafer_k_potential(WaferPotArgs a, T *__re
         pa[p] = (T)aa;
         pb[p] = (T)bb;
     }
+}
+
+// potential::generate (potential.rs:46-62) + ancillary arrays (potential.rs:101-110)
+// over every padded cell of the slab (ghost planes included).
+// grid (ceil(px/64), ceil(py/4), lz), block (64,4).
+template <typename T>
+__global__ __launch_bounds__(256) void wafer_k_potential(WaferPotArgs a, T *__restrict__ v,
+                                                         T *__restrict__ pa, T *__restrict__ pb)
+{
+    const int xp = blockIdx.x * 64 + threadIdx.x;
+    const int yp = blockIdx.y * 4 + threadIdx.y;
+    wafer_potential_cell<T>(a, blockIdx.z, yp, xp, v, pa, pb);
 }
 
 // a, b from an uploaded V (potential.rs:101-110)
@@ -154,6 +164,17 @@ __global__ __launch_bounds__(256) void wafer_k_ab(WaferGeom g, double dt, const 
     pb[p] = (T)bb;
 }
 
+// potential_sub_idx for FullCornell (potential.rs:326-341) at the UNPADDED global work index (i, j, k): shared by
+// wafer_k_potsub_fullcornell below and wafer_k_batch_potsub_fullcornell (wafer_setup_batch.hip.h)
+__device__ __forceinline__ double wafer_potsub_fullcornell_at(const WaferPotArgs &a, int i, int j, int k)
+{
+    const WaferGeom &g = a.g;
+    const double dz = (double)k - ((double)g.nz + 1.) / 2.;
+    const double r = a.dn * sqrt(wafer_r2(i, j, k, g.nx, g.ny, g.nz));
+    const double md = a.mu_t * 1. + a.xi_coef * (1. - a.dn * a.dn * dz * dz / (r * r)) * a.xi_fac;
+    return a.sig / md + 4. * a.mass;
+}
+
 // potential_sub_idx for FullCornell (potential.rs:326-341) on the UNPADDED
 // work index, stored at the work cell of the padded device layout.
 template <typename T>
@@ -164,11 +185,7 @@ __global__ __launch_bounds__(256) void wafer_k_potsub_fullcornell(WaferPotArgs a
     const int j = blockIdx.y * 4 + threadIdx.y;
     const int kl = blockIdx.z;
     if (i >= g.nx || j >= g.ny || kl >= g.nzl) return;
-    const int k = g.z_begin + kl;
-    const double dz = (double)k - ((double)g.nz + 1.) / 2.;
-    const double r = a.dn * sqrt(wafer_r2(i, j, k, g.nx, g.ny, g.nz));
-    const double md = a.mu_t * 1. + a.xi_coef * (1. - a.dn * a.dn * dz * dz / (r * r)) * a.xi_fac;
-    ps[g.at(g.lzp_of_work(kl), j + g.R, i + g.R)] = (T)(a.sig / md + 4. * a.mass);
+    ps[g.at(g.lzp_of_work(kl), j + g.R, i + g.R)] = (T)wafer_potsub_fullcornell_at(a, i, j, g.z_begin + kl);
 }
 
 // ---- initial conditions (config.rs:577-683) -----------------------------------
@@ -187,17 +204,13 @@ struct WaferIcArgs {
     double dn, mass, sig;
 };
 
-// Writes EVERY padded cell of the slab: the chosen profile inside the work
-// area, zero on the Dirichlet frame (config.rs:597-622).
-template <typename T>
-__global__ __launch_bounds__(256) void wafer_k_initial_condition(WaferIcArgs a, T *__restrict__ phi)
+// One padded cell (lzp, yp, xp) of a start: the chosen profile inside the work area, zero on the Dirichlet frame and on planes outside
+// the global grid (config.rs:597-622).  Shared by wafer_k_initial_condition below and wafer_k_batch_initial_condition
+// (wafer_setup_batch.hip.h): the Gaussian's counter RNG is keyed by the cell's own indices, so it is the same value in either.
+__device__ __forceinline__ double wafer_initial_condition_at(const WaferIcArgs &a, int lzp, int yp, int xp)
 {
     const WaferGeom &g = a.g;
-    const int xp = blockIdx.x * 64 + threadIdx.x;
-    const int yp = blockIdx.y * 4 + threadIdx.y;
-    const int lzp = blockIdx.z;
     const int zp = g.zp_of(lzp);
-    if (xp >= g.px || yp >= g.py) return;
     double val = 0.0;
     const bool in_grid = zp >= 0 && zp < g.pzg;
     const bool frame = !in_grid || xp < g.R || xp >= g.px - g.R || yp < g.R || yp >= g.py - g.R ||
@@ -236,7 +249,20 @@ __global__ __launch_bounds__(256) void wafer_k_initial_condition(WaferIcArgs a, 
             break;
         }
     }
-    phi[g.at(lzp, yp, xp)] = (T)val;
+    return val;
+}
+
+// Writes EVERY padded cell of the slab: the chosen profile inside the work
+// area, zero on the Dirichlet frame (config.rs:597-622).
+template <typename T>
+__global__ __launch_bounds__(256) void wafer_k_initial_condition(WaferIcArgs a, T *__restrict__ phi)
+{
+    const WaferGeom &g = a.g;
+    const int xp = blockIdx.x * 64 + threadIdx.x;
+    const int yp = blockIdx.y * 4 + threadIdx.y;
+    const int lzp = blockIdx.z;
+    if (xp >= g.px || yp >= g.py) return;
+    phi[g.at(lzp, yp, xp)] = (T)wafer_initial_condition_at(a, lzp, yp, xp);
 }
 
 // ---- symmetry constraints (config.rs:691-728) ---------------------------------------------------

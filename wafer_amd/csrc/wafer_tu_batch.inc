@@ -1,10 +1,11 @@
-// The launch layer of the batched ensemble kernels (wafer_stencil_batch.hip.h, wafer_gs_batch.hip.h), written once for both
+// The launch layer of the batched ensemble kernels (wafer_stencil_batch.hip.h, wafer_gs_batch.hip.h, wafer_setup_batch.hip.h), written once for both
 // geometry sources.  The including unit names its own as WAFER_TU_BATCH_GS: WaferGeom (wafer_tu_batch.hip: the one geometry of
 // a batch of one shape, a kernel argument) or WaferBatchGeomTable (wafer_tu_batch_mixed.hip: the device table of a batch of
 // several shapes), and gets the wafer_entry_batch_* overloads that take that type.  For each dtype -- 0 f64 <double, double>,
 // 1 f32 <float, double> (float storage, fp64 arithmetic), 2 f32fast <float, float> (float arithmetic in the ground-state step).
 #include "wafer_gs_batch.hip.h"
 #include "wafer_resample_batch.hip.h"
+#include "wafer_setup_batch.hip.h"
 
 namespace {
 
@@ -127,5 +128,42 @@ hipError_t wafer_entry_batch_norm2(bool f32, const GS &gs, const WaferBatchMembe
     if (e != hipSuccess) return e;
     if (f32) hipLaunchKernelGGL(wafer_k_batch_gs_reduce<true>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
     else hipLaunchKernelGGL(wafer_k_batch_gs_reduce<false>, dim3((unsigned)nact), dim3(256), 0, s, (const double *)partials, act, mem, scal, scal_stride, out_slot);
+    return hipGetLastError();
+}
+
+// ---- set-up (wafer_setup_batch.hip.h) ----------------------------------------------------------------------------------------
+hipError_t wafer_entry_batch_potential(bool f32, const GS &gs, const WaferBatchMember *mem, const WaferBatchSetupRec *rec, int nlisted,
+                                       int max_tiles, int max_planes, hipStream_t s)
+{
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nlisted), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_potential<float, GS>), grid, block, 0, s, gs, mem, rec);
+    else hipLaunchKernelGGL((wafer_k_batch_potential<double, GS>), grid, block, 0, s, gs, mem, rec);
+    return hipGetLastError();
+}
+
+hipError_t wafer_entry_batch_potsub_fullcornell(bool f32, const GS &gs, const WaferBatchMember *mem, const WaferBatchSetupRec *rec, int nlisted,
+                                                int max_tiles, int max_planes, hipStream_t s)
+{
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nlisted), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_potsub_fullcornell<float, GS>), grid, block, 0, s, gs, mem, rec);
+    else hipLaunchKernelGGL((wafer_k_batch_potsub_fullcornell<double, GS>), grid, block, 0, s, gs, mem, rec);
+    return hipGetLastError();
+}
+
+hipError_t wafer_entry_batch_initial_condition(bool f32, const GS &gs, const WaferBatchMember *mem, const WaferBatchSetupRec *rec, int nlisted,
+                                               int max_tiles, int max_planes, hipStream_t s)
+{
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nlisted), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_initial_condition<float, GS>), grid, block, 0, s, gs, mem, rec);
+    else hipLaunchKernelGGL((wafer_k_batch_initial_condition<double, GS>), grid, block, 0, s, gs, mem, rec);
+    return hipGetLastError();
+}
+
+hipError_t wafer_entry_batch_v_check(bool f32, const GS &gs, const WaferBatchMember *mem, const int *act, int nact, int max_tiles, int max_planes,
+                                     unsigned long long *words, hipStream_t s)
+{
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_planes, (unsigned)nact), block(WAFER_BATCH_TX, WAFER_BATCH_TY);
+    if (f32) hipLaunchKernelGGL((wafer_k_batch_v_check<float, GS>), grid, block, 0, s, gs, mem, act, words);
+    else hipLaunchKernelGGL((wafer_k_batch_v_check<double, GS>), grid, block, 0, s, gs, mem, act, words);
     return hipGetLastError();
 }

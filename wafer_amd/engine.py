@@ -61,6 +61,8 @@ EXPORTS = [
     "wafer_batch_create_mixed", "wafer_batch_create_mixed_states", "wafer_batch_num_shapes",
     "wafer_batch_symmetrise", "wafer_batch_set_potsub",
     "wafer_batch_resample", "wafer_batch_resample_member", "wafer_batch_last_resample_ms",
+    "wafer_batch_set_potentials_builtin", "wafer_batch_set_initial_conditions", "wafer_batch_download_array", "wafer_batch_get_potsub",
+    "wafer_batch_diag_member", "wafer_batch_diag_setup_counts",
 ]
 
 
@@ -267,6 +269,12 @@ def load_library():
     L.wafer_batch_resample.argtypes = [vp, u8p, C.c_int, C.c_uint32, dp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.wafer_batch_resample_member.argtypes = [vp, u8p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int]
     L.wafer_batch_last_resample_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.wafer_batch_set_potentials_builtin.argtypes = [vp, u8p, C.POINTER(C.c_int)]
+    L.wafer_batch_set_initial_conditions.argtypes = [vp, u8p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+    L.wafer_batch_download_array.argtypes = [vp, C.c_uint32, C.c_int, dp]
+    L.wafer_batch_get_potsub.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int), dp]
+    L.wafer_batch_diag_member.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.wafer_batch_diag_setup_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -341,6 +349,26 @@ def _dp(a: np.ndarray):
     if a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"]:
         raise TypeError("host arrays must be C-contiguous float64")
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _enum_entries(names, table, n_members: int, mask, what: str) -> list:
+    """names (one per member: a name of `table` or its index) as the ints the library takes.  The entries of members that `mask`
+    (None: everyone listed) leaves out are not looked at: an int goes through, anything else becomes 0.  A listed name the table does not hold is a ValueError; an
+    int goes through as it is (the library checks it)."""
+    names = list(names)
+    if len(names) != n_members:
+        raise ValueError("%s names must hold one entry per member (%d given, the batch has %d)" % (what, len(names), n_members))
+    out = []
+    for m, name in enumerate(names):
+        if mask is not None and not mask[m]:
+            out.append(name if isinstance(name, int) and not isinstance(name, bool) else 0)
+        elif isinstance(name, str):
+            if name not in table:
+                raise ValueError("member %d: unknown %s %r" % (m, what, name))
+            out.append(table.index(name))
+        else:
+            out.append(int(name))
+    return out
 
 
 class Context:
@@ -721,6 +749,10 @@ class Batch:
     bit for bit what Context.upload_phi_resampled / set_potential_resampled / set_potsub_resampled give a Context of its Params
     (basis "padded": the reference's production call; "work": its nx, ny, nz), with that call's bookkeeping; resample_state follows
     load_state's rules.  A refused call changes nothing.
+    set_potentials(names, active) / set_initial_conditions(names, seeds, active) set every listed member up in one launch each --
+    with ONE range check and read-back for all of them where a per-member call pays two launches, two read-backs and a synchronisation
+    each -- bit for bit what set_potential / set_initial_condition give member by member (setup_counts()).  download_array(i, which),
+    potsub(i) and member_info(i) read a member back as a Context's calls do.
     python -m wafer_amd.sweep drives whole wafer.yaml runs through batches with these calls: phases per state number, every run
     with its own screen_update, tolerance and max_steps, one evolve for all running members between block boundaries."""
 
@@ -797,6 +829,55 @@ class Batch:
 
     def set_initial_condition(self, i: int, name: str, seed: int = 0) -> None:
         self._check(self._L.wafer_batch_set_initial_condition(self._h, i, INITIAL_CONDITIONS.index(name), seed))
+
+    # -- set-up, many members in one launch --------------------------------------------------------
+    def set_potentials(self, names, active=None) -> None:
+        """Batch.set_potential(m, names[m]) for every listed member (active[m] != 0; None: all) at once: one launch that generates V,
+        one for the pot_sub arrays if a listed member is FullCornell, one range check and one read-back for all of them, each member
+        bit for bit what the per-member call gives.  names: one per member (a name of POTENTIALS or its index); the entries of
+        members not listed are ignored.  A refused call changes nothing."""
+        a = self._mask(active)
+        pots = _enum_entries(names, POTENTIALS, len(self.members), a, "potential")
+        self._check(self._L.wafer_batch_set_potentials_builtin(self._h, self._u8(a), (C.c_int * len(pots))(*pots)))
+
+    def set_initial_conditions(self, names, seeds=None, active=None) -> None:
+        """Batch.set_initial_condition(m, names[m], seeds[m]) for every listed member in ONE launch, no read-back (seeds None: 0)"""
+        a = self._mask(active)
+        ics = _enum_entries(names, INITIAL_CONDITIONS, len(self.members), a, "initial condition")
+        if seeds is None:
+            seeds = [0] * len(self.members)
+        if len(seeds) != len(self.members):
+            raise ValueError("seeds must hold one entry per member")
+        self._check(self._L.wafer_batch_set_initial_conditions(self._h, self._u8(a), (C.c_int * len(ics))(*ics),
+                                                               (C.c_uint64 * len(ics))(*[int(x) for x in seeds])))
+
+    def download_array(self, i: int, which: str) -> np.ndarray:
+        """Context.download_array of member i: "v", "a", "b" (padded) or "potsub" (the work shape; only where pot_sub is an array)"""
+        i = self._member(i)
+        idx = {"v": 0, "a": 1, "b": 2, "potsub": 3}[which]
+        out = np.zeros(self.members[i].work_shape if which == "potsub" else self.members[i].padded_shape)
+        self._check(self._L.wafer_batch_download_array(self._h, i, idx, _dp(out)))
+        return out
+
+    def potsub(self, i: int):
+        """(kind, scalar) of member i's pot_sub, as Context.potsub"""
+        kind, scalar = C.c_int(0), C.c_double(0.0)
+        self._check(self._L.wafer_batch_get_potsub(self._h, self._member(i), C.byref(kind), C.byref(scalar)))
+        return kind.value, scalar.value
+
+    def member_info(self, i: int) -> dict:
+        """member i's host record (wafer_batch_diag_member): member, have_pot, have_phi, potsub_kind, v_in_range, v_ysym, short_forms,
+        cur, states -- all ints; launches nothing"""
+        buf = C.create_string_buffer(256)
+        self._check(self._L.wafer_batch_diag_member(self._h, self._member(i), buf, len(buf)))
+        return {k: int(v) for k, v in (kv.split("=", 1) for kv in buf.value.decode().split())}
+
+    def setup_counts(self) -> tuple:
+        """(launches, read-backs) of the batched set-up paths since creation: set_potentials, set_initial_conditions and the one range
+        check behind resample_potential"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_setup_counts(self._h, C.byref(n), C.byref(r)))
+        return n.value, r.value
 
     def symmetrise(self, constraints, active=None) -> None:
         """Context.symmetrise for every active member (None: all) in one launch, member m with constraints[m]: a name of SYMMETRY

@@ -3,7 +3,7 @@ every time step ONE launch for all runs of a batch that are still going (wafer_a
 context per run.
 
     python -m wafer_amd.sweep -c a.yaml -c b.yaml ... [--output-dir DIR] [--input-dir DIR] [--max-batch N] [--seed S]
-                              [--progress] [--plan] [--mix-states]
+                              [--progress] [--plan] [--mix-states] [--batched-setup]
 
 Configuration reading and validation are the native driver's (`wafer-hip --check-config`, through wafer_amd.run.load_config), the
 input files, the directory names and the table are wafer_amd.run's, and every run computes what `wafer-hip` computes for its file:
@@ -38,6 +38,10 @@ with their mask -- with --input-dir, one upload and one launch per file however 
 are staged without a frame (pad 0); a ready-made `<stem>.npy` counts as framed for a run whose padded size it has and as plain data
 for every other run.  --plan lists the groups under "inputs" without converting or writing anything: the shape of a .npy or .csv is
 read from the file, for the other formats "shape", "copy" and "resample" are null.
+
+--batched-setup: the built-in potentials of a batch's runs are ONE Batch.set_potentials call with their mask and the generated starts
+of a phase ONE Batch.set_initial_conditions call with the same seeds, instead of one call per run: the same bits, one range check and
+one read-back per batch instead of one per run.  Opt-in; the default stays the per-member calls.
 """
 from __future__ import annotations
 
@@ -403,31 +407,41 @@ def apply_inputs(batch, runs: list, groups: list, load=_load) -> None:
                 batch.resample_phi(src, active=mask, basis="padded")
 
 
-def set_up_batch(batch, runs: list, load=_load) -> None:
+def set_up_batch(batch, runs: list, load=_load, batched: bool = False) -> None:
     """potentials, pot_sub overrides and the lower states from disk for every run of the batch, as wafer_amd.run sets a context up:
-    built-in potentials per member, everything that comes from a file through plan_inputs' groups"""
+    built-in potentials per member -- or, with batched=True, in ONE Batch.set_potentials call with their mask (--batched-setup: the
+    same bits) -- everything that comes from a file through plan_inputs' groups"""
+    builtin = []
     for r in runs:
         c = r.cfg
         if c["potential"] == "FromFile":                                  # potential.rs:80-86
             if input_file(r.input_dir, "potential", c["file_type"]) is None:
                 raise SystemExit(f"{r.config_path}: Error: LoadPotential: FileNotFound: {r.input_dir}/potential.*")
+        elif batched:
+            builtin.append(r)
         else:
             batch.set_potential(r.slot, c["potential"])
         for w in range(c["wavenum"]):                                     # grid.rs:35-39: converged lower states from disk
             if input_file(r.input_dir, f"wavefunction_{w}", c["file_type"]) is None:
                 raise SystemExit(f"{r.config_path}: Error: LoadWavefunction({w}): FileNotFound: {r.input_dir}/wavefunction_{w}.*")
+    if builtin:
+        names = ["NoPotential"] * len(runs)
+        for r in builtin:
+            names[r.slot] = r.cfg["potential"]
+        batch.set_potentials(names, active=_mask(runs, builtin))
     roles = {("potential", 0), ("potential_sub", 0)} | {("state", w) for r in runs for w in range(r.cfg["wavenum"])}
     groups = plan_inputs(runs, load, roles=roles)                          # (the starts are read by start_phase, phase by phase)
     apply_inputs(batch, runs, groups, load)
 
 
-def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load) -> None:
+def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load, batched: bool = False) -> None:
     """the start of state w for every run that takes part (grid.rs:60-100), then, for w = 0, one symmetrise with every run's
-    init_symmetry (config.rs:625)"""
+    init_symmetry (config.rs:625).  batched=True: the generated starts are ONE Batch.set_initial_conditions call with their mask and
+    the same seeds, instead of one call per member."""
     part = [r for r in runs if r.takes_part(w)]
     groups = plan_inputs(part, load, roles={("start", w)})
     from_file = {i for g in groups for i in g["members"]}
-    clones = []
+    clones, generated = [], []
     for r in part:
         r.cloned = False
         if r.index in from_file:
@@ -437,8 +451,15 @@ def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load) ->
             r.cloned = True
         elif r.cfg["init_condition"] == "FromFile":
             raise SystemExit(f"{r.config_path}: Error: SetInitialConditions: LoadWavefunction(0): FileNotFound: {r.input_dir}/wavefunction_0*.*")
+        elif batched:
+            generated.append(r)
         else:                                                             # grid.rs:99, config.rs:577-627
             batch.set_initial_condition(r.slot, r.cfg["init_condition"], seed=seed)
+    if generated:
+        names = ["Boolean"] * len(runs)
+        for r in generated:
+            names[r.slot] = r.cfg["init_condition"]
+        batch.set_initial_conditions(names, seeds=[seed] * len(runs), active=_mask(runs, generated))
     apply_inputs(batch, runs, groups, load)
     if clones:
         batch.clone_state_to_phi(w - 1, active=_mask(runs, clones))
@@ -449,8 +470,9 @@ def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load) ->
         batch.symmetrise(cons, active=_mask(runs, part))
 
 
-def run_batch(plan: dict, runs: list, seed: int, progress: bool) -> tuple:
-    """one batch of the plan from creation to its last phase -> (fused passes, one-step launches)"""
+def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False) -> tuple:
+    """one batch of the plan from creation to its last phase -> (fused passes, one-step launches).  batched: set_up_batch's and
+    start_phase's (--batched-setup)"""
     import wafer_amd
 
     pars = []
@@ -462,12 +484,12 @@ def run_batch(plan: dict, runs: list, seed: int, progress: bool) -> tuple:
     # (a state group of plan_batches(mix_states=True): the mixed-shape batch that has state stores)
     kind = dict(mixed_shapes=True, state_stores=True) if plan["needs_states"] and plan["mixed_shapes"] else dict(mixed_shapes=plan["mixed_shapes"])
     with wafer_amd.Batch(pars, **kind) as batch:
-        set_up_batch(batch, runs)
+        set_up_batch(batch, runs, batched=batched)
         late = [r for r in runs if r.cfg["wavenum"] > 0]
         if late:   # observables run over every member: a run that starts at a later state waits with its state 0 as phi
             batch.clone_state_to_phi(0, active=_mask(runs, late))
         for w in range(min(r.cfg["wavenum"] for r in runs), max(r.cfg["wavemax"] for r in runs) + 1):
-            start_phase(batch, runs, pars, w, seed)
+            start_phase(batch, runs, pars, w, seed, batched=batched)
             run_phase(batch, runs, w, progress=progress, push=plan["needs_states"])
         return batch.passes()
 
@@ -484,6 +506,9 @@ def main(argv=None) -> int:
     ap.add_argument("--plan", action="store_true", help="print the grouping as JSON and exit; touches no GPU")
     ap.add_argument("--mix-states", action="store_true",
                     help="runs with excited states share one mixed-shape batch per (stencil, dtype) instead of one batch per grid shape")
+    ap.add_argument("--batched-setup", action="store_true",
+                    help="built-in potentials and generated starts of a batch in one Batch.set_potentials / set_initial_conditions call "
+                         "instead of one call per run (the same results)")
     args = ap.parse_args(argv)
     if args.max_batch < 1:
         raise SystemExit("--max-batch must be >= 1")
@@ -528,7 +553,7 @@ def main(argv=None) -> int:
         members = [runs[i] for i in b["members"]]
         for r in members:
             r.batch = k
-        launches.append(run_batch(b, members, seed, args.progress))
+        launches.append(run_batch(b, members, seed, args.progress, batched=args.batched_setup))
     ok = True
     for r in runs:
         asked = r.cfg["wavemax"] - r.cfg["wavenum"] + 1
