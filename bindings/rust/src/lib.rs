@@ -181,6 +181,12 @@ extern "C" {
     pub fn wafer_download_state(ctx: *mut wafer_ctx, idx: u32, state: *mut f64) -> c_int;
     pub fn wafer_num_states(ctx: *mut wafer_ctx, out: *mut u32) -> c_int;
     pub fn wafer_clear_states(ctx: *mut wafer_ctx) -> c_int;
+    /// Rayleigh-Ritz on the first k <= 8 (WAFER_RITZ_MAX) stored states (include/wafer_hip.h): row-major k * k matrices,
+    /// coef[j * k + a] = component of input state j in output state a
+    pub fn wafer_ritz_solve(k: u32, h: *const f64, s: *const f64, evals: *mut f64, coef: *mut f64) -> c_int;
+    pub fn wafer_ritz_matrices(ctx: *mut wafer_ctx, k: u32, h: *mut f64, s: *mut f64) -> c_int;
+    pub fn wafer_rotate_states(ctx: *mut wafer_ctx, k: u32, coef: *const f64) -> c_int;
+    pub fn wafer_ritz(ctx: *mut wafer_ctx, k: u32, evals: *mut f64, coef: *mut f64, h: *mut f64, s: *mut f64) -> c_int;
     pub fn wafer_solve_state(
         ctx: *mut wafer_ctx, wnum: u32, tolerance: f64, screen_update: u64, has_max_steps: c_int, max_steps: u64,
         records: *mut wafer_block_record, max_records: usize, n_records: *mut usize, final_out: *mut wafer_observables_output,

@@ -219,6 +219,30 @@ int wafer_clone_state_to_phi(wafer_ctx *ctx, uint32_t idx);         /* w_store[w
 int wafer_num_states(wafer_ctx *ctx, uint32_t *out);
 int wafer_clear_states(wafer_ctx *ctx);
 
+/* ---- Rayleigh-Ritz on w_store -------------------------------------------- */
+/* The reference's Gram-Schmidt scheme (grid.rs:477-492) leaves the states of a near-degenerate shell, and any state stored
+ * before it had fully converged, mixed.  One Rayleigh-Ritz step on the first k stored states unmixes them: with
+ *   H_ij = <l_i| V - S / den |l_j>   (the energy integrand of compute_observables, grid.rs:325-332, between two states)
+ *   S_ij = <l_i|l_j>                 (sums over the work area, fp64 whatever the dtype)
+ * solve H c = e S c and replace the states by l'_a = sum_j c_ja l_j: S' = 1, H' = diag(e), e ascending, each no higher than
+ * what the single states gave.  Matrices are row-major k * k doubles; h[j * k + i] is the sum of l_i times (H l_j), so
+ * h[j * k + j] has the bits of wafer_observables' energy on state j and s[j * k + j] those of its norm2.
+ * k == 0 or k > WAFER_RITZ_MAX, and a context that owns a z-slab (z_count != 0), are WAFER_ERR_INVALID; k above the number of
+ * stored states, or no potential, WAFER_ERR_STATE.  A call that fails changes neither the store nor its outputs; phi is never
+ * touched.  Stored states are rounded to the dtype's storage once, after the rotation. */
+#define WAFER_RITZ_MAX 8
+/* host only, no context: the generalised symmetric eigenproblem of (h + h^T)/2 and (s + s^T)/2 by Cholesky and cyclic Jacobi.
+ * evals[k] ascending; coef[j * k + a] = component of input state j in output state a, each column's largest component positive.
+ * s not positive definite (linearly dependent states) or a non-finite entry: WAFER_ERR_STATE. */
+int wafer_ritz_solve(uint32_t k, const double *h, const double *s, double *evals, double *coef);
+/* H and S of the first k stored states with the context's V, stencil and denominator */
+int wafer_ritz_matrices(wafer_ctx *ctx, uint32_t k, double *h, double *s);
+/* l'_a = sum_j coef[j * k + a] l_j for the first k stored states, in place (frame and padding included: zeros stay zeros);
+ * everything the context derived from the store is recomputed or dropped */
+int wafer_rotate_states(wafer_ctx *ctx, uint32_t k, const double *coef);
+/* the three in sequence; h, s (the matrices before the rotation) may be NULL */
+int wafer_ritz(wafer_ctx *ctx, uint32_t k, double *evals, double *coef, double *h, double *s);
+
 /* ---- solve (grid.rs:50-246) for ONE state, snapshot branch excluded ------ */
 /* phi must hold the starting wavefunction.  Writes up to max_records rows,
  * *n_records = rows produced.  Returns WAFER_OK when converged (phi has then

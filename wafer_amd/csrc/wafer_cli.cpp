@@ -123,6 +123,7 @@ struct Config {
     bool save_wavefns = false, save_potential = false;
     std::string dtype = "f64"; // engine extension: optional `gpu.dtype`
     int device = 0;            // engine extension: optional `gpu.device`
+    bool ritz = false;         // engine extension: optional `gpu.ritz` -- one Rayleigh-Ritz step on the stored states after the last solve
 };
 
 static int index_of(const char *const *names, int n, const std::string &v)
@@ -195,6 +196,7 @@ static bool load_config(const std::string &path, Config &c, std::string &err)
     if (!boolean("output.save_wavefns", c.save_wavefns) || !boolean("output.save_potential", c.save_potential)) return false;
     if (kv.count("gpu.dtype")) c.dtype = kv["gpu.dtype"];
     if (kv.count("gpu.device")) c.device = atoi(kv["gpu.device"].c_str());
+    if (kv.count("gpu.ritz") && !boolean("gpu.ritz", c.ritz)) return false;
     // Config::parse, config.rs:362-370
     if (c.dt > c.dn * c.dn / 3.) { err = "ConfigParse: LargeDt: dt must be <= dn^2/3"; return false; }
     if (c.wavenum > c.wavemax) { err = "ConfigParse: LargeWavenum: wavenum must be <= wavemax"; return false; }
@@ -436,6 +438,19 @@ static std::string sanitize(const std::string &s)
     return out;
 }
 
+// the final row's arithmetic (output::finalise_measurement, output.rs:533-558)
+static wafer_observables_output final_measurement(uint32_t state, const wafer_observables_t &obs, uint32_t nx)
+{
+    wafer_observables_output fin;
+    const double r_norm = std::sqrt(obs.r2 / obs.norm2);
+    fin.state = state;
+    fin.energy = obs.energy / obs.norm2;
+    fin.binding_energy = (obs.energy - obs.v_infinity) / obs.norm2;
+    fin.r = r_norm;
+    fin.l_r = (double)nx / r_norm;
+    return fin;
+}
+
 #define CHECK(call)                                                                 \
     do {                                                                            \
         int rc_ = (call);                                                           \
@@ -500,14 +515,14 @@ int main(int argc, char **argv)
         printf("{\"project_name\": \"%s\", \"nx\": %u, \"ny\": %u, \"nz\": %u, \"dn\": %s, \"dt\": %s, \"tolerance\": %s, "
                "\"central_difference\": %d, \"max_steps\": %s, \"wavenum\": %u, \"wavemax\": %u, \"potential\": \"%s\", "
                "\"mass\": %s, \"init_condition\": \"%s\", \"sig\": %s, \"init_symmetry\": \"%s\", \"screen_update\": %llu, "
-               "\"snap_update\": %s, \"file_type\": \"%s\", \"save_wavefns\": %s, \"save_potential\": %s, \"dtype\": \"%s\"}\n",
+               "\"snap_update\": %s, \"file_type\": \"%s\", \"save_wavefns\": %s, \"save_potential\": %s, \"dtype\": \"%s\", \"ritz\": %s}\n",
                cfg.project_name.c_str(), cfg.nx, cfg.ny, cfg.nz, num_text(cfg.dn).c_str(), num_text(cfg.dt).c_str(),
                num_text(cfg.tolerance).c_str(), cfg.central_difference,
                cfg.has_max_steps ? std::to_string(cfg.max_steps).c_str() : "null", cfg.wavenum, cfg.wavemax,
                kPotentials[cfg.potential], num_text(cfg.mass).c_str(), kInitialConditions[cfg.init_condition],
                num_text(cfg.sig).c_str(), cfg.init_symmetry.c_str(), (unsigned long long)cfg.screen_update,
                cfg.has_snap_update ? std::to_string(cfg.snap_update).c_str() : "null", kFileTypes[cfg.file_type],
-               cfg.save_wavefns ? "true" : "false", cfg.save_potential ? "true" : "false", cfg.dtype.c_str());
+               cfg.save_wavefns ? "true" : "false", cfg.save_potential ? "true" : "false", cfg.dtype.c_str(), cfg.ritz ? "true" : "false");
         return 0;
     }
     const int symmetry = index_of(kSymmetry, 5, cfg.init_symmetry);
@@ -726,13 +741,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "state %u: %llu steps in %.3f s (%.4f ms per step, evolve + observables + normalise)\n", wnum,
                     (unsigned long long)step, st, step ? 1e3 * st / (double)step : 0.0);
         }
-        wafer_observables_output fin;
-        const double r_norm = std::sqrt(obs.r2 / obs.norm2);
-        fin.state = wnum;
-        fin.energy = obs.energy / obs.norm2;
-        fin.binding_energy = (obs.energy - obs.v_infinity) / obs.norm2;
-        fin.r = r_norm;
-        fin.l_r = (double)cfg.nx / r_norm;
+        const wafer_observables_output fin = final_measurement(wnum, obs, cfg.nx);
         if (converged) {
             print_summary(fin); // output::finalise_measurement, output.rs:533-558
             if (!write_observables(out_dir, cfg.file_type, fin, err)) { fprintf(stderr, "Error: SaveObservables: %s\n", err.c_str()); return 1; }
@@ -751,6 +760,35 @@ int main(int argc, char **argv)
             break;
         }
         CHECK(wafer_push_state(ctx)); // grid.rs:241
+    }
+    if (cfg.ritz) { // one Rayleigh-Ritz step on the converged set: unmixes near-degenerate states (include/wafer_hip.h)
+        uint32_t ns = 0;
+        CHECK(wafer_num_states(ctx, &ns));
+        if (exit_code != 0) {
+            fprintf(stderr, "Ritz: skipped, not every state converged\n");
+        } else if (ns < 2 || ns > WAFER_RITZ_MAX) {
+            fprintf(stderr, "Ritz: skipped, %u stored states (the step takes 2 .. %d)\n", ns, WAFER_RITZ_MAX);
+        } else {
+            double evals[WAFER_RITZ_MAX], coef[WAFER_RITZ_MAX * WAFER_RITZ_MAX], hm[WAFER_RITZ_MAX * WAFER_RITZ_MAX], sm[WAFER_RITZ_MAX * WAFER_RITZ_MAX];
+            CHECK(wafer_ritz(ctx, ns, evals, coef, hm, sm));
+            printf("Ritz\n");   // state, its energy before the step (H_aa / S_aa), the Ritz value
+            for (uint32_t a = 0; a < ns; ++a)
+                printf("%3u %s %s\n", a, pad_left(rust_lower_exp(hm[a * ns + a] / sm[a * ns + a], 10), 19).c_str(),
+                       pad_left(rust_lower_exp(evals[a], 10), 19).c_str());
+            printf("\n");
+            for (uint32_t a = 0; a < ns; ++a) {
+                wafer_observables_t obs;
+                CHECK(wafer_clone_state_to_phi(ctx, a));
+                CHECK(wafer_observables(ctx, &obs));
+                if (!write_observables(out_dir, cfg.file_type, final_measurement(a, obs, cfg.nx), err)) { fprintf(stderr, "Error: SaveObservables: %s\n", err.c_str()); return 1; }
+                if (cfg.save_wavefns) {
+                    host.resize(padded_len);
+                    CHECK(wafer_download_phi(ctx, host.data()));
+                    if (!write_array(out_dir + "/wavefunction_" + std::to_string(a) + ext, cfg.file_type, host.data(), cfg.nx, cfg.ny, cfg.nz, e, err))
+                        fprintf(stderr, "Warning: could not write wavefunction to disk: %s\n", err.c_str());
+                }
+            }
+        }
     }
     (void)t_start;
     struct timespec ts1;

@@ -138,6 +138,10 @@ struct wafer_ctx {
     double gram_host[WAFER_MAX_LOW * WAFER_MAX_LOW] = {0};
     double *scal = nullptr;     // SCAL_SLOTS doubles, device
     double *scal_host = nullptr; // pinned mirror
+    // Rayleigh-Ritz on the store (wafer_tu_ritz.hip): 2 k^2 rows of workgroup partials, their 2 k^2 sums and the k^2
+    // coefficients of a rotation, grown on first use
+    double *ritz_buf = nullptr;
+    size_t ritz_cap = 0;
 
     // launch geometry shared by the column-marching kernels
     int bx = 0, by = 0;

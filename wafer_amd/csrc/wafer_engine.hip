@@ -298,6 +298,7 @@ int wafer_ctx_destroy(wafer_ctx *c)
     if (c->partials) (void)hipFree(c->partials);
     if (c->scal) (void)hipFree(c->scal);
     if (c->gram) (void)hipFree(c->gram);
+    if (c->ritz_buf) (void)hipFree(c->ritz_buf);
     if (c->scal_host) (void)hipHostFree(c->scal_host);
     for (hipEvent_t e : {c->ev_start, c->ev_stop, c->ev_fork, c->ev_join, c->ev_bdry, c->ev_ex[0], c->ev_ex[1]})
         if (e) (void)hipEventDestroy(e);

@@ -260,6 +260,9 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_step_lds(WaferStepArgs a, int
     // fetched: its 128-byte line holds nothing else anyone reads, so every such request was an HBM read of its own -- 32 lines
     // per plane and row of tiles, 6.2 % of the reads at 512^3.  The lane requests the tile's own edge cell of that row instead
     // (a hit) and the value is replaced by the zero it stands for.
+    // The observables mode fetches these cells like any other: it runs once per block of steps, and it must read a frame as it
+    // is stored -- its sums are compared bit for bit with wafer_k_ritz_sums (wafer_ritz.hip.h) on states whose frame a host loaded,
+    // where the halo rows and planes, and the frame cells inside a lane's own vector, were read as stored all along.
     long long hcol_off[Cfg::HALO_X_ITERS];
     int hcol_lds[Cfg::HALO_X_ITERS];
     bool hcol_frame[Cfg::HALO_X_ITERS];
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_step_lds(WaferStepArgs a, int
         const int row = cidx / (2 * R), k = cidx % (2 * R);
         const int xw = (k < R) ? (x0 - 1 - k) : (x0 + TX + (k - R)); // work x, may be -R..nx+R-1
         const int y = y0 + row;
-        hcol_frame[q] = xw < 0 || xw >= g.nx;
+        hcol_frame[q] = !OBS && (xw < 0 || xw >= g.nx);
         hcol_off[q] = (long long)(y + R) * g.pitch + g.xoff + R + (hcol_frame[q] ? ((k < R) ? x0 : x0 + TX - 1) : xw);
         hcol_lds[q] = (row + R) * LP + ((k < R) ? (HX - 1 - k) : (HX + TX + (k - R)));
     }

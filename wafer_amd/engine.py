@@ -63,7 +63,9 @@ EXPORTS = [
     "wafer_batch_resample", "wafer_batch_resample_member", "wafer_batch_last_resample_ms",
     "wafer_batch_set_potentials_builtin", "wafer_batch_set_initial_conditions", "wafer_batch_download_array", "wafer_batch_get_potsub",
     "wafer_batch_diag_member", "wafer_batch_diag_setup_counts",
+    "wafer_ritz_solve", "wafer_ritz_matrices", "wafer_rotate_states", "wafer_ritz",
 ]
+RITZ_MAX = 8   # WAFER_RITZ_MAX
 
 
 class _DivPlan(C.Structure):
@@ -210,6 +212,10 @@ def load_library():
     L.wafer_clone_state_to_phi.argtypes = [vp, C.c_uint32]
     L.wafer_num_states.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.wafer_clear_states.argtypes = [vp]
+    L.wafer_ritz_solve.argtypes = [C.c_uint32, dp, dp, dp, dp]
+    L.wafer_ritz_matrices.argtypes = [vp, C.c_uint32, dp, dp]
+    L.wafer_rotate_states.argtypes = [vp, C.c_uint32, dp]
+    L.wafer_ritz.argtypes = [vp, C.c_uint32, dp, dp, dp, dp]
     L.wafer_solve_state.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint64, C.c_int, C.c_uint64,
                                     C.POINTER(_Record), C.c_size_t, C.POINTER(C.c_size_t),
                                     C.POINTER(_ObsOut)]
@@ -343,6 +349,22 @@ def div_plan_f32(den: float) -> _DivPlanF32:
     if rc != 0:
         raise WaferError(rc, L.wafer_last_error().decode())
     return p
+
+
+def ritz_solve(h, s):
+    """(evals, coef): wafer_ritz_solve -- host only, no GPU: the Rayleigh-Ritz step of the (k, k) matrices h and s, k <= RITZ_MAX.
+    evals ascend; coef[j, a] is the component of input state j in output state a"""
+    L = load_library()
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    s = np.ascontiguousarray(s, dtype=np.float64)
+    if h.ndim != 2 or h.shape[0] != h.shape[1] or s.shape != h.shape:
+        raise ValueError(f"h and s must be square matrices of one size, not {h.shape} and {s.shape}")
+    k = h.shape[0]
+    evals, coef = np.zeros(max(k, 1)), np.zeros((max(k, 1), max(k, 1)))
+    rc = L.wafer_ritz_solve(k, _dp(h), _dp(s), _dp(evals), _dp(coef))
+    if rc != 0:
+        raise WaferError(rc, L.wafer_last_error().decode())
+    return evals, coef
 
 
 def _dp(a: np.ndarray):
@@ -565,6 +587,33 @@ class Context:
 
     def clear_states(self) -> None:
         self._check(self._L.wafer_clear_states(self._h))
+
+    # -- Rayleigh-Ritz on w_store (include/wafer_hip.h) ------------------------------------------------
+    def _ritz_k(self, k) -> int:
+        return self.num_states() if k is None else int(k)
+
+    def ritz_matrices(self, k: int | None = None):
+        """-> (h, s), (k, k) each: h[j, i] = sum l_i (H l_j), s[j, i] = sum l_i l_j over the first k stored states (all of them
+        when k is None)"""
+        k = self._ritz_k(k)
+        h, s = np.zeros((max(k, 1), max(k, 1))), np.zeros((max(k, 1), max(k, 1)))
+        self._check(self._L.wafer_ritz_matrices(self._h, k, _dp(h), _dp(s)))
+        return h, s
+
+    def rotate_states(self, coef: np.ndarray) -> None:
+        """l'_a = sum_j coef[j, a] l_j for the first k = len(coef) stored states, in place"""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 2 or coef.shape[0] != coef.shape[1]:
+            raise ValueError(f"coef must be a square matrix, not {coef.shape}")
+        self._check(self._L.wafer_rotate_states(self._h, coef.shape[0], _dp(coef)))
+
+    def ritz(self, k: int | None = None) -> dict:
+        """matrices, solve, rotate -> {"evals": (k,), "coef": (k, k), "h": (k, k), "s": (k, k)}; h, s are those before the rotation"""
+        k = self._ritz_k(k)
+        n = max(k, 1)
+        evals, coef, h, s = np.zeros(n), np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
+        self._check(self._L.wafer_ritz(self._h, k, _dp(evals), _dp(coef), _dp(h), _dp(s)))
+        return {"evals": evals, "coef": coef, "h": h, "s": s}
 
     # -- solve (grid.rs:50-246) --------------------------------------------------------------
     def solve_state(self, wnum: int, tolerance: float, screen_update: int, max_steps=None,

@@ -182,6 +182,9 @@ def main(argv=None) -> int:
     if cfg["potential"] == "FromScript":
         raise SystemExit("wafer_amd.run: script potentials are a single-GPU feature (wafer-hip -s); "
                          "save the potential there and use potential: FromFile")
+    if cfg.get("ritz"):
+        raise SystemExit("wafer_amd.run: gpu.ritz: true (the Rayleigh-Ritz step on the stored states) is a wafer-hip feature; "
+                         "z-slab contexts have no such step")
 
     import torch
     import wafer_amd

@@ -523,6 +523,9 @@ def main(argv=None) -> int:
                              "(config.rs:702-725 indexes the 3-cell frame)")
         if c["screen_update"] < 1:
             raise SystemExit(f"{p}: a sweep needs screen_update >= 1")
+        if c.get("ritz"):
+            raise SystemExit(f"{p}: wafer_amd.sweep: gpu.ritz: true (the Rayleigh-Ritz step on the stored states) is a wafer-hip feature; "
+                             "batches have no such step")
     plan = plan_batches(cfgs, args.max_batch, mix_states=args.mix_states)
     if args.plan:
         inputs = []
