@@ -279,6 +279,16 @@ extern "C" {
     pub fn wafer_batch_get_potsub(b: *mut wafer_batch, member: u32, kind: *mut c_int, scalar: *mut f64) -> c_int;
     pub fn wafer_batch_diag_member(b: *mut wafer_batch, member: u32, buf: *mut c_char, n: usize) -> c_int;
     pub fn wafer_batch_diag_setup_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
+    /// Rayleigh-Ritz on the first `k[m]` stored states of every listed member (include/wafer_hip.h): `k` has n_members entries;
+    /// `h`, `s`, `coef` hold member m's row-major k[m] x k[m] matrix at `m * 64` (WAFER_RITZ_MAX^2), `evals` its k[m] values at
+    /// `m * 8`; `status` has n_members entries.  One sums launch, one reduce and one read-back for all members, one rotation launch.
+    pub fn wafer_batch_ritz_matrices(b: *mut wafer_batch, active: *const u8, k: *const u32, h: *mut f64, s: *mut f64) -> c_int;
+    pub fn wafer_batch_rotate_states(b: *mut wafer_batch, active: *const u8, k: *const u32, coef: *const f64) -> c_int;
+    pub fn wafer_batch_ritz(
+        b: *mut wafer_batch, active: *const u8, k: *const u32, evals: *mut f64, coef: *mut f64, h: *mut f64, s: *mut f64,
+        status: *mut c_int,
+    ) -> c_int;
+    pub fn wafer_batch_diag_ritz_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

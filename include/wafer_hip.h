@@ -706,6 +706,35 @@ int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n);
 /* excited steps and orthogonalise calls run in each form since creation */
 int wafer_batch_diag_gs_steps(wafer_batch *b, uint64_t *onepass, uint64_t *sequential);
 
+/* ---- Rayleigh-Ritz on the stores of a batch --------------------------------
+ * wafer_ritz_matrices, wafer_ritz_solve and wafer_rotate_states (above) on the first k[m] stored states of every listed member
+ * (active[m] != 0; NULL: all), each with its own k: one sums launch, one reduce launch and one read-back for all listed members
+ * whatever their number and shapes, the solves on the host, one rotation launch for the members that solved.  Every member gets
+ * bit for bit what a wafer_ctx of its own wafer_params, holding the same states and potential, gets from the three context calls.
+ * k has n_members entries; entries of members not listed are not read.  An empty list returns WAFER_OK and launches nothing.
+ * Every check for every listed member runs before anything is uploaded or launched, the refusal names the member, and a refused
+ * call changes no store and writes no output: k[m] == 0 or k[m] > WAFER_RITZ_MAX is WAFER_ERR_INVALID; k[m] above the member's
+ * state count, or no potential on it where the matrices are needed, WAFER_ERR_STATE; a non-finite coef entry of a listed member
+ * WAFER_ERR_INVALID.  A mixed-shape batch made without state stores refuses all three calls as it refuses every excited-state call.
+ * phi, the states beyond k[m] and the members not listed are never touched.  After a rotation the one-pass Gram-Schmidt form
+ * recomputes the rotated members' Gram matrices before its next step.
+ *
+ * h, s: n_members * WAFER_RITZ_MAX^2 doubles each; member m's k[m] x k[m] row-major matrices packed at m * WAFER_RITZ_MAX^2.
+ * Entries of members not listed are not written. */
+int wafer_batch_ritz_matrices(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *h, double *s);
+/* coef: as above, member m's k[m] x k[m] at m * WAFER_RITZ_MAX^2 */
+int wafer_batch_rotate_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, const double *coef);
+/* the three in sequence; evals: n_members * WAFER_RITZ_MAX; h, s may be NULL; status: n_members entries.
+ * A solve that fails (linearly dependent states, no Jacobi convergence) is that member's status, not the call's: the member gets
+ * status[m] = WAFER_ERR_STATE, its store and its evals / coef entries stay untouched, its h / s are still written where given;
+ * the other members are rotated and get WAFER_OK, the call returns WAFER_OK and wafer_last_error names the first failed member.
+ * Members not listed keep their status entry as passed in. */
+int wafer_batch_ritz(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *evals, double *coef,
+                     double *h, double *s, int *status);
+/* launches and read-backs of the three calls above since creation: wafer_batch_ritz_matrices 2 and 1, wafer_batch_rotate_states
+ * 1 and 0, wafer_batch_ritz 3 and 1, whatever the number of members and shapes (the lazy Gram refresh is the next excited step's) */
+int wafer_batch_diag_ritz_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
+
 #ifdef __cplusplus
 }
 #endif

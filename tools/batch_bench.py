@@ -45,7 +45,16 @@ of the same batch -- the code path a batch has without the batched calls, unchan
 SimpleCornell, Cube in turn) and starts (Boolean, Gaussian, Constant, Coulomb).  The parts are listed too ("*_potentials_ms",
 "*_starts_ms": the starts alone do not wait for the device).  --reps repetitions after one warm-up of each, every one listed; "ratio":
 per_member over batched, per repetition; "parity": V and phi of the first and the last member bit-identical after either; "setup_counts":
-the launches and read-backs one batched repetition adds.  Appended to profiles/batch_setup_rows.jsonl unless --out names another file."""
+the launches and read-backs one batched repetition adds.  Appended to profiles/batch_setup_rows.jsonl unless --out names another file.
+--ritz K: a mode of its own -- Rayleigh-Ritz on K stored states per member (orthonormal, seeded random; Harmonic).  One line per B: the
+members are --sizes' first size, or cycle through --mixed's shapes in one mixed-shape batch with state stores.  "batch_matrices_ms": host
+clock around Batch.ritz_matrices(K) (two launches and one read-back for all members: it returns with the sums), "ctx_matrices_ms": around
+B Contexts holding the same states calling ritz_matrices(K) one after another -- what a user does without the batched call;
+"batch_ritz_ms" / "ctx_ritz_ms": the same for Batch.ritz(K) and the contexts' ritz(K), each side followed by a download of the last
+member's state 0, which waits for the rotation.  --reps repetitions after one warm-up of each, every one listed, with "*_spread" =
+(max - min) / median; "ratio_*": ctx over batch, per repetition.  "parity": every member's h, s and every rotated state bit-identical on
+both sides after the last repetition; "ritz_counts": the launches and read-backs one Batch.ritz adds.  Appended to
+profiles/batch_ritz_rows.jsonl unless --out names another file."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -325,6 +334,78 @@ def setup_row(shapes, B, reps, ext=1, dtype="f64"):
     return out
 
 
+def ritz_row(shapes, B, K, reps, ext=1, dtype="f64"):
+    pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype,
+                             max_states=K) for k in range(B)]
+    out = {"mode": "ritz", "k": K, "shapes": [list(s) for s in shapes], "B": B, "reps": reps, "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1],
+           "dtype": dtype, "potential": "Harmonic"}
+    per_shape = {s: [store(pars[shapes.index(s)], K, seed=j) for j in range(2)] for s in dict.fromkeys(shapes)}   # (two stores per shape, shared out)
+    stores = [per_shape[shapes[k % len(shapes)]][(k // len(shapes)) % 2] for k in range(B)]
+    keys = ("batch_matrices_ms", "ctx_matrices_ms", "batch_ritz_ms", "ctx_ritz_ms")
+    for key in keys:
+        out[key] = []
+    mixed = len(set(shapes)) > 1
+    ctxs = [wafer_amd.Context(p) for p in pars]
+    try:
+        with wafer_amd.Batch(pars, mixed_shapes=mixed, state_stores=mixed) as b:
+            b.set_potentials(["Harmonic"] * B)
+            for k, c in enumerate(ctxs):
+                c.set_potential("Harmonic")
+                for i in range(K):
+                    c.load_state(i, stores[k][i])
+                    b.load_state(k, i, stores[k][i])
+
+            def batch_matrices():
+                t0 = time.perf_counter()
+                res = b.ritz_matrices(K)
+                return 1e3 * (time.perf_counter() - t0), res
+
+            def ctx_matrices():
+                t0 = time.perf_counter()
+                res = [c.ritz_matrices(K) for c in ctxs]
+                return 1e3 * (time.perf_counter() - t0), res
+
+            def batch_ritz():
+                t0 = time.perf_counter()
+                b.ritz(K)
+                b.download_state(B - 1, 0)   # (waits for the rotation)
+                return 1e3 * (time.perf_counter() - t0)
+
+            def ctx_ritz():
+                t0 = time.perf_counter()
+                for c in ctxs:
+                    c.ritz(K)
+                ctxs[-1].download_state(0)
+                return 1e3 * (time.perf_counter() - t0)
+
+            batch_matrices(), ctx_matrices(), batch_ritz(), ctx_ritz()   # warm-up of each: the buffers are made here
+            for _ in range(reps):
+                out["batch_matrices_ms"].append(batch_matrices()[0])
+                out["ctx_matrices_ms"].append(ctx_matrices()[0])
+                out["batch_ritz_ms"].append(batch_ritz())
+                out["ctx_ritz_ms"].append(ctx_ritz())
+            c0 = b.ritz_counts()
+            batch_ritz()
+            ctx_ritz()
+            out["ritz_counts"] = [x - y for x, y in zip(b.ritz_counts(), c0)]
+            same = lambda x, y: bool(np.array_equal(np.ascontiguousarray(x).view(np.int64), np.ascontiguousarray(y).view(np.int64)))
+            parity = True
+            for (bh, bs), (ch, cs) in zip(batch_matrices()[1], ctx_matrices()[1]):
+                parity = parity and same(bh, ch) and same(bs, cs)
+            for k, c in enumerate(ctxs):
+                parity = parity and all(same(b.download_state(k, i), c.download_state(i)) for i in range(K))
+            out["parity"] = parity
+            out["shapes_in_batch"] = b.num_shapes()
+    finally:
+        for c in ctxs:
+            c.close()
+    for key in keys:
+        out[key.replace("_ms", "_spread")] = (max(out[key]) - min(out[key])) / float(np.median(out[key]))
+    out["ratio_matrices"] = [c / h for c, h in zip(out["ctx_matrices_ms"], out["batch_matrices_ms"])]
+    out["ratio_ritz"] = [c / h for c, h in zip(out["ctx_ritz_ms"], out["batch_ritz_ms"])]
+    return out
+
+
 def rounded(d):
     if isinstance(d, dict):
         return {k: rounded(v) for k, v in d.items()}
@@ -356,7 +437,19 @@ def main():
     ap.add_argument("--resample-contexts-only", action="store_true", help="--resample: the contexts alone")
     ap.add_argument("--setup", type=int, metavar="B", help="time Batch.set_initial_conditions + set_potentials on B members against the loops of "
                     "per-member calls on the same batch (a mode of its own; --reps, --sizes or --mixed, --ext, --dtype apply)")
+    ap.add_argument("--ritz", type=int, metavar="K", help="time Batch.ritz_matrices and Batch.ritz on K stored states per member against B contexts "
+                    "calling ritz_matrices / ritz one after another (a mode of its own; --batch, --reps, --sizes or --mixed, --ext, --dtype apply)")
     a = ap.parse_args()
+    if a.ritz:
+        if not a.out:
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_ritz_rows.jsonl")
+        shapes = parse_shapes(a.mixed) if a.mixed else [(a.sizes[0],) * 3]
+        for B in a.batch:
+            line = json.dumps(rounded(ritz_row(shapes, B, a.ritz, a.reps, a.ext, a.dtype)))
+            print(line, flush=True)
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+        return
     if a.setup:
         if not a.out:
             a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_setup_rows.jsonl")

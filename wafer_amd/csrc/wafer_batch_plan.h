@@ -184,13 +184,16 @@ static inline std::vector<WaferBatchBlock> wafer_batch_fused_table(const WaferGe
 // one a context of that shape builds (ghost depth G, elements of esz bytes); shape_of[m]: member m's entry; off[m]: its element
 // offset in each array allocation = the sum of the padded totals of the members before it (one shape: m * geoms[0].total);
 // cells: the sum over all members.  overflow: cells, or cells * esz, passed the size of one allocation at member off.size() - 1,
-// where the walk stopped.
+// where the walk stopped.  misaligned: a member's span does not start or end on 16 bytes (the batched rotation of stored states walks
+// every span in whole 16-byte vectors, wafer_ritz_batch.hip.h); wafer_make_geom's pitch of whole 128-byte lines rules it out for
+// 4- and 8-byte elements alike, and creation fails loudly if that ever changes.
 struct WaferBatchLayout {
     std::vector<WaferGeom> geoms;
     std::vector<int> shape_of;
     std::vector<size_t> off;
     size_t cells = 0;
     bool overflow = false;
+    bool misaligned = false;
 };
 
 static inline WaferBatchLayout wafer_batch_layout(const int *nxyz, uint32_t n_members, int R, int G, size_t esz)
@@ -204,6 +207,7 @@ static inline WaferBatchLayout wafer_batch_layout(const int *nxyz, uint32_t n_me
         L.shape_of.push_back((int)k);
         L.off.push_back(L.cells);
         L.overflow = __builtin_add_overflow(L.cells, (size_t)L.geoms[k].total, &L.cells) || __builtin_mul_overflow(L.cells, esz, &bytes);
+        if (!L.overflow && ((L.off.back() * esz) % 16 != 0 || bytes % 16 != 0)) L.misaligned = true;
     }
     return L;
 }

@@ -33,6 +33,9 @@
 // its partials come from wafer_batch_gs_partition (wafer_batch_plan.h; `gsp`, and in its WaferBatchMember).  On several shapes they
 // are opt-in at creation (wafer_batch_create_mixed_states: `mixed_states`); a batch of several shapes made by
 // wafer_batch_create_mixed refuses the excited-state calls as it always has (refuse_mixed).
+// Rayleigh-Ritz on the stores (wafer_batch_ritz_matrices, wafer_batch_rotate_states, wafer_batch_ritz; kernels: wafer_ritz_batch.hip.h,
+// wafer_tu_ritz_batch.hip): a context's wafer_ritz_* for every listed member with its own k -- one sums launch, one reduce and one
+// read-back, the solves on the host (wafer_ritz.h), one rotation launch -- from a per-call table of (member, k, partials offset, span).
 #include <memory>
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
@@ -40,6 +43,8 @@
 #include "wafer_gs_batch.hip.h"
 #include "wafer_resample_batch.hip.h"
 #include "wafer_setup_batch.hip.h"
+#include "wafer_ritz_batch.hip.h"
+#include "wafer_ritz.h"
 
 struct wafer_batch {
     uint32_t n = 0;
@@ -115,6 +120,13 @@ struct wafer_batch {
     WaferBatchSetupRec *setup_dev = nullptr, *setup_host = nullptr;
     unsigned long long *vchk_dev = nullptr, *vchk_init = nullptr, *vchk_host = nullptr;
     uint64_t n_setup_launches = 0, n_setup_readbacks = 0;   // of the batched set-up paths since creation (wafer_batch_diag_setup_counts)
+    // Rayleigh-Ritz on the stores (wafer_ritz_batch.hip.h); everything below is made by the first call (ensure_ritz)
+    WaferBatchRitzRec *ritz_rec_dev = nullptr, *ritz_rec_host = nullptr;   // the per-call table, n entries
+    double *ritz_partials = nullptr;          // the listed members' 2 k^2 rows of obs_nb partials end to end; grown on demand
+    size_t ritz_cap = 0;                      // doubles
+    double *ritz_sums = nullptr, *ritz_sums_host = nullptr;   // [member][2][WAFER_RITZ_MAX^2]
+    double *ritz_coef = nullptr, *ritz_coef_host = nullptr;   // [member][WAFER_RITZ_MAX^2]
+    uint64_t n_ritz_launches = 0, n_ritz_readbacks = 0;       // of the three calls since creation (wafer_batch_diag_ritz_counts)
 };
 
 namespace {
@@ -171,10 +183,11 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
-                    (void *)b->gram_list_dev, (void *)b->rs_scratch, (void *)b->setup_dev, (void *)b->vchk_dev})
+                    (void *)b->gram_list_dev, (void *)b->rs_scratch, (void *)b->setup_dev, (void *)b->vchk_dev, (void *)b->ritz_rec_dev,
+                    (void *)b->ritz_partials, (void *)b->ritz_sums, (void *)b->ritz_coef})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host, (void *)b->setup_host,
-                    (void *)b->vchk_init, (void *)b->vchk_host})
+                    (void *)b->vchk_init, (void *)b->vchk_host, (void *)b->ritz_rec_host, (void *)b->ritz_sums_host, (void *)b->ritz_coef_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop, b->rs_start, b->rs_stop})
         if (e) (void)hipEventDestroy(e);
@@ -1059,6 +1072,151 @@ int set_initial_conditions(wafer_batch *b, const uint8_t *active, const int *ics
     return WAFER_OK;
 }
 
+// ---- Rayleigh-Ritz on the stores ---------------------------------------------------------------------------------------------
+constexpr size_t RITZ_KK = (size_t)WAFER_RITZ_MAX * WAFER_RITZ_MAX;
+
+// every check of a call for every listed member, before anything is uploaded or launched; *nlisted: their number
+int ritz_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, bool need_pot, const char *call, int *nlisted)
+{
+    TRY(refuse_mixed(b, call));
+    *nlisted = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (k[m] == 0 || k[m] > WAFER_RITZ_MAX)
+            return fail(WAFER_ERR_INVALID, "member %u: k = %u: Rayleigh-Ritz takes 1 .. %d states", m, k[m], WAFER_RITZ_MAX);
+        if (k[m] > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
+        if (need_pot && !b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
+        ++*nlisted;
+    }
+    return WAFER_OK;
+}
+
+int ensure_ritz(wafer_batch *b)
+{
+    if (b->ritz_coef_host) return WAFER_OK;   // (the last one made below)
+    if (!b->ritz_rec_dev) HIP_TRY(hipMalloc((void **)&b->ritz_rec_dev, sizeof(WaferBatchRitzRec) * b->n));
+    if (!b->ritz_rec_host) HIP_TRY(hipHostMalloc((void **)&b->ritz_rec_host, sizeof(WaferBatchRitzRec) * b->n, hipHostMallocDefault));
+    if (!b->ritz_sums) HIP_TRY(hipMalloc((void **)&b->ritz_sums, sizeof(double) * 2 * RITZ_KK * b->n));
+    if (!b->ritz_sums_host) HIP_TRY(hipHostMalloc((void **)&b->ritz_sums_host, sizeof(double) * 2 * RITZ_KK * b->n, hipHostMallocDefault));
+    if (!b->ritz_coef) HIP_TRY(hipMalloc((void **)&b->ritz_coef, sizeof(double) * RITZ_KK * b->n));
+    HIP_TRY(hipHostMalloc((void **)&b->ritz_coef_host, sizeof(double) * RITZ_KK * b->n, hipHostMallocDefault));
+    memset(b->ritz_coef_host, 0, sizeof(double) * RITZ_KK * b->n);
+    return WAFER_OK;
+}
+
+// ritz_partials holds at least `doubles`: grown on demand, as a context's ritz_buf (the stream is idle: the callers synchronised)
+int ensure_ritz_partials(wafer_batch *b, size_t doubles)
+{
+    if (b->ritz_cap >= doubles) return WAFER_OK;
+    if (b->ritz_partials) (void)hipFree(b->ritz_partials);
+    b->ritz_partials = nullptr;
+    b->ritz_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->ritz_partials, sizeof(double) * doubles));
+    b->ritz_cap = doubles;
+    return WAFER_OK;
+}
+
+// The per-call table of the listed members into ritz_rec_host and to the device: member, k, the prefix sums of 2 k^2 obs_nb, the
+// member's span in a slot allocation.  The stream is idle (the callers synchronised: ritz_rec_host is not read by an earlier copy).
+int upload_ritz_table(wafer_batch *b, const uint8_t *listed, const uint32_t *k, int *nact, int *max_nb, int *max_k, size_t *doubles)
+{
+    int n = 0;
+    size_t poff = 0;
+    *max_nb = *max_k = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (listed && !listed[m]) continue;
+        WaferBatchRitzRec &r = b->ritz_rec_host[n++];
+        r.member = (int)m;
+        r.k = (int)k[m];
+        r.poff = (long long)poff;
+        r.v0 = (long long)(b->off[m] * b->esz / 16);
+        r.n16 = (long long)((size_t)b->geom(m).total * b->esz / 16);
+        poff += 2 * (size_t)k[m] * k[m] * (size_t)b->mem[m].obs_nb;
+        *max_nb = std::max(*max_nb, b->mem[m].obs_nb);
+        *max_k = std::max(*max_k, (int)k[m]);
+    }
+    *nact = n;
+    *doubles = poff;
+    if (n) HIP_TRY(hipMemcpyAsync(b->ritz_rec_dev, b->ritz_rec_host, sizeof(WaferBatchRitzRec) * n, hipMemcpyHostToDevice, b->s));
+    return WAFER_OK;
+}
+
+// the allocations of the store slots the kernels may touch
+WaferRitzPtrs ritz_slots(const wafer_batch *b)
+{
+    WaferRitzPtrs st;
+    for (size_t l = 0; l < WAFER_RITZ_MAX && l < b->slots.size(); ++l) st.p[l] = b->slots[l];
+    return st;
+}
+
+// H and S of every listed member (checked: ritz_check) into ritz_sums_host: the sums launch, the reduce, one read-back
+int ritz_matrices_impl(wafer_batch *b, const uint8_t *active, const uint32_t *k)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    RoctxRange range_("wafer_batch_ritz_matrices");
+    TRY(ensure_ritz(b));
+    TRY(sync_members(b));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    int nact = 0, max_nb = 0, max_k = 0;
+    size_t doubles = 0;
+    for (uint32_t m = 0; m < b->n; ++m)
+        if (!active || active[m]) doubles += 2 * (size_t)k[m] * k[m] * (size_t)b->mem[m].obs_nb;
+    TRY(ensure_ritz_partials(b, doubles));
+    TRY(upload_ritz_table(b, active, k, &nact, &max_nb, &max_k, &doubles));
+    const WaferRitzPtrs st = ritz_slots(b);
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_ritz_sums(b->f32, b->g().R, gs, b->mem_dev, b->ritz_rec_dev, nact, max_nb, max_k, b->swz, st, b->ritz_partials,
+                                           b->ritz_sums, b->s);
+    });
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Rayleigh-Ritz sums launch failed: %s", hipGetErrorString(e));
+    b->n_ritz_launches += 2;
+    // the members from the first listed to the last in one copy
+    const size_t m0 = (size_t)b->ritz_rec_host[0].member, m1 = (size_t)b->ritz_rec_host[nact - 1].member + 1;
+    HIP_TRY(hipMemcpyAsync(b->ritz_sums_host + m0 * 2 * RITZ_KK, b->ritz_sums + m0 * 2 * RITZ_KK, sizeof(double) * 2 * RITZ_KK * (m1 - m0),
+                           hipMemcpyDeviceToHost, b->s));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    ++b->n_ritz_readbacks;
+    return WAFER_OK;
+}
+
+// member m's k x k matrices out of ritz_sums_host
+void ritz_unpack(const wafer_batch *b, uint32_t m, uint32_t k, double *h, double *s)
+{
+    const double *r = b->ritz_sums_host + (size_t)m * 2 * RITZ_KK;
+    for (size_t q = 0; q < (size_t)k * k; ++q) {
+        if (h) h[q] = r[q];
+        if (s) s[q] = r[RITZ_KK + q];
+    }
+}
+
+// the rotation of the listed members (checked; coef: member m's k[m] x k[m] at m * WAFER_RITZ_MAX^2, finite): one launch
+int ritz_rotate_impl(wafer_batch *b, const uint8_t *listed, const uint32_t *k, const double *coef)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    RoctxRange range_("wafer_batch_rotate_states");
+    TRY(ensure_ritz(b));
+    HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table and coefficients are not read by an earlier call's copy
+    int nact = 0, max_nb = 0, max_k = 0;
+    size_t doubles = 0;
+    TRY(upload_ritz_table(b, listed, k, &nact, &max_nb, &max_k, &doubles));
+    if (!nact) return WAFER_OK;
+    long long want = 1;
+    for (int q = 0; q < nact; ++q) {
+        const uint32_t m = (uint32_t)b->ritz_rec_host[q].member;
+        memcpy(b->ritz_coef_host + m * RITZ_KK, coef + m * RITZ_KK, sizeof(double) * k[m] * k[m]);
+        want = std::max(want, (b->ritz_rec_host[q].n16 + 255) / 256);
+    }
+    const size_t m0 = (size_t)b->ritz_rec_host[0].member, m1 = (size_t)b->ritz_rec_host[nact - 1].member + 1;
+    HIP_TRY(hipMemcpyAsync(b->ritz_coef + m0 * RITZ_KK, b->ritz_coef_host + m0 * RITZ_KK, sizeof(double) * RITZ_KK * (m1 - m0), hipMemcpyHostToDevice,
+                           b->s));
+    const int blocks = (int)std::min<long long>(want, (long long)b->num_cus * 8);
+    const hipError_t e = wafer_entry_batch_rotate_states(b->f32, b->ritz_rec_dev, nact, blocks, ritz_slots(b), b->ritz_coef, b->s);
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched rotation launch failed: %s", hipGetErrorString(e));
+    ++b->n_ritz_launches;
+    for (int q = 0; q < nact; ++q) mark_gram_stale(b, (uint32_t)b->ritz_rec_host[q].member);   // the one-pass form sees the new store
+    return WAFER_OK;
+}
+
 // ---- creation --------------------------------------------------------------------------------------------------------------
 // Every member's partition record and the places of its partials.  Observables: the partition wafer_launch_observables_lds gives a
 // single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
@@ -1165,6 +1323,9 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     if (L.overflow)
         return fail(WAFER_ERR_INVALID, "%u members of %zu padded cells up to member %u overflow the size of one allocation", n_members, L.cells,
                     (uint32_t)L.off.size() - 1);
+    if (L.misaligned)
+        return fail(WAFER_ERR_INVALID, "a member's span in the batch's allocations does not start and end on 16 bytes (elements of %zu bytes): "
+                                       "the rotation of stored states walks whole 16-byte vectors", esz);
 
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
@@ -1646,6 +1807,80 @@ int wafer_batch_diag_gs_steps(wafer_batch *b, uint64_t *onepass, uint64_t *seque
     if (!b || !onepass || !sequential) return fail(WAFER_ERR_INVALID, "null argument");
     *onepass = b->n_onepass;
     *sequential = b->n_sequential;
+    return WAFER_OK;
+}
+
+int wafer_batch_ritz_matrices(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *h, double *s)
+{
+    if (!b || !k || !h || !s) return fail(WAFER_ERR_INVALID, "null argument");
+    int nlisted = 0;
+    TRY(ritz_check(b, active, k, true, "wafer_batch_ritz_matrices", &nlisted));
+    if (!nlisted) return WAFER_OK;
+    TRY(ritz_matrices_impl(b, active, k));
+    for (uint32_t m = 0; m < b->n; ++m)
+        if (!active || active[m]) ritz_unpack(b, m, k[m], h + m * RITZ_KK, s + m * RITZ_KK);
+    return WAFER_OK;
+}
+
+int wafer_batch_rotate_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, const double *coef)
+{
+    if (!b || !k || !coef) return fail(WAFER_ERR_INVALID, "null argument");
+    int nlisted = 0;
+    TRY(ritz_check(b, active, k, false, "wafer_batch_rotate_states", &nlisted));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        for (uint32_t q = 0; q < k[m] * k[m]; ++q)
+            if (!std::isfinite(coef[m * RITZ_KK + q])) return fail(WAFER_ERR_INVALID, "member %u: coef[%u] is not finite", m, q);
+    }
+    if (!nlisted) return WAFER_OK;
+    return ritz_rotate_impl(b, active, k, coef);
+}
+
+int wafer_batch_ritz(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *evals, double *coef, double *h, double *s, int *status)
+{
+    if (!b || !k || !evals || !coef || !status) return fail(WAFER_ERR_INVALID, "null argument");
+    int nlisted = 0;
+    TRY(ritz_check(b, active, k, true, "wafer_batch_ritz", &nlisted));
+    if (!nlisted) return WAFER_OK;
+    TRY(ritz_matrices_impl(b, active, k));
+    // the solves: a member whose solve fails keeps its store and its evals / coef entries; that is its status, not the call's
+    std::vector<uint8_t> solved(b->n, 0);
+    std::vector<double> ev((size_t)WAFER_RITZ_MAX * b->n), cf(RITZ_KK * b->n, 0.0);
+    std::string first_failure;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        double hm[RITZ_KK], sm[RITZ_KK];
+        ritz_unpack(b, m, k[m], hm, sm);
+        const int rc = wafer_ritz_solve_host((int)k[m], hm, sm, ev.data() + (size_t)m * WAFER_RITZ_MAX, cf.data() + m * RITZ_KK);
+        solved[m] = rc == WAFER_RITZ_OK;
+        if (!solved[m] && first_failure.empty()) {
+            char msg[224];
+            if (rc == WAFER_RITZ_NO_CONVERGENCE)
+                snprintf(msg, sizeof msg, "member %u: Rayleigh-Ritz: the Jacobi iteration did not converge in %d sweeps", m, (int)WAFER_RITZ_SWEEPS);
+            else
+                snprintf(msg, sizeof msg, "member %u: Rayleigh-Ritz: the overlap matrix is not positive definite (linearly dependent states, "
+                                          "or a non-finite sum)", m);
+            first_failure = msg;
+        }
+    }
+    TRY(ritz_rotate_impl(b, solved.data(), k, cf.data()));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        ritz_unpack(b, m, k[m], h ? h + m * RITZ_KK : nullptr, s ? s + m * RITZ_KK : nullptr);
+        status[m] = solved[m] ? WAFER_OK : WAFER_ERR_STATE;
+        if (!solved[m]) continue;
+        for (size_t q = 0; q < (size_t)k[m] * k[m]; ++q) coef[m * RITZ_KK + q] = cf[m * RITZ_KK + q];
+        for (uint32_t q = 0; q < k[m]; ++q) evals[(size_t)m * WAFER_RITZ_MAX + q] = ev[(size_t)m * WAFER_RITZ_MAX + q];
+    }
+    if (!first_failure.empty()) (void)fail(WAFER_ERR_STATE, "%s", first_failure.c_str());   // wafer_last_error names the first failed member
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_ritz_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks)
+{
+    if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
+    *launches = b->n_ritz_launches;
+    *readbacks = b->n_ritz_readbacks;
     return WAFER_OK;
 }
 

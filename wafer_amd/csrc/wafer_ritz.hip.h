@@ -22,49 +22,17 @@ struct WaferRitzCfg {
     static constexpr int NW = R <= 2 ? 8 : 4;
 };
 
-// Column j = blockIdx.y: with w = l_j[c], S = the bracketed sum of l_j at c and vv = V[c], every work cell c adds
-//   h_i += vv * l_i[c] * w - (l_i[c] * S) / den        s_i += l_i[c] * w         for i < k
-// -- every operand widened to double, every operation fp64 and unfused.  For i == j the h term is the energy integrand of
-// wafer_k_step_lds<NLOW = -2> (grid.rs:325-332) and the s term its w * w, letter for letter, and the partition is that launch's:
-// NW waves x RY = 2 rows x VEC cells per lane (16 bytes of T), a.zchunk planes per workgroup, the same XCD swizzle, a lane's
-// cells taken in the order plane, row, cell -- so the diagonal sums have the bits of wafer_observables on the same state.
-// The frame cells of l_j enter S as they are stored (zeros in every state the engine itself produces); nothing outside the work
-// area is summed.  x neighbours outside the lane's own vector and the y, z neighbours come straight from global memory (L1 / L2):
-// the kernel runs a handful of times after a solve.
-// partials[(j * k + i) * pstride + workgroup] = the workgroup's h_i, partials[(k * k + j * k + i) * pstride + workgroup] = s_i;
-// no floating-point atomics.  wafer_k_reduce over the 2 k^2 rows follows.
+// The per-cell body of the sums kernels, one text for the context's kernel below and the batch's (wafer_ritz_batch.hip.h): the lane's
+// cells -- RY = 2 rows from work row yw, VEC cells from work column xi, planes [zs, ze) -- in the order plane, row, cell, adding
+// into h[i], s[i] for i < k.  lj: the column's state, pv: V, both logical pointers (plane 0, row 0); state i is st.p[i] + moff.
 template <int R, typename T>
-__global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_ritz_sums(WaferStepArgs a, int ntx, int nty, int swz, int k, WaferRitzPtrs st,
-                                                                               const T *__restrict__ pv, double *__restrict__ partials,
-                                                                               long long pstride)
+__device__ __forceinline__ void wafer_ritz_cells(const WaferGeom &g, int xi, int yw, int zs, int ze, int k, const T *__restrict__ lj,
+                                                 const WaferRitzPtrs &st, long long moff, const T *__restrict__ pv,
+                                                 const WaferDen<double> &den, double (&h)[WAFER_RITZ_MAX], double (&s)[WAFER_RITZ_MAX])
 {
-    constexpr int NW = WaferRitzCfg<R>::NW, RY = 2, KM = WAFER_RITZ_MAX;
+    constexpr int RY = 2, KM = WAFER_RITZ_MAX;
     using VT = typename WaferVec<T>::type;
-    constexpr int VEC = WaferVec<T>::N, TX = 64 * VEC, TY = NW * RY;
-    __shared__ double red[NW];
-    const WaferGeom &g = a.g;
-    int bid = blockIdx.x;
-    if (swz) bid = wafer_xcd_tile(bid, gridDim.x);
-    const int tx_i = bid % ntx;
-    const int ty_i = (bid / ntx) % nty;
-    const int tz_i = bid / (ntx * nty);
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int xi = tx_i * TX + lane * VEC;      // work-x of the lane's first cell
-    const int yw = ty_i * TY + wave * RY;       // work-y of the lane's first row
-    const int zs = a.lz_lo + tz_i * a.zchunk;
-    const int ze = min(zs + a.zchunk, a.lz_hi);
-    const int j = blockIdx.y;
-    // the column's state, by a select chain (an index into the argument block would be a private array)
-    const T *__restrict__ lj = static_cast<const T *>(st.p[0]);
-#pragma unroll
-    for (int i = 1; i < KM; ++i)
-        if (j == i) lj = static_cast<const T *>(st.p[i]);
-    const WaferDen<double> den = wafer_den<double>(a, a.v_in_range != 0);
-
-    double h[KM], s[KM];
-#pragma unroll
-    for (int i = 0; i < KM; ++i) h[i] = s[i] = 0.0;
+    constexpr int VEC = WaferVec<T>::N;
     for (int z = zs; z < ze; ++z) {
         const long long zo = (long long)z * g.plane;
 #pragma unroll
@@ -90,7 +58,7 @@ __global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_ritz_sums(Wa
             VT li[KM];
 #pragma unroll
             for (int i = 0; i < KM; ++i)
-                if (i < k) li[i] = *reinterpret_cast<const VT *>(static_cast<const T *>(st.p[i]) + c0);
+                if (i < k) li[i] = *reinterpret_cast<const VT *>(static_cast<const T *>(st.p[i]) + moff + c0);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 if (xi + v >= g.nx) continue;
@@ -120,6 +88,51 @@ __global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_ritz_sums(Wa
             }
         }
     }
+}
+
+// Column j = blockIdx.y: with w = l_j[c], S = the bracketed sum of l_j at c and vv = V[c], every work cell c adds
+//   h_i += vv * l_i[c] * w - (l_i[c] * S) / den        s_i += l_i[c] * w         for i < k
+// -- every operand widened to double, every operation fp64 and unfused.  For i == j the h term is the energy integrand of
+// wafer_k_step_lds<NLOW = -2> (grid.rs:325-332) and the s term its w * w, letter for letter, and the partition is that launch's:
+// NW waves x RY = 2 rows x VEC cells per lane (16 bytes of T), a.zchunk planes per workgroup, the same XCD swizzle, a lane's
+// cells taken in the order plane, row, cell -- so the diagonal sums have the bits of wafer_observables on the same state.
+// The frame cells of l_j enter S as they are stored (zeros in every state the engine itself produces); nothing outside the work
+// area is summed.  x neighbours outside the lane's own vector and the y, z neighbours come straight from global memory (L1 / L2):
+// the kernel runs a handful of times after a solve.
+// partials[(j * k + i) * pstride + workgroup] = the workgroup's h_i, partials[(k * k + j * k + i) * pstride + workgroup] = s_i;
+// no floating-point atomics.  wafer_k_reduce over the 2 k^2 rows follows.
+template <int R, typename T>
+__global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_ritz_sums(WaferStepArgs a, int ntx, int nty, int swz, int k, WaferRitzPtrs st,
+                                                                               const T *__restrict__ pv, double *__restrict__ partials,
+                                                                               long long pstride)
+{
+    constexpr int NW = WaferRitzCfg<R>::NW, RY = 2, KM = WAFER_RITZ_MAX;
+    constexpr int VEC = WaferVec<T>::N, TX = 64 * VEC, TY = NW * RY;
+    __shared__ double red[NW];
+    const WaferGeom &g = a.g;
+    int bid = blockIdx.x;
+    if (swz) bid = wafer_xcd_tile(bid, gridDim.x);
+    const int tx_i = bid % ntx;
+    const int ty_i = (bid / ntx) % nty;
+    const int tz_i = bid / (ntx * nty);
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int xi = tx_i * TX + lane * VEC;      // work-x of the lane's first cell
+    const int yw = ty_i * TY + wave * RY;       // work-y of the lane's first row
+    const int zs = a.lz_lo + tz_i * a.zchunk;
+    const int ze = min(zs + a.zchunk, a.lz_hi);
+    const int j = blockIdx.y;
+    // the column's state, by a select chain (an index into the argument block would be a private array)
+    const T *__restrict__ lj = static_cast<const T *>(st.p[0]);
+#pragma unroll
+    for (int i = 1; i < KM; ++i)
+        if (j == i) lj = static_cast<const T *>(st.p[i]);
+    const WaferDen<double> den = wafer_den<double>(a, a.v_in_range != 0);
+
+    double h[KM], s[KM];
+#pragma unroll
+    for (int i = 0; i < KM; ++i) h[i] = s[i] = 0.0;
+    wafer_ritz_cells<R, T>(g, xi, yw, zs, ze, k, lj, st, 0, pv, den, h, s);
 #pragma unroll
     for (int i = 0; i < KM; ++i)
         if (i < k) {   // k is workgroup-uniform: every wave reaches the same barriers

@@ -64,6 +64,7 @@ EXPORTS = [
     "wafer_batch_set_potentials_builtin", "wafer_batch_set_initial_conditions", "wafer_batch_download_array", "wafer_batch_get_potsub",
     "wafer_batch_diag_member", "wafer_batch_diag_setup_counts",
     "wafer_ritz_solve", "wafer_ritz_matrices", "wafer_rotate_states", "wafer_ritz",
+    "wafer_batch_ritz_matrices", "wafer_batch_rotate_states", "wafer_batch_ritz", "wafer_batch_diag_ritz_counts",
 ]
 RITZ_MAX = 8   # WAFER_RITZ_MAX
 
@@ -281,6 +282,11 @@ def load_library():
     L.wafer_batch_get_potsub.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int), dp]
     L.wafer_batch_diag_member.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
     L.wafer_batch_diag_setup_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    u32p = C.POINTER(C.c_uint32)
+    L.wafer_batch_ritz_matrices.argtypes = [vp, u8p, u32p, dp, dp]
+    L.wafer_batch_rotate_states.argtypes = [vp, u8p, u32p, dp]
+    L.wafer_batch_ritz.argtypes = [vp, u8p, u32p, dp, dp, dp, dp, C.POINTER(C.c_int)]
+    L.wafer_batch_diag_ritz_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -802,6 +808,11 @@ class Batch:
     with ONE range check and read-back for all of them where a per-member call pays two launches, two read-backs and a synchronisation
     each -- bit for bit what set_potential / set_initial_condition give member by member (setup_counts()).  download_array(i, which),
     potsub(i) and member_info(i) read a member back as a Context's calls do.
+    ritz_matrices(k, active) / rotate_states(coefs, active) / ritz(k, active): Context.ritz_matrices / rotate_states / ritz on the first
+    k[m] stored states of every listed member -- one sums launch, one reduce and one read-back for all members of any shapes, the
+    solves on the host, one rotation launch for the members that solved (ritz_counts()) -- each member bit for bit what a Context of
+    its Params with the same potential and states gets.  k: an int, one entry per member, or None for each member's state count.  A
+    member whose solve fails keeps its store and reports it in its "status"; the others are rotated.
     python -m wafer_amd.sweep drives whole wafer.yaml runs through batches with these calls: phases per state number, every run
     with its own screen_update, tolerance and max_steps, one evolve for all running members between block boundaries."""
 
@@ -1052,6 +1063,92 @@ class Batch:
     def clone_state_to_phi(self, idx: int, active=None) -> None:
         a = self._mask(active)
         self._check(self._L.wafer_batch_clone_state_to_phi(self._h, self._u8(a), idx))
+
+    # -- Rayleigh-Ritz on the stores (include/wafer_hip.h) ------------------------------------------------
+    def _ritz_ks(self, k, a) -> list:
+        """one k per member from an int (every listed member's), a sequence with one entry per member, or None (each member's own
+        state count); the listed entries checked against 1 .. RITZ_MAX and the member's max_states.  Entries of members not listed
+        are passed on as 0: the library does not read them."""
+        B = len(self.members)
+        if k is None:
+            ks = self.num_states()
+        elif np.ndim(k) == 0:
+            ks = [int(k)] * B
+        else:
+            ks = [0 if x is None else int(x) for x in k]
+            if len(ks) != B:
+                raise ValueError("k must hold one entry per member")
+        for m in range(B):
+            if a is not None and not a[m]:
+                ks[m] = 0
+                continue
+            if not 1 <= ks[m] <= RITZ_MAX:
+                raise ValueError("member %d: k = %d is outside 1 .. RITZ_MAX = %d" % (m, ks[m], RITZ_MAX))
+            if ks[m] > self.members[m].max_states:
+                raise ValueError("member %d: k = %d is above its max_states = %d" % (m, ks[m], self.members[m].max_states))
+        return ks
+
+    def ritz_matrices(self, k=None, active=None) -> list:
+        """Context.ritz_matrices(k[m]) for every listed member (active[m] != 0; None: all) in one sums launch, one reduce and one
+        read-back: per member (h, s), (k, k) each, bit for bit what a Context with its Params, potential and states gives; None for
+        the members not listed.  k: an int for every listed member, one entry per member, or None for each member's state count."""
+        a = self._mask(active)
+        ks = self._ritz_ks(k, a)
+        B = len(self.members)
+        h, s = np.zeros((B, RITZ_MAX * RITZ_MAX)), np.zeros((B, RITZ_MAX * RITZ_MAX))
+        self._check(self._L.wafer_batch_ritz_matrices(self._h, self._u8(a), (C.c_uint32 * B)(*ks), _dp(h), _dp(s)))
+        return [None if ks[m] == 0 else (h[m, :ks[m] ** 2].reshape(ks[m], ks[m]).copy(), s[m, :ks[m] ** 2].reshape(ks[m], ks[m]).copy())
+                for m in range(B)]
+
+    def rotate_states(self, coefs, active=None) -> None:
+        """Context.rotate_states(coefs[m]) for every listed member in ONE launch: l'_a = sum_j coefs[m][j, a] l_j over member m's first
+        k = len(coefs[m]) stored states, in place.  coefs: one (k, k) array per member, None for members not listed."""
+        a = self._mask(active)
+        B = len(self.members)
+        if len(coefs) != B:
+            raise ValueError("coefs must hold one entry per member")
+        ks, packed = [0] * B, np.zeros((B, RITZ_MAX * RITZ_MAX))
+        for m in range(B):
+            if a is not None and not a[m]:
+                continue
+            if coefs[m] is None:
+                raise ValueError("member %d: is listed but has no coef (shape (k, k))" % m)
+            c = np.ascontiguousarray(coefs[m], dtype=np.float64)
+            if c.ndim != 2 or c.shape[0] != c.shape[1]:
+                raise ValueError("member %d: coef must have shape (k, k), not %s" % (m, c.shape))
+            ks[m] = c.shape[0]
+            if 1 <= ks[m] <= RITZ_MAX:
+                packed[m, :ks[m] ** 2] = c.ravel()
+        ks = self._ritz_ks(ks, a)
+        self._check(self._L.wafer_batch_rotate_states(self._h, self._u8(a), (C.c_uint32 * B)(*ks), _dp(packed)))
+
+    def ritz(self, k=None, active=None) -> list:
+        """matrices, solve, rotate for every listed member: 3 launches and one read-back whatever the members and shapes.  Per member
+        {"evals": (k,), "coef": (k, k), "h": (k, k), "s": (k, k), "status": int} (h, s before the rotation), None for members not
+        listed.  A member whose solve fails (linearly dependent states) has status WAFER_ERR_STATE, evals and coef None, and keeps
+        its store; the others are rotated."""
+        a = self._mask(active)
+        ks = self._ritz_ks(k, a)
+        B, KK = len(self.members), RITZ_MAX * RITZ_MAX
+        evals, coef, h, s = np.zeros((B, RITZ_MAX)), np.zeros((B, KK)), np.zeros((B, KK)), np.zeros((B, KK))
+        st = (C.c_int * B)()
+        self._check(self._L.wafer_batch_ritz(self._h, self._u8(a), (C.c_uint32 * B)(*ks), _dp(evals), _dp(coef), _dp(h), _dp(s), st))
+        out = []
+        for m in range(B):
+            n = ks[m]
+            if n == 0:
+                out.append(None)
+                continue
+            ok = st[m] == WAFER_OK
+            out.append(dict(evals=evals[m, :n].copy() if ok else None, coef=coef[m, :n * n].reshape(n, n).copy() if ok else None,
+                            h=h[m, :n * n].reshape(n, n).copy(), s=s[m, :n * n].reshape(n, n).copy(), status=int(st[m])))
+        return out
+
+    def ritz_counts(self) -> tuple:
+        """(launches, read-backs) of ritz_matrices, rotate_states and ritz since creation: 2 and 1, 1 and 0, 3 and 1 per call"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_ritz_counts(self._h, C.byref(n), C.byref(r)))
+        return n.value, r.value
 
     def observables(self) -> list:
         """compute_observables (un-normalised) of every member"""

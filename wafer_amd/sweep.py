@@ -3,7 +3,7 @@ every time step ONE launch for all runs of a batch that are still going (wafer_a
 context per run.
 
     python -m wafer_amd.sweep -c a.yaml -c b.yaml ... [--output-dir DIR] [--input-dir DIR] [--max-batch N] [--seed S]
-                              [--progress] [--plan] [--mix-states] [--batched-setup]
+                              [--progress] [--plan] [--mix-states] [--batched-setup] [--ritz]
 
 Configuration reading and validation are the native driver's (`wafer-hip --check-config`, through wafer_amd.run.load_config), the
 input files, the directory names and the table are wafer_amd.run's, and every run computes what `wafer-hip` computes for its file:
@@ -42,6 +42,13 @@ read from the file, for the other formats "shape", "copy" and "resample" are nul
 --batched-setup: the built-in potentials of a batch's runs are ONE Batch.set_potentials call with their mask and the generated starts
 of a phase ONE Batch.set_initial_conditions call with the same seeds, instead of one call per run: the same bits, one range check and
 one read-back per batch instead of one per run.  Opt-in; the default stays the per-member calls.
+
+--ritz: every batch that has state stores ends with ritz_phase -- wafer-hip's `gpu.ritz` step for all of its runs in ONE Batch.ritz call
+(three launches and one read-back whatever the runs and shapes), each run with its own number of stored states.  A run takes part if
+every state it asked for converged and it holds 2 .. 8 states; its table.txt gains wafer-hip's "Ritz" block, its observables_N files
+and saved wavefunctions are rewritten from the rotated states, and its JSON line gains "ritz": {"evals": [...]} (null for a run that
+did not take part).  The `gpu.ritz` key of a wafer.yaml stays refused: the step is asked for per sweep, not per file.  Off by default;
+without it nothing changes.
 """
 from __future__ import annotations
 
@@ -112,6 +119,7 @@ class Run:
         self.lines: list = []        # table.txt, line by line
         self.states: list = []       # per state: dict(state, status, steps, energy)
         self.failed = False
+        self.ritz = None             # --ritz: dict(evals=[...]) once the run's states have been rotated
         self.boundaries: list = []   # the steps of this phase's block boundaries
         # the phase's loop variables (grid.rs:122-125)
         self.step, self.remaining, self.last_energy, self.cloned, self.running = 0, 0, sys.float_info.max, False, False
@@ -149,6 +157,23 @@ def _norm_energy(o: dict) -> float:
     return o["energy"] / o["norm2"] if o["norm2"] != 0.0 else math.nan
 
 
+def final_measurement(w: int, obs: dict, nx: int) -> dict:
+    """output::finalise_measurement's record of state w from the raw sums (output.rs:540-547)"""
+    r_norm = math.sqrt(obs["r2"] / obs["norm2"])
+    return dict(state=w, energy=obs["energy"] / obs["norm2"], binding_energy=(obs["energy"] - obs["v_infinity"]) / obs["norm2"],
+                r=r_norm, l_r=nx / r_norm)
+
+
+def write_observables(r, w: int, fin: dict) -> None:
+    """observables_w.json and .csv of run r"""
+    if r.out_dir is None:
+        return
+    with open(r.path(f"observables_{w}.json"), "w") as f:
+        json.dump(fin, f, indent=2)
+    with open(r.path(f"observables_{w}.csv"), "w") as f:
+        f.write("state,energy,binding_energy,r,l_r\n%d,%r,%r,%r,%r\n" % (w, fin["energy"], fin["binding_energy"], fin["r"], fin["l_r"]))
+
+
 def run_phase(batch, runs: list, w: int, progress: bool = False, push: bool = False, log=sys.stderr) -> None:
     """State w of every run of `runs` (the batch's members in slot order) that takes part, from the starts already in the batch:
     the loop of wafer_cli.cpp:666-753 per run, the batched calls shared as the module docstring says.  push: converged runs go to
@@ -161,17 +186,12 @@ def run_phase(batch, runs: list, w: int, progress: bool = False, push: bool = Fa
 
     def finish(r, obs, converged, status):
         r.running = False
-        r_norm = math.sqrt(obs["r2"] / obs["norm2"])
-        fin = dict(state=w, energy=obs["energy"] / obs["norm2"], binding_energy=(obs["energy"] - obs["v_infinity"]) / obs["norm2"],
-                   r=r_norm, l_r=r.cfg["nx"] / r_norm)
+        fin = final_measurement(w, obs, r.cfg["nx"])
         r.states.append(dict(state=w, status=status, steps=r.step, energy=fin["energy"]))
         if converged:                                                     # output.rs:533-558
             r.say(summary(fin))
+            write_observables(r, w, fin)
             if r.out_dir is not None:
-                with open(r.path(f"observables_{w}.json"), "w") as f:
-                    json.dump(fin, f, indent=2)
-                with open(r.path(f"observables_{w}.csv"), "w") as f:
-                    f.write("state,energy,binding_energy,r,l_r\n%d,%r,%r,%r,%r\n" % (w, fin["energy"], fin["binding_energy"], fin["r"], fin["l_r"]))
                 if r.cfg["snap_update"] is not None and os.path.exists(r.path(f"wavefunction_{w}_partial.npy")):
                     os.remove(r.path(f"wavefunction_{w}_partial.npy"))
         if r.cfg["save_wavefns"]:                                         # grid.rs:223-237: saved whether converged or not
@@ -252,6 +272,62 @@ def run_phase(batch, runs: list, w: int, progress: bool = False, push: bool = Fa
             finish(r, obs[r.slot], True, "Converged")
         if push and done:
             batch.push_state(active=_mask(runs, done))                    # grid.rs:241
+
+
+# ---- Rayleigh-Ritz on the converged sets (--ritz) ----------------------------------------------------------------------------------
+def ritz_phase(batch, runs: list, log=sys.stderr) -> None:
+    """wafer-hip's `gpu.ritz` step (wafer_cli.cpp:764-791) for every run of a batch with state stores, after its last phase: ONE
+    Batch.ritz call for the eligible runs, each with its own state count -- a run is eligible if it has not failed, every state it
+    asked for converged and it holds 2 .. RITZ_MAX states; any other run that holds states gets wafer-hip's line on `log`.  A rotated
+    run's table gains the block wafer-hip prints, and its observables_a files (and, with save_wavefns, wavefunction_a.npy) are
+    rewritten from the rotated states: per state number one clone_state_to_phi and one Batch.observables for all runs that have it.
+    A run whose solve fails (status != 0) keeps its files."""
+    from wafer_amd.engine import RITZ_MAX, WAFER_OK
+    from wafer_amd.run import rust_lower_exp
+
+    held = batch.num_states()
+    eligible = []
+    for r in runs:
+        r.ritz = None
+        ns = held[r.slot]
+        asked = r.cfg["wavemax"] - r.cfg["wavenum"] + 1
+        if r.failed or len(r.states) != asked or any(s["status"] != "Converged" for s in r.states):
+            if ns > 0:
+                print(f"run {r.index}: Ritz: skipped, not every state converged", file=log, flush=True)
+        elif ns < 2 or ns > RITZ_MAX:
+            if ns > 0:
+                print(f"run {r.index}: Ritz: skipped, {ns} stored states (the step takes 2 .. {RITZ_MAX})", file=log, flush=True)
+        else:
+            eligible.append(r)
+    if not eligible:
+        return
+    ks = [0] * len(runs)
+    for r in eligible:
+        ks[r.slot] = held[r.slot]
+    res = batch.ritz(k=ks, active=_mask(runs, eligible))
+    rotated = []
+    for r in eligible:
+        out = res[r.slot]
+        if out["status"] != WAFER_OK:
+            print(f"run {r.index}: Ritz: skipped, the overlap matrix is not positive definite", file=log, flush=True)
+            continue
+        rotated.append(r)
+        k = ks[r.slot]
+        r.ritz = dict(evals=[float(x) for x in out["evals"]])
+        r.say("Ritz")                                                     # state, its energy before the step (H_aa / S_aa), the Ritz value
+        for a in range(k):
+            r.say(f"{a:3d} {rust_lower_exp(out['h'][a][a] / out['s'][a][a], 10):>19} {rust_lower_exp(out['evals'][a], 10):>19}")
+        r.say("")
+    for a in range(max((ks[r.slot] for r in rotated), default=0)):
+        have = [r for r in rotated if ks[r.slot] > a]
+        batch.clone_state_to_phi(a, active=_mask(runs, have))
+        obs = batch.observables()
+        for r in have:
+            write_observables(r, a, final_measurement(a, obs[r.slot], r.cfg["nx"]))
+            if r.cfg["save_wavefns"]:
+                r.save_phi(batch, f"wavefunction_{a}")
+    for r in rotated:
+        r.write_table()
 
 
 # ---- set-up ---------------------------------------------------------------------------------------------------------------------
@@ -470,9 +546,9 @@ def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load, ba
         batch.symmetrise(cons, active=_mask(runs, part))
 
 
-def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False) -> tuple:
+def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False, ritz: bool = False) -> tuple:
     """one batch of the plan from creation to its last phase -> (fused passes, one-step launches).  batched: set_up_batch's and
-    start_phase's (--batched-setup)"""
+    start_phase's (--batched-setup).  ritz: a batch that has state stores ends with ritz_phase (--ritz)"""
     import wafer_amd
 
     pars = []
@@ -491,6 +567,8 @@ def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool =
         for w in range(min(r.cfg["wavenum"] for r in runs), max(r.cfg["wavemax"] for r in runs) + 1):
             start_phase(batch, runs, pars, w, seed, batched=batched)
             run_phase(batch, runs, w, progress=progress, push=plan["needs_states"])
+        if ritz and plan["needs_states"]:
+            ritz_phase(batch, runs)
         return batch.passes()
 
 
@@ -509,6 +587,9 @@ def main(argv=None) -> int:
     ap.add_argument("--batched-setup", action="store_true",
                     help="built-in potentials and generated starts of a batch in one Batch.set_potentials / set_initial_conditions call "
                          "instead of one call per run (the same results)")
+    ap.add_argument("--ritz", action="store_true",
+                    help="after the last phase of every batch with state stores, one Rayleigh-Ritz step on the converged states of its runs "
+                         "(what gpu.ritz: true does in wafer-hip), all runs of the batch in one Batch.ritz call")
     args = ap.parse_args(argv)
     if args.max_batch < 1:
         raise SystemExit("--max-batch must be >= 1")
@@ -524,8 +605,8 @@ def main(argv=None) -> int:
         if c["screen_update"] < 1:
             raise SystemExit(f"{p}: a sweep needs screen_update >= 1")
         if c.get("ritz"):
-            raise SystemExit(f"{p}: wafer_amd.sweep: gpu.ritz: true (the Rayleigh-Ritz step on the stored states) is a wafer-hip feature; "
-                             "batches have no such step")
+            raise SystemExit(f"{p}: wafer_amd.sweep: gpu.ritz: true (the Rayleigh-Ritz step on the stored states) is a wafer-hip key; "
+                             "a sweep takes the step for all of its runs with the command-line flag --ritz")
     plan = plan_batches(cfgs, args.max_batch, mix_states=args.mix_states)
     if args.plan:
         inputs = []
@@ -556,16 +637,20 @@ def main(argv=None) -> int:
         members = [runs[i] for i in b["members"]]
         for r in members:
             r.batch = k
-        launches.append(run_batch(b, members, seed, args.progress, batched=args.batched_setup))
+        more = dict(ritz=True) if args.ritz else {}   # (without the flag the call is what it has always been)
+        launches.append(run_batch(b, members, seed, args.progress, batched=args.batched_setup, **more))
     ok = True
     for r in runs:
         asked = r.cfg["wavemax"] - r.cfg["wavenum"] + 1
         converged = len(r.states) == asked and all(s["status"] == "Converged" for s in r.states)
         ok = ok and converged
         b = plan[r.batch]
-        print(json.dumps(dict(index=r.index, config=r.config_path, directory=r.out_dir, converged=converged, states=r.states, batch=r.batch,
-                              batch_members=b["members"], mixed_shapes=b["mixed_shapes"], fused_passes=launches[r.batch][0],
-                              single_steps=launches[r.batch][1])), flush=True)
+        line = dict(index=r.index, config=r.config_path, directory=r.out_dir, converged=converged, states=r.states, batch=r.batch,
+                    batch_members=b["members"], mixed_shapes=b["mixed_shapes"], fused_passes=launches[r.batch][0],
+                    single_steps=launches[r.batch][1])
+        if args.ritz:
+            line["ritz"] = r.ritz
+        print(json.dumps(line), flush=True)
     print(f"Sweep complete. Elapsed time: {time.perf_counter() - t0:.3f} seconds.\nOutput directory: {args.output_dir}", flush=True)
     return 0 if ok else 1
 
