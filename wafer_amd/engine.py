@@ -785,8 +785,8 @@ class Batch:
 
     mixed_shapes=True (wafer_batch_create_mixed): the members' nx, ny, nz may differ -- a convergence study in one batch.  The
     ground-state path (evolve with wnum = 0 under both step variants, observables, norm2, normalise, solve) gives every member the
-    bits of a Context of its own Params on every dtype, in one launch per step or pass for all shapes together (num_shapes(),
-    dispatch()["shapes"]).  With more than one distinct shape the calls that need the state stores (load_state, download_state,
+    bits of a Context of its own Params on every dtype (but norm2 on f64: the Context's partition of that sum is another, and the
+    two agree to 1e-12), in one launch per step or pass for all shapes together (num_shapes(), dispatch()["shapes"]).  With more than one distinct shape the calls that need the state stores (load_state, download_state,
     push_state, clear_states, clone_state_to_phi, orthogonalise, evolve with wnum > 0, solve_state, set_gs_variant(1)) raise
     WaferError -1 with "mixed-shape" in the message; with one distinct shape the batch is a plain Batch in every call.
     mixed_shapes=True, state_stores=True (wafer_batch_create_mixed_states) lifts that: every state-store and excited-state call
