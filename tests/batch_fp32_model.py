@@ -81,9 +81,10 @@ def orthogonalise(phi, lowers, storage, scalar=exact):
     return phi
 
 
-def excited_steps(cfg, v_stored, phi, lowers, steps, storage, scalar=exact):
-    """`steps` steps of the chain above from `phi`; a new array"""
-    a, b = ref.ab_of(v_stored, cfg.dt, np.float64, "registers")
+def excited_steps(cfg, v_stored, phi, lowers, steps, storage, scalar=exact, ab="registers"):
+    """`steps` steps of the chain above from `phi`; a new array.  ab: fp32_reference.ab_of's source ("stored": the arrays the
+    direct kernel, variant 0, streams)"""
+    a, b = ref.ab_of(v_stored, cfg.dt, np.float64, ab)
     den = ref.denominator(cfg)
     for _ in range(steps):
         phi = ref.step(phi, a, b, cfg.dt, den, cfg.ext, np.float64, storage)

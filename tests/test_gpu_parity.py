@@ -1002,9 +1002,10 @@ def test_two_excited_steps_per_pass_vs_oracle(wo, wa, wnum, potential, steps, mo
 def test_two_excited_steps_per_pass_on_fp32_storage(wo, wa, wnum, dtype, monkeypatch):
     """round 6: wafer_k_xstep2 on the storage tag of the three-step kernel (dtype f32, and f32fast, whose excited-state steps compute
     in fp64 too): the raw pass result, V, the stored states and their images are float in HBM, queues / LDS / sums double.  The
-    GROUND-state steps on this storage have a bit-level reference (tests/test_gpu_fp32_reference.py); these excited-state passes do
-    not (the regrouped sums differ from the one-step kernel's by construction, and every pass rounds what it stores to float):
-    held to the fp32-storage bar -- per cell within 3e-6 of the largest value of the fp64 ORACLE's state
+    GROUND-state steps on this storage have a bit-level reference (tests/test_gpu_fp32_reference.py); these excited-state passes
+    have a per-cell float model of their own (tests/x2_fp32_model.py, held against the GPU by tests/test_gpu_excited_fp32.py).  Here
+    they are compared with the fp64 oracle (the regrouped sums differ from the one-step kernel's by construction, and every pass
+    rounds what it stores to float): held to the fp32-storage bar -- per cell within 3e-6 of the largest value of the fp64 ORACLE's state
     after 12 steps, and no further from it than the one-step fp32-storage kernels are; ragged tiles, whole tiles, a grid smaller
     than a tile, every stored-state count; norm to 1e-5."""
     monkeypatch.setenv("WAFER_X2_MAX_K", "3")
