@@ -187,6 +187,12 @@ extern "C" {
     pub fn wafer_ritz_matrices(ctx: *mut wafer_ctx, k: u32, h: *mut f64, s: *mut f64) -> c_int;
     pub fn wafer_rotate_states(ctx: *mut wafer_ctx, k: u32, coef: *const f64) -> c_int;
     pub fn wafer_ritz(ctx: *mut wafer_ctx, k: u32, evals: *mut f64, coef: *mut f64, h: *mut f64, s: *mut f64) -> c_int;
+    /// Residuals r = H l - theta l (include/wafer_hip.h): source 0 = the first k stored states, 1 = phi (k = 1); `theta_in` null is
+    /// Rayleigh mode; `theta`, `r2`, `s` hold k doubles
+    pub fn wafer_residuals(
+        ctx: *mut wafer_ctx, source: c_int, k: u32, theta_in: *const f64, theta: *mut f64, r2: *mut f64, s: *mut f64,
+    ) -> c_int;
+    pub fn wafer_residual_to_phi(ctx: *mut wafer_ctx, idx: u32, theta: f64) -> c_int;
     pub fn wafer_solve_state(
         ctx: *mut wafer_ctx, wnum: u32, tolerance: f64, screen_update: u64, has_max_steps: c_int, max_steps: u64,
         records: *mut wafer_block_record, max_records: usize, n_records: *mut usize, final_out: *mut wafer_observables_output,
@@ -289,6 +295,12 @@ extern "C" {
         status: *mut c_int,
     ) -> c_int;
     pub fn wafer_batch_diag_ritz_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
+    /// wafer_residuals for every listed member: `theta_in`, `theta`, `r2`, `s` hold member m's k[m] values at `m * 8`
+    pub fn wafer_batch_residuals(
+        b: *mut wafer_batch, source: c_int, active: *const u8, k: *const u32, theta_in: *const f64, theta: *mut f64, r2: *mut f64,
+        s: *mut f64, status: *mut c_int,
+    ) -> c_int;
+    pub fn wafer_batch_diag_residual_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

@@ -243,6 +243,30 @@ int wafer_rotate_states(wafer_ctx *ctx, uint32_t k, const double *coef);
 /* the three in sequence; h, s (the matrices before the rotation) may be NULL */
 int wafer_ritz(wafer_ctx *ctx, uint32_t k, double *evals, double *coef, double *h, double *s);
 
+/* ---- residuals of w_store and of phi -------------------------------------- */
+/* How far a state is from an eigenstate of the discrete H (stencil, Dirichlet frame): with r = H l - theta l over the work area,
+ * some eigenvalue of H lies within rho = sqrt(r2 / s) of theta, where r2 = sum r^2 and s = sum l^2.  Per work cell c, every
+ * operand widened to double and every operation fp64 and unfused, whatever the dtype:
+ *   w = l[c]  vv = V[c]  S = the bracketed stencil sum of l at c (frame cells as stored)  hw = vv * w - S / den  r = hw - theta * w
+ * and the sums r2 += r * r, wh += w * hw, s += w * w run on the partition of wafer_observables, without floating-point atomics:
+ * s[j] has the bits of wafer_observables' norm2 and of wafer_ritz_matrices' s[j * k + j] on the same state.
+ * source: the first k stored states, or the current wavefunction (k must be 1).  theta_in: k finite doubles -- one sums launch,
+ * one reduce, one read-back, and theta receives a copy.  theta_in == NULL is Rayleigh mode: a first pass with theta = 0 gives
+ * theta_j = wh_j / s_j on the host, a second pass with that theta gives r2 and s (one pass cannot: expanding |H l - theta l|^2
+ * into three sums cancels to nothing on a nearly converged state).  If s_j is not finite or not > 0 the call fails with
+ * WAFER_ERR_STATE naming the state and writes nothing.
+ * Checked before any launch, and a refused call changes nothing: k == 0, k > WAFER_RITZ_MAX, k != 1 with WAFER_RESIDUAL_PHI, an
+ * unknown source, a non-finite theta_in and a context that owns a z-slab are WAFER_ERR_INVALID; k above the number of stored
+ * states, phi not set, or no potential, WAFER_ERR_STATE.  The call is read-only: the store, phi, the Gram matrices and the
+ * two-step pass's images keep every bit.  theta, r2, s: k doubles each. */
+#define WAFER_RESIDUAL_STATES 0   /* the first k stored states */
+#define WAFER_RESIDUAL_PHI    1   /* the current wavefunction; k must be 1 */
+int wafer_residuals(wafer_ctx *ctx, int source, uint32_t k, const double *theta_in, double *theta, double *r2, double *s);
+/* phi (the current buffer) = r of stored state idx with theta, rounded to the dtype's storage once; every other element of the
+ * array -- frame, pad and guard cells -- is written as zero, so phi is a valid wavefunction for every step kernel.  Sets phi;
+ * leaves the store alone.  No state idx or no potential: WAFER_ERR_STATE; a non-finite theta or a z-slab: WAFER_ERR_INVALID. */
+int wafer_residual_to_phi(wafer_ctx *ctx, uint32_t idx, double theta);
+
 /* ---- solve (grid.rs:50-246) for ONE state, snapshot branch excluded ------ */
 /* phi must hold the starting wavefunction.  Writes up to max_records rows,
  * *n_records = rows produced.  Returns WAFER_OK when converged (phi has then
@@ -734,6 +758,23 @@ int wafer_batch_ritz(wafer_batch *b, const uint8_t *active, const uint32_t *k, d
 /* launches and read-backs of the three calls above since creation: wafer_batch_ritz_matrices 2 and 1, wafer_batch_rotate_states
  * 1 and 0, wafer_batch_ritz 3 and 1, whatever the number of members and shapes (the lazy Gram refresh is the next excited step's) */
 int wafer_batch_diag_ritz_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
+
+/* ---- residuals on a batch ---------------------------------------------------
+ * wafer_residuals (above) for every listed member (active[m] != 0; NULL: all), each with its own k[m] and theta: per pass one sums
+ * launch, one reduce launch and one read-back for all listed members whatever their number and shapes -- theta_in given: 2
+ * launches and 1 read-back; theta_in == NULL (Rayleigh mode): twice that.  An empty list returns WAFER_OK and launches nothing.
+ * Every member gets bit for bit what a wafer_ctx of its own wafer_params, holding the same source and potential, gets from
+ * wafer_residuals.  k has n_members entries; theta_in, theta, r2, s hold n_members * WAFER_RITZ_MAX doubles, member m's k[m]
+ * values at m * WAFER_RITZ_MAX; status has n_members entries.  Entries of members not listed are neither read nor written.
+ * Every check of wafer_residuals runs for every listed member before anything is uploaded or launched and names the member.
+ * WAFER_RESIDUAL_STATES on a mixed-shape batch made without state stores is refused as every excited-state call there;
+ * WAFER_RESIDUAL_PHI is accepted on every batch.  In Rayleigh mode a member one of whose s_j is not finite or not > 0 gets
+ * status[m] = WAFER_ERR_STATE and keeps its output entries; the others get WAFER_OK and their results, the call returns WAFER_OK
+ * and wafer_last_error names the first such member.  Read-only like wafer_residuals. */
+int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, const uint32_t *k, const double *theta_in,
+                          double *theta, double *r2, double *s, int *status);
+/* launches and read-backs of wafer_batch_residuals since creation */
+int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
 
 #ifdef __cplusplus
 }

@@ -54,7 +54,14 @@ B Contexts holding the same states calling ritz_matrices(K) one after another --
 member's state 0, which waits for the rotation.  --reps repetitions after one warm-up of each, every one listed, with "*_spread" =
 (max - min) / median; "ratio_*": ctx over batch, per repetition.  "parity": every member's h, s and every rotated state bit-identical on
 both sides after the last repetition; "ritz_counts": the launches and read-backs one Batch.ritz adds.  Appended to
-profiles/batch_ritz_rows.jsonl unless --out names another file."""
+profiles/batch_ritz_rows.jsonl unless --out names another file.
+
+--residuals K: a mode of its own -- Batch.residuals on K stored states per member (the stores of --ritz).  One line per B:
+"batch_given_ms" / "ctx_given_ms": the wall clock around Batch.residuals(K, theta) (two launches and one read-back for all members) and
+around B Contexts calling residuals(K, theta) one after another; "batch_rayleigh_ms" / "ctx_rayleigh_ms": the same with theta=None (two
+passes); one warm-up, then --reps repetitions, all listed; "parity": every member's theta, r2 and norm2 compared == on both sides in both
+modes; "residual_counts_*": the launches and read-backs one call adds.  Appended to profiles/batch_residual_rows.jsonl unless --out names
+another file."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -406,6 +413,69 @@ def ritz_row(shapes, B, K, reps, ext=1, dtype="f64"):
     return out
 
 
+def residual_row(shapes, B, K, reps, ext=1, dtype="f64"):
+    """Batch.residuals on K stored states per member against B contexts calling residuals one after another, theta given and in
+    Rayleigh mode; every member's theta, r2 and norm2 compared == on both sides"""
+    pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype,
+                             max_states=K) for k in range(B)]
+    out = {"mode": "residuals", "k": K, "shapes": [list(s) for s in shapes], "B": B, "reps": reps,
+           "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype, "potential": "Harmonic"}
+    per_shape = {s: [store(pars[shapes.index(s)], K, seed=j) for j in range(2)] for s in dict.fromkeys(shapes)}   # (two stores per shape, shared out)
+    stores = [per_shape[shapes[k % len(shapes)]][(k // len(shapes)) % 2] for k in range(B)]
+    keys = ("batch_given_ms", "ctx_given_ms", "batch_rayleigh_ms", "ctx_rayleigh_ms")
+    for key in keys:
+        out[key] = []
+    theta = [[1.0 + 0.5 * j for j in range(K)]] * B
+    mixed = len(set(shapes)) > 1
+    ctxs = [wafer_amd.Context(p) for p in pars]
+    try:
+        with wafer_amd.Batch(pars, mixed_shapes=mixed, state_stores=mixed) as b:
+            b.set_potentials(["Harmonic"] * B)
+            for k, c in enumerate(ctxs):
+                c.set_potential("Harmonic")
+                for i in range(K):
+                    c.load_state(i, stores[k][i])
+                    b.load_state(k, i, stores[k][i])
+
+            def batch(th):
+                t0 = time.perf_counter()
+                res = b.residuals(K, theta=th)
+                return 1e3 * (time.perf_counter() - t0), res
+
+            def contexts(th):
+                t0 = time.perf_counter()
+                res = [c.residuals(K, theta=None if th is None else th[k]) for k, c in enumerate(ctxs)]
+                return 1e3 * (time.perf_counter() - t0), res
+
+            batch(theta), contexts(theta), batch(None), contexts(None)   # warm-up of each: the buffers are made here
+            for _ in range(reps):
+                out["batch_given_ms"].append(batch(theta)[0])
+                out["ctx_given_ms"].append(contexts(theta)[0])
+                out["batch_rayleigh_ms"].append(batch(None)[0])
+                out["ctx_rayleigh_ms"].append(contexts(None)[0])
+            c0 = b.residual_counts()
+            batch(theta)
+            c1 = b.residual_counts()
+            batch(None)
+            out["residual_counts_given"] = [x - y for x, y in zip(c1, c0)]
+            out["residual_counts_rayleigh"] = [x - y for x, y in zip(b.residual_counts(), c1)]
+            same = lambda x, y: bool(np.array_equal(np.ascontiguousarray(x).view(np.int64), np.ascontiguousarray(y).view(np.int64)))
+            parity = True
+            for th in (theta, None):
+                for br, cr in zip(batch(th)[1], contexts(th)[1]):
+                    parity = parity and all(same(br[name], cr[name]) for name in ("theta", "r2", "norm2"))
+            out["parity"] = parity
+            out["shapes_in_batch"] = b.num_shapes()
+    finally:
+        for c in ctxs:
+            c.close()
+    for key in keys:
+        out[key.replace("_ms", "_spread")] = (max(out[key]) - min(out[key])) / float(np.median(out[key]))
+    out["ratio_given"] = [c / h for c, h in zip(out["ctx_given_ms"], out["batch_given_ms"])]
+    out["ratio_rayleigh"] = [c / h for c, h in zip(out["ctx_rayleigh_ms"], out["batch_rayleigh_ms"])]
+    return out
+
+
 def rounded(d):
     if isinstance(d, dict):
         return {k: rounded(v) for k, v in d.items()}
@@ -439,7 +509,20 @@ def main():
                     "per-member calls on the same batch (a mode of its own; --reps, --sizes or --mixed, --ext, --dtype apply)")
     ap.add_argument("--ritz", type=int, metavar="K", help="time Batch.ritz_matrices and Batch.ritz on K stored states per member against B contexts "
                     "calling ritz_matrices / ritz one after another (a mode of its own; --batch, --reps, --sizes or --mixed, --ext, --dtype apply)")
+    ap.add_argument("--residuals", type=int, metavar="K", help="time Batch.residuals on K stored states per member, theta given and in Rayleigh "
+                    "mode, against B contexts calling residuals one after another (a mode of its own; --batch, --reps, --sizes or --mixed, --ext, "
+                    "--dtype apply)")
     a = ap.parse_args()
+    if a.residuals:
+        if not a.out:
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_residual_rows.jsonl")
+        shapes = parse_shapes(a.mixed) if a.mixed else [(a.sizes[0],) * 3]
+        for B in a.batch:
+            line = json.dumps(rounded(residual_row(shapes, B, a.residuals, a.reps, a.ext, a.dtype)))
+            print(line, flush=True)
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+        return
     if a.ritz:
         if not a.out:
             a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_ritz_rows.jsonl")

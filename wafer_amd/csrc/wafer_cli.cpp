@@ -124,6 +124,7 @@ struct Config {
     std::string dtype = "f64"; // engine extension: optional `gpu.dtype`
     int device = 0;            // engine extension: optional `gpu.device`
     bool ritz = false;         // engine extension: optional `gpu.ritz` -- one Rayleigh-Ritz step on the stored states after the last solve
+    bool residual = false;     // engine extension: optional `gpu.residual` -- theta and rho = |H l - theta l| / |l| of every stored state after the last solve
 };
 
 static int index_of(const char *const *names, int n, const std::string &v)
@@ -197,6 +198,7 @@ static bool load_config(const std::string &path, Config &c, std::string &err)
     if (kv.count("gpu.dtype")) c.dtype = kv["gpu.dtype"];
     if (kv.count("gpu.device")) c.device = atoi(kv["gpu.device"].c_str());
     if (kv.count("gpu.ritz") && !boolean("gpu.ritz", c.ritz)) return false;
+    if (kv.count("gpu.residual") && !boolean("gpu.residual", c.residual)) return false;
     // Config::parse, config.rs:362-370
     if (c.dt > c.dn * c.dn / 3.) { err = "ConfigParse: LargeDt: dt must be <= dn^2/3"; return false; }
     if (c.wavenum > c.wavemax) { err = "ConfigParse: LargeWavenum: wavenum must be <= wavemax"; return false; }
@@ -515,14 +517,16 @@ int main(int argc, char **argv)
         printf("{\"project_name\": \"%s\", \"nx\": %u, \"ny\": %u, \"nz\": %u, \"dn\": %s, \"dt\": %s, \"tolerance\": %s, "
                "\"central_difference\": %d, \"max_steps\": %s, \"wavenum\": %u, \"wavemax\": %u, \"potential\": \"%s\", "
                "\"mass\": %s, \"init_condition\": \"%s\", \"sig\": %s, \"init_symmetry\": \"%s\", \"screen_update\": %llu, "
-               "\"snap_update\": %s, \"file_type\": \"%s\", \"save_wavefns\": %s, \"save_potential\": %s, \"dtype\": \"%s\", \"ritz\": %s}\n",
+               "\"snap_update\": %s, \"file_type\": \"%s\", \"save_wavefns\": %s, \"save_potential\": %s, \"dtype\": \"%s\", \"ritz\": %s, "
+               "\"residual\": %s}\n",
                cfg.project_name.c_str(), cfg.nx, cfg.ny, cfg.nz, num_text(cfg.dn).c_str(), num_text(cfg.dt).c_str(),
                num_text(cfg.tolerance).c_str(), cfg.central_difference,
                cfg.has_max_steps ? std::to_string(cfg.max_steps).c_str() : "null", cfg.wavenum, cfg.wavemax,
                kPotentials[cfg.potential], num_text(cfg.mass).c_str(), kInitialConditions[cfg.init_condition],
                num_text(cfg.sig).c_str(), cfg.init_symmetry.c_str(), (unsigned long long)cfg.screen_update,
                cfg.has_snap_update ? std::to_string(cfg.snap_update).c_str() : "null", kFileTypes[cfg.file_type],
-               cfg.save_wavefns ? "true" : "false", cfg.save_potential ? "true" : "false", cfg.dtype.c_str(), cfg.ritz ? "true" : "false");
+               cfg.save_wavefns ? "true" : "false", cfg.save_potential ? "true" : "false", cfg.dtype.c_str(), cfg.ritz ? "true" : "false",
+               cfg.residual ? "true" : "false");
         return 0;
     }
     const int symmetry = index_of(kSymmetry, 5, cfg.init_symmetry);
@@ -788,6 +792,21 @@ int main(int argc, char **argv)
                         fprintf(stderr, "Warning: could not write wavefunction to disk: %s\n", err.c_str());
                 }
             }
+        }
+    }
+    if (cfg.residual) { // how far every stored state is from an eigenstate: its Rayleigh quotient and rho (include/wafer_hip.h)
+        uint32_t ns = 0;
+        CHECK(wafer_num_states(ctx, &ns));
+        if (ns < 1 || ns > WAFER_RITZ_MAX) {
+            fprintf(stderr, "Residual: skipped, %u stored states (the call takes 1 .. %d)\n", ns, WAFER_RITZ_MAX);
+        } else {
+            double theta[WAFER_RITZ_MAX], r2[WAFER_RITZ_MAX], s2[WAFER_RITZ_MAX];
+            CHECK(wafer_residuals(ctx, WAFER_RESIDUAL_STATES, ns, nullptr, theta, r2, s2));
+            printf("Residual\n");   // state, theta = <l|H|l> / <l|l>, rho
+            for (uint32_t a = 0; a < ns; ++a)
+                printf("%3u %s %s\n", a, pad_left(rust_lower_exp(theta[a], 10), 19).c_str(),
+                       pad_left(rust_lower_exp(std::sqrt(r2[a] / s2[a]), 10), 19).c_str());
+            printf("\n");
         }
     }
     (void)t_start;

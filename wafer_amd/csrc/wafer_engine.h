@@ -263,6 +263,10 @@ bool fuse2_applies(const wafer_ctx *c);
 int f3_table(wafer_ctx *c, int kind, int lz_lo, int lz_hi, int aux, const wafer_ctx::F3Table **out);
 int launch_dot(wafer_ctx *c, void *phi, void *lower, int out_slot, hipStream_t s);
 int recompute_gram(wafer_ctx *c);
+// ---- wafer_tu_ritz.hip
+// the argument block of the context's observables launch, and ritz_buf grown to hold `doubles`
+WaferStepArgs ritz_args(const wafer_ctx *c);
+int ensure_ritz_buf(wafer_ctx *c, size_t doubles);
 // ---- wafer_engine_comm.hip
 int exchange_halo_array(wafer_ctx *c, void *array, hipStream_t s, int planes);
 int exchange_halo(wafer_ctx *c, int buf, hipStream_t s, int planes);

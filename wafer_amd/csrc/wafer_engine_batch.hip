@@ -36,6 +36,8 @@
 // Rayleigh-Ritz on the stores (wafer_batch_ritz_matrices, wafer_batch_rotate_states, wafer_batch_ritz; kernels: wafer_ritz_batch.hip.h,
 // wafer_tu_ritz_batch.hip): a context's wafer_ritz_* for every listed member with its own k -- one sums launch, one reduce and one
 // read-back, the solves on the host (wafer_ritz.h), one rotation launch -- from a per-call table of (member, k, partials offset, span).
+// Residuals (wafer_batch_residuals; kernels: wafer_residual_batch.hip.h, wafer_tu_residual_batch.hip): a context's wafer_residuals for
+// every listed member with its own k and theta, on the stores or on phi -- one sums launch, one reduce and one read-back per pass.
 #include <memory>
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
@@ -44,6 +46,7 @@
 #include "wafer_resample_batch.hip.h"
 #include "wafer_setup_batch.hip.h"
 #include "wafer_ritz_batch.hip.h"
+#include "wafer_residual_batch.hip.h"
 #include "wafer_ritz.h"
 
 struct wafer_batch {
@@ -127,6 +130,10 @@ struct wafer_batch {
     double *ritz_sums = nullptr, *ritz_sums_host = nullptr;   // [member][2][WAFER_RITZ_MAX^2]
     double *ritz_coef = nullptr, *ritz_coef_host = nullptr;   // [member][WAFER_RITZ_MAX^2]
     uint64_t n_ritz_launches = 0, n_ritz_readbacks = 0;       // of the three calls since creation (wafer_batch_diag_ritz_counts)
+    // residuals (wafer_residual_batch.hip.h); made by the first call (ensure_residual).  The partials live in ritz_partials.
+    WaferBatchResidualRec *resid_rec_dev = nullptr, *resid_rec_host = nullptr;   // the per-call table, n entries
+    double *resid_sums = nullptr, *resid_sums_host = nullptr; // [member][3 WAFER_RITZ_MAX]: r2, wh, s of column j at j * 3
+    uint64_t n_resid_launches = 0, n_resid_readbacks = 0;     // of wafer_batch_residuals since creation (wafer_batch_diag_residual_counts)
 };
 
 namespace {
@@ -184,10 +191,11 @@ void destroy(wafer_batch *b)
     for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
                     (void *)b->gram_list_dev, (void *)b->rs_scratch, (void *)b->setup_dev, (void *)b->vchk_dev, (void *)b->ritz_rec_dev,
-                    (void *)b->ritz_partials, (void *)b->ritz_sums, (void *)b->ritz_coef})
+                    (void *)b->ritz_partials, (void *)b->ritz_sums, (void *)b->ritz_coef, (void *)b->resid_rec_dev, (void *)b->resid_sums})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host, (void *)b->setup_host,
-                    (void *)b->vchk_init, (void *)b->vchk_host, (void *)b->ritz_rec_host, (void *)b->ritz_sums_host, (void *)b->ritz_coef_host})
+                    (void *)b->vchk_init, (void *)b->vchk_host, (void *)b->ritz_rec_host, (void *)b->ritz_sums_host, (void *)b->ritz_coef_host,
+                    (void *)b->resid_rec_host, (void *)b->resid_sums_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop, b->rs_start, b->rs_stop})
         if (e) (void)hipEventDestroy(e);
@@ -1217,6 +1225,78 @@ int ritz_rotate_impl(wafer_batch *b, const uint8_t *listed, const uint32_t *k, c
     return WAFER_OK;
 }
 
+// ---- residuals of the stores and of phi ------------------------------------------------------------------------------------------
+constexpr size_t RESID_ROWS = 3 * (size_t)WAFER_RITZ_MAX;
+
+// every check of wafer_batch_residuals for every listed member, before anything is uploaded or launched; *nlisted: their number
+int residual_check(const wafer_batch *b, int source, const uint8_t *active, const uint32_t *k, const double *theta_in, int *nlisted)
+{
+    if (source != WAFER_RESIDUAL_STATES && source != WAFER_RESIDUAL_PHI) return fail(WAFER_ERR_INVALID, "unknown residual source %d", source);
+    if (source == WAFER_RESIDUAL_STATES) TRY(refuse_mixed(b, "wafer_batch_residuals (stored states)"));
+    *nlisted = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (k[m] == 0 || k[m] > WAFER_RITZ_MAX)
+            return fail(WAFER_ERR_INVALID, "member %u: k = %u: residuals take 1 .. %d states", m, k[m], WAFER_RITZ_MAX);
+        if (source == WAFER_RESIDUAL_PHI && k[m] != 1) return fail(WAFER_ERR_INVALID, "member %u: k = %u: the phi source is one array (k = 1)", m, k[m]);
+        if (theta_in)
+            for (uint32_t j = 0; j < k[m]; ++j)
+                if (!std::isfinite(theta_in[(size_t)m * WAFER_RITZ_MAX + j])) return fail(WAFER_ERR_INVALID, "member %u: theta_in[%u] is not finite", m, j);
+        if (source == WAFER_RESIDUAL_STATES && k[m] > b->nst[m])
+            return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
+        if (source == WAFER_RESIDUAL_PHI && !b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+        if (!b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
+        ++*nlisted;
+    }
+    return WAFER_OK;
+}
+
+int ensure_residual(wafer_batch *b)
+{
+    if (b->resid_sums_host) return WAFER_OK;   // (the last one made below)
+    if (!b->resid_rec_dev) HIP_TRY(hipMalloc((void **)&b->resid_rec_dev, sizeof(WaferBatchResidualRec) * b->n));
+    if (!b->resid_rec_host) HIP_TRY(hipHostMalloc((void **)&b->resid_rec_host, sizeof(WaferBatchResidualRec) * b->n, hipHostMallocDefault));
+    if (!b->resid_sums) HIP_TRY(hipMalloc((void **)&b->resid_sums, sizeof(double) * RESID_ROWS * b->n));
+    HIP_TRY(hipHostMalloc((void **)&b->resid_sums_host, sizeof(double) * RESID_ROWS * b->n, hipHostMallocDefault));
+    return WAFER_OK;
+}
+
+// One pass over the listed members (checked: residual_check; at least one): the per-call table with theta (member m's at
+// m * WAFER_RITZ_MAX; nullptr: zeros), the sums launch, the reduce and one read-back into resid_sums_host.
+int residual_pass(wafer_batch *b, int source, const uint8_t *listed, const uint32_t *k, const double *theta)
+{
+    HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table is not read by an earlier call's copy
+    int nact = 0, max_nb = 0, max_k = 0;
+    size_t poff = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (listed && !listed[m]) continue;
+        WaferBatchResidualRec &r = b->resid_rec_host[nact++];
+        r.member = (int)m;
+        r.k = (int)k[m];
+        r.poff = (long long)poff;
+        for (uint32_t j = 0; j < WAFER_RITZ_MAX; ++j) r.theta[j] = (theta && j < k[m]) ? theta[(size_t)m * WAFER_RITZ_MAX + j] : 0.0;
+        poff += 3 * (size_t)k[m] * (size_t)b->mem[m].obs_nb;
+        max_nb = std::max(max_nb, b->mem[m].obs_nb);
+        max_k = std::max(max_k, (int)k[m]);
+    }
+    TRY(ensure_ritz_partials(b, poff));
+    HIP_TRY(hipMemcpyAsync(b->resid_rec_dev, b->resid_rec_host, sizeof(WaferBatchResidualRec) * nact, hipMemcpyHostToDevice, b->s));
+    const WaferRitzPtrs st = ritz_slots(b);
+    const hipError_t e = with_geom(b, [&](const auto &gs) {
+        return wafer_entry_batch_residual_sums(b->f32, b->g().R, gs, b->mem_dev, b->resid_rec_dev, nact, max_nb, max_k, b->swz,
+                                               source == WAFER_RESIDUAL_PHI ? 1 : 0, st, b->ritz_partials, b->resid_sums, b->s);
+    });
+    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched residual sums launch failed: %s", hipGetErrorString(e));
+    b->n_resid_launches += 2;
+    // the members from the first listed to the last in one copy
+    const size_t m0 = (size_t)b->resid_rec_host[0].member, m1 = (size_t)b->resid_rec_host[nact - 1].member + 1;
+    HIP_TRY(hipMemcpyAsync(b->resid_sums_host + m0 * RESID_ROWS, b->resid_sums + m0 * RESID_ROWS, sizeof(double) * RESID_ROWS * (m1 - m0),
+                           hipMemcpyDeviceToHost, b->s));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    ++b->n_resid_readbacks;
+    return WAFER_OK;
+}
+
 // ---- creation --------------------------------------------------------------------------------------------------------------
 // Every member's partition record and the places of its partials.  Observables: the partition wafer_launch_observables_lds gives a
 // single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
@@ -1881,6 +1961,74 @@ int wafer_batch_diag_ritz_counts(wafer_batch *b, uint64_t *launches, uint64_t *r
     if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
     *launches = b->n_ritz_launches;
     *readbacks = b->n_ritz_readbacks;
+    return WAFER_OK;
+}
+
+int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, const uint32_t *k, const double *theta_in, double *theta, double *r2,
+                          double *s, int *status)
+{
+    if (!b || !k || !theta || !r2 || !s || !status) return fail(WAFER_ERR_INVALID, "null argument");
+    int nlisted = 0;
+    TRY(residual_check(b, source, active, k, theta_in, &nlisted));
+    if (!nlisted) return WAFER_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    RoctxRange range_("wafer_batch_residuals");
+    TRY(ensure_residual(b));
+    TRY(sync_members(b));
+    std::vector<uint8_t> ok(b->n, 0);
+    for (uint32_t m = 0; m < b->n; ++m) ok[m] = (!active || active[m]) ? 1 : 0;
+    std::vector<double> th((size_t)WAFER_RITZ_MAX * b->n, 0.0);
+    std::string first_failure;
+    if (theta_in) {
+        for (uint32_t m = 0; m < b->n; ++m)
+            for (uint32_t j = 0; ok[m] && j < k[m]; ++j) th[(size_t)m * WAFER_RITZ_MAX + j] = theta_in[(size_t)m * WAFER_RITZ_MAX + j];
+    } else {   // Rayleigh mode: theta_j = wh_j / s_j of a pass with theta = 0; a member without a quotient keeps its outputs: its status
+        TRY(residual_pass(b, source, ok.data(), k, nullptr));
+        bool any = false;
+        for (uint32_t m = 0; m < b->n; ++m) {
+            if (!ok[m]) continue;
+            const double *r = b->resid_sums_host + m * RESID_ROWS;
+            for (uint32_t j = 0; j < k[m]; ++j) {
+                const double sj = r[j * 3 + 2];
+                if (!std::isfinite(sj) || !(sj > 0.0)) {
+                    if (first_failure.empty()) {
+                        char msg[192];
+                        snprintf(msg, sizeof msg, "member %u: state %u: <l|l> = %g: no Rayleigh quotient (a zero or non-finite state)", m, j, sj);
+                        first_failure = msg;
+                    }
+                    ok[m] = 0;
+                    status[m] = WAFER_ERR_STATE;
+                    break;
+                }
+                th[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 1] / sj;
+            }
+            any = any || ok[m];
+        }
+        if (!any) {   // nobody left for the second pass
+            (void)fail(WAFER_ERR_STATE, "%s", first_failure.c_str());
+            return WAFER_OK;
+        }
+    }
+    TRY(residual_pass(b, source, ok.data(), k, th.data()));
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (!ok[m]) continue;
+        const double *r = b->resid_sums_host + m * RESID_ROWS;
+        for (uint32_t j = 0; j < k[m]; ++j) {
+            theta[(size_t)m * WAFER_RITZ_MAX + j] = th[(size_t)m * WAFER_RITZ_MAX + j];
+            r2[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 0];
+            s[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 2];
+        }
+        status[m] = WAFER_OK;
+    }
+    if (!first_failure.empty()) (void)fail(WAFER_ERR_STATE, "%s", first_failure.c_str());   // wafer_last_error names the first such member
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks)
+{
+    if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
+    *launches = b->n_resid_launches;
+    *readbacks = b->n_resid_readbacks;
     return WAFER_OK;
 }
 

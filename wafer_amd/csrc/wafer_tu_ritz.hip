@@ -5,6 +5,36 @@
 #include "wafer_ritz.hip.h"
 #include "wafer_ritz.h"
 
+namespace wafer_eng __attribute__((visibility("hidden"))) {
+// the argument block of the context's observables launch (wafer_observables)
+WaferStepArgs ritz_args(const wafer_ctx *c)
+{
+    WaferStepArgs sa{};
+    sa.g = c->g;
+    sa.lz_lo = c->g.G;
+    sa.lz_hi = c->g.G + c->g.nzl;
+    sa.dt = c->P.dt;
+    set_den_args(c, sa);
+    sa.target_blocks = c->num_cus;
+    sa.v_in_range = short_forms(c) ? 1 : 0;
+    return sa;
+}
+
+// ritz_buf: [2 k^2 rows of nb partials][2 k^2 sums][k^2 coefficients], for the largest k and nb asked for so far (the residual
+// calls of wafer_tu_residual.hip keep their 3 k rows and sums there too)
+int ensure_ritz_buf(wafer_ctx *c, size_t doubles)
+{
+    if (c->ritz_cap >= doubles) return WAFER_OK;
+    HIP_TRY(hipStreamSynchronize(c->s_main));
+    if (c->ritz_buf) (void)hipFree(c->ritz_buf);
+    c->ritz_buf = nullptr;
+    c->ritz_cap = 0;
+    HIP_TRY(hipMalloc((void **)&c->ritz_buf, sizeof(double) * doubles));
+    c->ritz_cap = doubles;
+    return WAFER_OK;
+}
+} // namespace wafer_eng
+
 namespace {
 // the partition of the context's observables launch (wafer_launch_observables_lds) and the sums launch on it
 template <typename T, int R>
@@ -45,20 +75,6 @@ auto by_type_and_reach(const wafer_ctx *c, F &&f)
     return f(double{}, std::integral_constant<int, 3>{});
 }
 
-// the argument block of the context's observables launch (wafer_observables)
-WaferStepArgs ritz_args(const wafer_ctx *c)
-{
-    WaferStepArgs sa{};
-    sa.g = c->g;
-    sa.lz_lo = c->g.G;
-    sa.lz_hi = c->g.G + c->g.nzl;
-    sa.dt = c->P.dt;
-    set_den_args(c, sa);
-    sa.target_blocks = c->num_cus;
-    sa.v_in_range = short_forms(c) ? 1 : 0;
-    return sa;
-}
-
 int check_k(const wafer_ctx *c, uint32_t k, bool need_pot)
 {
     if (!c) return fail(WAFER_ERR_INVALID, "null context");
@@ -68,19 +84,6 @@ int check_k(const wafer_ctx *c, uint32_t k, bool need_pot)
                                        "and the stored states their ghost planes)");
     if (k > c->states.size()) return fail(WAFER_ERR_STATE, "k = %u but w_store holds %zu states", k, c->states.size());
     if (need_pot && !c->have_pot) return fail(WAFER_ERR_STATE, "potential not set");
-    return WAFER_OK;
-}
-
-// ritz_buf: [2 k^2 rows of nb partials][2 k^2 sums][k^2 coefficients], for the largest k and nb asked for so far
-int ensure_ritz_buf(wafer_ctx *c, size_t doubles)
-{
-    if (c->ritz_cap >= doubles) return WAFER_OK;
-    HIP_TRY(hipStreamSynchronize(c->s_main));
-    if (c->ritz_buf) (void)hipFree(c->ritz_buf);
-    c->ritz_buf = nullptr;
-    c->ritz_cap = 0;
-    HIP_TRY(hipMalloc((void **)&c->ritz_buf, sizeof(double) * doubles));
-    c->ritz_cap = doubles;
     return WAFER_OK;
 }
 

@@ -65,8 +65,10 @@ EXPORTS = [
     "wafer_batch_diag_member", "wafer_batch_diag_setup_counts",
     "wafer_ritz_solve", "wafer_ritz_matrices", "wafer_rotate_states", "wafer_ritz",
     "wafer_batch_ritz_matrices", "wafer_batch_rotate_states", "wafer_batch_ritz", "wafer_batch_diag_ritz_counts",
+    "wafer_residuals", "wafer_residual_to_phi", "wafer_batch_residuals", "wafer_batch_diag_residual_counts",
 ]
 RITZ_MAX = 8   # WAFER_RITZ_MAX
+RESIDUAL_SOURCES = {"states": 0, "phi": 1}   # WAFER_RESIDUAL_STATES, WAFER_RESIDUAL_PHI
 
 
 class _DivPlan(C.Structure):
@@ -217,6 +219,8 @@ def load_library():
     L.wafer_ritz_matrices.argtypes = [vp, C.c_uint32, dp, dp]
     L.wafer_rotate_states.argtypes = [vp, C.c_uint32, dp]
     L.wafer_ritz.argtypes = [vp, C.c_uint32, dp, dp, dp, dp]
+    L.wafer_residuals.argtypes = [vp, C.c_int, C.c_uint32, dp, dp, dp, dp]
+    L.wafer_residual_to_phi.argtypes = [vp, C.c_uint32, C.c_double]
     L.wafer_solve_state.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint64, C.c_int, C.c_uint64,
                                     C.POINTER(_Record), C.c_size_t, C.POINTER(C.c_size_t),
                                     C.POINTER(_ObsOut)]
@@ -287,6 +291,8 @@ def load_library():
     L.wafer_batch_rotate_states.argtypes = [vp, u8p, u32p, dp]
     L.wafer_batch_ritz.argtypes = [vp, u8p, u32p, dp, dp, dp, dp, C.POINTER(C.c_int)]
     L.wafer_batch_diag_ritz_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.wafer_batch_residuals.argtypes = [vp, C.c_int, u8p, u32p, dp, dp, dp, dp, C.POINTER(C.c_int)]
+    L.wafer_batch_diag_residual_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -621,6 +627,36 @@ class Context:
         self._check(self._L.wafer_ritz(self._h, k, _dp(evals), _dp(coef), _dp(h), _dp(s)))
         return {"evals": evals, "coef": coef, "h": h, "s": s}
 
+    # -- residuals of w_store and of phi (include/wafer_hip.h) -------------------------------------------
+    def residuals(self, k: int | None = None, theta=None, source: str = "states") -> dict:
+        """r = H l - theta l of the first k stored states (all of them when k is None), or of phi (source="phi", k = 1):
+        {"theta": (k,), "r2": (k,) sum r^2, "norm2": (k,) sum l^2, "rho": (k,) sqrt(r2 / norm2)} -- some eigenvalue of the discrete
+        H lies within rho[j] of theta[j].  theta: k values, or None for each source's Rayleigh quotient (a second pass).  Read-only."""
+        if source not in RESIDUAL_SOURCES:
+            raise ValueError("source must be 'states' or 'phi', not %r" % (source,))
+        k = (1 if source == "phi" else self.num_states()) if k is None else int(k)
+        if not 1 <= k <= RITZ_MAX:
+            raise ValueError("k = %d is outside 1 .. RITZ_MAX = %d" % (k, RITZ_MAX))
+        if source == "phi" and k != 1:
+            raise ValueError("k = %d: the phi source is one array (k = 1)" % k)
+        tin = None
+        if theta is not None:
+            tin = np.ascontiguousarray(np.atleast_1d(theta), dtype=np.float64)
+            if tin.shape != (k,):
+                raise ValueError("theta must hold k = %d values, not shape %s" % (k, tin.shape))
+            if not np.all(np.isfinite(tin)):
+                raise ValueError("theta must be finite")
+        th, r2, s = np.zeros(k), np.zeros(k), np.zeros(k)
+        self._check(self._L.wafer_residuals(self._h, RESIDUAL_SOURCES[source], k, None if tin is None else _dp(tin), _dp(th), _dp(r2), _dp(s)))
+        return {"theta": th, "r2": r2, "norm2": s, "rho": np.sqrt(r2 / s)}
+
+    def residual_to_phi(self, idx: int, theta: float) -> None:
+        """phi = H l - theta l of stored state idx (zeros outside the work area); the store is left alone"""
+        theta = float(theta)
+        if not np.isfinite(theta):
+            raise ValueError("theta must be finite")
+        self._check(self._L.wafer_residual_to_phi(self._h, int(idx), theta))
+
     # -- solve (grid.rs:50-246) --------------------------------------------------------------
     def solve_state(self, wnum: int, tolerance: float, screen_update: int, max_steps=None,
                     max_records: int = 100000):
@@ -813,6 +849,9 @@ class Batch:
     solves on the host, one rotation launch for the members that solved (ritz_counts()) -- each member bit for bit what a Context of
     its Params with the same potential and states gets.  k: an int, one entry per member, or None for each member's state count.  A
     member whose solve fails keeps its store and reports it in its "status"; the others are rotated.
+    residuals(k, theta, active, source): Context.residuals for every listed member -- theta and rho = |H l - theta l| / |l| of its first
+    k[m] stored states, or of its phi on any batch (source="phi") -- one sums launch, one reduce and one read-back per pass for all
+    members of any shapes (residual_counts()), each member its Context's bits; read-only.
     python -m wafer_amd.sweep drives whole wafer.yaml runs through batches with these calls: phases per state number, every run
     with its own screen_update, tolerance and max_steps, one evolve for all running members between block boundaries."""
 
@@ -1148,6 +1187,66 @@ class Batch:
         """(launches, read-backs) of ritz_matrices, rotate_states and ritz since creation: 2 and 1, 1 and 0, 3 and 1 per call"""
         n, r = C.c_uint64(0), C.c_uint64(0)
         self._check(self._L.wafer_batch_diag_ritz_counts(self._h, C.byref(n), C.byref(r)))
+        return n.value, r.value
+
+    # -- residuals of the stores and of phi (include/wafer_hip.h) ----------------------------------------
+    def residuals(self, k=None, theta=None, active=None, source: str = "states") -> list:
+        """Context.residuals(k[m], theta[m], source) for every listed member (active[m] != 0; None: all): per pass one sums launch, one
+        reduce and one read-back whatever the members and shapes (residual_counts()).  Per member {"theta", "r2", "norm2", "rho":
+        (k,) each, "status": int}, bit for bit what a Context with its Params, potential and source gives; None for the members not
+        listed.  k: as Batch.ritz (source="phi": 1).  theta: one sequence of k[m] values per member (None for members not listed), or
+        None for Rayleigh quotients; there a member with a zero or non-finite state has status WAFER_ERR_STATE and None for the rest."""
+        if source not in RESIDUAL_SOURCES:
+            raise ValueError("source must be 'states' or 'phi', not %r" % (source,))
+        a = self._mask(active)
+        B = len(self.members)
+        if source == "phi":
+            ks = [1] * B if k is None else ([int(k)] * B if np.ndim(k) == 0 else [0 if x is None else int(x) for x in k])
+            if len(ks) != B:
+                raise ValueError("k must hold one entry per member")
+            for m in range(B):
+                if a is not None and not a[m]:
+                    ks[m] = 0
+                elif ks[m] != 1:
+                    raise ValueError("member %d: k = %d: the phi source is one array (k = 1)" % (m, ks[m]))
+        else:
+            ks = self._ritz_ks(k, a)
+        tin = None
+        if theta is not None:
+            if len(theta) != B:
+                raise ValueError("theta must hold one entry per member")
+            tin = np.zeros((B, RITZ_MAX))
+            for m in range(B):
+                if ks[m] == 0:
+                    continue
+                if theta[m] is None:
+                    raise ValueError("member %d: is listed but has no theta" % m)
+                t = np.atleast_1d(np.asarray(theta[m], dtype=np.float64))
+                if t.shape != (ks[m],):
+                    raise ValueError("member %d: theta must hold k = %d values, not shape %s" % (m, ks[m], t.shape))
+                if not np.all(np.isfinite(t)):
+                    raise ValueError("member %d: theta must be finite" % m)
+                tin[m, :ks[m]] = t
+        th, r2, s = np.zeros((B, RITZ_MAX)), np.zeros((B, RITZ_MAX)), np.zeros((B, RITZ_MAX))
+        st = (C.c_int * B)()
+        self._check(self._L.wafer_batch_residuals(self._h, RESIDUAL_SOURCES[source], self._u8(a), (C.c_uint32 * B)(*ks),
+                                                  None if tin is None else _dp(tin), _dp(th), _dp(r2), _dp(s), st))
+        out = []
+        for m in range(B):
+            n = ks[m]
+            if n == 0:
+                out.append(None)
+            elif st[m] != WAFER_OK:
+                out.append(dict(theta=None, r2=None, norm2=None, rho=None, status=int(st[m])))
+            else:
+                out.append(dict(theta=th[m, :n].copy(), r2=r2[m, :n].copy(), norm2=s[m, :n].copy(), rho=np.sqrt(r2[m, :n] / s[m, :n]),
+                                status=int(st[m])))
+        return out
+
+    def residual_counts(self) -> tuple:
+        """(launches, read-backs) of residuals since creation: 2 and 1 per call with theta given, 4 and 2 per Rayleigh-mode call"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_residual_counts(self._h, C.byref(n), C.byref(r)))
         return n.value, r.value
 
     def observables(self) -> list:

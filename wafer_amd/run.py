@@ -185,6 +185,9 @@ def main(argv=None) -> int:
     if cfg.get("ritz"):
         raise SystemExit("wafer_amd.run: gpu.ritz: true (the Rayleigh-Ritz step on the stored states) is a wafer-hip feature; "
                          "z-slab contexts have no such step")
+    if cfg.get("residual"):
+        raise SystemExit("wafer_amd.run: gpu.residual: true (the residuals of the stored states) is a wafer-hip feature; "
+                         "z-slab contexts have no such call")
 
     import torch
     import wafer_amd

@@ -3,7 +3,7 @@ every time step ONE launch for all runs of a batch that are still going (wafer_a
 context per run.
 
     python -m wafer_amd.sweep -c a.yaml -c b.yaml ... [--output-dir DIR] [--input-dir DIR] [--max-batch N] [--seed S]
-                              [--progress] [--plan] [--mix-states] [--batched-setup] [--ritz]
+                              [--progress] [--plan] [--mix-states] [--batched-setup] [--ritz] [--residuals]
 
 Configuration reading and validation are the native driver's (`wafer-hip --check-config`, through wafer_amd.run.load_config), the
 input files, the directory names and the table are wafer_amd.run's, and every run computes what `wafer-hip` computes for its file:
@@ -49,6 +49,11 @@ every state it asked for converged and it holds 2 .. 8 states; its table.txt gai
 and saved wavefunctions are rewritten from the rotated states, and its JSON line gains "ritz": {"evals": [...]} (null for a run that
 did not take part).  The `gpu.ritz` key of a wafer.yaml stays refused: the step is asked for per sweep, not per file.  Off by default;
 without it nothing changes.
+
+--residuals: every batch ends with residual_phase -- ONE Batch.residuals call in Rayleigh mode for all of its runs, on the stored states
+where the batch has state stores (after the --ritz step), on phi in a ground-state batch -- and a run's JSON line gains
+"residuals": {"theta": [...], "rho": [...]}: some eigenvalue of the run's discrete H lies within rho[j] of theta[j] (null for a run that
+did not take part).  The `gpu.residual` key of a wafer.yaml stays refused like `gpu.ritz`.  Off by default; without it nothing changes.
 """
 from __future__ import annotations
 
@@ -120,6 +125,7 @@ class Run:
         self.states: list = []       # per state: dict(state, status, steps, energy)
         self.failed = False
         self.ritz = None             # --ritz: dict(evals=[...]) once the run's states have been rotated
+        self.residuals = None        # --residuals: dict(theta=[...], rho=[...]) once the run has taken part in residual_phase
         self.boundaries: list = []   # the steps of this phase's block boundaries
         # the phase's loop variables (grid.rs:122-125)
         self.step, self.remaining, self.last_energy, self.cloned, self.running = 0, 0, sys.float_info.max, False, False
@@ -328,6 +334,34 @@ def ritz_phase(batch, runs: list, log=sys.stderr) -> None:
                 r.save_phi(batch, f"wavefunction_{a}")
     for r in rotated:
         r.write_table()
+
+
+# ---- residuals of the results (--residuals) ---------------------------------------------------------------------------------------
+def residual_phase(batch, runs: list, states: bool) -> None:
+    """theta and rho = |H l - theta l| / |l| of every run's results after the batch's last phase, in ONE Batch.residuals call in
+    Rayleigh mode.  states: the batch has state stores -- every run that holds at least one stored state takes part with its first
+    min(held, RITZ_MAX); else a ground-state batch -- every run that has not failed takes part with its phi.  A run that took part
+    gets r.residuals = dict(theta=[...], rho=[...]); the others, and a run whose state has no Rayleigh quotient, None."""
+    from wafer_amd.engine import RITZ_MAX, WAFER_OK
+
+    for r in runs:
+        r.residuals = None
+    if states:
+        held = batch.num_states()
+        part = [r for r in runs if held[r.slot] > 0]
+        ks = [0] * len(runs)
+        for r in part:
+            ks[r.slot] = min(held[r.slot], RITZ_MAX)
+    else:
+        part = [r for r in runs if not r.failed]
+        ks = [1 if r in part else 0 for r in runs]
+    if not part:
+        return
+    res = batch.residuals(k=ks, active=_mask(runs, part), source="states" if states else "phi")
+    for r in part:
+        out = res[r.slot]
+        if out["status"] == WAFER_OK:
+            r.residuals = dict(theta=[float(x) for x in out["theta"]], rho=[float(x) for x in out["rho"]])
 
 
 # ---- set-up ---------------------------------------------------------------------------------------------------------------------
@@ -546,9 +580,10 @@ def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load, ba
         batch.symmetrise(cons, active=_mask(runs, part))
 
 
-def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False, ritz: bool = False) -> tuple:
+def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False, ritz: bool = False, residuals: bool = False) -> tuple:
     """one batch of the plan from creation to its last phase -> (fused passes, one-step launches).  batched: set_up_batch's and
-    start_phase's (--batched-setup).  ritz: a batch that has state stores ends with ritz_phase (--ritz)"""
+    start_phase's (--batched-setup).  ritz: a batch that has state stores ends with ritz_phase (--ritz).  residuals: every batch ends
+    with residual_phase, after ritz_phase (--residuals)"""
     import wafer_amd
 
     pars = []
@@ -569,6 +604,8 @@ def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool =
             run_phase(batch, runs, w, progress=progress, push=plan["needs_states"])
         if ritz and plan["needs_states"]:
             ritz_phase(batch, runs)
+        if residuals:
+            residual_phase(batch, runs, states=plan["needs_states"])
         return batch.passes()
 
 
@@ -590,6 +627,9 @@ def main(argv=None) -> int:
     ap.add_argument("--ritz", action="store_true",
                     help="after the last phase of every batch with state stores, one Rayleigh-Ritz step on the converged states of its runs "
                          "(what gpu.ritz: true does in wafer-hip), all runs of the batch in one Batch.ritz call")
+    ap.add_argument("--residuals", action="store_true",
+                    help="after the last phase of every batch (after the --ritz step), theta and rho = |H l - theta l| / |l| of every run's "
+                         "stored states -- of its phi in a ground-state batch -- in one Batch.residuals call; a JSON line gains \"residuals\"")
     args = ap.parse_args(argv)
     if args.max_batch < 1:
         raise SystemExit("--max-batch must be >= 1")
@@ -607,6 +647,9 @@ def main(argv=None) -> int:
         if c.get("ritz"):
             raise SystemExit(f"{p}: wafer_amd.sweep: gpu.ritz: true (the Rayleigh-Ritz step on the stored states) is a wafer-hip key; "
                              "a sweep takes the step for all of its runs with the command-line flag --ritz")
+        if c.get("residual"):
+            raise SystemExit(f"{p}: wafer_amd.sweep: gpu.residual: true (the residuals of the stored states) is a wafer-hip key; "
+                             "a sweep computes them for all of its runs with the command-line flag --residuals")
     plan = plan_batches(cfgs, args.max_batch, mix_states=args.mix_states)
     if args.plan:
         inputs = []
@@ -637,7 +680,9 @@ def main(argv=None) -> int:
         members = [runs[i] for i in b["members"]]
         for r in members:
             r.batch = k
-        more = dict(ritz=True) if args.ritz else {}   # (without the flag the call is what it has always been)
+        more = dict(ritz=True) if args.ritz else {}   # (without the flags the call is what it has always been)
+        if args.residuals:
+            more["residuals"] = True
         launches.append(run_batch(b, members, seed, args.progress, batched=args.batched_setup, **more))
     ok = True
     for r in runs:
@@ -650,6 +695,8 @@ def main(argv=None) -> int:
                     single_steps=launches[r.batch][1])
         if args.ritz:
             line["ritz"] = r.ritz
+        if args.residuals:
+            line["residuals"] = r.residuals
         print(json.dumps(line), flush=True)
     print(f"Sweep complete. Elapsed time: {time.perf_counter() - t0:.3f} seconds.\nOutput directory: {args.output_dir}", flush=True)
     return 0 if ok else 1
