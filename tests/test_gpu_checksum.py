@@ -43,12 +43,15 @@ def bits_equal(a, b):
 
 def special_phi(padded_shape, ext, dtype, seed=1):
     """N(0, 1) over the WHOLE padded array -- the frame is non-zero on purpose: it must not count -- with work cells set to
-    -0.0, 0.0, +-inf and the smallest normal number of the storage type; on f64 also a NaN and a subnormal"""
+    -0.0, 0.0, +-inf and the smallest normal number of the storage type; on f64 also a NaN and a subnormal; on the float dtypes
+    also the smallest float subnormal, +-2^-149 (a float array must hold it, and the sum must count its bits)"""
     phi = np.random.default_rng(seed).standard_normal(padded_shape)
     work = phi[ext:-ext, ext:-ext, ext:-ext]
     specials = [-0.0, 0.0, np.inf, -np.inf, float(np.finfo(np.float64 if dtype == "f64" else np.float32).tiny)]
     if dtype == "f64":
         specials += [np.nan, 5e-324]
+    else:
+        specials += [2.0 ** -149, -2.0 ** -149]
     for i, v in enumerate(specials):
         work[np.unravel_index((1 + 7919 * i) % work.size, work.shape)] = v
     return phi
@@ -86,6 +89,8 @@ def test_whole_grid(wa, shape, ext, dtype):
         held = stored(ctx, dtype)
         if dtype == "f64":
             assert bits_equal(held, phi)
+        else:
+            assert (work_of(held, ext) == -2.0 ** -149).any()      # the float array holds the subnormal (no flush to zero)
         want = model(work_of(held, ext), 0, dtype)
         assert ctx.checksum() == want
         assert ctx.checksum() == want          # the sum's device word is cleared between calls
