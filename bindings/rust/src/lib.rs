@@ -187,6 +187,9 @@ extern "C" {
     pub fn wafer_ritz_matrices(ctx: *mut wafer_ctx, k: u32, h: *mut f64, s: *mut f64) -> c_int;
     pub fn wafer_rotate_states(ctx: *mut wafer_ctx, k: u32, coef: *const f64) -> c_int;
     pub fn wafer_ritz(ctx: *mut wafer_ctx, k: u32, evals: *mut f64, coef: *mut f64, h: *mut f64, s: *mut f64) -> c_int;
+    /// The first k stored states advanced by `n_steps` plain steps each (no projection, no normalisation): the bits of
+    /// wafer_evolve(ctx, 0, n_steps) on each; phi and `cur` are left alone
+    pub fn wafer_evolve_states(ctx: *mut wafer_ctx, k: u32, n_steps: u64) -> c_int;
     /// Residuals r = H l - theta l (include/wafer_hip.h): source 0 = the first k stored states, 1 = phi (k = 1); `theta_in` null is
     /// Rayleigh mode; `theta`, `r2`, `s` hold k doubles
     pub fn wafer_residuals(
@@ -301,6 +304,10 @@ extern "C" {
         s: *mut f64, status: *mut c_int,
     ) -> c_int;
     pub fn wafer_batch_diag_residual_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
+    /// wafer_evolve_states for every listed member with its own k[m] (0: nothing), one launch per step for all of them
+    pub fn wafer_batch_evolve_states(b: *mut wafer_batch, active: *const u8, k: *const u32, n_steps: u64) -> c_int;
+    pub fn wafer_batch_diag_store_step(b: *mut wafer_batch, buf: *mut c_char, n: usize) -> c_int;
+    pub fn wafer_batch_diag_store_counts(b: *mut wafer_batch, launches: *mut u64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

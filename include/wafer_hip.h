@@ -243,6 +243,18 @@ int wafer_rotate_states(wafer_ctx *ctx, uint32_t k, const double *coef);
 /* the three in sequence; h, s (the matrices before the rotation) may be NULL */
 int wafer_ritz(wafer_ctx *ctx, uint32_t k, double *evals, double *coef, double *h, double *s);
 
+/* ---- stepping w_store (subspace iteration) -------------------------------- */
+/* The first k stored states advance by n_steps plain imaginary-time steps each (n_steps == 0 takes one): no projection and no
+ * normalisation.  Afterwards every one of them holds, bit for bit, what phi would hold after wafer_evolve(ctx, 0, n_steps) had phi
+ * started as that state, on every dtype -- the context runs its own ground-state passes on the state and one shadow array.  phi,
+ * the current buffer, the states from k on and V keep every bit; phi need not be set.  The Gram matrix is recomputed and the
+ * two-step pass's images are dropped, as after wafer_rotate_states.  Step the block, take one wafer_ritz step, compare the Ritz
+ * energies with the last block's: state i then converges with the gap to the first level outside the block.
+ * k == 0, k > WAFER_RITZ_MAX and a context that owns a z-slab are WAFER_ERR_INVALID; k above the number of stored states, or no
+ * potential, WAFER_ERR_STATE; a refused call changes nothing.  wafer_last_evolve_ms afterwards gives the whole call's time and
+ * n_steps. */
+int wafer_evolve_states(wafer_ctx *ctx, uint32_t k, uint64_t n_steps);
+
 /* ---- residuals of w_store and of phi -------------------------------------- */
 /* How far a state is from an eigenstate of the discrete H (stencil, Dirichlet frame): with r = H l - theta l over the work area,
  * some eigenvalue of H lies within rho = sqrt(r2 / s) of theta, where r2 = sum r^2 and s = sum l^2.  Per work cell c, every
@@ -775,6 +787,26 @@ int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, con
                           double *theta, double *r2, double *s, int *status);
 /* launches and read-backs of wafer_batch_residuals since creation */
 int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
+
+/* ---- stepping the stores of a batch -----------------------------------------
+ * wafer_evolve_states (above) for every listed member (active[m] != 0; NULL: all), each with its own k[m]: ONE launch per step
+ * advances states 0 .. k[m] - 1 of all listed members, whatever their number and shapes, with V loaded and a, b formed once per
+ * cell for the (up to four) states a workgroup steps.  Every stepped state holds bit for bit what phi of a wafer_ctx of the member's
+ * wafer_params holds after wafer_evolve(ctx, 0, n_steps) from that state, on f64, f32 and f32fast.  phi, the states from k[m] on, V,
+ * the current buffers and every member not listed keep every bit.  k has n_members entries; entries of members not listed are not
+ * read, and a listed member with k[m] == 0 costs nothing.  n_steps == 0 takes one step.
+ * Steps run between the slots and shadow slots laid out as they are (made and zeroed by the first call that needs them); after an
+ * odd number of steps one batched copy brings the listed members' states back, so a call is n_steps launches or n_steps + 1.
+ * Every check for every listed member runs before anything is allocated or launched, names the member, and a refused call changes
+ * nothing: k[m] > WAFER_RITZ_MAX is WAFER_ERR_INVALID; k[m] above the member's state count, or no potential on a member with
+ * k[m] > 0, WAFER_ERR_STATE; a mixed-shape batch made without state stores refuses the call as every excited-state call.
+ * Afterwards the one-pass Gram-Schmidt form recomputes the listed members' Gram matrices before its next step, and
+ * wafer_batch_last_evolve_ms gives the call's time and n_steps. */
+int wafer_batch_evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint64_t n_steps);
+/* one line of key=value: kernel= (the instantiation), states_per_workgroup=, shapes= */
+int wafer_batch_diag_store_step(wafer_batch *b, char *buf, size_t n);
+/* launches of wafer_batch_evolve_states since creation: n_steps per call, plus one where n_steps is odd */
+int wafer_batch_diag_store_counts(wafer_batch *b, uint64_t *launches);
 
 #ifdef __cplusplus
 }

@@ -61,7 +61,16 @@ profiles/batch_ritz_rows.jsonl unless --out names another file.
 around B Contexts calling residuals(K, theta) one after another; "batch_rayleigh_ms" / "ctx_rayleigh_ms": the same with theta=None (two
 passes); one warm-up, then --reps repetitions, all listed; "parity": every member's theta, r2 and norm2 compared == on both sides in both
 modes; "residual_counts_*": the launches and read-backs one call adds.  Appended to profiles/batch_residual_rows.jsonl unless --out names
-another file."""
+another file.
+
+--store-step K: a mode of its own -- Batch.evolve_states on K stored states per member (the stores of --ritz; every size of --sizes, Harmonic).
+One line per B, HIP events around the launches of --steps steps (an even number: no trailing copy), one warm-up call of --warmup steps,
+then --reps repetitions, all listed: "store_us_per_step" and "store_gups" (B x K x cells x steps / time) for Batch.evolve_states(steps, K);
+"dup_us_per_step" / "dup_gups" for Batch.evolve(steps) on a batch of B x K members (the same cells stepped, with V and a, b duplicated per
+state; one step per launch, the default dispatch); "gs_us_per_step" / "gs_gups" (B x cells x steps / time) for Batch.evolve(steps,
+wnum=K-1) on the B members -- what an excited step costs today.  "ratio_dup": dup over store, per repetition.  "parity": every state of
+the first and the last member bit-identical to a Context's evolve(0, steps) from the same state.  "store_dispatch": the kernel line;
+"store_launches": what one timed call adds.  Appended to profiles/batch_store_step_rows.jsonl unless --out names another file."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -476,6 +485,71 @@ def residual_row(shapes, B, K, reps, ext=1, dtype="f64"):
     return out
 
 
+def store_step_row(n, B, K, steps, warmup, reps, ext=1, dtype="f64"):
+    """Batch.evolve_states(steps, K) on B members against Batch.evolve on B x K members and against excited steps with wnum = K - 1"""
+    steps += steps % 2   # (an even number of steps: no trailing copy in the timed calls)
+    pars = [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype, max_states=K)
+            for k in range(B)]
+    cells = n ** 3
+    out = {"mode": "store_step", "k": K, "shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "reps": reps,
+           "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype, "potential": "Harmonic"}
+    stores = [store(pars[0], K, seed=j) for j in range(2)]   # (two stores, shared out)
+    for key in ("store_us_per_step", "dup_us_per_step", "gs_us_per_step"):
+        out[key] = []
+    same = lambda x, y: bool(np.array_equal(np.ascontiguousarray(x).view(np.int64), np.ascontiguousarray(y).view(np.int64)))
+    with wafer_amd.Batch(pars) as b:
+        b.set_potentials(["Harmonic"] * B)
+        b.set_initial_conditions(["Gaussian"] * B)
+        for k in range(B):
+            for i in range(K):
+                b.load_state(k, i, stores[k % 2][i])
+        out["store_dispatch"] = b.store_dispatch()
+        parity = True
+        for k in sorted({0, B - 1}):   # before anything is timed: `steps` steps of every state against a context
+            with wafer_amd.Context(pars[k]) as ctx:
+                ctx.set_potential("Harmonic")
+                want = []
+                for i in range(K):
+                    ctx.upload_phi(stores[k % 2][i])
+                    ctx.evolve(0, steps)
+                    want.append(ctx.download_phi())
+            b.evolve_states(steps, K, active=[int(m == k) for m in range(B)])
+            parity = parity and all(same(b.download_state(k, i), want[i]) for i in range(K))
+        out["parity"] = parity
+        b.evolve_states(warmup + warmup % 2, K)
+        b.last_evolve_ms()
+        c0 = b.store_counts()
+        for _ in range(reps):
+            b.evolve_states(steps, K)
+            ms, st = b.last_evolve_ms()
+            out["store_us_per_step"].append(1e3 * ms / st)
+        out["store_launches"] = (b.store_counts() - c0) // reps
+        if K > 1:   # excited steps against K - 1 of the (no longer orthonormal, but that costs the same) states
+            b.evolve(warmup, wnum=K - 1)
+            b.last_evolve_ms()
+            for _ in range(reps):
+                b.evolve(steps, wnum=K - 1)
+                ms, st = b.last_evolve_ms()
+                out["gs_us_per_step"].append(1e3 * ms / st)
+            out["gs_dispatch"] = b.gs_dispatch(K - 1)
+    dup = [pars[k // K] for k in range(B * K)]
+    with wafer_amd.Batch(dup) as d:
+        d.set_potentials(["Harmonic"] * (B * K))
+        d.set_initial_conditions(["Gaussian"] * (B * K))
+        out["dup_dispatch"] = d.dispatch()["kernel"]
+        d.evolve(warmup)
+        d.last_evolve_ms()
+        for _ in range(reps):
+            d.evolve(steps)
+            ms, st = d.last_evolve_ms()
+            out["dup_us_per_step"].append(1e3 * ms / st)
+    out["store_gups"] = [B * K * cells / (us * 1e-6) / 1e9 for us in out["store_us_per_step"]]
+    out["dup_gups"] = [B * K * cells / (us * 1e-6) / 1e9 for us in out["dup_us_per_step"]]
+    out["gs_gups"] = [B * cells / (us * 1e-6) / 1e9 for us in out["gs_us_per_step"]]
+    out["ratio_dup"] = [x / y for x, y in zip(out["dup_us_per_step"], out["store_us_per_step"])]
+    return out
+
+
 def rounded(d):
     if isinstance(d, dict):
         return {k: rounded(v) for k, v in d.items()}
@@ -512,7 +586,20 @@ def main():
     ap.add_argument("--residuals", type=int, metavar="K", help="time Batch.residuals on K stored states per member, theta given and in Rayleigh "
                     "mode, against B contexts calling residuals one after another (a mode of its own; --batch, --reps, --sizes or --mixed, --ext, "
                     "--dtype apply)")
+    ap.add_argument("--store-step", type=int, metavar="K", help="time Batch.evolve_states on K stored states per member against Batch.evolve on "
+                    "B x K members and against excited steps with wnum = K - 1 (a mode of its own; --batch, --steps, --warmup, --reps, --sizes, --ext, "
+                    "--dtype apply)")
     a = ap.parse_args()
+    if a.store_step:
+        if not a.out:
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_store_step_rows.jsonl")
+        for n in a.sizes:
+            for B in a.batch:
+                line = json.dumps(rounded(store_step_row(n, B, a.store_step, a.steps, a.warmup, a.reps, a.ext, a.dtype)))
+                print(line, flush=True)
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+        return
     if a.residuals:
         if not a.out:
             a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_residual_rows.jsonl")

@@ -179,6 +179,33 @@ static inline std::vector<WaferBatchBlock> wafer_batch_fused_table(const WaferGe
     return t;
 }
 
+// ---- stepping the state stores (wafer_batch_evolve_states, wafer_store_step_batch.hip.h) --------------------------------------
+// A workgroup of wafer_k_batch_store_step steps up to WAFER_STORE_SG states of its tile; the grid's second extent is the number of
+// such groups the largest listed k needs.
+#define WAFER_STORE_SG 4
+static inline int wafer_batch_store_groups(uint32_t max_k) { return (int)((max_k + WAFER_STORE_SG - 1) / WAFER_STORE_SG); }
+
+// A call of n_steps steps (0 takes one): step s reads the slots when s is even and their shadows when it is odd, and writes the
+// other set, so after an odd number of steps the results stand in the shadows and ONE batched copy of the listed members' states
+// brings them back (copy_back) -- a trailing copy, never a leading one.  launches: steps, or steps + 1, whatever the batch holds;
+// 0 where no listed member has k > 0 (max_k == 0).
+struct WaferBatchStorePlan {
+    uint64_t steps = 0, launches = 0;
+    int groups = 0;
+    bool copy_back = false;
+};
+static inline bool wafer_batch_store_src_is_shadow(uint64_t s) { return (s & 1) != 0; }
+static inline WaferBatchStorePlan wafer_batch_store_plan(uint64_t n_steps, uint32_t max_k)
+{
+    WaferBatchStorePlan p;
+    p.steps = n_steps == 0 ? 1 : n_steps;
+    p.groups = wafer_batch_store_groups(max_k);
+    if (max_k == 0) return p;
+    p.copy_back = (p.steps & 1) != 0;
+    p.launches = p.steps + (p.copy_back ? 1 : 0);
+    return p;
+}
+
 // ---- the batch's layout ------------------------------------------------------------------------------------------------------
 // The distinct geometries of the members' shapes (nxyz: nx, ny, nz of member m at [3 m ..]) in order of first appearance, each the
 // one a context of that shape builds (ghost depth G, elements of esz bytes); shape_of[m]: member m's entry; off[m]: its element

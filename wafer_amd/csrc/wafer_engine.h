@@ -115,6 +115,7 @@ struct wafer_ctx {
     int cur = 0;
     void *v = nullptr, *a = nullptr, *b = nullptr, *potsub = nullptr;
     std::vector<void *> states;
+    void *state_shadow = nullptr;   // wafer_evolve_states: the second buffer of the state being stepped; made by the first call
     // two excited-state steps per pass (wafer_stencil_x2.hip.h): M_j = A l_j of the first x2_ready stored states, the matrix
     // <l_j, M_i> (device) and the load transform's coefficient block
     std::vector<void *> mstates;

@@ -287,7 +287,7 @@ int wafer_ctx_destroy(wafer_ctx *c)
     if (c->s_own) (void)hipStreamSynchronize(c->s_own);
     if (c->s_aux) (void)hipStreamSynchronize(c->s_aux);
     if (c->s_aux2) (void)hipStreamSynchronize(c->s_aux2);
-    for (void *p : {c->phi[0], c->phi[1], c->v, c->a, c->b, c->potsub})
+    for (void *p : {c->phi[0], c->phi[1], c->v, c->a, c->b, c->potsub, c->state_shadow})
         if (p) (void)hipFree(alloc_base(c, p));
     for (void *p : c->states)
         if (p) (void)hipFree(alloc_base(c, p));

@@ -38,6 +38,9 @@
 // read-back, the solves on the host (wafer_ritz.h), one rotation launch -- from a per-call table of (member, k, partials offset, span).
 // Residuals (wafer_batch_residuals; kernels: wafer_residual_batch.hip.h, wafer_tu_residual_batch.hip): a context's wafer_residuals for
 // every listed member with its own k and theta, on the stores or on phi -- one sums launch, one reduce and one read-back per pass.
+// Stepping the stores (wafer_batch_evolve_states; kernels: wafer_store_step_batch.hip.h, wafer_tu_store_step_batch*.hip): the first k[m]
+// stored states of every listed member advance by n plain steps, one launch per step over the listed members' workgroup table,
+// between the slots and shadow slots laid out as they are; an odd n ends with one batched copy back into the slots.
 #include <memory>
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
@@ -47,6 +50,7 @@
 #include "wafer_setup_batch.hip.h"
 #include "wafer_ritz_batch.hip.h"
 #include "wafer_residual_batch.hip.h"
+#include "wafer_store_step_batch.hip.h"
 #include "wafer_ritz.h"
 
 struct wafer_batch {
@@ -87,6 +91,7 @@ struct wafer_batch {
         int K = 0;
     };
     BlockTable blk, blkk;                     // the one-step kernel's, and the fused pass's (wafer_k_batch_stepk) for the same active set
+    BlockTable blks;                          // the store step's (wafer_k_batch_store_step): the one-step table over the listed members with k > 0
     int step_variant = -1;                    // wafer_batch_set_step_variant
     uint64_t n_fused_passes = 0, n_single_steps = 0;   // launches since creation (wafer_batch_diag_passes)
     int *act_dev = nullptr, *act_host = nullptr;
@@ -134,6 +139,10 @@ struct wafer_batch {
     WaferBatchResidualRec *resid_rec_dev = nullptr, *resid_rec_host = nullptr;   // the per-call table, n entries
     double *resid_sums = nullptr, *resid_sums_host = nullptr; // [member][3 WAFER_RITZ_MAX]: r2, wh, s of column j at j * 3
     uint64_t n_resid_launches = 0, n_resid_readbacks = 0;     // of wafer_batch_residuals since creation (wafer_batch_diag_residual_counts)
+    // stepping the stores (wafer_store_step_batch.hip.h): shadow l is laid out as slot l is, zeroed, made by the first call that needs it
+    std::vector<void *> shadows;
+    int *store_k_dev = nullptr, *store_k_host = nullptr;      // [member]: the call's k (0: not listed)
+    uint64_t n_store_launches = 0;                            // of wafer_batch_evolve_states since creation (wafer_batch_diag_store_counts)
 };
 
 namespace {
@@ -188,14 +197,16 @@ void destroy(wafer_batch *b)
         if (p) (void)hipFree(p);
     for (void *p : b->slots)
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
+    for (void *p : b->shadows)
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->blks.dev, (void *)b->store_k_dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
                     (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
                     (void *)b->gram_list_dev, (void *)b->rs_scratch, (void *)b->setup_dev, (void *)b->vchk_dev, (void *)b->ritz_rec_dev,
                     (void *)b->ritz_partials, (void *)b->ritz_sums, (void *)b->ritz_coef, (void *)b->resid_rec_dev, (void *)b->resid_sums})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host, (void *)b->setup_host,
                     (void *)b->vchk_init, (void *)b->vchk_host, (void *)b->ritz_rec_host, (void *)b->ritz_sums_host, (void *)b->ritz_coef_host,
-                    (void *)b->resid_rec_host, (void *)b->resid_sums_host})
+                    (void *)b->resid_rec_host, (void *)b->resid_sums_host, (void *)b->store_k_host})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {b->ev_start, b->ev_stop, b->rs_start, b->rs_stop})
         if (e) (void)hipEventDestroy(e);
@@ -419,13 +430,14 @@ void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
     return static_cast<char *>(b->slots[l]) + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
 }
 
-// slots [0, n) exist (zeros: frames, pads and guard zones of every member)
-int ensure_slots(wafer_batch *b, uint32_t n)
+// entries [0, n) of `v` exist (zeros: frames, pads and guard zones of every member).  v: the store's slots, or their shadows
+// (wafer_batch_evolve_states), laid out alike
+int ensure_slots(wafer_batch *b, std::vector<void *> &v, uint32_t n)
 {
-    while (b->slots.size() < n) {
+    while (v.size() < n) {
         void *p = nullptr;
         HIP_TRY(hipMalloc(&p, b->cells * b->esz));
-        b->slots.push_back(p);
+        v.push_back(p);
         HIP_TRY(hipMemsetAsync(p, 0, b->cells * b->esz, b->s));
     }
     return WAFER_OK;
@@ -454,7 +466,7 @@ int push_states(wafer_batch *b, const uint8_t *active)
         TRY(check_capacity(b, m));
         need = std::max(need, b->nst[m] + 1);
     }
-    TRY(ensure_slots(b, need));
+    TRY(ensure_slots(b, b->slots, need));
     for (uint32_t m = 0; m < b->n; ++m) {
         if (active && !active[m]) continue;
         const wafer_ctx *c = b->views[m];
@@ -908,7 +920,7 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
     if (!nlisted) return WAFER_OK;
 
     HIP_TRY(hipSetDevice(b->device));
-    if (target == WAFER_RESAMPLE_STATE) TRY(ensure_slots(b, idx + 1));
+    if (target == WAFER_RESAMPLE_STATE) TRY(ensure_slots(b, b->slots, idx + 1));
     b->rs_timing_valid = false;   // (a call that fails below leaves no half-recorded pair behind)
     if (host) TRY(ensure_scratch(b, 2 * (size_t)sx * sy * sz));   // (before the events: growing it synchronises, frees and allocates)
     HIP_TRY(hipEventRecord(b->rs_start, b->s));
@@ -1294,6 +1306,83 @@ int residual_pass(wafer_batch *b, int source, const uint8_t *listed, const uint3
                            hipMemcpyDeviceToHost, b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
     ++b->n_resid_readbacks;
+    return WAFER_OK;
+}
+
+// ---- stepping the stores -----------------------------------------------------------------------------------------------------
+// every check of wafer_batch_evolve_states for every listed member, before anything is allocated, uploaded or launched.
+// A listed member with k[m] == 0 is allowed and costs nothing.  *max_k: the largest k among the listed members.
+int store_step_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t *max_k)
+{
+    TRY(refuse_mixed(b, "wafer_batch_evolve_states"));
+    *max_k = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (k[m] > WAFER_RITZ_MAX) return fail(WAFER_ERR_INVALID, "member %u: k = %u: wafer_batch_evolve_states steps at most %d states", m, k[m], WAFER_RITZ_MAX);
+        if (k[m] > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
+        if (k[m] && !b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
+        *max_k = std::max(*max_k, k[m]);
+    }
+    return WAFER_OK;
+}
+
+// n_steps plain steps of the first k[m] stored states of every listed member (wafer_batch_plan.h: wafer_batch_store_plan): one
+// launch per step between the slots and their shadows, and after an odd number of steps one batched copy back into the slots.
+int evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint64_t n_steps)
+{
+    uint32_t max_k = 0;
+    TRY(store_step_check(b, active, k, &max_k));
+    HIP_TRY(hipSetDevice(b->device));
+    RoctxRange range_("wafer_batch_evolve_states");
+    const WaferBatchStorePlan plan = wafer_batch_store_plan(n_steps, max_k);
+    std::vector<uint8_t> listed(b->n);
+    for (uint32_t m = 0; m < b->n; ++m) listed[m] = ((!active || active[m]) && k[m] > 0) ? 1 : 0;
+    if (max_k) {
+        TRY(ensure_slots(b, b->shadows, max_k));   // (zeroed: the kernel writes work cells only, frames and pads stay zeros)
+        TRY(ensure_ritz(b));   // (the copy's per-call table)
+        if (!b->store_k_dev) HIP_TRY(hipMalloc((void **)&b->store_k_dev, sizeof(int) * b->n));
+        if (!b->store_k_host) HIP_TRY(hipHostMalloc((void **)&b->store_k_host, sizeof(int) * b->n, hipHostMallocDefault));
+        TRY(sync_members(b));
+        TRY(build_blocks(b, b->blks, listed.data(), 1));
+        HIP_TRY(hipStreamSynchronize(b->s));   // the pinned tables are not read by an earlier call's copy
+        for (uint32_t m = 0; m < b->n; ++m) b->store_k_host[m] = listed[m] ? (int)k[m] : 0;
+        HIP_TRY(hipMemcpyAsync(b->store_k_dev, b->store_k_host, sizeof(int) * b->n, hipMemcpyHostToDevice, b->s));
+    }
+    int nact = 0, max_nb = 0, mk = 0;
+    size_t doubles = 0;
+    long long want = 1;
+    if (plan.copy_back) {
+        TRY(upload_ritz_table(b, listed.data(), k, &nact, &max_nb, &mk, &doubles));
+        for (int q = 0; q < nact; ++q) want = std::max(want, (b->ritz_rec_host[q].n16 + 255) / 256);
+    }
+    WaferRitzPtrs slots, shadows;
+    for (uint32_t l = 0; l < max_k; ++l) {
+        slots.p[l] = b->slots[l];
+        shadows.p[l] = b->shadows[l];
+    }
+    HIP_TRY(hipEventRecord(b->ev_start, b->s));
+    if (max_k && !b->blks.host.empty()) {
+        for (uint64_t st = 0; st < plan.steps; ++st) {   // no host synchronisation in here
+            const bool from_shadow = wafer_batch_store_src_is_shadow(st);
+            const hipError_t e = with_geom(b, [&](const auto &gs) {
+                return wafer_entry_batch_store_step(b->dtype, b->g().R, gs, b->mem_dev, b->blks.dev, (int)b->blks.host.size(), plan.groups, b->store_k_dev,
+                                                    from_shadow ? shadows : slots, from_shadow ? slots : shadows, b->s);
+            });
+            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched store step launch failed: %s", hipGetErrorString(e));
+            ++b->n_store_launches;
+        }
+        if (plan.copy_back && nact) {
+            const int blocks = (int)std::min<long long>(want, (long long)b->num_cus * 8);
+            const hipError_t e = wafer_entry_batch_store_copy(b->ritz_rec_dev, nact, blocks, shadows, slots, b->s);
+            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched store copy launch failed: %s", hipGetErrorString(e));
+            ++b->n_store_launches;
+        }
+    }
+    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
+    b->last_steps = plan.steps;
+    b->timing_valid = true;
+    for (uint32_t m = 0; m < b->n; ++m)
+        if (listed[m]) mark_gram_stale(b, m);   // the one-pass form sees the new store
     return WAFER_OK;
 }
 
@@ -1708,7 +1797,7 @@ int wafer_batch_load_state(wafer_batch *b, uint32_t member, uint32_t idx, const 
     HIP_TRY(hipSetDevice(b->device));
     if (idx > b->nst[member]) return fail(WAFER_ERR_STATE, "member %u: states must be loaded in order", member);
     if (idx == b->nst[member]) TRY(check_capacity(b, member));
-    TRY(ensure_slots(b, idx + 1));
+    TRY(ensure_slots(b, b->slots, idx + 1));
     TRY(upload_padded(b->views[member], state, slot_ptr(b, idx, member)));
     if (idx == b->nst[member]) ++b->nst[member];
     mark_gram_stale(b, member);
@@ -2029,6 +2118,28 @@ int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_
     if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
     *launches = b->n_resid_launches;
     *readbacks = b->n_resid_readbacks;
+    return WAFER_OK;
+}
+
+int wafer_batch_evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint64_t n_steps)
+{
+    if (!b || !k) return fail(WAFER_ERR_INVALID, "null argument");
+    return evolve_states(b, active, k, n_steps);
+}
+
+int wafer_batch_diag_store_step(wafer_batch *b, char *buf, size_t n)
+{
+    if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
+    static const char *const types[] = {"double,double", "float,double", "float,float"};
+    snprintf(buf, n, "kernel=wafer_k_batch_store_step<%d,%s,%s> states_per_workgroup=%d shapes=%zu", b->g().R, types[b->dtype],
+             b->mixed ? "WaferBatchGeomTable" : "WaferGeom", WAFER_STORE_SG, b->geoms.size());
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_store_counts(wafer_batch *b, uint64_t *launches)
+{
+    if (!b || !launches) return fail(WAFER_ERR_INVALID, "null argument");
+    *launches = b->n_store_launches;
     return WAFER_OK;
 }
 

@@ -799,6 +799,26 @@ static int launch_pass(wafer_ctx *c, const WaferPass &p, uint32_t wnum, SingleLa
     }
 }
 
+// the passes of a call of `steps` steps on phi[cur] (wafer_evolve's body between its two events): cur and halo_valid follow
+static int evolve_passes(wafer_ctx *c, uint32_t wnum, uint64_t steps, bool x2)
+{
+    const WaferPassFacts facts = pass_facts(c, wnum, x2);
+    SingleLaunch hv;
+    for (uint64_t s = 0; s < steps;) {
+        const WaferPass p = wafer_next_pass(facts, s, steps, c->halo_valid, hv.active);
+        if (p.drain_first) {   // before any other kind of pass; the planner is asked again with the ghost planes the drain leaves
+            TRY(hv.drain(c));
+            continue;
+        }
+        const int dst = c->cur ^ 1;
+        TRY(launch_pass(c, p, wnum, hv));
+        if (p.kind != WAFER_PASS_X2_TAIL) c->cur = dst;   // (x2_run has moved cur itself, once per pass)
+        c->halo_valid = p.valid_after;
+        s += p.steps;
+    }
+    return hv.drain(c);   // ... and before ev_stop, and before anything that follows this call on the main stream
+}
+
 } // namespace wafer_eng
 
 extern "C" {
@@ -816,26 +836,57 @@ int wafer_evolve(wafer_ctx *c, uint32_t wnum, uint64_t n_steps)
     bool x2 = false;
     if (wnum > 0 && steps >= 4) TRY(x2_agree(c, wnum, &x2));
     if (x2) TRY(ensure_x2(c, wnum));
-    const WaferPassFacts facts = pass_facts(c, wnum, x2);
     HIP_TRY(hipEventRecord(c->ev_start, c->s_main));
-    SingleLaunch hv;
-    for (uint64_t s = 0; s < steps;) {
-        const WaferPass p = wafer_next_pass(facts, s, steps, c->halo_valid, hv.active);
-        if (p.drain_first) {   // before any other kind of pass; the planner is asked again with the ghost planes the drain leaves
-            TRY(hv.drain(c));
-            continue;
-        }
-        const int dst = c->cur ^ 1;
-        TRY(launch_pass(c, p, wnum, hv));
-        if (p.kind != WAFER_PASS_X2_TAIL) c->cur = dst;   // (x2_run has moved cur itself, once per pass)
-        c->halo_valid = p.valid_after;
-        s += p.steps;
-    }
-    TRY(hv.drain(c));   // ... and before ev_stop, and before anything that follows this call on the main stream
+    TRY(evolve_passes(c, wnum, steps, x2));
     HIP_TRY(hipEventRecord(c->ev_stop, c->s_main));
     c->last_steps = steps;
     c->timing_valid = true;
     return WAFER_OK;
+}
+
+// The first k stored states advanced by n_steps plain steps each, by the context's own ground-state passes: for every state, phi's
+// two buffers are pointed at the state and the shadow array, wafer_evolve(ctx, 0, n)'s passes run, the state's slot becomes whichever
+// buffer holds the result and the other is the shadow from then on.  phi, cur, have_phi and halo_valid come back exactly.
+int wafer_evolve_states(wafer_ctx *c, uint32_t k, uint64_t n_steps)
+{
+    if (!c) return fail(WAFER_ERR_INVALID, "null context");
+    if (k == 0 || k > WAFER_RITZ_MAX) return fail(WAFER_ERR_INVALID, "k = %u: wafer_evolve_states steps 1 .. %d states", k, WAFER_RITZ_MAX);
+    if (c->P.z_count != 0)
+        return fail(WAFER_ERR_INVALID, "wafer_evolve_states is not available on a context that owns a z-slab (the stored states carry no ghost planes)");
+    if (k > c->states.size()) return fail(WAFER_ERR_STATE, "k = %u but w_store holds %zu states", k, c->states.size());
+    if (!c->have_pot) return fail(WAFER_ERR_STATE, "potential not set");
+    HIP_TRY(hipSetDevice(c->P.device));
+    RoctxRange range_("wafer_evolve_states");
+    const uint64_t steps = n_steps == 0 ? 1 : n_steps;
+    if (!c->state_shadow) TRY(alloc_grid_array(c, &c->state_shadow, c->s_main));
+    void *const phi0 = c->phi[0], *const phi1 = c->phi[1];
+    const int cur = c->cur, halo_valid = c->halo_valid;
+    const bool have_phi = c->have_phi;
+    HIP_TRY(hipEventRecord(c->ev_start, c->s_main));
+    int rc = WAFER_OK;
+    for (uint32_t j = 0; j < k && rc == WAFER_OK; ++j) {
+        c->phi[0] = c->states[j];
+        c->phi[1] = c->state_shadow;
+        c->cur = 0;
+        c->halo_valid = 0;
+        c->have_phi = true;
+        rc = evolve_passes(c, 0, steps, false);
+        if (rc == WAFER_OK) {   // (a failed pass leaves the slot where it was)
+            c->states[j] = c->phi[c->cur];
+            c->state_shadow = c->phi[c->cur ^ 1];
+        }
+    }
+    c->phi[0] = phi0;
+    c->phi[1] = phi1;
+    c->cur = cur;
+    c->halo_valid = halo_valid;
+    c->have_phi = have_phi;
+    TRY(rc);
+    HIP_TRY(hipEventRecord(c->ev_stop, c->s_main));
+    c->last_steps = steps;
+    c->timing_valid = true;
+    // the store changed: the Gram matrix is recomputed, and the two-step pass rebuilds its images M_j on demand
+    return recompute_gram(c);
 }
 
 int wafer_last_evolve_ms(wafer_ctx *c, float *ms, uint64_t *steps)

@@ -66,6 +66,7 @@ EXPORTS = [
     "wafer_ritz_solve", "wafer_ritz_matrices", "wafer_rotate_states", "wafer_ritz",
     "wafer_batch_ritz_matrices", "wafer_batch_rotate_states", "wafer_batch_ritz", "wafer_batch_diag_ritz_counts",
     "wafer_residuals", "wafer_residual_to_phi", "wafer_batch_residuals", "wafer_batch_diag_residual_counts",
+    "wafer_evolve_states", "wafer_batch_evolve_states", "wafer_batch_diag_store_step", "wafer_batch_diag_store_counts",
 ]
 RITZ_MAX = 8   # WAFER_RITZ_MAX
 RESIDUAL_SOURCES = {"states": 0, "phi": 1}   # WAFER_RESIDUAL_STATES, WAFER_RESIDUAL_PHI
@@ -293,6 +294,10 @@ def load_library():
     L.wafer_batch_diag_ritz_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.wafer_batch_residuals.argtypes = [vp, C.c_int, u8p, u32p, dp, dp, dp, dp, C.POINTER(C.c_int)]
     L.wafer_batch_diag_residual_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.wafer_evolve_states.argtypes = [vp, C.c_uint32, C.c_uint64]
+    L.wafer_batch_evolve_states.argtypes = [vp, u8p, u32p, C.c_uint64]
+    L.wafer_batch_diag_store_step.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.wafer_batch_diag_store_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -402,6 +407,69 @@ def _enum_entries(names, table, n_members: int, mask, what: str) -> list:
             out.append(table.index(name))
         else:
             out.append(int(name))
+    return out
+
+
+# ---- subspace iteration on the state stores: the driver, written once -----------------------------------------------------------
+BLOCK_CONVERGED, BLOCK_MAX_BLOCKS, BLOCK_DEPENDENT = WAFER_OK, WAFER_ERR_MAX_STEP, WAFER_ERR_STATE
+
+
+def block_solve_loop(step, ritz, residuals, k, tolerance: float, steps_per_block: int, max_blocks: int) -> list:
+    """Subspace iteration over a set of members, backend-free (Context.solve_block, Batch.solve_block and the numpy model of the
+    tests all call this).  k: one state count per member (0 or None: the member takes no part).  Three callables over the members
+    still `going` (a sorted list of member indices):
+        step(going, n)              advances the first k[m] stored states of every member in `going` by n plain steps
+        ritz(going)                 one Rayleigh-Ritz step on each -> {m: (status, evals)}; status WAFER_OK, or WAFER_ERR_STATE where the
+                                    states have become linearly dependent (evals is then ignored)
+        residuals(going, theta)     rho of the rotated states with theta[m] = the Ritz energies -> {m: rho}
+    Per block: step, Ritz, diff_j = |e_j - e_last_j| (inf in the first block), residuals; a row {"block", "steps", "evals", "diff",
+    "rho"} is recorded.  A member is done when max_j diff_j < tolerance -- the reference's stopping rule applied to every state of
+    the block; rho is reported and never decides (the semi-implicit step's invariant subspaces are not H's: rho has a floor of
+    O(dt V)).  Done members leave `going`.
+    -> per member None, or {"status", "message", "blocks", "steps", "evals", "diff", "rho", "rows"}: status BLOCK_CONVERGED (WAFER_OK),
+    BLOCK_MAX_BLOCKS (WAFER_ERR_MAX_STEP: max_blocks reached, a status and not an exception) or BLOCK_DEPENDENT (WAFER_ERR_STATE: the
+    Ritz step found the states linearly dependent; the message says to shorten steps_per_block)."""
+    ks = [0 if x is None else int(x) for x in k]
+    steps_per_block, max_blocks, tolerance = int(steps_per_block), int(max_blocks), float(tolerance)
+    if steps_per_block < 1 or max_blocks < 1:
+        raise ValueError("steps_per_block and max_blocks must be >= 1")
+    if not tolerance > 0.0:
+        raise ValueError("tolerance must be > 0")
+    out = [None if n == 0 else dict(status=BLOCK_MAX_BLOCKS, message="", blocks=0, steps=0, evals=None, diff=None, rho=None, rows=[])
+           for n in ks]
+    going = [m for m, n in enumerate(ks) if n > 0]
+    last = {m: None for m in going}
+    for block in range(1, max_blocks + 1):
+        if not going:
+            break
+        step(list(going), steps_per_block)
+        solved = ritz(list(going))
+        alive = []
+        for m in going:
+            status, evals = solved[m]
+            o = out[m]
+            o["blocks"], o["steps"] = block, block * steps_per_block
+            if status != WAFER_OK:
+                o["status"] = BLOCK_DEPENDENT
+                o["message"] = ("member %d: after block %d (%d steps) the Ritz step found the %d states linearly dependent: every state has "
+                                "collapsed onto the lowest ones; shorten steps_per_block (now %d)" % (m, block, o["steps"], ks[m], steps_per_block))
+                continue
+            evals = np.array(evals, dtype=np.float64)[:ks[m]]
+            o["diff"] = np.full(ks[m], np.inf) if last[m] is None else np.abs(evals - last[m])
+            o["evals"] = last[m] = evals
+            alive.append(m)
+        rho = residuals(list(alive), {m: out[m]["evals"] for m in alive}) if alive else {}
+        going = []
+        for m in alive:
+            o = out[m]
+            o["rho"] = np.array(rho[m], dtype=np.float64)[:ks[m]]
+            o["rows"].append(dict(block=block, steps=o["steps"], evals=o["evals"].copy(), diff=o["diff"].copy(), rho=o["rho"].copy()))
+            if float(np.max(o["diff"])) < tolerance:
+                o["status"] = BLOCK_CONVERGED
+            else:
+                going.append(m)
+    for m in going:
+        out[m]["message"] = "member %d: max_blocks = %d reached with max diff %g >= tolerance %g" % (m, max_blocks, float(np.max(out[m]["diff"])), tolerance)
     return out
 
 
@@ -626,6 +694,41 @@ class Context:
         evals, coef, h, s = np.zeros(n), np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
         self._check(self._L.wafer_ritz(self._h, k, _dp(evals), _dp(coef), _dp(h), _dp(s)))
         return {"evals": evals, "coef": coef, "h": h, "s": s}
+
+    # -- stepping w_store: subspace iteration (include/wafer_hip.h) --------------------------------------
+    def evolve_states(self, k: int, steps: int) -> None:
+        """the first k stored states advanced by `steps` plain steps each (no projection, no normalisation): every one holds the
+        bits of clone_state_to_phi(j); evolve(0, steps).  phi and the current buffer are left alone."""
+        self._check(self._L.wafer_evolve_states(self._h, int(k), int(steps)))
+
+    def seed_states(self, k: int, seed: int) -> None:
+        """k fresh stored states: the Gaussian initial condition with seed + j, pushed, for j = 0 .. k-1.  OVERWRITES phi (it holds
+        the last of them afterwards); the store is not cleared first."""
+        for j in range(int(k)):
+            self.set_initial_condition("Gaussian", int(seed) + j)
+            self.push_state()
+
+    def solve_block(self, k: int, tolerance: float, steps_per_block: int, max_blocks: int) -> dict:
+        """Subspace iteration on the first k stored states (block_solve_loop): evolve_states(k, steps_per_block), ritz(k), the Ritz
+        energies against the last block's, residuals(k, theta=evals) -- until every |e_j - e_last_j| < tolerance.
+        -> {"status", "message", "blocks", "steps", "evals", "diff", "rho", "rows"}"""
+        k = int(k)
+
+        def step(going, n):
+            self.evolve_states(k, n)
+
+        def ritz(going):
+            try:
+                return {0: (WAFER_OK, self.ritz(k)["evals"])}
+            except WaferError as e:
+                if e.code != WAFER_ERR_STATE:
+                    raise
+                return {0: (WAFER_ERR_STATE, None)}
+
+        def residuals(going, theta):
+            return {0: self.residuals(k, theta=theta[0])["rho"]}
+
+        return block_solve_loop(step, ritz, residuals, [k], tolerance, steps_per_block, max_blocks)[0]
 
     # -- residuals of w_store and of phi (include/wafer_hip.h) -------------------------------------------
     def residuals(self, k: int | None = None, theta=None, source: str = "states") -> dict:
@@ -1188,6 +1291,78 @@ class Batch:
         n, r = C.c_uint64(0), C.c_uint64(0)
         self._check(self._L.wafer_batch_diag_ritz_counts(self._h, C.byref(n), C.byref(r)))
         return n.value, r.value
+
+    # -- stepping the stores: subspace iteration (include/wafer_hip.h) ------------------------------------
+    def _store_ks(self, k, a) -> list:
+        """one k per member as _ritz_ks takes it, but 0 is allowed (the member costs nothing) and members not listed get 0"""
+        B = len(self.members)
+        ks = self.num_states() if k is None else ([int(k)] * B if np.ndim(k) == 0 else [0 if x is None else int(x) for x in k])
+        if len(ks) != B:
+            raise ValueError("k must hold one entry per member")
+        for m in range(B):
+            if a is not None and not a[m]:
+                ks[m] = 0
+            elif ks[m] < 0:
+                raise ValueError("member %d: k = %d is negative" % (m, ks[m]))
+        return ks
+
+    def evolve_states(self, steps: int, k=None, active=None) -> None:
+        """Context.evolve_states(k[m], steps) for every listed member (active[m] != 0; None: all) in ONE launch per step, whatever the
+        members and shapes (plus one batched copy where `steps` is odd: store_counts()).  k: an int for every listed member, one
+        entry per member, or None for each member's state count.  phi, the other states and the members not listed keep every bit."""
+        a = self._mask(active)
+        ks = self._store_ks(k, a)
+        self._check(self._L.wafer_batch_evolve_states(self._h, self._u8(a), (C.c_uint32 * len(ks))(*ks), int(steps)))
+
+    def seed_states(self, k: int, seed: int, active=None) -> None:
+        """k fresh stored states on every listed member: the Gaussian initial condition with seed + j, pushed, for j = 0 .. k-1 (every
+        listed member gets the same seeds).  OVERWRITES phi of the listed members; the stores are not cleared first."""
+        a = self._mask(active)
+        B = len(self.members)
+        for j in range(int(k)):
+            self.set_initial_conditions(["Gaussian"] * B, [int(seed) + j] * B, active=a)
+            self.push_state(active=a)
+
+    def store_dispatch(self) -> dict:
+        """what evolve_states launches: kernel, states_per_workgroup, shapes"""
+        buf = C.create_string_buffer(512)
+        self._check(self._L.wafer_batch_diag_store_step(self._h, buf, len(buf)))
+        d = dict(kv.split("=", 1) for kv in buf.value.decode().split())
+        for key in ("states_per_workgroup", "shapes"):
+            d[key] = int(d[key])
+        return d
+
+    def store_counts(self) -> int:
+        """launches of evolve_states since creation: `steps` per call, plus one where `steps` is odd"""
+        n = C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_store_counts(self._h, C.byref(n)))
+        return n.value
+
+    def solve_block(self, k, tolerance: float, steps_per_block: int, max_blocks: int, active=None) -> list:
+        """Context.solve_block for every listed member at once (block_solve_loop): per block one evolve_states, one ritz and one
+        residuals call over the members still going; a member whose Ritz energies all moved by less than `tolerance` leaves the
+        active set, as in Batch.solve.  -> per member the dict of Context.solve_block, None for members not listed (or with k 0)."""
+        a = self._mask(active)
+        ks = self._store_ks(k, a)
+        B = len(self.members)
+
+        def mask(going):
+            m = np.zeros(B, dtype=np.uint8)
+            m[going] = 1
+            return m
+
+        def step(going, n):
+            self.evolve_states(n, ks, active=mask(going))
+
+        def ritz(going):
+            r = self.ritz(ks, active=mask(going))
+            return {m: (r[m]["status"], r[m]["evals"]) for m in going}
+
+        def residuals(going, theta):
+            r = self.residuals(ks, theta=[theta.get(m) for m in range(B)], active=mask(going))
+            return {m: r[m]["rho"] for m in going}
+
+        return block_solve_loop(step, ritz, residuals, ks, tolerance, steps_per_block, max_blocks)
 
     # -- residuals of the stores and of phi (include/wafer_hip.h) ----------------------------------------
     def residuals(self, k=None, theta=None, active=None, source: str = "states") -> list:
