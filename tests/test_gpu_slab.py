@@ -395,6 +395,47 @@ def test_three_step_kernel_on_slabs_bit_exact(wa, world, shape, steps, cycle, ov
         assert all(n <= 3 + 2 + 3 for n in fabric.halo_calls), fabric.halo_calls
 
 
+@pytest.mark.parametrize("overlap", [0, 1, 2])
+def test_three_step_kernel_on_slabs_without_the_division_plan_bit_exact(wa, overlap, monkeypatch):
+    """the case above on its smallest shape with WAFER_FLAG_UNPLANNED_DIV on the base Params: every slab runs the VIR = false
+    instantiations (overlap 2: the single-launch pass, MODE = 1) and the assembled slabs hold one context's bits"""
+    monkeypatch.setenv("WAFER_FUSE3_MIN_NY", "1")
+    world, shape, steps = F3_SLAB_CASES[0]
+    kw = dict(dn=0.2, dt=0.004, mass=1.0, central_difference=1, unplanned_div=True)
+    base = wa.Params(*shape, halo_depth=3, **kw)
+    with wa.Context(wa.Params(*shape, **kw)) as ctx:
+        ctx.set_potential("Coulomb")
+        ctx.set_initial_condition("Boolean")
+        ctx.evolve(0, steps)
+        assert ctx.stencil_kernel_instance().startswith("wafer_k_step3_fused<double, double, false, 0,"), ctx.stencil_kernel_instance()
+        ctx.evolve(0, 5)
+        ctx.evolve(0, 9)
+        want = ctx.download_phi()
+
+    def body(ctx, rank):
+        assert ctx.stencil_kernel_name() == "wafer_k_step3_fused" and ctx.steps_per_launch() == 3
+        assert ctx.div_plan().checked == 0
+        ctx.set_overlap(overlap)
+        ctx.set_potential("Coulomb")
+        ctx.set_initial_condition("Boolean")
+        ctx.evolve(0, steps)
+        instance = ctx.stencil_kernel_instance()      # (the launch and this call are on the slab's own thread)
+        ctx.evolve(0, 5)
+        ctx.evolve(0, 9)
+        return ctx.download_phi(), instance
+
+    res, fabric = run_slabs(wa, base, world, body, connect=False)
+    for _, instance in res:
+        print(f"overlap {overlap}: {instance}")
+        assert instance.startswith("wafer_k_step3_fused<double, double, false, "), instance
+    got = assemble(base, world, [phi for phi, _ in res])
+    if not np.array_equal(got, want):
+        from wafer_amd.slab import partition
+        planes = sorted(set(np.argwhere(got != want)[:, 2].tolist()))
+        raise AssertionError(f"{int(np.sum(got != want))} cells differ on padded planes {planes}; slabs (z_begin, z_count): "
+                             f"{[partition(shape[2], world, r) for r in range(world)]}; halo calls {fabric.halo_calls}")
+
+
 @pytest.mark.parametrize("world,shape,steps", [(2, (40, 24, 10), 12), (3, (140, 40, 13), 9), (2, (300, 70, 96), 15), (4, (130, 33, 17), 6),
                                                (2, (1100, 300, 80), 9)])   # the last: more than 64 tiles, i.e. short pieces in the schedule
 def test_single_launch_pass_thin_and_uneven_slabs_bit_exact(wa, world, shape, steps, monkeypatch):
