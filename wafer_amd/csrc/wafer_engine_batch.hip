@@ -52,20 +52,52 @@
 #include "wafer_residual_batch.hip.h"
 #include "wafer_store_step_batch.hip.h"
 #include "wafer_ritz.h"
+#include "wafer_buffers.h"
+
+// the engine's two memory policies and its copy policy (wafer_buffers.h), the holders on them, and a holder's status through HIP_TRY
+struct DeviceMem {
+    static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static int alloc(void **p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+struct StreamCopy {
+    using stream = hipStream_t;
+    static int copy(void *dst, const void *src, size_t n, bool up, stream s) { return (int)hipMemcpyAsync(dst, src, n, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, s); }
+};
+template <typename T> using DevArray = Array<T, DeviceMem>;
+template <typename T> using DevGrow = GrowArray<T, DeviceMem>;
+template <typename T> using Mirror = HostDev<T, DeviceMem, PinnedMem, StreamCopy>;
+#define BUF_TRY(expr) HIP_TRY((hipError_t)(expr))
+// by dtype: its name in the diag_* strings, and the kernels' <.., T, C>
+constexpr const char *DTYPE_NAMES[] = {"f64", "f32", "f32fast"};
+constexpr const char *KERNEL_TYPES[] = {"double,double", "float,double", "float,float"};
 
 struct wafer_batch {
+    // The stream, declared first: it goes last, behind every buffer.
+    struct Stream {
+        hipStream_t h = nullptr;
+        Stream() = default;
+        Stream(const Stream &) = delete;
+        ~Stream()
+        {
+            if (h) (void)hipStreamDestroy(h);
+        }
+        operator hipStream_t() const { return h; }
+    } s;
     uint32_t n = 0;
     std::vector<wafer_params> P;
     int device = 0, num_cus = 256;
     WaferTuning tune;
-    hipStream_t s = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     // the layout (wafer_batch_layout): the distinct geometries in order of first appearance.  mixed: more than one
     std::vector<WaferGeom> geoms;
     std::vector<int> shape_of;                // member m's entry in geoms
     std::vector<size_t> off;                  // member m's element offset in each array allocation
     size_t cells = 0;                         // elements of each array allocation: every member's total, end to end
-    WaferGeom *geoms_dev = nullptr;
+    DevArray<WaferGeom> geoms_dev;
     bool mixed = false;
     bool mixed_states = false;                // several shapes WITH state stores (wafer_batch_create_mixed_states)
     WaferBatchGsPartition gsp;                // every member's Gram-Schmidt partition and the places of its partials
@@ -76,17 +108,16 @@ struct wafer_batch {
     int dtype = WAFER_F64;                    // every member's (check_member)
     bool f32 = false;                         // float storage (f32 and f32fast)
     size_t esz = 8;                           // bytes per element of every array and store slot
-    void *alloc[4] = {nullptr, nullptr, nullptr, nullptr};   // phi[0], phi[1], V, pot_sub
+    DevArray<char> alloc[4];                  // phi[0], phi[1], V, pot_sub: cells * esz bytes each
     std::vector<wafer_ctx *> views;
-    double *view_scal = nullptr, *view_scal_host = nullptr;  // SCAL_SLOTS per view
+    Mirror<double> view_scal;                 // SCAL_SLOTS per view
     // device tables
     std::vector<WaferBatchMember> mem;
-    WaferBatchMember *mem_dev = nullptr;
+    DevArray<WaferBatchMember> mem_dev;
     // a workgroup table on the device, with the active set and the steps per pass it was built for
     struct BlockTable {
         std::vector<WaferBatchBlock> host;
-        WaferBatchBlock *dev = nullptr;
-        size_t cap = 0;
+        DevGrow<WaferBatchBlock> dev;
         std::vector<uint8_t> key;
         int K = 0;
     };
@@ -94,55 +125,68 @@ struct wafer_batch {
     BlockTable blks;                          // the store step's (wafer_k_batch_store_step): the one-step table over the listed members with k > 0
     int step_variant = -1;                    // wafer_batch_set_step_variant
     uint64_t n_fused_passes = 0, n_single_steps = 0;   // launches since creation (wafer_batch_diag_passes)
-    int *act_dev = nullptr, *act_host = nullptr;
-    int *sym_dev = nullptr, *sym_host = nullptr;      // [member]: the constraints of the last wafer_batch_symmetrise
+    Mirror<int> act;
+    Mirror<int> sym;                          // [member]: the constraints of the last wafer_batch_symmetrise
     // observables: every member on the single context's partition of its shape (mem[].obs_*)
     int swz = 0;
-    double *partials = nullptr;               // member m's [4][obs_nb] at mem[m].obs_off
-    double *sums = nullptr, *sums_host = nullptr;   // [member][4]
-    double *n2 = nullptr, *n2_host = nullptr;        // [member]
+    DevArray<double> partials;                // member m's [4][obs_nb] at mem[m].obs_off
+    Mirror<double> sums;                      // [member][4]
+    Mirror<double> n2;                        // [member]
     uint64_t last_steps = 0;
     bool timing_valid = false;
     // w_store: slot l of every member in one allocation laid out as the arrays are, made by the first push or load that needs it
-    std::vector<void *> slots;
+    std::vector<DevArray<char>> slots;
     std::vector<uint32_t> nst;                // states member m holds
     // excited states: norm2 at gs_scal[m * gs_stride], the overlap with state l at [m * gs_stride + 1 + l]; made at first use
     int gs_stride = 0;
-    double *gs_partials = nullptr;            // member m's rows at gsp.row_off(m, rows); wafer_batch_norm2's at mem[m].n2_off (partials_doubles)
-    double *gs_scal = nullptr, *gs_host = nullptr;
+    DevGrow<double> gs_partials;              // member m's rows at gsp.row_off(m, rows); wafer_batch_norm2's at mem[m].n2_off (partials_doubles)
+    Mirror<double> gs_scal;
     // the one-pass form (wafer_batch_set_gs_variant); everything below is made by its first use (ensure_onepass)
     int gs_variant = -1;
     uint64_t n_onepass = 0, n_sequential = 0;   // excited steps and orthogonalise calls in each form (wafer_batch_diag_gs_steps)
     bool onepass_ready = false;               // gs_partials holds WAFER_GS_ONE_ROWS rows per member, the Gram storage exists
-    double *gram = nullptr;                   // [member][WAFER_MAX_LOW^2]: G_ji = <state j | state i>, i < j
-    double *gram_partials = nullptr;          // member m's [WAFER_GRAM_PAIRS][gsp.nb[m]] at gsp.row_off(m, WAFER_GRAM_PAIRS)
-    int *gram_list_dev = nullptr, *gram_list_host = nullptr;   // the members to recompute, then their state counts: 2 n ints
+    DevArray<double> gram;                    // [member][WAFER_MAX_LOW^2]: G_ji = <state j | state i>, i < j
+    DevArray<double> gram_partials;           // member m's [WAFER_GRAM_PAIRS][gsp.nb[m]] at gsp.row_off(m, WAFER_GRAM_PAIRS)
+    Mirror<int> gram_list;                    // the members to recompute, then their state counts: 2 n ints
     std::vector<uint8_t> gram_stale;          // member m's store changed since its Gram matrix was formed
     // wafer_batch_resample: a host source as uploaded ([sx][sy][sz]) and, behind it, transposed to x-fastest; grown on demand
-    double *rs_scratch = nullptr;
-    size_t rs_cap = 0;                        // doubles
+    DevGrow<double> rs_scratch;
     hipEvent_t rs_start = nullptr, rs_stop = nullptr;   // around the last call's upload, transpose and launch (wafer_batch_last_resample_ms)
     bool rs_timing_valid = false;
     // batched set-up (wafer_setup_batch.hip.h): one record per listed member, and the range check's three words per listed member --
     // on the device, their start values (~0, 0, 0) and the read-back, pinned; all n entries long, made at creation
-    WaferBatchSetupRec *setup_dev = nullptr, *setup_host = nullptr;
-    unsigned long long *vchk_dev = nullptr, *vchk_init = nullptr, *vchk_host = nullptr;
+    Mirror<WaferBatchSetupRec> setup;
+    Mirror<unsigned long long> vchk;
+    Array<unsigned long long, PinnedMem> vchk_init;
     uint64_t n_setup_launches = 0, n_setup_readbacks = 0;   // of the batched set-up paths since creation (wafer_batch_diag_setup_counts)
     // Rayleigh-Ritz on the stores (wafer_ritz_batch.hip.h); everything below is made by the first call (ensure_ritz)
-    WaferBatchRitzRec *ritz_rec_dev = nullptr, *ritz_rec_host = nullptr;   // the per-call table, n entries
-    double *ritz_partials = nullptr;          // the listed members' 2 k^2 rows of obs_nb partials end to end; grown on demand
-    size_t ritz_cap = 0;                      // doubles
-    double *ritz_sums = nullptr, *ritz_sums_host = nullptr;   // [member][2][WAFER_RITZ_MAX^2]
-    double *ritz_coef = nullptr, *ritz_coef_host = nullptr;   // [member][WAFER_RITZ_MAX^2]
+    Mirror<WaferBatchRitzRec> ritz_rec;       // the per-call table, n entries
+    DevGrow<double> ritz_partials;            // the listed members' 2 k^2 rows of obs_nb partials end to end; grown on demand
+    Mirror<double> ritz_sums;                 // [member][2][WAFER_RITZ_MAX^2]
+    Mirror<double> ritz_coef;                 // [member][WAFER_RITZ_MAX^2]
     uint64_t n_ritz_launches = 0, n_ritz_readbacks = 0;       // of the three calls since creation (wafer_batch_diag_ritz_counts)
     // residuals (wafer_residual_batch.hip.h); made by the first call (ensure_residual).  The partials live in ritz_partials.
-    WaferBatchResidualRec *resid_rec_dev = nullptr, *resid_rec_host = nullptr;   // the per-call table, n entries
-    double *resid_sums = nullptr, *resid_sums_host = nullptr; // [member][3 WAFER_RITZ_MAX]: r2, wh, s of column j at j * 3
+    Mirror<WaferBatchResidualRec> resid_rec;  // the per-call table, n entries
+    Mirror<double> resid_sums;                // [member][3 WAFER_RITZ_MAX]: r2, wh, s of column j at j * 3
     uint64_t n_resid_launches = 0, n_resid_readbacks = 0;     // of wafer_batch_residuals since creation (wafer_batch_diag_residual_counts)
     // stepping the stores (wafer_store_step_batch.hip.h): shadow l is laid out as slot l is, zeroed, made by the first call that needs it
-    std::vector<void *> shadows;
-    int *store_k_dev = nullptr, *store_k_host = nullptr;      // [member]: the call's k (0: not listed)
+    std::vector<DevArray<char>> shadows;
+    Mirror<int> store_k;                      // [member]: the call's k (0: not listed)
     uint64_t n_store_launches = 0;                            // of wafer_batch_evolve_states since creation (wafer_batch_diag_store_counts)
+    // Lets a batch go: the stream drains, the views go -- they borrow every array and the stream, except a and b (ensure_ab) -- then
+    // the events; behind this body every holder frees its block, and the stream goes last.
+    ~wafer_batch()
+    {
+        (void)hipSetDevice(device);
+        if (s) (void)hipStreamSynchronize(s);
+        for (wafer_ctx *v : views) {
+            for (void *p : {v->a, v->b})
+                if (p) (void)hipFree(alloc_base(v, p));
+            delete v;
+        }
+        for (hipEvent_t e : {ev_start, ev_stop, rs_start, rs_stop})
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -182,36 +226,6 @@ int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0, bool
             return fail(WAFER_ERR_INVALID, "member %u: halo_depth = %u differs from member 0's %u", i, m->halo_depth, m0->halo_depth);
     }
     return WAFER_OK;
-}
-
-void destroy(wafer_batch *b)
-{
-    (void)hipSetDevice(b->device);
-    if (b->s) (void)hipStreamSynchronize(b->s);
-    for (wafer_ctx *v : b->views) {   // views borrow every array and the stream, except a and b (ensure_ab)
-        for (void *p : {v->a, v->b})
-            if (p) (void)hipFree(alloc_base(v, p));
-        delete v;
-    }
-    for (void *p : b->alloc)
-        if (p) (void)hipFree(p);
-    for (void *p : b->slots)
-        if (p) (void)hipFree(p);
-    for (void *p : b->shadows)
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal, (void *)b->mem_dev, (void *)b->geoms_dev, (void *)b->blk.dev, (void *)b->blkk.dev, (void *)b->blks.dev, (void *)b->store_k_dev, (void *)b->act_dev, (void *)b->sym_dev, (void *)b->partials, (void *)b->sums,
-                    (void *)b->n2, (void *)b->gs_partials, (void *)b->gs_scal, (void *)b->gram, (void *)b->gram_partials,
-                    (void *)b->gram_list_dev, (void *)b->rs_scratch, (void *)b->setup_dev, (void *)b->vchk_dev, (void *)b->ritz_rec_dev,
-                    (void *)b->ritz_partials, (void *)b->ritz_sums, (void *)b->ritz_coef, (void *)b->resid_rec_dev, (void *)b->resid_sums})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->view_scal_host, (void *)b->act_host, (void *)b->sym_host, (void *)b->sums_host, (void *)b->n2_host, (void *)b->gs_host, (void *)b->gram_list_host, (void *)b->setup_host,
-                    (void *)b->vchk_init, (void *)b->vchk_host, (void *)b->ritz_rec_host, (void *)b->ritz_sums_host, (void *)b->ritz_coef_host,
-                    (void *)b->resid_rec_host, (void *)b->resid_sums_host, (void *)b->store_k_host})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {b->ev_start, b->ev_stop, b->rs_start, b->rs_stop})
-        if (e) (void)hipEventDestroy(e);
-    if (b->s) (void)hipStreamDestroy(b->s);
-    delete b;
 }
 
 int check_member_index(const wafer_batch *b, uint32_t m)
@@ -260,19 +274,19 @@ int sync_members(wafer_batch *b)
     }
     if (!changed) return WAFER_OK;
     HIP_TRY(hipStreamSynchronize(b->s));   // no launch in flight reads the table
-    HIP_TRY(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * b->n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->mem_dev, b->mem.data(), b->mem_dev.bytes(), hipMemcpyHostToDevice));
     return WAFER_OK;
 }
 
-// the active members' slots into act_dev; returns their number
+// the active members' slots into act, host and device; returns their number
 int upload_active(wafer_batch *b, const uint8_t *active, int *nact)
 {
-    HIP_TRY(hipStreamSynchronize(b->s));   // act_host is read by a copy of an earlier call
+    HIP_TRY(hipStreamSynchronize(b->s));   // act's host side is read by a copy of an earlier call
     int k = 0;
     for (uint32_t m = 0; m < b->n; ++m)
-        if (!active || active[m]) b->act_host[k++] = (int)m;
+        if (!active || active[m]) b->act[k++] = (int)m;
     *nact = k;
-    if (k) HIP_TRY(hipMemcpyAsync(b->act_dev, b->act_host, sizeof(int) * k, hipMemcpyHostToDevice, b->s));
+    if (k) BUF_TRY(b->act.upload(k, b->s));
     return WAFER_OK;
 }
 
@@ -286,12 +300,7 @@ int build_blocks(wafer_batch *b, wafer_batch::BlockTable &t, const uint8_t *acti
     t.host = K > 1 ? wafer_batch_fused_table(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, K, WAFER_BATCHK_TX, WAFER_BATCHK_TY)
                    : wafer_batch_step_table(b->geoms.data(), b->shape_of.data(), key.data(), b->n, b->num_cus, WAFER_BATCH_TX, WAFER_BATCH_TY);
     HIP_TRY(hipStreamSynchronize(b->s));
-    if (t.host.size() > t.cap || !t.dev) {
-        if (t.dev) HIP_TRY(hipFree(t.dev));
-        t.dev = nullptr;
-        t.cap = std::max<size_t>(t.host.size(), 1);
-        HIP_TRY(hipMalloc((void **)&t.dev, sizeof(WaferBatchBlock) * t.cap));
-    }
+    BUF_TRY(t.dev.reserve(std::max<size_t>(t.host.size(), 1)));
     if (!t.host.empty()) HIP_TRY(hipMemcpy(t.dev, t.host.data(), sizeof(WaferBatchBlock) * t.host.size(), hipMemcpyHostToDevice));
     t.key = key;
     t.K = K;
@@ -321,21 +330,29 @@ hipError_t with_geom(const wafer_batch *b, F &&launch)
     return b->mixed ? launch(WaferBatchGeomTable{b->geoms_dev}) : launch(b->g());
 }
 
+// a launch's status as the call's: `what` names the kernel in the message
+int launched(const char *what, hipError_t e)
+{
+    return e == hipSuccess ? WAFER_OK : fail(WAFER_ERR_HIP, "batched %s launch failed: %s", what, hipGetErrorString(e));
+}
+template <typename F>
+int launch(const wafer_batch *b, const char *what, F &&f) { return launched(what, with_geom(b, f)); }
+
 // The grid of the kernels that run one 64 x 4 tile of one plane per workgroup (normalise, symmetrise, resample): the largest tile
-// and plane counts among the members in act_host -- of their work boxes, or (padded) of their padded boxes, frame and ghost planes
+// and plane counts among the members in act -- of their work boxes, or (padded) of their padded boxes, frame and ghost planes
 // included.
 void max_tiles_planes(const wafer_batch *b, int nact, bool padded, int *max_tiles, int *max_planes)
 {
     *max_tiles = *max_planes = 0;
     for (int k = 0; k < nact; ++k) {
-        const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
+        const WaferGeom &g = b->geom((uint32_t)b->act[k]);
         const int x = padded ? g.px : g.nx, y = padded ? g.py : g.ny;
         *max_tiles = std::max(*max_tiles, ((x + WAFER_BATCH_TX - 1) / WAFER_BATCH_TX) * ((y + WAFER_BATCH_TY - 1) / WAFER_BATCH_TY));
         *max_planes = std::max(*max_planes, padded ? g.lz : g.nzl);
     }
 }
 
-// the four raw sums of the active members into sums_host[m * 4 ..]
+// the four raw sums of the active members into sums[m * 4 ..] on the host
 int observables(wafer_batch *b, const uint8_t *active)
 {
     HIP_TRY(hipSetDevice(b->device));
@@ -346,19 +363,18 @@ int observables(wafer_batch *b, const uint8_t *active)
     if (!nact) return WAFER_OK;
     RoctxRange range_("wafer_batch_observables");
     int max_nb = 0;   // the grid is as wide as the largest launched member's partition
-    for (int k = 0; k < nact; ++k) max_nb = std::max(max_nb, b->mem[b->act_host[k]].obs_nb);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_observables(b->f32, b->g().R, gs, b->mem_dev, b->act_dev, nact, max_nb, b->swz, b->partials, b->sums, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched observables launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(b->sums_host, b->sums, sizeof(double) * 4 * b->n, hipMemcpyDeviceToHost, b->s));
+    for (int k = 0; k < nact; ++k) max_nb = std::max(max_nb, b->mem[b->act[k]].obs_nb);
+    TRY(launch(b, "observables", [&](const auto &gs) {
+        return wafer_entry_batch_observables(b->f32, b->g().R, gs, b->mem_dev, b->act.dev, nact, max_nb, b->swz, b->partials, b->sums.dev, b->s);
+    }));
+    BUF_TRY(b->sums.download(b->sums.host.size(), b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
     return WAFER_OK;
 }
 
 void obs_of(const wafer_batch *b, uint32_t m, wafer_observables_t *o)
 {
-    const double *r = b->sums_host + (size_t)m * 4;
+    const double *r = &b->sums[(size_t)m * 4];
     o->energy = r[0];
     o->norm2 = r[1];
     o->v_infinity = (b->views[m]->potsub_kind == WAFER_POTSUB_NONE) ? 0.0 : r[2];   // grid.rs:425
@@ -376,11 +392,9 @@ int normalise(wafer_batch *b, const uint8_t *active, const double *norm2_dev, in
     if (!nact) return WAFER_OK;
     int max_tiles, max_planes;
     max_tiles_planes(b, nact, false, &max_tiles, &max_planes);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_normalise(b->f32, gs, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, norm2_dev, stride, b->s);
+    return launch(b, "normalise", [&](const auto &gs) {
+        return wafer_entry_batch_normalise(b->f32, gs, b->mem_dev, b->act.dev, nact, max_tiles, max_planes, norm2_dev, stride, b->s);
     });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched normalise launch failed: %s", hipGetErrorString(e));
-    return WAFER_OK;
 }
 
 // config::symmetrise_wavefunction (config.rs:691-728) for every active member with a constraint, each with its own: the checks and
@@ -405,16 +419,15 @@ int symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
     HIP_TRY(hipSetDevice(b->device));
     TRY(sync_members(b));
     int nact = 0;
-    TRY(upload_active(b, hit.data(), &nact));   // (synchronises the stream: sym_host is not read by an earlier call's copy either)
-    for (uint32_t m = 0; m < b->n; ++m) b->sym_host[m] = hit[m] ? constraints[m] : 0;
-    HIP_TRY(hipMemcpyAsync(b->sym_dev, b->sym_host, sizeof(int) * b->n, hipMemcpyHostToDevice, b->s));
+    TRY(upload_active(b, hit.data(), &nact));   // (synchronises the stream: sym's host side is not read by an earlier call's copy either)
+    for (uint32_t m = 0; m < b->n; ++m) b->sym[m] = hit[m] ? constraints[m] : 0;
+    BUF_TRY(b->sym.upload(b->n, b->s));
     int max_tiles, max_planes;   // of the padded boxes: the kernel writes the frame's zeros too
     max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
     RoctxRange range_("wafer_batch_symmetrise");
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_symmetrise(b->f32, gs, b->mem_dev, b->act_dev, nact, b->sym_dev, max_tiles, max_planes, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched symmetrise launch failed: %s", hipGetErrorString(e));
+    TRY(launch(b, "symmetrise", [&](const auto &gs) {
+        return wafer_entry_batch_symmetrise(b->f32, gs, b->mem_dev, b->act.dev, nact, b->sym.dev, max_tiles, max_planes, b->s);
+    }));
     for (uint32_t m = 0; m < b->n; ++m) {
         if (!hit[m]) continue;
         b->views[m]->cur ^= 1;
@@ -427,18 +440,18 @@ int symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
 // member m's state l as a logical pointer (plane 0, row 0), like the views' arrays
 void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
 {
-    return static_cast<char *>(b->slots[l]) + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
+    return b->slots[l] + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
 }
 
 // entries [0, n) of `v` exist (zeros: frames, pads and guard zones of every member).  v: the store's slots, or their shadows
 // (wafer_batch_evolve_states), laid out alike
-int ensure_slots(wafer_batch *b, std::vector<void *> &v, uint32_t n)
+int ensure_slots(wafer_batch *b, std::vector<DevArray<char>> &v, uint32_t n)
 {
     while (v.size() < n) {
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, b->cells * b->esz));
-        v.push_back(p);
-        HIP_TRY(hipMemsetAsync(p, 0, b->cells * b->esz, b->s));
+        DevArray<char> p;
+        BUF_TRY(p.make(b->cells * b->esz));
+        v.push_back(std::move(p));
+        HIP_TRY(hipMemsetAsync(v.back(), 0, v.back().bytes(), b->s));
     }
     return WAFER_OK;
 }
@@ -486,13 +499,10 @@ size_t partials_doubles(const wafer_batch *b, int rows) { return std::max((size_
 
 int ensure_gs(wafer_batch *b)
 {
-    if (b->gs_scal) return WAFER_OK;
-    const size_t nsc = (size_t)b->gs_stride * b->n;
-    const size_t npart = partials_doubles(b, 1);
-    HIP_TRY(hipMalloc((void **)&b->gs_partials, sizeof(double) * npart));
-    HIP_TRY(hipHostMalloc((void **)&b->gs_host, sizeof(double) * nsc, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&b->gs_scal, sizeof(double) * nsc));
-    HIP_TRY(hipMemsetAsync(b->gs_scal, 0, sizeof(double) * nsc, b->s));
+    if (b->gs_scal.dev) return WAFER_OK;   // (made last: a call that failed before it starts over, and leaks nothing)
+    BUF_TRY(b->gs_partials.reserve(partials_doubles(b, 1)));
+    BUF_TRY(b->gs_scal.make((size_t)b->gs_stride * b->n));
+    HIP_TRY(hipMemsetAsync(b->gs_scal.dev, 0, b->gs_scal.dev.bytes(), b->s));
     return WAFER_OK;
 }
 
@@ -504,16 +514,14 @@ int gs_max_nb(const wafer_batch *b, const int *list, int n)
     return nb;
 }
 
-// one elementwise launch (+ its reduce into slot out_slot) over the members in act_dev; lower, dotwith: store slots, -1 none
+// one elementwise launch (+ its reduce into slot out_slot) over the members in act; lower, dotwith: store slots, -1 none
 int gs_launch(wafer_batch *b, int mode, int nact, int flip, int coef_slot, int lower, int dotwith, int out_slot)
 {
-    const int max_nb = gs_max_nb(b, b->act_host, nact);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        const WaferBatchGsArgs a{flip, b->gs_stride, coef_slot, lower >= 0 ? b->slots[lower] : nullptr, dotwith >= 0 ? b->slots[dotwith] : nullptr};
-        return wafer_entry_batch_gs(b->f32, mode, gs, a, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, out_slot, b->gs_partials, b->s);
+    const int max_nb = gs_max_nb(b, b->act.host, nact);
+    return launch(b, "Gram-Schmidt", [&](const auto &gs) {
+        const WaferBatchGsArgs a{flip, b->gs_stride, coef_slot, lower >= 0 ? b->slots[lower].get() : nullptr, dotwith >= 0 ? b->slots[dotwith].get() : nullptr};
+        return wafer_entry_batch_gs(b->f32, mode, gs, a, b->mem_dev, b->act.dev, nact, max_nb, b->gs_scal.dev, out_slot, b->gs_partials, b->s);
     });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram-Schmidt launch failed: %s", hipGetErrorString(e));
-    return WAFER_OK;
 }
 
 // ---- the one-pass form ---------------------------------------------------------------------------------------------------------
@@ -525,22 +533,13 @@ int ensure_onepass(wafer_batch *b)
 {
     if (b->onepass_ready) return WAFER_OK;
     TRY(ensure_gs(b));
-    double *wider = nullptr;   // (the new buffer first: a failed allocation leaves the sequential form's partials in place)
-    HIP_TRY(hipMalloc((void **)&wider, sizeof(double) * partials_doubles(b, WAFER_GS_ONE_ROWS)));
-    const hipError_t e = hipStreamSynchronize(b->s);   // no launch in flight writes the partials that go back
-    if (e != hipSuccess) {
-        (void)hipFree(wider);
-        return fail(WAFER_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(b->gs_partials);
-    b->gs_partials = wider;
-    if (!b->gram) {
-        HIP_TRY(hipMalloc((void **)&b->gram, sizeof(double) * WAFER_MAX_LOW * WAFER_MAX_LOW * b->n));
-        HIP_TRY(hipMemsetAsync(b->gram, 0, sizeof(double) * WAFER_MAX_LOW * WAFER_MAX_LOW * b->n, b->s));
-    }
-    if (!b->gram_partials) HIP_TRY(hipMalloc((void **)&b->gram_partials, sizeof(double) * (size_t)b->gsp.doubles(WAFER_GRAM_PAIRS)));
-    if (!b->gram_list_dev) HIP_TRY(hipMalloc((void **)&b->gram_list_dev, sizeof(int) * 2 * b->n));
-    if (!b->gram_list_host) HIP_TRY(hipHostMalloc((void **)&b->gram_list_host, sizeof(int) * 2 * b->n, hipHostMallocDefault));
+    HIP_TRY(hipStreamSynchronize(b->s));   // no launch in flight writes the partials that go back
+    // (reserve makes the new buffer first: a failed allocation leaves the sequential form's partials in place)
+    BUF_TRY(b->gs_partials.reserve(partials_doubles(b, WAFER_GS_ONE_ROWS)));
+    BUF_TRY(b->gram.make((size_t)WAFER_MAX_LOW * WAFER_MAX_LOW * b->n));
+    HIP_TRY(hipMemsetAsync(b->gram, 0, b->gram.bytes(), b->s));
+    BUF_TRY(b->gram_partials.make((size_t)b->gsp.doubles(WAFER_GRAM_PAIRS)));
+    BUF_TRY(b->gram_list.make(2 * (size_t)b->n));
     b->gram_stale.assign(b->n, 1);
     b->onepass_ready = true;
     return WAFER_OK;
@@ -552,13 +551,13 @@ WaferBatchGsOneArgs onepass_args(const wafer_batch *b, int flip, uint32_t nslots
     WaferBatchGsOneArgs a;
     a.flip = flip;
     a.scal_stride = b->gs_stride;
-    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? b->slots[l] : nullptr;
+    for (uint32_t l = 0; l < WAFER_MAX_LOW; ++l) a.low[l] = l < nslots ? b->slots[l].get() : nullptr;
     return a;
 }
 
 // the Gram matrices of the active members whose stores changed since they were formed: one launch and its reduce, in stream
 // order behind the copies that changed the stores.  (Called once per call, before its first step, after upload_active's
-// synchronisation: gram_list_host is not read by an earlier call's copy any more.)
+// synchronisation: gram_list's host side is not read by an earlier call's copy any more.)
 int refresh_gram(wafer_batch *b, const uint8_t *active)
 {
     int nlist = 0, nl = 0;
@@ -567,34 +566,30 @@ int refresh_gram(wafer_batch *b, const uint8_t *active)
         b->gram_stale[m] = 0;
         const int cnt = (int)std::min<uint32_t>(b->nst[m], WAFER_MAX_LOW);
         if (cnt < 2) continue;   // no pair
-        b->gram_list_host[nlist++] = (int)m;
+        b->gram_list[nlist++] = (int)m;
         nl = std::max(nl, cnt);
     }
     if (!nlist) return WAFER_OK;
-    for (int k = 0; k < nlist; ++k) b->gram_list_host[nlist + k] = (int)std::min<uint32_t>(b->nst[b->gram_list_host[k]], WAFER_MAX_LOW);
-    HIP_TRY(hipMemcpyAsync(b->gram_list_dev, b->gram_list_host, sizeof(int) * 2 * nlist, hipMemcpyHostToDevice, b->s));
-    const int max_nb = gs_max_nb(b, b->gram_list_host, nlist);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_gram(b->f32, nl, gs, onepass_args(b, 0, (uint32_t)nl), b->mem_dev, b->gram_list_dev, b->gram_list_dev + nlist, nlist,
+    for (int k = 0; k < nlist; ++k) b->gram_list[nlist + k] = (int)std::min<uint32_t>(b->nst[b->gram_list[k]], WAFER_MAX_LOW);
+    BUF_TRY(b->gram_list.upload(2 * (size_t)nlist, b->s));
+    const int max_nb = gs_max_nb(b, b->gram_list.host, nlist);
+    return launch(b, "Gram matrix", [&](const auto &gs) {
+        return wafer_entry_batch_gram(b->f32, nl, gs, onepass_args(b, 0, (uint32_t)nl), b->mem_dev, b->gram_list.dev, b->gram_list.dev + nlist, nlist,
                                       max_nb, b->gram, b->gram_partials, b->s);
     });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Gram matrix launch failed: %s", hipGetErrorString(e));
-    return WAFER_OK;
 }
 
-// sums, reduce, apply on phi[cur ^ flip] of the members in act_dev: the step's tail (normalise_first) or orthogonalise alone
+// sums, reduce, apply on phi[cur ^ flip] of the members in act: the step's tail (normalise_first) or orthogonalise alone
 int gs_onepass(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_first)
 {
-    const int max_nb = gs_max_nb(b, b->act_host, nact);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, gs, onepass_args(b, flip, wnum), b->mem_dev, b->act_dev, nact, max_nb,
-                                            b->gs_scal, b->gram, b->gs_partials, b->s);
+    const int max_nb = gs_max_nb(b, b->act.host, nact);
+    return launch(b, "one-pass Gram-Schmidt", [&](const auto &gs) {
+        return wafer_entry_batch_gs_onepass(b->f32, (int)wnum, normalise_first, gs, onepass_args(b, flip, wnum), b->mem_dev, b->act.dev, nact, max_nb,
+                                            b->gs_scal.dev, b->gram, b->gs_partials, b->s);
     });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched one-pass Gram-Schmidt launch failed: %s", hipGetErrorString(e));
-    return WAFER_OK;
 }
 
-// grid.rs:679-680 (normalise: norm2 and the scaling first) and :477-492 on phi[cur ^ flip] of the members in act_dev
+// grid.rs:679-680 (normalise: norm2 and the scaling first) and :477-492 on phi[cur ^ flip] of the members in act
 int gs_chain(wafer_batch *b, int nact, int flip, uint32_t wnum, bool normalise_first)
 {
     if (normalise_first) {
@@ -639,11 +634,10 @@ int evolve_state(wafer_batch *b, const uint8_t *active, uint32_t wnum, uint64_t 
         while (left > 0) {   // no host synchronisation in here: every scalar stays on the device
             const int k = wafer_batch_next_pass(left, K, have2);
             const int flip = (int)(launches & 1);
-            const hipError_t e = with_geom(b, [&](const auto &gs) {
+            TRY(launch(b, "step", [&](const auto &gs) {
                 return k > 1 ? wafer_entry_batch_stepk(step_dtype, b->g().R, k, gs, b->mem_dev, b->blkk.dev, (int)b->blkk.host.size(), flip, b->s)
                              : wafer_entry_batch_step(step_dtype, b->g().R, gs, b->mem_dev, b->blk.dev, (int)b->blk.host.size(), flip, b->s);
-            });
-            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched step launch failed: %s", hipGetErrorString(e));
+            }));
             ++launches;
             ++(k > 1 ? b->n_fused_passes : b->n_single_steps);
             left -= (uint64_t)k;
@@ -737,7 +731,7 @@ int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t s
             }
         }
         // :130, the members' norm2 straight from the sums on the device (the same doubles the host holds)
-        TRY(normalise(b, norm.data(), b->sums + 1, 4));
+        TRY(normalise(b, norm.data(), b->sums.dev + 1, 4));
         if (wnum) TRY(orthogonalise(b, norm.data(), wnum));        // :133-135
         for (uint32_t m = 0; m < n; ++m) {
             if (!run[m]) continue;
@@ -785,54 +779,51 @@ int solve(wafer_batch *b, uint32_t wnum, bool push, double tolerance, uint64_t s
 }
 
 // ---- the range check of many members at once -----------------------------------------------------------------------------------
-// the safe answers for the members in act_host, whose V was written but could not be checked: no mirrored reads, the long forms
-void v_unknown(wafer_batch *b, int nact)
+// the safe answers for the members in act, whose V was written but could not be checked: no mirrored reads, the long forms.
+// Returns rc, the status of what failed.
+int v_unknown(wafer_batch *b, int nact, int rc)
 {
     for (int k = 0; k < nact; ++k) {
-        wafer_ctx *c = b->views[b->act_host[k]];
+        wafer_ctx *c = b->views[b->act[k]];
         c->v_ysym = c->v_in_range = false;
         for (int &a : c->x2_agreed) a = -1;
     }
     (void)sync_members(b);
+    return rc;
 }
 
-// check_v_range (wafer_engine.hip) for the members in act_host / act_dev, whose V has just been written and whose v_ysym the writer
+// check_v_range (wafer_engine.hip) for the members in act, whose V has just been written and whose v_ysym the writer
 // cleared before its first store: the words' start values in one copy, ONE launch (wafer_k_batch_v_check), one read-back and one
 // stream synchronisation, then per member the context's bookkeeping -- v_in_range by the same predicate, v_ysym, x2_agreed -- and the
 // device member table as the views stand now.  A HIP error leaves every one of them with both flags off (v_unknown).
 int check_v_listed(wafer_batch *b, int nact)
 {
-    const size_t bytes = sizeof(unsigned long long) * 3 * (size_t)nact;
     auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(b->vchk_dev, b->vchk_init, bytes, hipMemcpyHostToDevice, b->s));
+        BUF_TRY(StreamCopy::copy(b->vchk.dev, b->vchk_init, sizeof(unsigned long long) * 3 * (size_t)nact, true, b->s));
         int max_tiles = 0, max_planes = 0;
         for (int k = 0; k < nact; ++k) {
-            const WaferGeom &g = b->geom((uint32_t)b->act_host[k]);
+            const WaferGeom &g = b->geom((uint32_t)b->act[k]);
             max_tiles = std::max(max_tiles, wafer_v_check_tiles(g, (int)b->esz));
             max_planes = std::max(max_planes, g.lz);
         }
-        const hipError_t e = with_geom(b, [&](const auto &gs) {
-            return wafer_entry_batch_v_check(b->f32, gs, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, b->vchk_dev, b->s);
-        });
-        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched range check launch failed: %s", hipGetErrorString(e));
+        TRY(launch(b, "range check", [&](const auto &gs) {
+            return wafer_entry_batch_v_check(b->f32, gs, b->mem_dev, b->act.dev, nact, max_tiles, max_planes, b->vchk.dev, b->s);
+        }));
         ++b->n_setup_launches;
-        HIP_TRY(hipMemcpyAsync(b->vchk_host, b->vchk_dev, bytes, hipMemcpyDeviceToHost, b->s));
+        BUF_TRY(b->vchk.download(3 * (size_t)nact, b->s));
         HIP_TRY(hipStreamSynchronize(b->s));
         ++b->n_setup_readbacks;
         return WAFER_OK;
     };
     const int rc = run();
-    if (rc != WAFER_OK) {
-        v_unknown(b, nact);
-        return rc;
-    }
+    if (rc != WAFER_OK) return v_unknown(b, nact, rc);
     for (int k = 0; k < nact; ++k) {
-        wafer_ctx *c = b->views[b->act_host[k]];
+        wafer_ctx *c = b->views[b->act[k]];
         double lo, hi;
-        memcpy(&lo, &b->vchk_host[3 * k], 8);
-        memcpy(&hi, &b->vchk_host[3 * k + 1], 8);
+        memcpy(&lo, &b->vchk[3 * k], 8);
+        memcpy(&hi, &b->vchk[3 * k + 1], 8);
         c->v_in_range = (lo > 0x1p-400) && (hi < 0x1p400);   // a NaN anywhere makes hi a NaN: false
-        c->v_ysym = b->vchk_host[3 * k + 2] == 0;
+        c->v_ysym = b->vchk[3 * k + 2] == 0;
         for (int &a : c->x2_agreed) a = -1;
     }
     return sync_members(b);
@@ -842,13 +833,9 @@ int check_v_listed(wafer_batch *b, int nact)
 // the resample scratch holds at least `doubles` doubles: grown on demand, never per call, freed with the batch
 int ensure_scratch(wafer_batch *b, size_t doubles)
 {
-    if (doubles <= b->rs_cap) return WAFER_OK;
+    if (doubles <= b->rs_scratch.size()) return WAFER_OK;
     HIP_TRY(hipStreamSynchronize(b->s));   // no launch in flight reads the scratch that goes back
-    if (b->rs_scratch) HIP_TRY(hipFree(b->rs_scratch));
-    b->rs_scratch = nullptr;
-    b->rs_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->rs_scratch, sizeof(double) * doubles));
-    b->rs_cap = doubles;
+    BUF_TRY(b->rs_scratch.reserve(doubles));
     return WAFER_OK;
 }
 
@@ -948,14 +935,13 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
     max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
     void *dst0 = target == WAFER_RESAMPLE_PHI ? b->alloc[0] : target == WAFER_RESAMPLE_POTENTIAL ? b->alloc[2]
                : target == WAFER_RESAMPLE_POTSUB ? b->alloc[3] : b->slots[idx];
-    void *dst1 = target == WAFER_RESAMPLE_PHI ? b->alloc[1] : dst0;
+    void *dst1 = target == WAFER_RESAMPLE_PHI ? b->alloc[1].get() : dst0;
     {
         RoctxRange range_("wafer_batch_resample");
-        const hipError_t e = with_geom(b, [&](const auto &gs) {
-            return wafer_entry_batch_trilerp(b->f32, !host && b->f32, gs, b->mem_dev, b->act_dev, nact, max_tiles, max_planes, src, dst0, dst1,
+        TRY(launch(b, "resample", [&](const auto &gs) {
+            return wafer_entry_batch_trilerp(b->f32, !host && b->f32, gs, b->mem_dev, b->act.dev, nact, max_tiles, max_planes, src, dst0, dst1,
                                              target == WAFER_RESAMPLE_PHI, basis, b->s);
-        });
-        if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched resample launch failed: %s", hipGetErrorString(e));
+        }));
     }
     HIP_TRY(hipEventRecord(b->rs_stop, b->s));
     b->rs_timing_valid = true;
@@ -970,10 +956,7 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
             break;
         case WAFER_RESAMPLE_POTENTIAL: {
             const int rc = refresh_ab(c);
-            if (rc != WAFER_OK) {
-                v_unknown(b, nact);
-                return rc;
-            }
+            if (rc != WAFER_OK) return v_unknown(b, nact, rc);
             c->vgen_type = 0;
             c->potsub_kind = WAFER_POTSUB_NONE;   // potential.rs:357-358: FromFile has no pot_sub of its own
             c->potsub_scalar = 0.0;
@@ -996,15 +979,15 @@ int resample(wafer_batch *b, const uint8_t *active, int target, uint32_t idx, co
 }
 
 // ---- set-up of many members at once ------------------------------------------------------------------------------------------
-// one record per member in act_host (upload_active has synchronised the stream: setup_host is not read by an earlier call's copy)
+// one record per member in act (upload_active has synchronised the stream: setup's host side is not read by an earlier call's copy)
 int upload_setup(wafer_batch *b, int nact, const int *kinds, const uint64_t *seeds)
 {
     double k[4];
     pot_host_constants(k);
     for (int i = 0; i < nact; ++i) {
-        const int m = b->act_host[i];
+        const int m = b->act[i];
         const wafer_ctx *c = b->views[m];
-        WaferBatchSetupRec &r = b->setup_host[i];
+        WaferBatchSetupRec &r = b->setup[i];
         r.member = m;
         r.kind = kinds[m];
         r.seed = seeds ? seeds[m] : 0;
@@ -1013,7 +996,7 @@ int upload_setup(wafer_batch *b, int nact, const int *kinds, const uint64_t *see
         r.pa = c->a;
         r.pb = c->b;
     }
-    HIP_TRY(hipMemcpyAsync(b->setup_dev, b->setup_host, sizeof(WaferBatchSetupRec) * nact, hipMemcpyHostToDevice, b->s));
+    BUF_TRY(b->setup.upload(nact, b->s));
     return WAFER_OK;
 }
 
@@ -1037,26 +1020,22 @@ int set_potentials(wafer_batch *b, const uint8_t *active, const int *potentials)
     int nact = 0;
     TRY(upload_active(b, active, &nact));
     TRY(upload_setup(b, nact, potentials, nullptr));
-    for (int k = 0; k < nact; ++k) b->views[b->act_host[k]]->v_ysym = false;   // V is about to change: check_v_listed re-establishes it
+    for (int k = 0; k < nact; ++k) b->views[b->act[k]]->v_ysym = false;   // V is about to change: check_v_listed re-establishes it
     int max_tiles, max_planes;
     max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
     RoctxRange range_("wafer_batch_set_potentials");
-    hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_potential(b->f32, gs, b->mem_dev, b->setup_dev, nact, max_tiles, max_planes, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched potential launch failed: %s", hipGetErrorString(e));
+    TRY(launch(b, "potential", [&](const auto &gs) {
+        return wafer_entry_batch_potential(b->f32, gs, b->mem_dev, b->setup.dev, nact, max_tiles, max_planes, b->s);
+    }));
     ++b->n_setup_launches;
     if (fullcornell) {
-        e = with_geom(b, [&](const auto &gs) {
-            return wafer_entry_batch_potsub_fullcornell(b->f32, gs, b->mem_dev, b->setup_dev, nact, max_tiles, max_planes, b->s);
+        const int rc = launch(b, "pot_sub", [&](const auto &gs) {
+            return wafer_entry_batch_potsub_fullcornell(b->f32, gs, b->mem_dev, b->setup.dev, nact, max_tiles, max_planes, b->s);
         });
-        if (e != hipSuccess) {
-            v_unknown(b, nact);
-            return fail(WAFER_ERR_HIP, "batched pot_sub launch failed: %s", hipGetErrorString(e));
-        }
+        if (rc != WAFER_OK) return v_unknown(b, nact, rc);
         ++b->n_setup_launches;
     }
-    for (int k = 0; k < nact; ++k) builtin_potential_set(b->views[b->act_host[k]], potentials[b->act_host[k]]);
+    for (int k = 0; k < nact; ++k) builtin_potential_set(b->views[b->act[k]], potentials[b->act[k]]);
     return check_v_listed(b, nact);
 }
 
@@ -1079,13 +1058,12 @@ int set_initial_conditions(wafer_batch *b, const uint8_t *active, const int *ics
     int max_tiles, max_planes;
     max_tiles_planes(b, nact, true, &max_tiles, &max_planes);
     RoctxRange range_("wafer_batch_set_initial_conditions");
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_initial_condition(b->f32, gs, b->mem_dev, b->setup_dev, nact, max_tiles, max_planes, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched initial condition launch failed: %s", hipGetErrorString(e));
+    TRY(launch(b, "initial condition", [&](const auto &gs) {
+        return wafer_entry_batch_initial_condition(b->f32, gs, b->mem_dev, b->setup.dev, nact, max_tiles, max_planes, b->s);
+    }));
     ++b->n_setup_launches;
     for (int k = 0; k < nact; ++k) {
-        wafer_ctx *c = b->views[b->act_host[k]];
+        wafer_ctx *c = b->views[b->act[k]];
         c->have_phi = true;
         c->halo_valid = c->g.G;   // every ghost plane was generated from global indices
     }
@@ -1113,63 +1091,64 @@ int ritz_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, b
 
 int ensure_ritz(wafer_batch *b)
 {
-    if (b->ritz_coef_host) return WAFER_OK;   // (the last one made below)
-    if (!b->ritz_rec_dev) HIP_TRY(hipMalloc((void **)&b->ritz_rec_dev, sizeof(WaferBatchRitzRec) * b->n));
-    if (!b->ritz_rec_host) HIP_TRY(hipHostMalloc((void **)&b->ritz_rec_host, sizeof(WaferBatchRitzRec) * b->n, hipHostMallocDefault));
-    if (!b->ritz_sums) HIP_TRY(hipMalloc((void **)&b->ritz_sums, sizeof(double) * 2 * RITZ_KK * b->n));
-    if (!b->ritz_sums_host) HIP_TRY(hipHostMalloc((void **)&b->ritz_sums_host, sizeof(double) * 2 * RITZ_KK * b->n, hipHostMallocDefault));
-    if (!b->ritz_coef) HIP_TRY(hipMalloc((void **)&b->ritz_coef, sizeof(double) * RITZ_KK * b->n));
-    HIP_TRY(hipHostMalloc((void **)&b->ritz_coef_host, sizeof(double) * RITZ_KK * b->n, hipHostMallocDefault));
-    memset(b->ritz_coef_host, 0, sizeof(double) * RITZ_KK * b->n);
+    if (b->ritz_coef.dev) return WAFER_OK;   // (made last: a call that failed before it starts over)
+    BUF_TRY(b->ritz_rec.make(b->n));
+    BUF_TRY(b->ritz_sums.make(2 * RITZ_KK * b->n));
+    BUF_TRY(b->ritz_coef.make(RITZ_KK * b->n));
+    memset(b->ritz_coef.host, 0, b->ritz_coef.host.bytes());
     return WAFER_OK;
 }
 
-// ritz_partials holds at least `doubles`: grown on demand, as a context's ritz_buf (the stream is idle: the callers synchronised)
-int ensure_ritz_partials(wafer_batch *b, size_t doubles)
-{
-    if (b->ritz_cap >= doubles) return WAFER_OK;
-    if (b->ritz_partials) (void)hipFree(b->ritz_partials);
-    b->ritz_partials = nullptr;
-    b->ritz_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->ritz_partials, sizeof(double) * doubles));
-    b->ritz_cap = doubles;
-    return WAFER_OK;
-}
+// What a per-call table gives its call: the listed members' number, the widest partition and the largest k among them, the grid of a
+// kernel that walks their spans in 16-byte vectors, the length of their partials end to end, the first listed member and the last + 1.
+struct CallTable {
+    int nact = 0, max_nb = 0, max_k = 0, blocks = 1;
+    size_t doubles = 0, m0 = 0, m1 = 0;
+};
 
-// The per-call table of the listed members into ritz_rec_host and to the device: member, k, the prefix sums of 2 k^2 obs_nb, the
-// member's span in a slot allocation.  The stream is idle (the callers synchronised: ritz_rec_host is not read by an earlier copy).
-int upload_ritz_table(wafer_batch *b, const uint8_t *listed, const uint32_t *k, int *nact, int *max_nb, int *max_k, size_t *doubles)
+// The per-call table of the listed members into t's host side and to the device: member, k, the prefix sums of the member's rows of
+// obs_nb partials -- 2 k^2 and the member's span in a slot allocation (WaferBatchRitzRec), or 3 k and theta (WaferBatchResidualRec:
+// member m's at m * WAFER_RITZ_MAX; nullptr: zeros).  partials: ritz_partials holds them when this returns, grown on demand as a
+// context's ritz_buf.  The stream is idle (the callers synchronised: t's host side is not read by an earlier copy, and no launch
+// reads partials that go back).
+template <typename Rec>
+int upload_table(wafer_batch *b, Mirror<Rec> &t, const uint8_t *listed, const uint32_t *k, const double *theta, bool partials, CallTable *c)
 {
-    int n = 0;
-    size_t poff = 0;
-    *max_nb = *max_k = 0;
+    constexpr bool ritz = std::is_same<Rec, WaferBatchRitzRec>::value;
     for (uint32_t m = 0; m < b->n; ++m) {
         if (listed && !listed[m]) continue;
-        WaferBatchRitzRec &r = b->ritz_rec_host[n++];
+        Rec &r = t[c->nact++];
         r.member = (int)m;
         r.k = (int)k[m];
-        r.poff = (long long)poff;
-        r.v0 = (long long)(b->off[m] * b->esz / 16);
-        r.n16 = (long long)((size_t)b->geom(m).total * b->esz / 16);
-        poff += 2 * (size_t)k[m] * k[m] * (size_t)b->mem[m].obs_nb;
-        *max_nb = std::max(*max_nb, b->mem[m].obs_nb);
-        *max_k = std::max(*max_k, (int)k[m]);
+        r.poff = (long long)c->doubles;
+        if constexpr (ritz) {
+            r.v0 = (long long)(b->off[m] * b->esz / 16);
+            r.n16 = (long long)((size_t)b->geom(m).total * b->esz / 16);
+            c->blocks = std::max(c->blocks, (int)std::min<long long>((r.n16 + 255) / 256, (long long)b->num_cus * 8));
+        } else {
+            for (uint32_t j = 0; j < WAFER_RITZ_MAX; ++j) r.theta[j] = (theta && j < k[m]) ? theta[(size_t)m * WAFER_RITZ_MAX + j] : 0.0;
+        }
+        c->doubles += (ritz ? 2 * (size_t)k[m] * k[m] : 3 * (size_t)k[m]) * (size_t)b->mem[m].obs_nb;
+        c->max_nb = std::max(c->max_nb, b->mem[m].obs_nb);
+        c->max_k = std::max(c->max_k, (int)k[m]);
     }
-    *nact = n;
-    *doubles = poff;
-    if (n) HIP_TRY(hipMemcpyAsync(b->ritz_rec_dev, b->ritz_rec_host, sizeof(WaferBatchRitzRec) * n, hipMemcpyHostToDevice, b->s));
+    if (!c->nact) return WAFER_OK;
+    c->m0 = (size_t)t[0].member;
+    c->m1 = (size_t)t[c->nact - 1].member + 1;
+    if (partials) BUF_TRY(b->ritz_partials.reserve(c->doubles));
+    BUF_TRY(t.upload(c->nact, b->s));
     return WAFER_OK;
 }
 
-// the allocations of the store slots the kernels may touch
-WaferRitzPtrs ritz_slots(const wafer_batch *b)
+// the allocations of the store slots (or of their shadows) the kernels may touch
+WaferRitzPtrs ritz_slots(const std::vector<DevArray<char>> &v)
 {
     WaferRitzPtrs st;
-    for (size_t l = 0; l < WAFER_RITZ_MAX && l < b->slots.size(); ++l) st.p[l] = b->slots[l];
+    for (size_t l = 0; l < WAFER_RITZ_MAX && l < v.size(); ++l) st.p[l] = v[l];
     return st;
 }
 
-// H and S of every listed member (checked: ritz_check) into ritz_sums_host: the sums launch, the reduce, one read-back
+// H and S of every listed member (checked: ritz_check) into ritz_sums' host side: the sums launch, the reduce, one read-back
 int ritz_matrices_impl(wafer_batch *b, const uint8_t *active, const uint32_t *k)
 {
     HIP_TRY(hipSetDevice(b->device));
@@ -1177,32 +1156,24 @@ int ritz_matrices_impl(wafer_batch *b, const uint8_t *active, const uint32_t *k)
     TRY(ensure_ritz(b));
     TRY(sync_members(b));
     HIP_TRY(hipStreamSynchronize(b->s));
-    int nact = 0, max_nb = 0, max_k = 0;
-    size_t doubles = 0;
-    for (uint32_t m = 0; m < b->n; ++m)
-        if (!active || active[m]) doubles += 2 * (size_t)k[m] * k[m] * (size_t)b->mem[m].obs_nb;
-    TRY(ensure_ritz_partials(b, doubles));
-    TRY(upload_ritz_table(b, active, k, &nact, &max_nb, &max_k, &doubles));
-    const WaferRitzPtrs st = ritz_slots(b);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_ritz_sums(b->f32, b->g().R, gs, b->mem_dev, b->ritz_rec_dev, nact, max_nb, max_k, b->swz, st, b->ritz_partials,
-                                           b->ritz_sums, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched Rayleigh-Ritz sums launch failed: %s", hipGetErrorString(e));
+    CallTable c;
+    TRY(upload_table(b, b->ritz_rec, active, k, nullptr, true, &c));
+    const WaferRitzPtrs st = ritz_slots(b->slots);
+    TRY(launch(b, "Rayleigh-Ritz sums", [&](const auto &gs) {
+        return wafer_entry_batch_ritz_sums(b->f32, b->g().R, gs, b->mem_dev, b->ritz_rec.dev, c.nact, c.max_nb, c.max_k, b->swz, st, b->ritz_partials,
+                                           b->ritz_sums.dev, b->s);
+    }));
     b->n_ritz_launches += 2;
-    // the members from the first listed to the last in one copy
-    const size_t m0 = (size_t)b->ritz_rec_host[0].member, m1 = (size_t)b->ritz_rec_host[nact - 1].member + 1;
-    HIP_TRY(hipMemcpyAsync(b->ritz_sums_host + m0 * 2 * RITZ_KK, b->ritz_sums + m0 * 2 * RITZ_KK, sizeof(double) * 2 * RITZ_KK * (m1 - m0),
-                           hipMemcpyDeviceToHost, b->s));
+    BUF_TRY(b->ritz_sums.download(2 * RITZ_KK * (c.m1 - c.m0), b->s, 2 * RITZ_KK * c.m0));
     HIP_TRY(hipStreamSynchronize(b->s));
     ++b->n_ritz_readbacks;
     return WAFER_OK;
 }
 
-// member m's k x k matrices out of ritz_sums_host
+// member m's k x k matrices out of ritz_sums' host side
 void ritz_unpack(const wafer_batch *b, uint32_t m, uint32_t k, double *h, double *s)
 {
-    const double *r = b->ritz_sums_host + (size_t)m * 2 * RITZ_KK;
+    const double *r = &b->ritz_sums[(size_t)m * 2 * RITZ_KK];
     for (size_t q = 0; q < (size_t)k * k; ++q) {
         if (h) h[q] = r[q];
         if (s) s[q] = r[RITZ_KK + q];
@@ -1216,24 +1187,17 @@ int ritz_rotate_impl(wafer_batch *b, const uint8_t *listed, const uint32_t *k, c
     RoctxRange range_("wafer_batch_rotate_states");
     TRY(ensure_ritz(b));
     HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table and coefficients are not read by an earlier call's copy
-    int nact = 0, max_nb = 0, max_k = 0;
-    size_t doubles = 0;
-    TRY(upload_ritz_table(b, listed, k, &nact, &max_nb, &max_k, &doubles));
-    if (!nact) return WAFER_OK;
-    long long want = 1;
-    for (int q = 0; q < nact; ++q) {
-        const uint32_t m = (uint32_t)b->ritz_rec_host[q].member;
-        memcpy(b->ritz_coef_host + m * RITZ_KK, coef + m * RITZ_KK, sizeof(double) * k[m] * k[m]);
-        want = std::max(want, (b->ritz_rec_host[q].n16 + 255) / 256);
+    CallTable c;
+    TRY(upload_table(b, b->ritz_rec, listed, k, nullptr, false, &c));
+    if (!c.nact) return WAFER_OK;
+    for (int q = 0; q < c.nact; ++q) {
+        const uint32_t m = (uint32_t)b->ritz_rec[q].member;
+        memcpy(&b->ritz_coef[m * RITZ_KK], coef + m * RITZ_KK, sizeof(double) * k[m] * k[m]);
     }
-    const size_t m0 = (size_t)b->ritz_rec_host[0].member, m1 = (size_t)b->ritz_rec_host[nact - 1].member + 1;
-    HIP_TRY(hipMemcpyAsync(b->ritz_coef + m0 * RITZ_KK, b->ritz_coef_host + m0 * RITZ_KK, sizeof(double) * RITZ_KK * (m1 - m0), hipMemcpyHostToDevice,
-                           b->s));
-    const int blocks = (int)std::min<long long>(want, (long long)b->num_cus * 8);
-    const hipError_t e = wafer_entry_batch_rotate_states(b->f32, b->ritz_rec_dev, nact, blocks, ritz_slots(b), b->ritz_coef, b->s);
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched rotation launch failed: %s", hipGetErrorString(e));
+    BUF_TRY(b->ritz_coef.upload(RITZ_KK * (c.m1 - c.m0), b->s, RITZ_KK * c.m0));
+    TRY(launched("rotation", wafer_entry_batch_rotate_states(b->f32, b->ritz_rec.dev, c.nact, c.blocks, ritz_slots(b->slots), b->ritz_coef.dev, b->s)));
     ++b->n_ritz_launches;
-    for (int q = 0; q < nact; ++q) mark_gram_stale(b, (uint32_t)b->ritz_rec_host[q].member);   // the one-pass form sees the new store
+    for (int q = 0; q < c.nact; ++q) mark_gram_stale(b, (uint32_t)b->ritz_rec[q].member);   // the one-pass form sees the new store
     return WAFER_OK;
 }
 
@@ -1265,45 +1229,26 @@ int residual_check(const wafer_batch *b, int source, const uint8_t *active, cons
 
 int ensure_residual(wafer_batch *b)
 {
-    if (b->resid_sums_host) return WAFER_OK;   // (the last one made below)
-    if (!b->resid_rec_dev) HIP_TRY(hipMalloc((void **)&b->resid_rec_dev, sizeof(WaferBatchResidualRec) * b->n));
-    if (!b->resid_rec_host) HIP_TRY(hipHostMalloc((void **)&b->resid_rec_host, sizeof(WaferBatchResidualRec) * b->n, hipHostMallocDefault));
-    if (!b->resid_sums) HIP_TRY(hipMalloc((void **)&b->resid_sums, sizeof(double) * RESID_ROWS * b->n));
-    HIP_TRY(hipHostMalloc((void **)&b->resid_sums_host, sizeof(double) * RESID_ROWS * b->n, hipHostMallocDefault));
+    if (b->resid_sums.dev) return WAFER_OK;   // (made last: a call that failed before it starts over)
+    BUF_TRY(b->resid_rec.make(b->n));
+    BUF_TRY(b->resid_sums.make(RESID_ROWS * b->n));
     return WAFER_OK;
 }
 
 // One pass over the listed members (checked: residual_check; at least one): the per-call table with theta (member m's at
-// m * WAFER_RITZ_MAX; nullptr: zeros), the sums launch, the reduce and one read-back into resid_sums_host.
+// m * WAFER_RITZ_MAX; nullptr: zeros), the sums launch, the reduce and one read-back into resid_sums' host side.
 int residual_pass(wafer_batch *b, int source, const uint8_t *listed, const uint32_t *k, const double *theta)
 {
     HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table is not read by an earlier call's copy
-    int nact = 0, max_nb = 0, max_k = 0;
-    size_t poff = 0;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (listed && !listed[m]) continue;
-        WaferBatchResidualRec &r = b->resid_rec_host[nact++];
-        r.member = (int)m;
-        r.k = (int)k[m];
-        r.poff = (long long)poff;
-        for (uint32_t j = 0; j < WAFER_RITZ_MAX; ++j) r.theta[j] = (theta && j < k[m]) ? theta[(size_t)m * WAFER_RITZ_MAX + j] : 0.0;
-        poff += 3 * (size_t)k[m] * (size_t)b->mem[m].obs_nb;
-        max_nb = std::max(max_nb, b->mem[m].obs_nb);
-        max_k = std::max(max_k, (int)k[m]);
-    }
-    TRY(ensure_ritz_partials(b, poff));
-    HIP_TRY(hipMemcpyAsync(b->resid_rec_dev, b->resid_rec_host, sizeof(WaferBatchResidualRec) * nact, hipMemcpyHostToDevice, b->s));
-    const WaferRitzPtrs st = ritz_slots(b);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_residual_sums(b->f32, b->g().R, gs, b->mem_dev, b->resid_rec_dev, nact, max_nb, max_k, b->swz,
-                                               source == WAFER_RESIDUAL_PHI ? 1 : 0, st, b->ritz_partials, b->resid_sums, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched residual sums launch failed: %s", hipGetErrorString(e));
+    CallTable c;
+    TRY(upload_table(b, b->resid_rec, listed, k, theta, true, &c));
+    const WaferRitzPtrs st = ritz_slots(b->slots);
+    TRY(launch(b, "residual sums", [&](const auto &gs) {
+        return wafer_entry_batch_residual_sums(b->f32, b->g().R, gs, b->mem_dev, b->resid_rec.dev, c.nact, c.max_nb, c.max_k, b->swz,
+                                               source == WAFER_RESIDUAL_PHI ? 1 : 0, st, b->ritz_partials, b->resid_sums.dev, b->s);
+    }));
     b->n_resid_launches += 2;
-    // the members from the first listed to the last in one copy
-    const size_t m0 = (size_t)b->resid_rec_host[0].member, m1 = (size_t)b->resid_rec_host[nact - 1].member + 1;
-    HIP_TRY(hipMemcpyAsync(b->resid_sums_host + m0 * RESID_ROWS, b->resid_sums + m0 * RESID_ROWS, sizeof(double) * RESID_ROWS * (m1 - m0),
-                           hipMemcpyDeviceToHost, b->s));
+    BUF_TRY(b->resid_sums.download(RESID_ROWS * (c.m1 - c.m0), b->s, RESID_ROWS * c.m0));
     HIP_TRY(hipStreamSynchronize(b->s));
     ++b->n_resid_readbacks;
     return WAFER_OK;
@@ -1340,41 +1285,28 @@ int evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint
     if (max_k) {
         TRY(ensure_slots(b, b->shadows, max_k));   // (zeroed: the kernel writes work cells only, frames and pads stay zeros)
         TRY(ensure_ritz(b));   // (the copy's per-call table)
-        if (!b->store_k_dev) HIP_TRY(hipMalloc((void **)&b->store_k_dev, sizeof(int) * b->n));
-        if (!b->store_k_host) HIP_TRY(hipHostMalloc((void **)&b->store_k_host, sizeof(int) * b->n, hipHostMallocDefault));
+        if (!b->store_k.dev) BUF_TRY(b->store_k.make(b->n));
         TRY(sync_members(b));
         TRY(build_blocks(b, b->blks, listed.data(), 1));
         HIP_TRY(hipStreamSynchronize(b->s));   // the pinned tables are not read by an earlier call's copy
-        for (uint32_t m = 0; m < b->n; ++m) b->store_k_host[m] = listed[m] ? (int)k[m] : 0;
-        HIP_TRY(hipMemcpyAsync(b->store_k_dev, b->store_k_host, sizeof(int) * b->n, hipMemcpyHostToDevice, b->s));
+        for (uint32_t m = 0; m < b->n; ++m) b->store_k[m] = listed[m] ? (int)k[m] : 0;
+        BUF_TRY(b->store_k.upload(b->n, b->s));
     }
-    int nact = 0, max_nb = 0, mk = 0;
-    size_t doubles = 0;
-    long long want = 1;
-    if (plan.copy_back) {
-        TRY(upload_ritz_table(b, listed.data(), k, &nact, &max_nb, &mk, &doubles));
-        for (int q = 0; q < nact; ++q) want = std::max(want, (b->ritz_rec_host[q].n16 + 255) / 256);
-    }
-    WaferRitzPtrs slots, shadows;
-    for (uint32_t l = 0; l < max_k; ++l) {
-        slots.p[l] = b->slots[l];
-        shadows.p[l] = b->shadows[l];
-    }
+    CallTable c;
+    if (plan.copy_back) TRY(upload_table(b, b->ritz_rec, listed.data(), k, nullptr, false, &c));
+    const WaferRitzPtrs slots = ritz_slots(b->slots), shadows = ritz_slots(b->shadows);   // (the kernels touch the first k[m] <= max_k of each)
     HIP_TRY(hipEventRecord(b->ev_start, b->s));
     if (max_k && !b->blks.host.empty()) {
         for (uint64_t st = 0; st < plan.steps; ++st) {   // no host synchronisation in here
             const bool from_shadow = wafer_batch_store_src_is_shadow(st);
-            const hipError_t e = with_geom(b, [&](const auto &gs) {
-                return wafer_entry_batch_store_step(b->dtype, b->g().R, gs, b->mem_dev, b->blks.dev, (int)b->blks.host.size(), plan.groups, b->store_k_dev,
-                                                    from_shadow ? shadows : slots, from_shadow ? slots : shadows, b->s);
-            });
-            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched store step launch failed: %s", hipGetErrorString(e));
+            TRY(launch(b, "store step", [&](const auto &gs) {
+                return wafer_entry_batch_store_step(b->dtype, b->g().R, gs, b->mem_dev, b->blks.dev, (int)b->blks.host.size(), plan.groups,
+                                                    b->store_k.dev, from_shadow ? shadows : slots, from_shadow ? slots : shadows, b->s);
+            }));
             ++b->n_store_launches;
         }
-        if (plan.copy_back && nact) {
-            const int blocks = (int)std::min<long long>(want, (long long)b->num_cus * 8);
-            const hipError_t e = wafer_entry_batch_store_copy(b->ritz_rec_dev, nact, blocks, shadows, slots, b->s);
-            if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched store copy launch failed: %s", hipGetErrorString(e));
+        if (plan.copy_back && c.nact) {
+            TRY(launched("store copy", wafer_entry_batch_store_copy(b->ritz_rec.dev, c.nact, c.blocks, shadows, slots, b->s)));
             ++b->n_store_launches;
         }
     }
@@ -1391,6 +1323,9 @@ int evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint
 // single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
 // (WaferLdsCfg::TX), and the z-chunk that follows from them -- with its [4][obs_nb] partials end to end (one shape: member m's at
 // m * 4 * obs_nb).  norm2: n2_nb workgroups, the partials end to end likewise.  The kernels read all of it from the records.
+constexpr int (*LDS_ZCHUNK[2][3])(const WaferTuning &, const WaferGeom &, int, int, int) = {   // wafer_lds_zchunk<T, R> at [float storage][R - 1]
+    {wafer_lds_zchunk<double, 1>, wafer_lds_zchunk<double, 2>, wafer_lds_zchunk<double, 3>},
+    {wafer_lds_zchunk<float, 1>, wafer_lds_zchunk<float, 2>, wafer_lds_zchunk<float, 3>}};
 int init_partitions(wafer_batch *b)
 {
     const int R = b->g().R;
@@ -1405,14 +1340,7 @@ int init_partitions(wafer_batch *b)
         WaferBatchMember &e = b->mem[m];
         memset(&e, 0, sizeof e);
         const WaferGeom &g = b->geom(m);
-        if (b->f32)
-            e.obs_zchunk = R == 1   ? wafer_lds_zchunk<float, 1>(b->tune, g, g.nzl, ry, b->num_cus)
-                           : R == 2 ? wafer_lds_zchunk<float, 2>(b->tune, g, g.nzl, ry, b->num_cus)
-                                    : wafer_lds_zchunk<float, 3>(b->tune, g, g.nzl, ry, b->num_cus);
-        else
-            e.obs_zchunk = R == 1   ? wafer_lds_zchunk<double, 1>(b->tune, g, g.nzl, ry, b->num_cus)
-                           : R == 2 ? wafer_lds_zchunk<double, 2>(b->tune, g, g.nzl, ry, b->num_cus)
-                                    : wafer_lds_zchunk<double, 3>(b->tune, g, g.nzl, ry, b->num_cus);
+        e.obs_zchunk = LDS_ZCHUNK[b->f32 ? 1 : 0][R - 1](b->tune, g, g.nzl, ry, b->num_cus);
         e.shape = b->shape_of[m];
         e.obs_ntx = (g.nx + TX - 1) / TX;
         e.obs_nty = (g.ny + TY - 1) / TY;
@@ -1426,7 +1354,7 @@ int init_partitions(wafer_batch *b)
         obs_total += 4 * (size_t)e.obs_nb;
         b->n2_doubles += (size_t)e.n2_nb;
     }
-    HIP_TRY(hipMalloc((void **)&b->partials, sizeof(double) * obs_total));
+    BUF_TRY(b->partials.make(obs_total));
     return WAFER_OK;
 }
 
@@ -1456,9 +1384,9 @@ int init_views(wafer_batch *b)
         if (p.flags & WAFER_FLAG_UNPLANNED_DIV) c->div_plan.checked = c->div_plan_f.checked = 0;
         void **arr[4] = {&c->phi[0], &c->phi[1], &c->v, &c->potsub};
         for (int k = 0; k < 4; ++k)
-            *arr[k] = static_cast<char *>(b->alloc[k]) + (b->off[m] + (size_t)g.base_off) * b->esz;
-        c->scal = b->view_scal + (size_t)m * SCAL_SLOTS;
-        c->scal_host = b->view_scal_host + (size_t)m * SCAL_SLOTS;
+            *arr[k] = b->alloc[k] + (b->off[m] + (size_t)g.base_off) * b->esz;
+        c->scal = b->view_scal.dev + (size_t)m * SCAL_SLOTS;
+        c->scal_host = &b->view_scal[(size_t)m * SCAL_SLOTS];
         c->kernel_name = "wafer_k_batch_step";
         WaferBatchMember &e = b->mem[m];
         e.phi[0] = c->phi[0];
@@ -1504,7 +1432,7 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p0.device));
 
-    std::unique_ptr<wafer_batch, void (*)(wafer_batch *)> owner(new wafer_batch(), destroy);   // (a failure below frees what exists)
+    std::unique_ptr<wafer_batch> owner(new wafer_batch());   // (a failure below frees what exists)
     wafer_batch *b = owner.get();
     b->n = n_members;
     b->P.assign(members, members + n_members);
@@ -1523,46 +1451,35 @@ int create_batch(const wafer_params *members, uint32_t n_members, bool same_shap
     b->nst.assign(n_members, 0);
     for (uint32_t m = 0; m < n_members; ++m) b->gs_stride = std::max(b->gs_stride, 1 + (int)members[m].max_states);
     if (b->mixed) {
-        static const char *const types[] = {"double,double", "float,double", "float,float"};
         char name[96];
-        snprintf(name, sizeof name, "wafer_k_batch_step<%d,%s,WaferBatchGeomTable>", R, types[b->dtype]);
+        snprintf(name, sizeof name, "wafer_k_batch_step<%d,%s,WaferBatchGeomTable>", R, KERNEL_TYPES[b->dtype]);
         b->kernel_name = name;
     }
-    HIP_TRY(hipStreamCreateWithFlags(&b->s, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&b->ev_start));
-    HIP_TRY(hipEventCreate(&b->ev_stop));
-    HIP_TRY(hipEventCreate(&b->rs_start));
-    HIP_TRY(hipEventCreate(&b->rs_stop));
-    for (void *&a : b->alloc) {   // one allocation per array kind, zeros: frames, pads and guard zones of every member
-        HIP_TRY(hipMalloc(&a, b->cells * esz));
-        HIP_TRY(hipMemsetAsync(a, 0, b->cells * esz, b->s));
+    HIP_TRY(hipStreamCreateWithFlags(&b->s.h, hipStreamNonBlocking));
+    for (hipEvent_t *e : {&b->ev_start, &b->ev_stop, &b->rs_start, &b->rs_stop}) HIP_TRY(hipEventCreate(e));
+    for (DevArray<char> &a : b->alloc) {   // one allocation per array kind, zeros: frames, pads and guard zones of every member
+        BUF_TRY(a.make(b->cells * esz));
+        HIP_TRY(hipMemsetAsync(a, 0, a.bytes(), b->s));
     }
-    HIP_TRY(hipMalloc((void **)&b->view_scal, sizeof(double) * SCAL_SLOTS * n_members));
-    HIP_TRY(hipMemsetAsync(b->view_scal, 0, sizeof(double) * SCAL_SLOTS * n_members, b->s));
-    HIP_TRY(hipHostMalloc((void **)&b->view_scal_host, sizeof(double) * SCAL_SLOTS * n_members, hipHostMallocDefault));
+    BUF_TRY(b->view_scal.make((size_t)SCAL_SLOTS * n_members));
+    HIP_TRY(hipMemsetAsync(b->view_scal.dev, 0, b->view_scal.dev.bytes(), b->s));
     TRY(init_partitions(b));
-    HIP_TRY(hipMalloc((void **)&b->sums, sizeof(double) * 4 * n_members));
-    HIP_TRY(hipHostMalloc((void **)&b->sums_host, sizeof(double) * 4 * n_members, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&b->n2, sizeof(double) * n_members));
-    HIP_TRY(hipHostMalloc((void **)&b->n2_host, sizeof(double) * n_members, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&b->act_dev, sizeof(int) * n_members));
-    HIP_TRY(hipHostMalloc((void **)&b->act_host, sizeof(int) * n_members, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&b->sym_dev, sizeof(int) * n_members));
-    HIP_TRY(hipHostMalloc((void **)&b->sym_host, sizeof(int) * n_members, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&b->mem_dev, sizeof(WaferBatchMember) * n_members));
-    HIP_TRY(hipMalloc((void **)&b->setup_dev, sizeof(WaferBatchSetupRec) * n_members));
-    HIP_TRY(hipHostMalloc((void **)&b->setup_host, sizeof(WaferBatchSetupRec) * n_members, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&b->vchk_dev, sizeof(unsigned long long) * 3 * n_members));
-    HIP_TRY(hipHostMalloc((void **)&b->vchk_init, sizeof(unsigned long long) * 3 * n_members, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&b->vchk_host, sizeof(unsigned long long) * 3 * n_members, hipHostMallocDefault));
+    BUF_TRY(b->sums.make(4 * (size_t)n_members));
+    BUF_TRY(b->n2.make(n_members));
+    BUF_TRY(b->act.make(n_members));
+    BUF_TRY(b->sym.make(n_members));
+    BUF_TRY(b->mem_dev.make(n_members));
+    BUF_TRY(b->setup.make(n_members));
+    BUF_TRY(b->vchk.make(3 * (size_t)n_members));
+    BUF_TRY(b->vchk_init.make(3 * (size_t)n_members));
     for (uint32_t m = 0; m < n_members; ++m) {
         b->vchk_init[3 * m] = ~0ull;
         b->vchk_init[3 * m + 1] = b->vchk_init[3 * m + 2] = 0ull;
     }
-    HIP_TRY(hipMalloc((void **)&b->geoms_dev, sizeof(WaferGeom) * b->geoms.size()));
-    HIP_TRY(hipMemcpy(b->geoms_dev, b->geoms.data(), sizeof(WaferGeom) * b->geoms.size(), hipMemcpyHostToDevice));
+    BUF_TRY(b->geoms_dev.make(b->geoms.size()));
+    HIP_TRY(hipMemcpy(b->geoms_dev, b->geoms.data(), b->geoms_dev.bytes(), hipMemcpyHostToDevice));
     TRY(init_views(b));
-    HIP_TRY(hipMemcpy(b->mem_dev, b->mem.data(), sizeof(WaferBatchMember) * n_members, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->mem_dev, b->mem.data(), b->mem_dev.bytes(), hipMemcpyHostToDevice));
     HIP_TRY(hipStreamSynchronize(b->s));
     *out = owner.release();
     return WAFER_OK;
@@ -1596,7 +1513,7 @@ int wafer_batch_num_shapes(wafer_batch *b, uint32_t *n_shapes)
 
 int wafer_batch_destroy(wafer_batch *b)
 {
-    if (b) destroy(b);
+    delete b;   // (~wafer_batch: what exists goes, the stream last)
     return WAFER_OK;
 }
 
@@ -1724,10 +1641,10 @@ int wafer_batch_normalise(wafer_batch *b, const uint8_t *active, const double *n
 {
     if (!b || !norm2) return fail(WAFER_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->s));   // n2_host is read by a copy of an earlier call
-    memcpy(b->n2_host, norm2, sizeof(double) * b->n);
-    HIP_TRY(hipMemcpyAsync(b->n2, b->n2_host, sizeof(double) * b->n, hipMemcpyHostToDevice, b->s));
-    return normalise(b, active, b->n2, 1);
+    HIP_TRY(hipStreamSynchronize(b->s));   // n2's host side is read by a copy of an earlier call
+    memcpy(b->n2.host, norm2, b->n2.host.bytes());
+    BUF_TRY(b->n2.upload(b->n, b->s));
+    return normalise(b, active, b->n2.dev, 1);
 }
 
 int wafer_batch_solve(wafer_batch *b, double tolerance, uint64_t screen_update, int has_max_steps, uint64_t max_steps,
@@ -1772,13 +1689,12 @@ int wafer_batch_norm2(wafer_batch *b, double *out)
     // double), the chain's on doubles (wafer_gs_blocks)
     int max_nb = 0;
     for (uint32_t m = 0; m < b->n; ++m) max_nb = std::max(max_nb, b->mem[m].n2_nb);
-    const hipError_t e = with_geom(b, [&](const auto &gs) {
-        return wafer_entry_batch_norm2(b->f32, gs, b->mem_dev, b->act_dev, nact, max_nb, b->gs_scal, b->gs_stride, 0, b->gs_partials, b->s);
-    });
-    if (e != hipSuccess) return fail(WAFER_ERR_HIP, "batched norm2 launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(b->gs_host, b->gs_scal, sizeof(double) * (size_t)b->gs_stride * b->n, hipMemcpyDeviceToHost, b->s));
+    TRY(launch(b, "norm2", [&](const auto &gs) {
+        return wafer_entry_batch_norm2(b->f32, gs, b->mem_dev, b->act.dev, nact, max_nb, b->gs_scal.dev, b->gs_stride, 0, b->gs_partials, b->s);
+    }));
+    BUF_TRY(b->gs_scal.download(b->gs_scal.host.size(), b->s));
     HIP_TRY(hipStreamSynchronize(b->s));
-    for (uint32_t m = 0; m < b->n; ++m) out[m] = b->gs_host[(size_t)m * b->gs_stride];
+    for (uint32_t m = 0; m < b->n; ++m) out[m] = b->gs_scal[(size_t)m * b->gs_stride];
     return WAFER_OK;
 }
 
@@ -1836,10 +1752,7 @@ int wafer_batch_clear_states(wafer_batch *b, const uint8_t *active)
     }
     if (b->slots.size() > keep) {   // slots no member uses any more go back
         HIP_TRY(hipStreamSynchronize(b->s));
-        while (b->slots.size() > keep) {
-            (void)hipFree(b->slots.back());
-            b->slots.pop_back();
-        }
+        b->slots.resize(keep);
     }
     return WAFER_OK;
 }
@@ -1903,24 +1816,22 @@ int wafer_batch_diag_dispatch(wafer_batch *b, char *buf, size_t n)
 {
     if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
     static const char *const stencils[] = {"", "ThreePoint", "FivePoint", "SevenPoint"};
-    static const char *const dtypes[] = {"f64", "f32", "f32fast"};
-    static const char *const types[] = {"", ",float,double", ",float,float"};   // the kernels' <.., T, C> beside the fp64 default
-    static const char *const types_mixed[] = {",double,double,WaferBatchGeomTable", ",float,double,WaferBatchGeomTable",
-                                              ",float,float,WaferBatchGeomTable"};   // several shapes: the geometry source after them
-    const char *const *tn = b->mixed ? types_mixed : types;
+    char tn[48] = "";   // the kernels' <.., T, C> beside the fp64 default; several shapes: all of them, and the geometry source after them
+    if (b->mixed) snprintf(tn, sizeof tn, ",%s,WaferBatchGeomTable", KERNEL_TYPES[b->dtype]);
+    else if (b->dtype != WAFER_F64) snprintf(tn, sizeof tn, ",%s", KERNEL_TYPES[b->dtype]);
     const int R = b->g().R, K = steps_per_pass(b);
     char kernel[96], tile[32];
     const char *remainder = "none";
     if (K > 1) {
-        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d%s>", R, K, tn[b->dtype]);
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_stepk<%d,%d%s>", R, K, tn);
         snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCHK_TX, WAFER_BATCHK_TY);
         remainder = have_two_step(b, K) ? "stepk2+step" : "step";
     } else {
-        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d%s>", R, tn[b->dtype]);
+        snprintf(kernel, sizeof kernel, "wafer_k_batch_step<%d%s>", R, tn);
         snprintf(tile, sizeof tile, "%dx%d", WAFER_BATCH_TX, WAFER_BATCH_TY);
     }
     const int len = snprintf(buf, n, "stencil=%s kernel=%s steps_per_pass=%d tile=%s lds_bytes=%d remainder=%s variant=%d dtype=%s", stencils[R], kernel, K,
-                             tile, K > 1 ? wafer_batch_stepk_lds_bytes(b->dtype, R, K) : 0, remainder, b->step_variant, dtypes[b->dtype]);
+                             tile, K > 1 ? wafer_batch_stepk_lds_bytes(b->dtype, R, K) : 0, remainder, b->step_variant, DTYPE_NAMES[b->dtype]);
     if (b->mixed && len > 0 && (size_t)len < n) snprintf(buf + len, n - (size_t)len, " shapes=%zu", b->geoms.size());
     return WAFER_OK;
 }
@@ -1945,7 +1856,6 @@ int wafer_batch_set_gs_variant(wafer_batch *b, int variant)
 int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n)
 {
     if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
-    static const char *const dtypes[] = {"f64", "f32", "f32fast"};
     const char *T = b->f32 ? "float" : "double";
     // what the one-pass form allocated on first use: the Gram matrices, their partials, the member lists, and the growth of gs_partials
     const size_t onepass_bytes = !b->onepass_ready ? 0
@@ -1966,7 +1876,7 @@ int wafer_batch_diag_gs(wafer_batch *b, uint32_t wnum, char *buf, size_t n)
         snprintf(kernels, sizeof kernels, "wafer_k_batch_step");
     }
     const int len = snprintf(buf, n, "wnum=%u form=%s launches_per_step=%d kernels=%s variant=%d dtype=%s onepass_bytes=%zu", wnum,
-                             onepass ? "onepass" : "sequential", launches, kernels, b->gs_variant, dtypes[b->dtype], onepass_bytes);
+                             onepass ? "onepass" : "sequential", launches, kernels, b->gs_variant, DTYPE_NAMES[b->dtype], onepass_bytes);
     if (b->mixed_states && len > 0 && (size_t)len < n) snprintf(buf + len, n - (size_t)len, " shapes=%zu", b->geoms.size());
     return WAFER_OK;
 }
@@ -2076,7 +1986,7 @@ int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, con
         bool any = false;
         for (uint32_t m = 0; m < b->n; ++m) {
             if (!ok[m]) continue;
-            const double *r = b->resid_sums_host + m * RESID_ROWS;
+            const double *r = &b->resid_sums[m * RESID_ROWS];
             for (uint32_t j = 0; j < k[m]; ++j) {
                 const double sj = r[j * 3 + 2];
                 if (!std::isfinite(sj) || !(sj > 0.0)) {
@@ -2101,7 +2011,7 @@ int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, con
     TRY(residual_pass(b, source, ok.data(), k, th.data()));
     for (uint32_t m = 0; m < b->n; ++m) {
         if (!ok[m]) continue;
-        const double *r = b->resid_sums_host + m * RESID_ROWS;
+        const double *r = &b->resid_sums[m * RESID_ROWS];
         for (uint32_t j = 0; j < k[m]; ++j) {
             theta[(size_t)m * WAFER_RITZ_MAX + j] = th[(size_t)m * WAFER_RITZ_MAX + j];
             r2[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 0];
@@ -2130,8 +2040,7 @@ int wafer_batch_evolve_states(wafer_batch *b, const uint8_t *active, const uint3
 int wafer_batch_diag_store_step(wafer_batch *b, char *buf, size_t n)
 {
     if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
-    static const char *const types[] = {"double,double", "float,double", "float,float"};
-    snprintf(buf, n, "kernel=wafer_k_batch_store_step<%d,%s,%s> states_per_workgroup=%d shapes=%zu", b->g().R, types[b->dtype],
+    snprintf(buf, n, "kernel=wafer_k_batch_store_step<%d,%s,%s> states_per_workgroup=%d shapes=%zu", b->g().R, KERNEL_TYPES[b->dtype],
              b->mixed ? "WaferBatchGeomTable" : "WaferGeom", WAFER_STORE_SG, b->geoms.size());
     return WAFER_OK;
 }
