@@ -190,6 +190,13 @@ extern "C" {
     /// The first k stored states advanced by `n_steps` plain steps each (no projection, no normalisation): the bits of
     /// wafer_evolve(ctx, 0, n_steps) on each; phi and `cur` are left alone
     pub fn wafer_evolve_states(ctx: *mut wafer_ctx, k: u32, n_steps: u64) -> c_int;
+    /// Host only: the coefficients of the scaled Chebyshev filter of `degree` steps that damps [a, b] and has magnitude 1 at a0 < a;
+    /// `al`, `be` hold `degree` doubles, `cc` one
+    pub fn wafer_filter_coefficients(degree: u32, a: f64, b: f64, a0: f64, al: *mut f64, be: *mut f64, cc: *mut f64) -> c_int;
+    /// That polynomial of H applied to the first k stored states, one launch per state and step; phi and `cur` are left alone
+    pub fn wafer_filter_states(ctx: *mut wafer_ctx, k: u32, degree: u32, a: f64, b: f64, a0: f64) -> c_int;
+    /// Gershgorin's upper bound of H's spectrum: W / den + max V over the work cells
+    pub fn wafer_spectral_bound(ctx: *mut wafer_ctx, ub: *mut f64) -> c_int;
     /// Residuals r = H l - theta l (include/wafer_hip.h): source 0 = the first k stored states, 1 = phi (k = 1); `theta_in` null is
     /// Rayleigh mode; `theta`, `r2`, `s` hold k doubles
     pub fn wafer_residuals(
@@ -308,6 +315,12 @@ extern "C" {
     pub fn wafer_batch_evolve_states(b: *mut wafer_batch, active: *const u8, k: *const u32, n_steps: u64) -> c_int;
     pub fn wafer_batch_diag_store_step(b: *mut wafer_batch, buf: *mut c_char, n: usize) -> c_int;
     pub fn wafer_batch_diag_store_counts(b: *mut wafer_batch, launches: *mut u64) -> c_int;
+    /// wafer_filter_states for every listed member with its own k[m] and interval, one launch per recurrence step for all of them
+    pub fn wafer_batch_filter_states(
+        b: *mut wafer_batch, active: *const u8, k: *const u32, degree: u32, a: *const f64, bb: *const f64, a0: *const f64,
+    ) -> c_int;
+    pub fn wafer_batch_spectral_bound(b: *mut wafer_batch, active: *const u8, ub: *mut f64) -> c_int;
+    pub fn wafer_batch_diag_filter_counts(b: *mut wafer_batch, launches: *mut u64, bound_launches: *mut u64) -> c_int;
 }
 
 /// `Err(message)` for any non-zero status; a Wafer integration maps it to an `ErrorKind`.

@@ -255,6 +255,35 @@ int wafer_ritz(wafer_ctx *ctx, uint32_t k, double *evals, double *coef, double *
  * n_steps. */
 int wafer_evolve_states(wafer_ctx *ctx, uint32_t k, uint64_t n_steps);
 
+/* ---- filtering w_store (Chebyshev-filtered subspace iteration) ------------ */
+/* A degree-m scaled Chebyshev polynomial of the discrete H itself (Zhou, Saad, Tiago, Chelikowsky 2006) applied to the first k
+ * stored states: [a, b] is the interval to damp, a0 < a the anchor at which the polynomial has magnitude 1.  Because the polynomial
+ * is in H, the fixed points of filter + wafer_ritz are H's eigenvectors and wafer_residuals' rho falls to rounding level -- unlike
+ * wafer_evolve_states, whose semi-implicit step leaves rho at O(dt V).
+ * The coefficients, on the host, every operation a double operation of its own:
+ *   e = (b - a) / 2    cc = (b + a) / 2    sigma = e / (a0 - cc)    gamma = 2 / sigma
+ *   step 1:      al = sigma / e,  be = 0
+ *   step i >= 2: s2 = 1 / (gamma - sigma)    al = (2 s2) / e    be = sigma s2    sigma = s2
+ * and step i per work cell c, fp64 and unfused on every dtype, operands widened from the storage type and y rounded to it once:
+ *   w = cur[c]    hw = V[c] w - S / den    t = hw - cc w    y = al t    i >= 2: y = y - be prev[c]    out[c] = y
+ * with S the bracketed stencil sum of cur at c (frame cells as stored), exactly as in wafer_residual_to_phi (the step with al = 1,
+ * cc = theta).  Step 1 reads the state and writes a shadow array (zeros outside the work cells); step i >= 2 writes its result over
+ * the iterate before last, in place: two arrays per state, no more.  The result of an even degree keeps the state's frame cells,
+ * that of an odd degree has zeros there.
+ * host only, no context: al[degree], be[degree] (be[0] = 0) and cc.  degree == 0 or > WAFER_FILTER_MAX_DEGREE, a non-finite value
+ * or anything but a0 < a < b: WAFER_ERR_INVALID, nothing written. */
+#define WAFER_FILTER_MAX_DEGREE 256
+int wafer_filter_coefficients(uint32_t degree, double a, double b, double a0, double *al, double *be, double *cc);
+/* One launch per state and step.  phi, the current buffer, the states from k on and V keep every bit; phi need not be set.  The
+ * Gram matrix is recomputed and the two-step pass's images are dropped, as after wafer_evolve_states.  k == 0, k > WAFER_RITZ_MAX,
+ * a refused interval or degree, and a context that owns a z-slab are WAFER_ERR_INVALID; k above the number of stored states, or no
+ * potential, WAFER_ERR_STATE; a refused call changes nothing.  wafer_last_evolve_ms afterwards gives the call's time and degree. */
+int wafer_filter_states(wafer_ctx *ctx, uint32_t k, uint32_t degree, double a, double b, double a0);
+/* An upper bound of H's spectrum for b, by Gershgorin: ub = W / den + max V over the work cells, with den the kernels' own
+ * (2, 24, 360 dn^2 mass) and W = 12, 192, 3264 the sum of the absolute stencil weights, centre included.  The maximum is exact.
+ * No potential: WAFER_ERR_STATE; a context that owns a z-slab: WAFER_ERR_INVALID. */
+int wafer_spectral_bound(wafer_ctx *ctx, double *ub);
+
 /* ---- residuals of w_store and of phi -------------------------------------- */
 /* How far a state is from an eigenstate of the discrete H (stencil, Dirichlet frame): with r = H l - theta l over the work area,
  * some eigenvalue of H lies within rho = sqrt(r2 / s) of theta, where r2 = sum r^2 and s = sum l^2.  Per work cell c, every
@@ -807,6 +836,29 @@ int wafer_batch_evolve_states(wafer_batch *b, const uint8_t *active, const uint3
 int wafer_batch_diag_store_step(wafer_batch *b, char *buf, size_t n);
 /* launches of wafer_batch_evolve_states since creation: n_steps per call, plus one where n_steps is odd */
 int wafer_batch_diag_store_counts(wafer_batch *b, uint64_t *launches);
+
+/* ---- filtering the stores of a batch ----------------------------------------
+ * wafer_filter_states (above) for every listed member (active[m] != 0; NULL: all), each with its own k[m] and its own interval
+ * a0[m] < a[m] < b[m] (n_members entries each), one degree per call: ONE launch per recurrence step for all listed members
+ * whatever their number and shapes, V and the member's coefficients loaded once per cell for the (up to four) states a workgroup
+ * filters.  Every filtered state holds bit for bit what a wafer_ctx of the member's wafer_params holds after wafer_filter_states
+ * on the same state, on f64, f32 and f32fast.  phi, the states from k[m] on, V, the current buffers and every member not listed
+ * keep every bit.  Entries of members not listed are not read; a listed member with k[m] == 0 costs nothing and its interval is
+ * not read.  Steps run between the slots and the shadow slots of wafer_batch_evolve_states; after an odd degree one batched copy
+ * brings the states back, so a call is degree launches or degree + 1.  No new device memory beyond the shadows.
+ * Every check for every listed member runs before anything is allocated or launched, names the member, and a refused call
+ * changes nothing: degree == 0 or > WAFER_FILTER_MAX_DEGREE, k[m] > WAFER_RITZ_MAX or a refused interval is WAFER_ERR_INVALID;
+ * k[m] above the member's state count, or no potential on a member with k[m] > 0, WAFER_ERR_STATE; a mixed-shape batch made
+ * without state stores refuses the call as every excited-state call.  Afterwards the one-pass Gram-Schmidt form recomputes the
+ * listed members' Gram matrices before its next step, and wafer_batch_last_evolve_ms gives the call's time and degree. */
+int wafer_batch_filter_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t degree, const double *a,
+                              const double *bb, const double *a0);
+/* wafer_spectral_bound for every listed member into ub[m] (n_members entries; others untouched): one launch and one read-back
+ * whatever the members and shapes, on every batch.  A listed member without a potential: WAFER_ERR_STATE, nothing written. */
+int wafer_batch_spectral_bound(wafer_batch *b, const uint8_t *active, double *ub);
+/* launches of wafer_batch_filter_states (degree per call, plus one where degree is odd) and of wafer_batch_spectral_bound (one per
+ * call) since creation */
+int wafer_batch_diag_filter_counts(wafer_batch *b, uint64_t *launches, uint64_t *bound_launches);
 
 #ifdef __cplusplus
 }

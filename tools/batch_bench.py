@@ -70,7 +70,16 @@ then --reps repetitions, all listed: "store_us_per_step" and "store_gups" (B x K
 state; one step per launch, the default dispatch); "gs_us_per_step" / "gs_gups" (B x cells x steps / time) for Batch.evolve(steps,
 wnum=K-1) on the B members -- what an excited step costs today.  "ratio_dup": dup over store, per repetition.  "parity": every state of
 the first and the last member bit-identical to a Context's evolve(0, steps) from the same state.  "store_dispatch": the kernel line;
-"store_launches": what one timed call adds.  Appended to profiles/batch_store_step_rows.jsonl unless --out names another file."""
+"store_launches": what one timed call adds.  Appended to profiles/batch_store_step_rows.jsonl unless --out names another file.
+
+--filter K: a mode of its own -- Batch.filter_states on K stored states per member beside Batch.evolve_states on the same batch in the same
+session (the arguments of --store-step).  One line per B, HIP events around the launches: --steps filter steps per repetition, in calls of an
+even degree of at most 200 (no trailing copy), after --warmup steps; the interval is a0 = 0 < a = 10 < b = each member's spectral_bound()
+(V >= 0: nothing grows).  "filter_us_per_step" / "filter_gups" and "store_us_per_step" / "store_gups" (B x K x cells x steps / time),
+"ratio_filter": filter over store, per repetition.  "parity": before anything is timed, every state of the first and the last member after a
+call of degree "parity_degree" == tests/filter_model.py's on the bits.  "solver": with --solver, one solve_filtered and one solve_block of the
+loaded batch (k = K, wall clock, blocks, stencil passes per state) -- they stop on different rules and converge to different numbers.
+Appended to profiles/batch_filter_rows.jsonl unless --out names another file."""
 import argparse, json, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -550,6 +559,84 @@ def store_step_row(n, B, K, steps, warmup, reps, ext=1, dtype="f64"):
     return out
 
 
+def filter_row(n, B, K, steps, warmup, reps, ext=1, dtype="f64", solver=False):
+    """Batch.filter_states beside Batch.evolve_states on the same B members and K states.  The timed calls put the anchor a0 at
+    Harmonic's lowest level (about 1.5), so that a call of degree 200 leaves the lowest component of a state about as large as it
+    was: the timed data neither collapse nor grow ("end_max_abs": the largest magnitude in member 0's first state after the last
+    timed call, with the plain steps of evolve_states in between)."""
+    from tests import filter_model as fm
+    steps += steps % 2
+    pars = [wafer_amd.Params(n, n, n, dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype, max_states=K)
+            for k in range(B)]
+    cells = n ** 3
+    out = {"mode": "filter", "k": K, "shape": [n, n, n], "B": B, "steps": steps, "warmup": warmup, "reps": reps,
+           "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype, "potential": "Harmonic", "parity_degree": 4}
+    stores = [store(pars[0], K, seed=j) for j in range(2)]   # (two stores, shared out)
+    storage = np.float64 if dtype == "f64" else np.float32
+    same = lambda x, y: bool(np.array_equal(np.ascontiguousarray(x).view(np.int64), np.ascontiguousarray(y).view(np.int64)))
+
+    def calls(total):
+        """even degrees of at most 200 that add up to `total` (even)"""
+        d = []
+        while total > 0:
+            d.append(min(200, total))
+            total -= d[-1]
+        return d
+
+    with wafer_amd.Batch(pars) as b:
+        b.set_potentials(["Harmonic"] * B)
+        b.set_initial_conditions(["Gaussian"] * B)
+
+        def load():
+            for k in range(B):
+                for i in range(K):
+                    b.load_state(k, i, stores[k % 2][i])
+
+        load()
+        ub = b.spectral_bound()
+        a0, a = 1.5, 10.0
+        out["interval"] = {"a0": a0, "a": a}
+        parity = True
+        for k in sorted({0, B - 1}):   # before anything is timed
+            starts = [b.download_state(k, i) for i in range(K)]   # (as stored: rounded to the storage type)
+            b.filter_states(4, a, ub, a0, K, active=[int(m == k) for m in range(B)])
+            v = b.download_array(k, "v")
+            cfg = fm.Cfg(ext, pars[k].dn, pars[k].mass)
+            parity = parity and ub[k] == fm.bound(cfg, v)
+            parity = parity and all(same(b.download_state(k, i), fm.filter(cfg, v, starts[i], 4, a, ub[k], a0, storage)) for i in range(K))
+        out["parity"] = bool(parity)
+        runs = (("filter_us_per_step", lambda d: b.filter_states(d, a, ub, a0, K)), ("store_us_per_step", lambda d: b.evolve_states(d, K)))
+        load()
+        for key, run in runs:
+            out[key] = []
+            for d in calls(warmup + warmup % 2):
+                run(d)
+        b.last_evolve_ms()
+        for _ in range(reps):   # the two alternate: what else the machine does meets both alike
+            for key, run in runs:
+                ms_all = 0.0
+                for d in calls(steps):
+                    run(d)
+                    ms_all += b.last_evolve_ms()[0]
+                out[key].append(1e3 * ms_all / steps)
+        end = b.download_state(0, 0)
+        out["end_max_abs"] = float(np.max(np.abs(end))) if np.all(np.isfinite(end)) else float("nan")
+        if solver:
+            out["solver"] = {}
+            for name, run, per_block in (("solve_filtered", lambda: b.solve_filtered(K, 1e-10, 30, 60), 30), ("solve_block", lambda: b.solve_block(K, 1e-10, 50, 400), 50)):
+                load()
+                t0 = time.perf_counter()
+                rs = run()
+                wall = time.perf_counter() - t0
+                out["solver"][name] = {"wall_s": wall, "blocks": [r["blocks"] for r in rs], "status": [r["status"] for r in rs],
+                                       "passes_per_state": max(r["blocks"] for r in rs) * per_block,
+                                       "e0_member0": float(rs[0]["evals"][0]), "max_rho_member0": float(np.max(rs[0]["rho"][:K - 1]))}
+    out["filter_gups"] = [B * K * cells / (us * 1e-6) / 1e9 for us in out["filter_us_per_step"]]
+    out["store_gups"] = [B * K * cells / (us * 1e-6) / 1e9 for us in out["store_us_per_step"]]
+    out["ratio_filter"] = [x / y for x, y in zip(out["filter_us_per_step"], out["store_us_per_step"])]
+    return out
+
+
 def rounded(d):
     if isinstance(d, dict):
         return {k: rounded(v) for k, v in d.items()}
@@ -589,7 +676,22 @@ def main():
     ap.add_argument("--store-step", type=int, metavar="K", help="time Batch.evolve_states on K stored states per member against Batch.evolve on "
                     "B x K members and against excited steps with wnum = K - 1 (a mode of its own; --batch, --steps, --warmup, --reps, --sizes, --ext, "
                     "--dtype apply)")
+    ap.add_argument("--filter", type=int, metavar="K", help="time Batch.filter_states on K stored states per member beside Batch.evolve_states on the "
+                    "same batch (a mode of its own; --batch, --steps, --warmup, --reps, --sizes, --ext, --dtype apply)")
+    ap.add_argument("--solver", action="store_true", help="--filter: also one solve_filtered and one solve_block of the batch (k = K)")
     a = ap.parse_args()
+    if a.filter:
+        if not a.out:
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_filter_rows.jsonl")
+        for n in a.sizes:
+            for B in a.batch:
+                row = filter_row(n, B, a.filter, a.steps, a.warmup, a.reps, a.ext, a.dtype, a.solver)
+                exact = {key: row.pop(key) for key in ("solver", "end_max_abs") if key in row}   # (energies, rho and magnitudes keep every digit)
+                line = json.dumps({**rounded(row), **exact})
+                print(line, flush=True)
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+        return
     if a.store_step:
         if not a.out:
             a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_store_step_rows.jsonl")

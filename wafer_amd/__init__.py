@@ -6,4 +6,4 @@ driver.  There is no CPU fallback: importing `engine` without the built
 library, or creating a context without a GPU, raises.
 """
 from .engine import (Batch, Context, Params, WaferError, POTENTIALS, INITIAL_CONDITIONS,  # noqa: F401
-                     load_library, library_path, ritz_solve, block_solve_loop)
+                     load_library, library_path, ritz_solve, block_solve_loop, filter_coefficients, filtered_solve_loop)

@@ -212,6 +212,9 @@ static inline double wafer_stencil_den(int R, double dn, double mass)
     const double lead = (R == 1) ? 2. : (R == 2) ? 24. : 360.;
     return lead * dn * dn * mass;
 }
+// the sum of the absolute weights of wafer_stencil_sum, centre included: by Gershgorin no eigenvalue of H lies above
+// wafer_stencil_abs_weight(R) / den + max V (wafer_spectral_bound)
+static inline double wafer_stencil_abs_weight(int R) { return (R == 1) ? 12. : (R == 2) ? 192. : 3264.; }
 // WaferStepArgs::v_in_range: the kernels may take the short arithmetic forms (wafer_recip for b, three instructions for x / den)
 static inline bool short_forms(const wafer_ctx *c) { return c->v_in_range && c->div_plan.checked != 0 && (!c->f32_arith || c->div_plan_f.checked != 0); }
 static inline void set_den_args(const wafer_ctx *c, WaferStepArgs &a)

@@ -41,6 +41,9 @@
 // Stepping the stores (wafer_batch_evolve_states; kernels: wafer_store_step_batch.hip.h, wafer_tu_store_step_batch*.hip): the first k[m]
 // stored states of every listed member advance by n plain steps, one launch per step over the listed members' workgroup table,
 // between the slots and shadow slots laid out as they are; an odd n ends with one batched copy back into the slots.
+// Filtering the stores (wafer_batch_filter_states; kernels: wafer_store_filter_batch.hip.h, wafer_tu_store_filter_batch*.hip): a
+// degree-m Chebyshev polynomial of H itself on the same states, tables and two sets of slots, one launch per recurrence step, each
+// member with its own interval; wafer_batch_spectral_bound gives the interval's upper end from one launch and one read-back.
 #include <memory>
 #include "wafer_engine.h"
 #include "wafer_stencil_lds.hip.h"
@@ -51,6 +54,8 @@
 #include "wafer_ritz_batch.hip.h"
 #include "wafer_residual_batch.hip.h"
 #include "wafer_store_step_batch.hip.h"
+#include "wafer_store_filter_batch.hip.h"
+#include "wafer_filter.h"
 #include "wafer_ritz.h"
 #include "wafer_buffers.h"
 
@@ -173,6 +178,11 @@ struct wafer_batch {
     std::vector<DevArray<char>> shadows;
     Mirror<int> store_k;                      // [member]: the call's k (0: not listed)
     uint64_t n_store_launches = 0;                            // of wafer_batch_evolve_states since creation (wafer_batch_diag_store_counts)
+    // filtering the stores (wafer_store_filter_batch.hip.h), made by the first call: every step's al, be, cc of every member, step i's
+    // at (i - 1) * n; and the spectral bound's one word per listed member with its pinned zeros
+    Mirror<WaferFilterCoef> filt_coef;
+    Mirror<unsigned long long> vmax;
+    uint64_t n_filter_launches = 0, n_bound_launches = 0;     // of wafer_batch_filter_states / wafer_batch_spectral_bound since creation
     // Lets a batch go: the stream drains, the views go -- they borrow every array and the stream, except a and b (ensure_ab) -- then
     // the events; behind this body every holder frees its block, and the stream goes last.
     ~wafer_batch()
@@ -1255,15 +1265,16 @@ int residual_pass(wafer_batch *b, int source, const uint8_t *listed, const uint3
 }
 
 // ---- stepping the stores -----------------------------------------------------------------------------------------------------
-// every check of wafer_batch_evolve_states for every listed member, before anything is allocated, uploaded or launched.
+// every check of wafer_batch_evolve_states (and of wafer_batch_filter_states on its states: `call` names the one in the messages) for
+// every listed member, before anything is allocated, uploaded or launched.
 // A listed member with k[m] == 0 is allowed and costs nothing.  *max_k: the largest k among the listed members.
-int store_step_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t *max_k)
+int store_step_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, const char *call, uint32_t *max_k)
 {
-    TRY(refuse_mixed(b, "wafer_batch_evolve_states"));
+    TRY(refuse_mixed(b, call));
     *max_k = 0;
     for (uint32_t m = 0; m < b->n; ++m) {
         if (active && !active[m]) continue;
-        if (k[m] > WAFER_RITZ_MAX) return fail(WAFER_ERR_INVALID, "member %u: k = %u: wafer_batch_evolve_states steps at most %d states", m, k[m], WAFER_RITZ_MAX);
+        if (k[m] > WAFER_RITZ_MAX) return fail(WAFER_ERR_INVALID, "member %u: k = %u: %s steps at most %d states", m, k[m], call, WAFER_RITZ_MAX);
         if (k[m] > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
         if (k[m] && !b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
         *max_k = std::max(*max_k, k[m]);
@@ -1276,7 +1287,7 @@ int store_step_check(const wafer_batch *b, const uint8_t *active, const uint32_t
 int evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint64_t n_steps)
 {
     uint32_t max_k = 0;
-    TRY(store_step_check(b, active, k, &max_k));
+    TRY(store_step_check(b, active, k, "wafer_batch_evolve_states", &max_k));
     HIP_TRY(hipSetDevice(b->device));
     RoctxRange range_("wafer_batch_evolve_states");
     const WaferBatchStorePlan plan = wafer_batch_store_plan(n_steps, max_k);
@@ -1315,6 +1326,102 @@ int evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint
     b->timing_valid = true;
     for (uint32_t m = 0; m < b->n; ++m)
         if (listed[m]) mark_gram_stale(b, m);   // the one-pass form sees the new store
+    return WAFER_OK;
+}
+
+// ---- filtering the stores ----------------------------------------------------------------------------------------------------
+// wafer_batch_filter_states: the degree, store_step_check's checks and every listed member's interval, before anything is allocated,
+// uploaded or launched; then `degree` launches between the slots and their shadows (wafer_batch_filter_plan) and, after an odd
+// degree, the store step's batched copy back into the slots.
+int filter_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t degree, const double *a, const double *bb, const double *a0)
+{
+    if (degree == 0 || degree > WAFER_FILTER_MAX_DEGREE)
+        return fail(WAFER_ERR_INVALID, "degree = %u: wafer_batch_filter_states takes 1 .. %d", degree, WAFER_FILTER_MAX_DEGREE);
+    uint32_t max_k = 0;
+    TRY(store_step_check(b, active, k, "wafer_batch_filter_states", &max_k));
+    for (uint32_t m = 0; m < b->n; ++m)
+        if ((!active || active[m]) && k[m] && !wafer_filter_interval_ok(a[m], bb[m], a0[m]))
+            return fail(WAFER_ERR_INVALID, "member %u: the interval needs finite a0 < a < b (a0 = %g, a = %g, b = %g)", m, a0[m], a[m], bb[m]);
+    HIP_TRY(hipSetDevice(b->device));
+    RoctxRange range_("wafer_batch_filter_states");
+    const WaferBatchFilterPlan plan = wafer_batch_filter_plan(degree, max_k);
+    std::vector<uint8_t> listed(b->n);
+    for (uint32_t m = 0; m < b->n; ++m) listed[m] = ((!active || active[m]) && k[m] > 0) ? 1 : 0;
+    CallTable c;
+    if (max_k) {
+        TRY(ensure_slots(b, b->shadows, max_k));   // (zeroed: the kernel writes work cells only, frames and pads stay zeros)
+        TRY(ensure_ritz(b));   // (the copy's per-call table)
+        if (!b->store_k.dev) BUF_TRY(b->store_k.make(b->n));
+        if (!b->filt_coef.dev) BUF_TRY(b->filt_coef.make((size_t)WAFER_FILTER_MAX_DEGREE * b->n));
+        TRY(sync_members(b));
+        TRY(build_blocks(b, b->blks, listed.data(), 1));
+        HIP_TRY(hipStreamSynchronize(b->s));   // the pinned tables are not read by an earlier call's copy
+        std::vector<double> al(degree), be(degree);
+        for (uint32_t m = 0; m < b->n; ++m) {
+            b->store_k[m] = listed[m] ? (int)k[m] : 0;
+            double cc = 0.0;
+            if (listed[m]) (void)wafer_filter_coefficients_host(degree, a[m], bb[m], a0[m], al.data(), be.data(), &cc);   // (checked above)
+            for (uint32_t i = 0; i < degree; ++i) b->filt_coef[(size_t)i * b->n + m] = listed[m] ? WaferFilterCoef{al[i], be[i], cc} : WaferFilterCoef{0., 0., 0.};
+        }
+        BUF_TRY(b->store_k.upload(b->n, b->s));
+        BUF_TRY(b->filt_coef.upload((size_t)degree * b->n, b->s));
+        if (plan.copy_back) TRY(upload_table(b, b->ritz_rec, listed.data(), k, nullptr, false, &c));
+    }
+    const WaferRitzPtrs slots = ritz_slots(b->slots), shadows = ritz_slots(b->shadows);   // (the kernels touch the first k[m] <= max_k of each)
+    HIP_TRY(hipEventRecord(b->ev_start, b->s));
+    if (max_k && !b->blks.host.empty()) {
+        for (uint64_t i = 1; i <= plan.steps; ++i) {   // no host synchronisation in here
+            const bool from_shadow = wafer_batch_filter_src_is_shadow(i);
+            TRY(launch(b, "store filter", [&](const auto &gs) {
+                return wafer_entry_batch_store_filter(b->f32, b->g().R, gs, b->mem_dev, b->blks.dev, (int)b->blks.host.size(), plan.groups, b->store_k.dev,
+                                                      b->filt_coef.dev + (i - 1) * b->n, i == 1 ? 1 : 0, from_shadow ? shadows : slots,
+                                                      from_shadow ? slots : shadows, b->s);
+            }));
+            ++b->n_filter_launches;
+        }
+        if (plan.copy_back && c.nact) {
+            TRY(launched("store copy", wafer_entry_batch_store_copy(b->ritz_rec.dev, c.nact, c.blocks, shadows, slots, b->s)));
+            ++b->n_filter_launches;
+        }
+    }
+    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
+    b->last_steps = plan.steps;
+    b->timing_valid = true;
+    for (uint32_t m = 0; m < b->n; ++m)
+        if (listed[m]) mark_gram_stale(b, m);   // the one-pass form sees the new store
+    return WAFER_OK;
+}
+
+// ub[m] = W_R / den + max V over member m's work cells, for every listed member: one launch, one read-back
+int spectral_bound(wafer_batch *b, const uint8_t *active, double *ub)
+{
+    int nlisted = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (!b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
+        ++nlisted;
+    }
+    if (!nlisted) return WAFER_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->vmax.dev) BUF_TRY(b->vmax.make(b->n));
+    TRY(sync_members(b));
+    int nact = 0;
+    TRY(upload_active(b, active, &nact));   // (synchronises the stream: vmax's host side is not read by an earlier call's copy either)
+    for (int q = 0; q < nact; ++q) b->vmax[q] = 0;   // below every key
+    BUF_TRY(b->vmax.upload((size_t)nact, b->s));
+    int max_tiles, max_planes;
+    max_tiles_planes(b, nact, false, &max_tiles, &max_planes);
+    TRY(launch(b, "spectral bound", [&](const auto &gs) {
+        return wafer_entry_batch_v_max(b->f32, gs, b->mem_dev, b->act.dev, nact, max_tiles, max_planes, b->vmax.dev, b->s);
+    }));
+    ++b->n_bound_launches;
+    BUF_TRY(b->vmax.download((size_t)nact, b->s));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    for (int q = 0; q < nact; ++q) {
+        const uint32_t m = (uint32_t)b->act[q];
+        const wafer_params &P = b->P[m];
+        ub[m] = wafer_stencil_abs_weight(P.central_difference) / wafer_stencil_den(P.central_difference, P.dn, P.mass) + wafer_order_value(b->vmax[q]);
+    }
     return WAFER_OK;
 }
 
@@ -2035,6 +2142,27 @@ int wafer_batch_evolve_states(wafer_batch *b, const uint8_t *active, const uint3
 {
     if (!b || !k) return fail(WAFER_ERR_INVALID, "null argument");
     return evolve_states(b, active, k, n_steps);
+}
+
+int wafer_batch_filter_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t degree, const double *a, const double *bb,
+                              const double *a0)
+{
+    if (!b || !k || !a || !bb || !a0) return fail(WAFER_ERR_INVALID, "null argument");
+    return filter_states(b, active, k, degree, a, bb, a0);
+}
+
+int wafer_batch_spectral_bound(wafer_batch *b, const uint8_t *active, double *ub)
+{
+    if (!b || !ub) return fail(WAFER_ERR_INVALID, "null argument");
+    return spectral_bound(b, active, ub);
+}
+
+int wafer_batch_diag_filter_counts(wafer_batch *b, uint64_t *launches, uint64_t *bound_launches)
+{
+    if (!b || !launches || !bound_launches) return fail(WAFER_ERR_INVALID, "null argument");
+    *launches = b->n_filter_launches;
+    *bound_launches = b->n_bound_launches;
+    return WAFER_OK;
 }
 
 int wafer_batch_diag_store_step(wafer_batch *b, char *buf, size_t n)

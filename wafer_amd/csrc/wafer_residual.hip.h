@@ -1,6 +1,8 @@
 // Residuals r = H l - theta l of stored states and of phi (gfx950): the sums |r|^2, <l|H|l>, <l|l> (wafer_k_residual_sums) and
-// r itself as a wavefunction array (wafer_k_residual_write).  The entry points are in wafer_tu_residual.hip; the batch's kernels
-// over the member table are in wafer_residual_batch.hip.h.
+// r itself as a wavefunction array (wafer_k_residual_write).  On the writer's partition and body: one step of the Chebyshev filter
+// of a stored state (wafer_k_filter_step); and the largest V over the work cells, for the filter's upper bound (wafer_k_v_max).
+// The entry points are in wafer_tu_residual.hip; the batch's kernels over the member table are in wafer_residual_batch.hip.h
+// and wafer_store_filter_batch.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -21,14 +23,20 @@ struct WaferResidualTheta {
 //   w = l[c]   vv = V[c]   S = the bracketed stencil sum of l at c (frame cells as they are stored)   q = S / den
 //   hw = vv * w - q        r = hw - theta * w
 //   r2 += r * r            wh += w * hw            s += w * w
-// WRITE: (T)r goes to dst[c] instead, a whole 16-byte vector per lane whose cells beyond column nx - 1 are zeros (they are pad or
-// frame cells of the destination: the pitch holds whole tiles, wafer_geom.h); nothing is summed.
-template <int R, typename T, bool WRITE>
+// MODE 1 (WRITE): (T)r goes to dst[c] instead, a whole 16-byte vector per lane whose cells beyond column nx - 1 are zeros (they are
+// pad or frame cells of the destination: the pitch holds whole tiles, wafer_geom.h); nothing is summed.
+// MODE 2, 3: a step of the Chebyshev filter (wafer_k_filter_step below; wafer_filter.h) with cc = theta,
+//   t = hw - cc * w        y = al * t        MODE 3: y = y - be * prev[c]
+// MODE 2 (the first step) stores (T)y as MODE 1 stores (T)r -- the residual writer is this step with al = 1.  MODE 3 takes prev[c]
+// from dst itself, loaded before the store, and writes work cells only: the new iterate goes over the one before last, in place.
+enum { WAFER_CELLS_SUMS = 0, WAFER_CELLS_WRITE = 1, WAFER_CELLS_FILTER_FIRST = 2, WAFER_CELLS_FILTER_NEXT = 3 };
+template <int R, typename T, int MODE>
 __device__ __forceinline__ void wafer_residual_cells(const WaferGeom &g, int xi, int yw, int zs, int ze, const T *__restrict__ lj,
                                                      const T *__restrict__ pv, const WaferDen<double> &den, double theta,
-                                                     T *__restrict__ dst, double &r2, double &wh, double &s)
+                                                     T *__restrict__ dst, double &r2, double &wh, double &s, double al = 1.0, double be = 0.0)
 {
     constexpr int RY = 2;
+    constexpr bool WRITE = MODE != WAFER_CELLS_SUMS, NEXT = MODE == WAFER_CELLS_FILTER_NEXT;
     using VT = typename WaferVec<T>::type;
     constexpr int VEC = WaferVec<T>::N;
     for (int z = zs; z < ze; ++z) {
@@ -54,9 +62,10 @@ __device__ __forceinline__ void wafer_residual_cells(const WaferGeom &g, int xi,
             }
             const VT vv4 = *reinterpret_cast<const VT *>(pv + c0);
             VT out;
+            if (NEXT) out = *reinterpret_cast<const VT *>(dst + c0);   // prev, and what the cells beyond column nx - 1 keep
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                if (WRITE) out[v] = (T)0;
+                if (WRITE && !NEXT) out[v] = (T)0;
                 if (xi + v >= g.nx) continue;
                 double xs[2 * R + 1], ys[2 * R + 1], zz[2 * R + 1];
                 const double w = (double)wv[v];
@@ -77,8 +86,12 @@ __device__ __forceinline__ void wafer_residual_cells(const WaferGeom &g, int xi,
                 const double q = wafer_div_invariant<double>(S, den);
                 const double hw = vv * w - q;
                 const double res = hw - theta * w;
-                if (WRITE) {
+                if (MODE == WAFER_CELLS_WRITE) {
                     out[v] = (T)res;
+                } else if (WRITE) {
+                    double y = al * res;
+                    if (NEXT) y = y - be * (double)out[v];
+                    out[v] = (T)y;
                 } else {
                     r2 += res * res;
                     wh += w * hw;
@@ -135,13 +148,37 @@ __global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_residual_sum
     const WaferDen<double> den = wafer_den<double>(a, a.v_in_range != 0);
 
     double r2 = 0.0, wh = 0.0, s = 0.0;
-    wafer_residual_cells<R, T, false>(g, xi, yw, zs, ze, lj, pv, den, th, nullptr, r2, wh, s);
+    wafer_residual_cells<R, T, WAFER_CELLS_SUMS>(g, xi, yw, zs, ze, lj, pv, den, th, nullptr, r2, wh, s);
     const double r2s = wafer_block_sum<NW>(r2, red, tid);
     if (tid == 0) partials[(size_t)(j * 3 + 0) * pstride + blockIdx.x] = r2s;
     const double whs = wafer_block_sum<NW>(wh, red, tid);
     if (tid == 0) partials[(size_t)(j * 3 + 1) * pstride + blockIdx.x] = whs;
     const double ss = wafer_block_sum<NW>(s, red, tid);
     if (tid == 0) partials[(size_t)(j * 3 + 2) * pstride + blockIdx.x] = ss;
+}
+
+// Zeros into every 16-byte vector of dst's allocation that holds no work cell (n16 vectors from the allocation's base
+// dst - g.base_off), by a grid-stride loop of workgroups of NT threads.
+template <int R, typename T, int NT>
+__device__ __forceinline__ void wafer_zero_outside_work(const WaferStepArgs &a, T *__restrict__ dst, long long n16, int tid)
+{
+    using VT = typename WaferVec<T>::type;
+    constexpr int VEC = WaferVec<T>::N;
+    const WaferGeom &g = a.g;
+    VT *__restrict__ base = reinterpret_cast<VT *>(dst - g.base_off);
+    const int x0 = g.xoff + R;   // the first work column of a row, in elements from the row's start
+    VT zero;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) zero[v] = (T)0;
+    for (long long q = (long long)blockIdx.x * NT + tid; q < n16; q += (long long)gridDim.x * NT) {
+        const long long e = q * VEC;
+        const int zp = (int)(e / g.plane) - g.gz;           // local plane, row and column of the vector's first element
+        const long long rem = e % g.plane;
+        const int yp = (int)(rem / g.pitch) - g.gy;
+        const int col = (int)(rem % g.pitch);
+        const bool work = zp >= a.lz_lo && zp < a.lz_hi && yp >= R && yp < R + g.ny && col >= x0 && col < x0 + g.nx;
+        if (!work) base[q] = zero;
+    }
 }
 
 // The writer: dst = r of the source lj with theta, a valid wavefunction array.  The work cells come from the body above on the
@@ -155,7 +192,6 @@ __global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_residual_wri
                                                                                     long long n16)
 {
     using Tile = WaferResidualTile<R, T>;
-    using VT = typename WaferVec<T>::type;
     constexpr int NW = Tile::NW, VEC = Tile::VEC;
     const WaferGeom &g = a.g;
     int bid = blockIdx.x;
@@ -171,20 +207,85 @@ __global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_residual_wri
     const int ze = min(zs + a.zchunk, a.lz_hi);
     const WaferDen<double> den = wafer_den<double>(a, a.v_in_range != 0);
     double r2 = 0.0, wh = 0.0, s = 0.0;
-    wafer_residual_cells<R, T, true>(g, xi, yw, zs, ze, lj, pv, den, theta, dst, r2, wh, s);
+    wafer_residual_cells<R, T, WAFER_CELLS_WRITE>(g, xi, yw, zs, ze, lj, pv, den, theta, dst, r2, wh, s);
+    wafer_zero_outside_work<R, T, NW * 64>(a, dst, n16, tid);
+}
 
-    VT *__restrict__ base = reinterpret_cast<VT *>(dst - g.base_off);
-    const int x0 = g.xoff + R;   // the first work column of a row, in elements from the row's start
-    VT zero;
+// One step of the Chebyshev filter on one stored state (wafer_filter_states; the coefficients: wafer_filter.h), on the writer's
+// partition and per-cell body: per work cell c, fp64 and unfused whatever T,
+//   hw = V[c] cur[c] - S / den        t = hw - cc cur[c]        y = al t        not FIRST: y = y - be prev[c]        out[c] = (T)y
+// FIRST: out is another array than cur and every vector of it that holds no work cell gets zeros, as from the writer.  Otherwise out
+// IS prev: the lane loads prev[c] before it stores, nobody else reads or writes that cell, and only work cells change.
+template <int R, typename T, bool FIRST>
+__global__ __launch_bounds__(WaferRitzCfg<R>::NW * 64) void wafer_k_filter_step(WaferStepArgs a, int ntx, int nty, int swz, const T *__restrict__ cur,
+                                                                                 const T *__restrict__ pv, T *__restrict__ out, double al, double be,
+                                                                                 double cc, long long n16)
+{
+    using Tile = WaferResidualTile<R, T>;
+    constexpr int NW = Tile::NW, VEC = Tile::VEC;
+    const WaferGeom &g = a.g;
+    int bid = blockIdx.x;
+    if (swz) bid = wafer_xcd_tile(bid, gridDim.x);
+    const int tx_i = bid % ntx;
+    const int ty_i = (bid / ntx) % nty;
+    const int tz_i = bid / (ntx * nty);
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int xi = tx_i * Tile::TX + lane * VEC;
+    const int yw = ty_i * Tile::TY + wave * Tile::RY;
+    const int zs = a.lz_lo + tz_i * a.zchunk;
+    const int ze = min(zs + a.zchunk, a.lz_hi);
+    const WaferDen<double> den = wafer_den<double>(a, a.v_in_range != 0);
+    double r2 = 0.0, wh = 0.0, s = 0.0;
+    wafer_residual_cells<R, T, FIRST ? WAFER_CELLS_FILTER_FIRST : WAFER_CELLS_FILTER_NEXT>(g, xi, yw, zs, ze, cur, pv, den, cc, out, r2, wh, s, al, be);
+    if (FIRST) wafer_zero_outside_work<R, T, NW * 64>(a, out, n16, tid);
+}
+
+// ---- the largest V over the work cells (wafer_spectral_bound, wafer_batch_spectral_bound) -------------------------------------
+// A double as a 64-bit key whose unsigned order is the numeric order (a NaN sorts beyond the infinity of its sign),
+// and back.  The maximum of keys is exact, so the bound's V term has the bits of the largest stored value, widened.
+__host__ __device__ __forceinline__ unsigned long long wafer_order_key(double x)
+{
+    unsigned long long u;
+    __builtin_memcpy(&u, &x, 8);
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__host__ __device__ __forceinline__ double wafer_order_value(unsigned long long k)
+{
+    const unsigned long long u = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+    double x;
+    __builtin_memcpy(&x, &u, 8);
+    return x;
+}
+
+// One 64 x 4 tile of one work plane of v (a logical pointer): the workgroup's largest key into *word by at most one integer
+// atomicMax, skipped where the word, read first, is already as large (it only ever rises; the host starts it at 0, below every
+// key).  A workgroup beyond the geometry's tiles or planes leaves as a whole before any load or barrier.  Block (64, 4).
+template <typename T>
+__device__ __forceinline__ void wafer_v_max_tile(const WaferGeom &g, const T *__restrict__ v, int tile, int plane, unsigned long long *word)
+{
+    const int ntx = (g.nx + 63) / 64;
+    if (plane >= g.nzl || tile >= ntx * ((g.ny + 3) / 4)) return;
+    const int i = (tile % ntx) * 64 + threadIdx.x, j = (tile / ntx) * 4 + threadIdx.y;
+    unsigned long long key = 0;
+    if (i < g.nx && j < g.ny) key = wafer_order_key((double)v[(long long)(g.G + plane) * g.plane + (long long)(j + g.R) * g.pitch + g.xoff + g.R + i]);
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) zero[v] = (T)0;
-    for (long long q = (long long)blockIdx.x * (NW * 64) + tid; q < n16; q += (long long)gridDim.x * (NW * 64)) {
-        const long long e = q * VEC;
-        const int zp = (int)(e / g.plane) - g.gz;           // local plane, row and column of the vector's first element
-        const long long rem = e % g.plane;
-        const int yp = (int)(rem / g.pitch) - g.gy;
-        const int col = (int)(rem % g.pitch);
-        const bool work = zp >= a.lz_lo && zp < a.lz_hi && yp >= R && yp < R + g.ny && col >= x0 && col < x0 + g.nx;
-        if (!work) base[q] = zero;
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long k2 = __shfl_down(key, off, 64);
+        key = k2 > key ? k2 : key;
     }
+    __shared__ unsigned long long part[4];
+    if (threadIdx.x == 0) part[threadIdx.y] = key;
+    __syncthreads();
+    if (threadIdx.x != 0 || threadIdx.y != 0) return;
+#pragma unroll
+    for (int w = 1; w < 4; ++w) key = part[w] > key ? part[w] : key;
+    if (key > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, key);
+}
+
+// a context's: grid (tiles, planes)
+template <typename T>
+__global__ __launch_bounds__(256) void wafer_k_v_max(WaferGeom g, const T *__restrict__ v, unsigned long long *__restrict__ word)
+{
+    wafer_v_max_tile<T>(g, v, blockIdx.x, blockIdx.y, word);
 }

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(NW * 64) void wafer_k_batch_residual_sums(GS gs, co
     const WaferDen<double> den{m.den, m.zh, m.zl, m.short_forms != 0};
 
     double r2 = 0.0, wh = 0.0, s = 0.0;
-    wafer_residual_cells<R, T, false>(g, xi, yw, zs, ze, lj, static_cast<const T *>(m.v), den, th, nullptr, r2, wh, s);
+    wafer_residual_cells<R, T, WAFER_CELLS_SUMS>(g, xi, yw, zs, ze, lj, static_cast<const T *>(m.v), den, th, nullptr, r2, wh, s);
     const double r2s = wafer_block_sum<NW>(r2, red, tid);
     if (tid == 0) partials[(size_t)poff + (size_t)(j * 3 + 0) * nb + blockIdx.x] = r2s;
     const double whs = wafer_block_sum<NW>(wh, red, tid);

@@ -67,6 +67,8 @@ EXPORTS = [
     "wafer_batch_ritz_matrices", "wafer_batch_rotate_states", "wafer_batch_ritz", "wafer_batch_diag_ritz_counts",
     "wafer_residuals", "wafer_residual_to_phi", "wafer_batch_residuals", "wafer_batch_diag_residual_counts",
     "wafer_evolve_states", "wafer_batch_evolve_states", "wafer_batch_diag_store_step", "wafer_batch_diag_store_counts",
+    "wafer_filter_coefficients", "wafer_filter_states", "wafer_spectral_bound", "wafer_batch_filter_states", "wafer_batch_spectral_bound",
+    "wafer_batch_diag_filter_counts",
 ]
 RITZ_MAX = 8   # WAFER_RITZ_MAX
 RESIDUAL_SOURCES = {"states": 0, "phi": 1}   # WAFER_RESIDUAL_STATES, WAFER_RESIDUAL_PHI
@@ -298,6 +300,12 @@ def load_library():
     L.wafer_batch_evolve_states.argtypes = [vp, u8p, u32p, C.c_uint64]
     L.wafer_batch_diag_store_step.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.wafer_batch_diag_store_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.wafer_filter_coefficients.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, dp, dp, dp]
+    L.wafer_filter_states.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double]
+    L.wafer_spectral_bound.argtypes = [vp, dp]
+    L.wafer_batch_filter_states.argtypes = [vp, u8p, u32p, C.c_uint32, dp, dp, dp]
+    L.wafer_batch_spectral_bound.argtypes = [vp, u8p, dp]
+    L.wafer_batch_diag_filter_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if L.wafer_abi_version() != 1:
         raise ImportError("libwafer_hip.so ABI version mismatch")
     _lib = L
@@ -470,6 +478,108 @@ def block_solve_loop(step, ritz, residuals, k, tolerance: float, steps_per_block
                 going.append(m)
     for m in going:
         out[m]["message"] = "member %d: max_blocks = %d reached with max diff %g >= tolerance %g" % (m, max_blocks, float(np.max(out[m]["diff"])), tolerance)
+    return out
+
+
+# ---- Chebyshev-filtered subspace iteration on the state stores: the driver, written once ----------------------------------------
+FILTER_MAX_DEGREE = 256
+FILTER_CONVERGED, FILTER_MAX_BLOCKS, FILTER_DEPENDENT, FILTER_NO_INTERVAL = WAFER_OK, WAFER_ERR_MAX_STEP, WAFER_ERR_STATE, WAFER_ERR_INVALID
+
+
+def filter_coefficients(degree: int, a: float, b: float, a0: float):
+    """(al, be, cc): wafer_filter_coefficients -- host only, no GPU: the `degree` steps' coefficients of the scaled Chebyshev filter
+    that damps [a, b] and has magnitude 1 at a0 < a"""
+    L = load_library()
+    n = max(int(degree), 1)
+    al, be, cc = np.zeros(n), np.zeros(n), np.zeros(1)
+    rc = L.wafer_filter_coefficients(int(degree), float(a), float(b), float(a0), _dp(al), _dp(be), _dp(cc))
+    if rc != 0:
+        raise WaferError(rc, L.wafer_last_error().decode())
+    return al, be, float(cc[0])
+
+
+def filtered_solve_loop(bound, filt, ritz, residuals, k, tolerance: float, degree: int, max_blocks: int, guard: int = 1) -> list:
+    """Chebyshev-filtered subspace iteration over a set of members, backend-free (Context.solve_filtered, Batch.solve_filtered and the
+    numpy model of the tests all call this; block_solve_loop's sibling: its step callable is not told the last Ritz values).  k: one
+    state count per member (0 or None: the member takes no part); k[m] - guard >= 1.  Four callables over the members still `going`:
+        bound(going)                an upper bound of H's spectrum -> {m: ub}
+        filt(going, degree, iv)     applies the degree-`degree` filter with iv[m] = (a, b, a0) to the first k[m] stored states
+        ritz(going)                 one Rayleigh-Ritz step on each -> {m: (status, evals)}; WAFER_ERR_STATE where it fails
+        residuals(going, theta)     rho of the rotated states with theta[m] = the Ritz values -> {m: rho}
+    One Ritz step on the starts; then per block and member a0 = evals[0], a = evals[k - 1], b = ub, the filter, Ritz, residuals; a
+    row {"block", "steps" (filter steps so far), "evals", "diff", "rho"}.  A member is done when rho_j < tolerance for the first
+    k - guard states: the polynomial is in H, so the fixed points are H's eigenvectors and rho decides.  The guard states are never
+    waited for: their gap to the damped interval [evals[k - 1], ub] is zero by construction.
+    -> per member None, or {"status", "message", "blocks", "steps", "evals", "diff", "rho", "rows"}: FILTER_CONVERGED (WAFER_OK),
+    FILTER_MAX_BLOCKS (WAFER_ERR_MAX_STEP), FILTER_DEPENDENT (WAFER_ERR_STATE: Ritz found the states non-finite or dependent; the
+    message says to lower `degree`) or FILTER_NO_INTERVAL (WAFER_ERR_INVALID: evals[k - 1] <= evals[0], or evals[k - 1] >= ub)."""
+    ks = [0 if x is None else int(x) for x in k]
+    degree, max_blocks, tolerance, guard = int(degree), int(max_blocks), float(tolerance), int(guard)
+    if degree < 1 or degree > FILTER_MAX_DEGREE or max_blocks < 1:
+        raise ValueError("degree must be 1 .. %d and max_blocks >= 1" % FILTER_MAX_DEGREE)
+    if not tolerance > 0.0:
+        raise ValueError("tolerance must be > 0")
+    if guard < 1 or any(n > 0 and n - guard < 1 for n in ks):
+        raise ValueError("guard must be >= 1 and every k - guard >= 1")
+    out = [None if n == 0 else dict(status=FILTER_MAX_BLOCKS, message="", blocks=0, steps=0, evals=None, diff=None, rho=None, rows=[])
+           for n in ks]
+    going = [m for m, n in enumerate(ks) if n > 0]
+    if not going:
+        return out
+    ub = bound(list(going))
+
+    def solve(members, block):
+        """Ritz on `members`: evals and diff into out, -> those it succeeded on"""
+        solved = ritz(list(members))
+        alive = []
+        for m in members:
+            status, evals = solved[m]
+            o = out[m]
+            if status != WAFER_OK:
+                o["status"] = FILTER_DEPENDENT
+                o["message"] = ("member %d: after block %d (%d filter steps) the Ritz step found the %d states non-finite or linearly "
+                                "dependent: lower degree (now %d)" % (m, block, block * degree, ks[m], degree))
+                continue
+            evals = np.array(evals, dtype=np.float64)[:ks[m]]
+            o["diff"] = np.full(ks[m], np.inf) if o["evals"] is None else np.abs(evals - o["evals"])
+            o["evals"] = evals
+            alive.append(m)
+        return alive
+
+    going = solve(going, 0)
+    for block in range(1, max_blocks + 1):
+        iv, ready = {}, []
+        for m in going:
+            e = out[m]["evals"]
+            if not e[-1] > e[0]:
+                out[m]["status"] = FILTER_NO_INTERVAL
+                out[m]["message"] = "member %d: block %d: evals[%d] = %r <= evals[0] = %r: no interval to damp" % (m, block, ks[m] - 1, e[-1], e[0])
+            elif not e[-1] < ub[m]:
+                out[m]["status"] = FILTER_NO_INTERVAL
+                out[m]["message"] = "member %d: block %d: evals[%d] = %r >= the spectral bound %r" % (m, block, ks[m] - 1, e[-1], ub[m])
+            else:
+                iv[m] = (float(e[-1]), float(ub[m]), float(e[0]))
+                ready.append(m)
+        if not ready:
+            going = []
+            break
+        filt(list(ready), degree, iv)
+        for m in ready:
+            out[m]["blocks"], out[m]["steps"] = block, block * degree
+        alive = solve(ready, block)
+        rho = residuals(list(alive), {m: out[m]["evals"] for m in alive}) if alive else {}
+        going = []
+        for m in alive:
+            o = out[m]
+            o["rho"] = np.array(rho[m], dtype=np.float64)[:ks[m]]
+            o["rows"].append(dict(block=block, steps=o["steps"], evals=o["evals"].copy(), diff=o["diff"].copy(), rho=o["rho"].copy()))
+            if float(np.max(o["rho"][:ks[m] - guard])) < tolerance:
+                o["status"] = FILTER_CONVERGED
+            else:
+                going.append(m)
+    for m in going:
+        out[m]["message"] = "member %d: max_blocks = %d reached with max rho %g >= tolerance %g" % (
+            m, max_blocks, float(np.max(out[m]["rho"][:ks[m] - guard])), tolerance)
     return out
 
 
@@ -729,6 +839,35 @@ class Context:
             return {0: self.residuals(k, theta=theta[0])["rho"]}
 
         return block_solve_loop(step, ritz, residuals, [k], tolerance, steps_per_block, max_blocks)[0]
+
+    # -- filtering w_store: Chebyshev-filtered subspace iteration (include/wafer_hip.h) ------------------
+    def filter_states(self, k: int, degree: int, a: float, b: float, a0: float) -> None:
+        """the degree-`degree` scaled Chebyshev polynomial of H that damps [a, b] and has magnitude 1 at a0 < a, applied to the first k
+        stored states (one launch per state and step).  phi and the current buffer are left alone."""
+        self._check(self._L.wafer_filter_states(self._h, int(k), int(degree), float(a), float(b), float(a0)))
+
+    def spectral_bound(self) -> float:
+        """Gershgorin's upper bound of H's spectrum: W / den + max V over the work cells"""
+        ub = np.zeros(1)
+        self._check(self._L.wafer_spectral_bound(self._h, _dp(ub)))
+        return float(ub[0])
+
+    def solve_filtered(self, k: int, tolerance: float, degree: int, max_blocks: int, guard: int = 1) -> dict:
+        """Chebyshev-filtered subspace iteration on the first k stored states (filtered_solve_loop): ritz(k), then per block
+        filter_states(k, degree, evals[k - 1], spectral_bound(), evals[0]), ritz(k), residuals(k, theta=evals) -- until rho < tolerance
+        on the first k - guard states.  -> {"status", "message", "blocks", "steps", "evals", "diff", "rho", "rows"}"""
+        k = int(k)
+
+        def ritz(going):
+            try:
+                return {0: (WAFER_OK, self.ritz(k)["evals"])}
+            except WaferError as e:
+                if e.code != WAFER_ERR_STATE:
+                    raise
+                return {0: (WAFER_ERR_STATE, None)}
+
+        return filtered_solve_loop(lambda going: {0: self.spectral_bound()}, lambda going, n, iv: self.filter_states(k, n, *iv[0]), ritz,
+                                   lambda going, theta: {0: self.residuals(k, theta=theta[0])["rho"]}, [k], tolerance, degree, max_blocks, guard)[0]
 
     # -- residuals of w_store and of phi (include/wafer_hip.h) -------------------------------------------
     def residuals(self, k: int | None = None, theta=None, source: str = "states") -> dict:
@@ -1337,6 +1476,61 @@ class Batch:
         n = C.c_uint64(0)
         self._check(self._L.wafer_batch_diag_store_counts(self._h, C.byref(n)))
         return n.value
+
+    def filter_states(self, degree: int, a, b, a0, k=None, active=None) -> None:
+        """Context.filter_states(k[m], degree, a[m], b[m], a0[m]) for every listed member (active[m] != 0; None: all) in ONE launch per
+        recurrence step, whatever the members and shapes (plus one batched copy where `degree` is odd: filter_counts()).  a, b, a0: one
+        entry per member, or a number for everyone.  phi, the other states and the members not listed keep every bit."""
+        act = self._mask(active)
+        ks = self._store_ks(k, act)
+        B = len(self.members)
+        iv = [np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (B,))) for x in (a, b, a0)]
+        self._check(self._L.wafer_batch_filter_states(self._h, self._u8(act), (C.c_uint32 * B)(*ks), int(degree), _dp(iv[0]), _dp(iv[1]), _dp(iv[2])))
+
+    def spectral_bound(self, active=None) -> list:
+        """Context.spectral_bound() of every listed member (None for the others): one launch and one read-back"""
+        act = self._mask(active)
+        ub = np.full(len(self.members), np.nan)
+        self._check(self._L.wafer_batch_spectral_bound(self._h, self._u8(act), _dp(ub)))
+        return [float(ub[m]) if act is None or act[m] else None for m in range(len(self.members))]
+
+    def filter_counts(self) -> tuple:
+        """(launches of filter_states: `degree` per call, plus one where it is odd; launches of spectral_bound) since creation"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_filter_counts(self._h, C.byref(n), C.byref(r)))
+        return n.value, r.value
+
+    def solve_filtered(self, k, tolerance: float, degree: int, max_blocks: int, guard: int = 1, active=None) -> list:
+        """Context.solve_filtered for every listed member at once (filtered_solve_loop): per block one filter_states, one ritz and one
+        residuals call over the members still going, each with its own interval; a member whose first k - guard states have
+        rho < tolerance leaves the active set and stays as it is.  -> per member the dict of Context.solve_filtered, None for members
+        not listed (or with k 0)."""
+        act = self._mask(active)
+        ks = self._store_ks(k, act)
+        B = len(self.members)
+
+        def mask(going):
+            m = np.zeros(B, dtype=np.uint8)
+            m[going] = 1
+            return m
+
+        def bound(going):
+            ub = self.spectral_bound(active=mask(going))
+            return {m: ub[m] for m in going}
+
+        def filt(going, n, iv):
+            cols = [[iv[m][q] if m in iv else 0.0 for m in range(B)] for q in range(3)]
+            self.filter_states(n, cols[0], cols[1], cols[2], ks, active=mask(going))
+
+        def ritz(going):
+            r = self.ritz(ks, active=mask(going))
+            return {m: (r[m]["status"], r[m]["evals"]) for m in going}
+
+        def residuals(going, theta):
+            r = self.residuals(ks, theta=[theta.get(m) for m in range(B)], active=mask(going))
+            return {m: r[m]["rho"] for m in going}
+
+        return filtered_solve_loop(bound, filt, ritz, residuals, ks, tolerance, degree, max_blocks, guard)
 
     def solve_block(self, k, tolerance: float, steps_per_block: int, max_blocks: int, active=None) -> list:
         """Context.solve_block for every listed member at once (block_solve_loop): per block one evolve_states, one ritz and one
