@@ -1,7 +1,7 @@
 """A batch's lazily made buffer groups, one life each: create a batch, use ONE group (or none), close it -- and last one batch that
 uses all of them in sequence, held bit for bit to a second, fresh batch running the same sequence in the same process.
 
-The groups are what wafer_engine_batch.hip makes on first use: the sequential Gram-Schmidt buffers (norm2), the one-pass buffers grown
+The groups are what wafer_engine_batch.hip and wafer_engine_batch_stores.hip make on first use: the sequential Gram-Schmidt buffers (norm2), the one-pass buffers grown
 from them (set_gs_variant(1) and an excited step), the resample scratch and its growth, the Rayleigh-Ritz tables, the residual tables
 (on phi, with no ritz call before), the shadows, store_k and the copy table of evolve_states with an odd step count, and the store's
 slots shrinking and regrowing (clear_states after three pushes, then one push).  A batch that closes after any one of them must free

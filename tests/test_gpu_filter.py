@@ -226,6 +226,63 @@ def test_a_state_does_not_depend_on_k_or_on_who_else_is_listed(wa):
     assert same(solo[0][0], ls[0]) and same(solo[2][0], ls[0]) and not same(full[0][7], ls[7])
 
 
+@pytest.mark.parametrize("shapes,dtype,ext", [(SHAPES, "f64", 1), (SHAPES, "f32", 3), ([SHAPES[0]] * 3, "f64", 1)])
+def test_evolve_states_and_filter_states_interleaved_on_one_batch(wa, shapes, dtype, ext):
+    """evolve_states and filter_states are two callers of one host pass and share its tables (the workgroup table of the listed members,
+    the per-member k, the shadows, the copy table): the two calls alternate on one batch with changing k and lists, odd and even
+    counts, and after every call every stored state of every member holds the bits one Context per member holds after the same
+    calls; phi, V, pot_sub and the states from k[m] on stay, and each call's launches go to its own counter."""
+    B, nst, seed = 3, [3, 5, 4], 900 + ext
+    calls = [("evolve", 3, (3, 0, 4), None), ("filter", 3, (2, 5, 0), (1, 1, 0)), ("evolve", 2, None, None), ("filter", 4, (3, 5, 4), None)]
+    members = [member(wa, shape, ext, dtype, m) for m, shape in enumerate(shapes)]
+    states = arrays_for(members, dtype, ext, nst, seed)
+    phis = [a[0] for a in arrays_for(members, dtype, ext, [1] * B, seed + 5000)]
+    ivs = [interval(m) for m in range(B)]
+    ctxs = [wa.Context(p) for p in members]
+    try:
+        for m, ctx in enumerate(ctxs):
+            ctx.set_potential("Harmonic")
+            ctx.upload_phi(phis[m])
+            for j, l in enumerate(states[m]):
+                ctx.load_state(j, l)
+        with make_batch(wa, members, ["Harmonic"] * B, states, phis) as b:
+            assert b.num_shapes() == len(set(shapes))
+            for m in range(B):
+                set_sub(b, members[m], m, seed)
+            vs = [b.download_array(m, "v") for m in range(B)]
+            subs = [sub_of(b, m) for m in range(B)]
+            held = [[l.copy() for l in states[m]] for m in range(B)]
+            n_store, n_filter = 0, 0
+            assert b.store_counts() == 0 and b.filter_counts()[0] == 0
+            for c, (what, n, k, active) in enumerate(calls):
+                ks = [(nst[m] if k is None else k[m]) if active is None or active[m] else 0 for m in range(B)]
+                if what == "evolve":
+                    b.evolve_states(n, k, active=active)
+                    n_store += n + n % 2
+                else:
+                    b.filter_states(n, [iv[0] for iv in ivs], [iv[1] for iv in ivs], [iv[2] for iv in ivs], k, active=active)
+                    n_filter += n + n % 2
+                assert (b.store_counts(), b.filter_counts()[0]) == (n_store, n_filter), (c, what)
+                assert b.last_evolve_ms()[1] == n
+                for m in range(B):
+                    if ks[m] and what == "evolve":
+                        ctxs[m].evolve_states(ks[m], n)
+                    elif ks[m]:
+                        ctxs[m].filter_states(ks[m], n, *ivs[m])
+                    for j in range(nst[m]):
+                        got = b.download_state(m, j)
+                        assert same(got, ctxs[m].download_state(j)), ("context", c, what, shapes[m], dtype, ext, m, j)
+                        assert same(got, held[m][j]) == (j >= ks[m]), ("from k on, and only there, a state stays", c, what, m, j)
+                        assert np.all(np.isfinite(got)) and np.any(got)
+                        held[m][j] = got
+                    assert same(b.download_phi(m), phis[m]), ("phi", c, m)
+                    assert same(b.download_array(m, "v"), vs[m]), ("V", c, m)
+                    assert same_sub(sub_of(b, m), subs[m]), ("pot_sub", c, m)
+    finally:
+        for ctx in ctxs:
+            ctx.close()
+
+
 # ---- 2. contexts ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype,ext", COMBOS)
 def test_context_bits_are_the_models_and_a_one_member_batchs(wa, dtype, ext):

@@ -207,26 +207,14 @@ static inline WaferBatchStorePlan wafer_batch_store_plan(uint64_t n_steps, uint3
 }
 
 // ---- filtering the state stores (wafer_batch_filter_states, wafer_store_filter_batch.hip.h; wafer_filter_states) ---------------
-// The launches of a call of `degree` steps on slots and shadow slots (the context's one shadow array alike): step 1 reads the
+// The launches of a call of `degree` >= 1 steps on slots and shadow slots (the context's one shadow array alike): step 1 reads the
 // slots and writes the shadows; step i >= 2 reads the set step i - 1 wrote and writes its result over the iterate before last, in
-// place, which lies in the other set.  So step i reads the slots when i is odd and the shadows when i is even, and after an odd
-// degree the result stands in the shadows: one trailing copy brings it back (a batch), or the two pointers change places (a context).
-struct WaferBatchFilterPlan {
-    uint64_t steps = 0, launches = 0;
-    int groups = 0;
-    bool copy_back = false;
-};
-static inline bool wafer_batch_filter_src_is_shadow(uint64_t i) { return (i & 1) == 0; }   // i = 1 .. degree
-static inline WaferBatchFilterPlan wafer_batch_filter_plan(uint32_t degree, uint32_t max_k)
-{
-    WaferBatchFilterPlan p;
-    p.steps = degree;
-    p.groups = wafer_batch_store_groups(max_k);
-    if (max_k == 0) return p;
-    p.copy_back = (degree & 1) != 0;
-    p.launches = p.steps + (p.copy_back ? 1 : 0);
-    return p;
-}
+// place, which lies in the other set.  So step i = 1 .. degree reads what step i - 1 of the store plan reads, and the call is the
+// store plan of `degree` steps: after an odd degree the result stands in the shadows and one trailing copy brings it back (a batch),
+// or the two pointers change places (a context).
+using WaferBatchFilterPlan = WaferBatchStorePlan;
+static inline bool wafer_batch_filter_src_is_shadow(uint64_t i) { return wafer_batch_store_src_is_shadow(i - 1); }
+static inline WaferBatchFilterPlan wafer_batch_filter_plan(uint32_t degree, uint32_t max_k) { return wafer_batch_store_plan(degree, max_k); }
 
 // ---- the batch's layout ------------------------------------------------------------------------------------------------------
 // The distinct geometries of the members' shapes (nxyz: nx, ny, nz of member m at [3 m ..]) in order of first appearance, each the

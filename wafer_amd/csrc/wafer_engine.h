@@ -4,7 +4,8 @@
 //   wafer_engine_schedules.hip  which kernel advances what: variants, workgroup tables, launches, reductions, wafer_evolve, observables
 //   wafer_engine_comm.hip       z-slabs: halo exchange through the hooks, the single-launch pass, peer stores
 //   wafer_engine_solve.hip      grid.rs:50-246 for one state (host loop)
-//   wafer_engine_batch.hip      batched ensembles (wafer_batch_*): the batch, its member views, every batched call
+//   wafer_engine_batch.hip      batched ensembles (wafer_batch_*): the batch, its member views, set-up, steps, Gram-Schmidt, solve
+//   wafer_engine_batch_stores.hip  ... their Rayleigh-Ritz, residuals, store steps and filter; both units share wafer_engine_batch.h
 //   wafer_buffers.h             the owning holders of the batch's device and pinned buffers (plain C++, no HIP header)
 //   wafer_passes.h              which pass of wafer_evolve comes next, from what every rank of a decomposed run shares (plain C++)
 #pragma once

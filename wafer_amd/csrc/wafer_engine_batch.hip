@@ -33,210 +33,15 @@
 // its partials come from wafer_batch_gs_partition (wafer_batch_plan.h; `gsp`, and in its WaferBatchMember).  On several shapes they
 // are opt-in at creation (wafer_batch_create_mixed_states: `mixed_states`); a batch of several shapes made by
 // wafer_batch_create_mixed refuses the excited-state calls as it always has (refuse_mixed).
-// Rayleigh-Ritz on the stores (wafer_batch_ritz_matrices, wafer_batch_rotate_states, wafer_batch_ritz; kernels: wafer_ritz_batch.hip.h,
-// wafer_tu_ritz_batch.hip): a context's wafer_ritz_* for every listed member with its own k -- one sums launch, one reduce and one
-// read-back, the solves on the host (wafer_ritz.h), one rotation launch -- from a per-call table of (member, k, partials offset, span).
-// Residuals (wafer_batch_residuals; kernels: wafer_residual_batch.hip.h, wafer_tu_residual_batch.hip): a context's wafer_residuals for
-// every listed member with its own k and theta, on the stores or on phi -- one sums launch, one reduce and one read-back per pass.
-// Stepping the stores (wafer_batch_evolve_states; kernels: wafer_store_step_batch.hip.h, wafer_tu_store_step_batch*.hip): the first k[m]
-// stored states of every listed member advance by n plain steps, one launch per step over the listed members' workgroup table,
-// between the slots and shadow slots laid out as they are; an odd n ends with one batched copy back into the slots.
-// Filtering the stores (wafer_batch_filter_states; kernels: wafer_store_filter_batch.hip.h, wafer_tu_store_filter_batch*.hip): a
-// degree-m Chebyshev polynomial of H itself on the same states, tables and two sets of slots, one launch per recurrence step, each
-// member with its own interval; wafer_batch_spectral_bound gives the interval's upper end from one launch and one read-back.
+// The calls on the state stores beyond Gram-Schmidt -- Rayleigh-Ritz, residuals, stepping and filtering the stores, the spectral
+// bound -- are wafer_engine_batch_stores.hip; what the two units share is wafer_engine_batch.h.
 #include <memory>
-#include "wafer_engine.h"
+#include "wafer_engine_batch.h"
 #include "wafer_stencil_lds.hip.h"
-#include "wafer_stencil_batch.hip.h"
 #include "wafer_gs_batch.hip.h"
 #include "wafer_resample_batch.hip.h"
-#include "wafer_setup_batch.hip.h"
-#include "wafer_ritz_batch.hip.h"
-#include "wafer_residual_batch.hip.h"
-#include "wafer_store_step_batch.hip.h"
-#include "wafer_store_filter_batch.hip.h"
-#include "wafer_filter.h"
-#include "wafer_ritz.h"
-#include "wafer_buffers.h"
 
-// the engine's two memory policies and its copy policy (wafer_buffers.h), the holders on them, and a holder's status through HIP_TRY
-struct DeviceMem {
-    static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
-    static void free(void *p) { (void)hipFree(p); }
-};
-struct PinnedMem {
-    static int alloc(void **p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
-    static void free(void *p) { (void)hipHostFree(p); }
-};
-struct StreamCopy {
-    using stream = hipStream_t;
-    static int copy(void *dst, const void *src, size_t n, bool up, stream s) { return (int)hipMemcpyAsync(dst, src, n, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, s); }
-};
-template <typename T> using DevArray = Array<T, DeviceMem>;
-template <typename T> using DevGrow = GrowArray<T, DeviceMem>;
-template <typename T> using Mirror = HostDev<T, DeviceMem, PinnedMem, StreamCopy>;
-#define BUF_TRY(expr) HIP_TRY((hipError_t)(expr))
-// by dtype: its name in the diag_* strings, and the kernels' <.., T, C>
-constexpr const char *DTYPE_NAMES[] = {"f64", "f32", "f32fast"};
-constexpr const char *KERNEL_TYPES[] = {"double,double", "float,double", "float,float"};
-
-struct wafer_batch {
-    // The stream, declared first: it goes last, behind every buffer.
-    struct Stream {
-        hipStream_t h = nullptr;
-        Stream() = default;
-        Stream(const Stream &) = delete;
-        ~Stream()
-        {
-            if (h) (void)hipStreamDestroy(h);
-        }
-        operator hipStream_t() const { return h; }
-    } s;
-    uint32_t n = 0;
-    std::vector<wafer_params> P;
-    int device = 0, num_cus = 256;
-    WaferTuning tune;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    // the layout (wafer_batch_layout): the distinct geometries in order of first appearance.  mixed: more than one
-    std::vector<WaferGeom> geoms;
-    std::vector<int> shape_of;                // member m's entry in geoms
-    std::vector<size_t> off;                  // member m's element offset in each array allocation
-    size_t cells = 0;                         // elements of each array allocation: every member's total, end to end
-    DevArray<WaferGeom> geoms_dev;
-    bool mixed = false;
-    bool mixed_states = false;                // several shapes WITH state stores (wafer_batch_create_mixed_states)
-    WaferBatchGsPartition gsp;                // every member's Gram-Schmidt partition and the places of its partials
-    size_t n2_doubles = 0;                    // every member's wafer_batch_norm2 partials (mem[].n2_nb), end to end
-    const WaferGeom &g() const { return geoms[0]; }               // what every shape shares (R, G), and THE geometry of one shape
-    const WaferGeom &geom(uint32_t m) const { return geoms[shape_of[m]]; }
-    std::string kernel_name = "wafer_k_batch_step";
-    int dtype = WAFER_F64;                    // every member's (check_member)
-    bool f32 = false;                         // float storage (f32 and f32fast)
-    size_t esz = 8;                           // bytes per element of every array and store slot
-    DevArray<char> alloc[4];                  // phi[0], phi[1], V, pot_sub: cells * esz bytes each
-    std::vector<wafer_ctx *> views;
-    Mirror<double> view_scal;                 // SCAL_SLOTS per view
-    // device tables
-    std::vector<WaferBatchMember> mem;
-    DevArray<WaferBatchMember> mem_dev;
-    // a workgroup table on the device, with the active set and the steps per pass it was built for
-    struct BlockTable {
-        std::vector<WaferBatchBlock> host;
-        DevGrow<WaferBatchBlock> dev;
-        std::vector<uint8_t> key;
-        int K = 0;
-    };
-    BlockTable blk, blkk;                     // the one-step kernel's, and the fused pass's (wafer_k_batch_stepk) for the same active set
-    BlockTable blks;                          // the store step's (wafer_k_batch_store_step): the one-step table over the listed members with k > 0
-    int step_variant = -1;                    // wafer_batch_set_step_variant
-    uint64_t n_fused_passes = 0, n_single_steps = 0;   // launches since creation (wafer_batch_diag_passes)
-    Mirror<int> act;
-    Mirror<int> sym;                          // [member]: the constraints of the last wafer_batch_symmetrise
-    // observables: every member on the single context's partition of its shape (mem[].obs_*)
-    int swz = 0;
-    DevArray<double> partials;                // member m's [4][obs_nb] at mem[m].obs_off
-    Mirror<double> sums;                      // [member][4]
-    Mirror<double> n2;                        // [member]
-    uint64_t last_steps = 0;
-    bool timing_valid = false;
-    // w_store: slot l of every member in one allocation laid out as the arrays are, made by the first push or load that needs it
-    std::vector<DevArray<char>> slots;
-    std::vector<uint32_t> nst;                // states member m holds
-    // excited states: norm2 at gs_scal[m * gs_stride], the overlap with state l at [m * gs_stride + 1 + l]; made at first use
-    int gs_stride = 0;
-    DevGrow<double> gs_partials;              // member m's rows at gsp.row_off(m, rows); wafer_batch_norm2's at mem[m].n2_off (partials_doubles)
-    Mirror<double> gs_scal;
-    // the one-pass form (wafer_batch_set_gs_variant); everything below is made by its first use (ensure_onepass)
-    int gs_variant = -1;
-    uint64_t n_onepass = 0, n_sequential = 0;   // excited steps and orthogonalise calls in each form (wafer_batch_diag_gs_steps)
-    bool onepass_ready = false;               // gs_partials holds WAFER_GS_ONE_ROWS rows per member, the Gram storage exists
-    DevArray<double> gram;                    // [member][WAFER_MAX_LOW^2]: G_ji = <state j | state i>, i < j
-    DevArray<double> gram_partials;           // member m's [WAFER_GRAM_PAIRS][gsp.nb[m]] at gsp.row_off(m, WAFER_GRAM_PAIRS)
-    Mirror<int> gram_list;                    // the members to recompute, then their state counts: 2 n ints
-    std::vector<uint8_t> gram_stale;          // member m's store changed since its Gram matrix was formed
-    // wafer_batch_resample: a host source as uploaded ([sx][sy][sz]) and, behind it, transposed to x-fastest; grown on demand
-    DevGrow<double> rs_scratch;
-    hipEvent_t rs_start = nullptr, rs_stop = nullptr;   // around the last call's upload, transpose and launch (wafer_batch_last_resample_ms)
-    bool rs_timing_valid = false;
-    // batched set-up (wafer_setup_batch.hip.h): one record per listed member, and the range check's three words per listed member --
-    // on the device, their start values (~0, 0, 0) and the read-back, pinned; all n entries long, made at creation
-    Mirror<WaferBatchSetupRec> setup;
-    Mirror<unsigned long long> vchk;
-    Array<unsigned long long, PinnedMem> vchk_init;
-    uint64_t n_setup_launches = 0, n_setup_readbacks = 0;   // of the batched set-up paths since creation (wafer_batch_diag_setup_counts)
-    // Rayleigh-Ritz on the stores (wafer_ritz_batch.hip.h); everything below is made by the first call (ensure_ritz)
-    Mirror<WaferBatchRitzRec> ritz_rec;       // the per-call table, n entries
-    DevGrow<double> ritz_partials;            // the listed members' 2 k^2 rows of obs_nb partials end to end; grown on demand
-    Mirror<double> ritz_sums;                 // [member][2][WAFER_RITZ_MAX^2]
-    Mirror<double> ritz_coef;                 // [member][WAFER_RITZ_MAX^2]
-    uint64_t n_ritz_launches = 0, n_ritz_readbacks = 0;       // of the three calls since creation (wafer_batch_diag_ritz_counts)
-    // residuals (wafer_residual_batch.hip.h); made by the first call (ensure_residual).  The partials live in ritz_partials.
-    Mirror<WaferBatchResidualRec> resid_rec;  // the per-call table, n entries
-    Mirror<double> resid_sums;                // [member][3 WAFER_RITZ_MAX]: r2, wh, s of column j at j * 3
-    uint64_t n_resid_launches = 0, n_resid_readbacks = 0;     // of wafer_batch_residuals since creation (wafer_batch_diag_residual_counts)
-    // stepping the stores (wafer_store_step_batch.hip.h): shadow l is laid out as slot l is, zeroed, made by the first call that needs it
-    std::vector<DevArray<char>> shadows;
-    Mirror<int> store_k;                      // [member]: the call's k (0: not listed)
-    uint64_t n_store_launches = 0;                            // of wafer_batch_evolve_states since creation (wafer_batch_diag_store_counts)
-    // filtering the stores (wafer_store_filter_batch.hip.h), made by the first call: every step's al, be, cc of every member, step i's
-    // at (i - 1) * n; and the spectral bound's one word per listed member with its pinned zeros
-    Mirror<WaferFilterCoef> filt_coef;
-    Mirror<unsigned long long> vmax;
-    uint64_t n_filter_launches = 0, n_bound_launches = 0;     // of wafer_batch_filter_states / wafer_batch_spectral_bound since creation
-    // Lets a batch go: the stream drains, the views go -- they borrow every array and the stream, except a and b (ensure_ab) -- then
-    // the events; behind this body every holder frees its block, and the stream goes last.
-    ~wafer_batch()
-    {
-        (void)hipSetDevice(device);
-        if (s) (void)hipStreamSynchronize(s);
-        for (wafer_ctx *v : views) {
-            for (void *p : {v->a, v->b})
-                if (p) (void)hipFree(alloc_base(v, p));
-            delete v;
-        }
-        for (hipEvent_t e : {ev_start, ev_stop, rs_start, rs_stop})
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-namespace {
-
-int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0, bool same_shape = true)
-{
-    if (m->struct_size != sizeof(wafer_params))
-        return fail(WAFER_ERR_INVALID, "member %u: wafer_params.struct_size %u != %zu (ABI mismatch)", i, m->struct_size, sizeof(wafer_params));
-    if (m->nx < 1 || m->ny < 1 || m->nz < 1) return fail(WAFER_ERR_INVALID, "member %u: grid size must be >= 1", i);
-    if (m->central_difference < 1 || m->central_difference > 3)
-        return fail(WAFER_ERR_INVALID, "member %u: central_difference must be 1 (Three), 2 (Five) or 3 (SevenPoint)", i);
-    if (m->dtype != WAFER_F64 && m->dtype != WAFER_F32 && m->dtype != WAFER_F32_FAST)
-        return fail(WAFER_ERR_INVALID, "member %u: bad dtype %d (f64 = 0, f32 = 1, f32fast = 2)", i, (int)m->dtype);
-    if (m->z_count != 0) return fail(WAFER_ERR_INVALID, "member %u: z_count must be 0 (a batch holds no z-slabs)", i);
-    if (!(m->dn > 0) || !(m->dt > 0) || !(m->mass > 0)) return fail(WAFER_ERR_INVALID, "member %u: dn, dt, mass must be > 0", i);
-    const double den = wafer_stencil_den(m->central_difference, m->dn, m->mass);
-    if (!std::isnormal(den) || !std::isnormal(1.0 / den))
-        return fail(WAFER_ERR_INVALID, "member %u: dn^2 * mass = %g is outside the range of normal doubles (or its reciprocal is)", i,
-                    m->dn * m->dn * m->mass);
-    if (!(m->flags & WAFER_FLAG_SKIP_DT_CHECK) && m->dt > m->dn * m->dn / 3.)   // config.rs:362-365
-        return fail(WAFER_ERR_INVALID, "member %u: LargeDt: dt must be <= dn^2/3 (config.rs:363)", i);
-    if (m->halo_depth != 0 && (int)m->halo_depth < m->central_difference)
-        return fail(WAFER_ERR_INVALID, "member %u: halo_depth must be >= ext", i);
-    if (m0) {
-        if (m->dtype != m0->dtype)
-            return fail(WAFER_ERR_INVALID, "member %u: dtype = %d differs from member 0's %d (a batch holds one dtype)", i, (int)m->dtype, (int)m0->dtype);
-        if (same_shape) {   // (wafer_batch_create_mixed: every member its own)
-            if (m->nx != m0->nx) return fail(WAFER_ERR_INVALID, "member %u: nx = %u differs from member 0's %u", i, m->nx, m0->nx);
-            if (m->ny != m0->ny) return fail(WAFER_ERR_INVALID, "member %u: ny = %u differs from member 0's %u", i, m->ny, m0->ny);
-            if (m->nz != m0->nz) return fail(WAFER_ERR_INVALID, "member %u: nz = %u differs from member 0's %u", i, m->nz, m0->nz);
-        }
-        if (m->central_difference != m0->central_difference)
-            return fail(WAFER_ERR_INVALID, "member %u: central_difference = %d differs from member 0's %d", i, m->central_difference,
-                        m0->central_difference);
-        if (m->device != m0->device) return fail(WAFER_ERR_INVALID, "member %u: device = %d differs from member 0's %d", i, m->device, m0->device);
-        if (m->halo_depth != m0->halo_depth)   // (the batch's one geometry is built with it)
-            return fail(WAFER_ERR_INVALID, "member %u: halo_depth = %u differs from member 0's %u", i, m->halo_depth, m0->halo_depth);
-    }
-    return WAFER_OK;
-}
+namespace wafer_eng __attribute__((visibility("hidden"))) {
 
 int check_member_index(const wafer_batch *b, uint32_t m)
 {
@@ -251,19 +56,6 @@ int refuse_mixed(const wafer_batch *b, const char *call)
     if (!b->mixed || b->mixed_states) return WAFER_OK;
     return fail(WAFER_ERR_INVALID, "%s: not available on a mixed-shape batch (%zu distinct shapes): excited states need one shape per batch",
                 call, b->geoms.size());
-}
-
-// every active member has phi (and, with need_pot, a potential: `what` ends that message) and at least wnum stored states
-int check_ready(const wafer_batch *b, const uint8_t *active, bool need_pot, const char *what, uint32_t wnum)
-{
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        const wafer_ctx *c = b->views[m];
-        if (need_pot && (!c->have_pot || !c->have_phi)) return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set%s", m, what);
-        if (!c->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
-        if (wnum > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: wnum %u but w_store holds %u states", m, wnum, b->nst[m]);
-    }
-    return WAFER_OK;
 }
 
 // the member table as the views stand now (potential range, pot_sub, current buffer), to the device if it changed
@@ -317,36 +109,11 @@ int build_blocks(wafer_batch *b, wafer_batch::BlockTable &t, const uint8_t *acti
     return WAFER_OK;
 }
 
-// Steps per launch of a ground-state evolve: the fused pass where an instantiation exists and the variant asks for it.
-// The default (-1), per stencil (index R), follows the measured rows of DESIGN.md section 5 "Batches".
-constexpr bool WAFER_BATCH_FUSED_BY_DEFAULT[4] = {false, false, false, false};
-int steps_per_pass(const wafer_batch *b)
-{
-    const int R = b->g().R;
-    const int K = R == 1 ? 3 : 2;
-    const bool fused = b->step_variant < 0 ? WAFER_BATCH_FUSED_BY_DEFAULT[R] : b->step_variant == 1;
-    if (!fused || wafer_batch_stepk_lds_bytes(b->dtype, R, K) == 0) return 1;
-    return K;
-}
-
-// a call's remainder of two steps is one pass where the two-step instantiation exists beside the K-step one
-bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->dtype, b->g().R, 2) != 0; }
-
-// The one place that chooses where the kernels read the geometry from: launch(gs) with the batch's one geometry (a kernel
-// argument) or with its device table of several.  Every wafer_entry_batch_* entry point has an overload for either.
-template <typename F>
-hipError_t with_geom(const wafer_batch *b, F &&launch)
-{
-    return b->mixed ? launch(WaferBatchGeomTable{b->geoms_dev}) : launch(b->g());
-}
-
 // a launch's status as the call's: `what` names the kernel in the message
 int launched(const char *what, hipError_t e)
 {
     return e == hipSuccess ? WAFER_OK : fail(WAFER_ERR_HIP, "batched %s launch failed: %s", what, hipGetErrorString(e));
 }
-template <typename F>
-int launch(const wafer_batch *b, const char *what, F &&f) { return launched(what, with_geom(b, f)); }
 
 // The grid of the kernels that run one 64 x 4 tile of one plane per workgroup (normalise, symmetrise, resample): the largest tile
 // and plane counts among the members in act -- of their work boxes, or (padded) of their padded boxes, frame and ghost planes
@@ -361,6 +128,100 @@ void max_tiles_planes(const wafer_batch *b, int nact, bool padded, int *max_tile
         *max_planes = std::max(*max_planes, padded ? g.lz : g.nzl);
     }
 }
+
+// member m's state l as a logical pointer (plane 0, row 0), like the views' arrays
+void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
+{
+    return b->slots[l] + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
+}
+
+// entries [0, n) of `v` exist (zeros: frames, pads and guard zones of every member).  v: the store's slots, or their shadows
+// (wafer_batch_evolve_states), laid out alike
+int ensure_slots(wafer_batch *b, std::vector<DevArray<char>> &v, uint32_t n)
+{
+    while (v.size() < n) {
+        DevArray<char> p;
+        BUF_TRY(p.make(b->cells * b->esz));
+        v.push_back(std::move(p));
+        HIP_TRY(hipMemsetAsync(v.back(), 0, v.back().bytes(), b->s));
+    }
+    return WAFER_OK;
+}
+
+// member m's store changed: its Gram matrix (the one-pass form's, if it exists) is recomputed before the next one-pass call
+void mark_gram_stale(wafer_batch *b, uint32_t m)
+{
+    if (!b->gram_stale.empty()) b->gram_stale[m] = 1;
+}
+
+} // namespace wafer_eng
+
+namespace {
+
+int check_member(const wafer_params *m, uint32_t i, const wafer_params *m0, bool same_shape = true)
+{
+    if (m->struct_size != sizeof(wafer_params))
+        return fail(WAFER_ERR_INVALID, "member %u: wafer_params.struct_size %u != %zu (ABI mismatch)", i, m->struct_size, sizeof(wafer_params));
+    if (m->nx < 1 || m->ny < 1 || m->nz < 1) return fail(WAFER_ERR_INVALID, "member %u: grid size must be >= 1", i);
+    if (m->central_difference < 1 || m->central_difference > 3)
+        return fail(WAFER_ERR_INVALID, "member %u: central_difference must be 1 (Three), 2 (Five) or 3 (SevenPoint)", i);
+    if (m->dtype != WAFER_F64 && m->dtype != WAFER_F32 && m->dtype != WAFER_F32_FAST)
+        return fail(WAFER_ERR_INVALID, "member %u: bad dtype %d (f64 = 0, f32 = 1, f32fast = 2)", i, (int)m->dtype);
+    if (m->z_count != 0) return fail(WAFER_ERR_INVALID, "member %u: z_count must be 0 (a batch holds no z-slabs)", i);
+    if (!(m->dn > 0) || !(m->dt > 0) || !(m->mass > 0)) return fail(WAFER_ERR_INVALID, "member %u: dn, dt, mass must be > 0", i);
+    const double den = wafer_stencil_den(m->central_difference, m->dn, m->mass);
+    if (!std::isnormal(den) || !std::isnormal(1.0 / den))
+        return fail(WAFER_ERR_INVALID, "member %u: dn^2 * mass = %g is outside the range of normal doubles (or its reciprocal is)", i,
+                    m->dn * m->dn * m->mass);
+    if (!(m->flags & WAFER_FLAG_SKIP_DT_CHECK) && m->dt > m->dn * m->dn / 3.)   // config.rs:362-365
+        return fail(WAFER_ERR_INVALID, "member %u: LargeDt: dt must be <= dn^2/3 (config.rs:363)", i);
+    if (m->halo_depth != 0 && (int)m->halo_depth < m->central_difference)
+        return fail(WAFER_ERR_INVALID, "member %u: halo_depth must be >= ext", i);
+    if (m0) {
+        if (m->dtype != m0->dtype)
+            return fail(WAFER_ERR_INVALID, "member %u: dtype = %d differs from member 0's %d (a batch holds one dtype)", i, (int)m->dtype, (int)m0->dtype);
+        if (same_shape) {   // (wafer_batch_create_mixed: every member its own)
+            if (m->nx != m0->nx) return fail(WAFER_ERR_INVALID, "member %u: nx = %u differs from member 0's %u", i, m->nx, m0->nx);
+            if (m->ny != m0->ny) return fail(WAFER_ERR_INVALID, "member %u: ny = %u differs from member 0's %u", i, m->ny, m0->ny);
+            if (m->nz != m0->nz) return fail(WAFER_ERR_INVALID, "member %u: nz = %u differs from member 0's %u", i, m->nz, m0->nz);
+        }
+        if (m->central_difference != m0->central_difference)
+            return fail(WAFER_ERR_INVALID, "member %u: central_difference = %d differs from member 0's %d", i, m->central_difference,
+                        m0->central_difference);
+        if (m->device != m0->device) return fail(WAFER_ERR_INVALID, "member %u: device = %d differs from member 0's %d", i, m->device, m0->device);
+        if (m->halo_depth != m0->halo_depth)   // (the batch's one geometry is built with it)
+            return fail(WAFER_ERR_INVALID, "member %u: halo_depth = %u differs from member 0's %u", i, m->halo_depth, m0->halo_depth);
+    }
+    return WAFER_OK;
+}
+
+// every active member has phi (and, with need_pot, a potential: `what` ends that message) and at least wnum stored states
+int check_ready(const wafer_batch *b, const uint8_t *active, bool need_pot, const char *what, uint32_t wnum)
+{
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        const wafer_ctx *c = b->views[m];
+        if (need_pot && (!c->have_pot || !c->have_phi)) return fail(WAFER_ERR_STATE, "member %u: potential and phi must be set%s", m, what);
+        if (!c->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
+        if (wnum > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: wnum %u but w_store holds %u states", m, wnum, b->nst[m]);
+    }
+    return WAFER_OK;
+}
+
+// Steps per launch of a ground-state evolve: the fused pass where an instantiation exists and the variant asks for it.
+// The default (-1), per stencil (index R), follows the measured rows of DESIGN.md section 5 "Batches".
+constexpr bool WAFER_BATCH_FUSED_BY_DEFAULT[4] = {false, false, false, false};
+int steps_per_pass(const wafer_batch *b)
+{
+    const int R = b->g().R;
+    const int K = R == 1 ? 3 : 2;
+    const bool fused = b->step_variant < 0 ? WAFER_BATCH_FUSED_BY_DEFAULT[R] : b->step_variant == 1;
+    if (!fused || wafer_batch_stepk_lds_bytes(b->dtype, R, K) == 0) return 1;
+    return K;
+}
+
+// a call's remainder of two steps is one pass where the two-step instantiation exists beside the K-step one
+bool have_two_step(const wafer_batch *b, int K) { return K > 2 && wafer_batch_stepk_lds_bytes(b->dtype, b->g().R, 2) != 0; }
 
 // the four raw sums of the active members into sums[m * 4 ..] on the host
 int observables(wafer_batch *b, const uint8_t *active)
@@ -447,35 +308,10 @@ int symmetrise(wafer_batch *b, const uint8_t *active, const int *constraints)
 }
 
 // ---- w_store ---------------------------------------------------------------------------------------------------------------
-// member m's state l as a logical pointer (plane 0, row 0), like the views' arrays
-void *slot_ptr(const wafer_batch *b, uint32_t l, uint32_t m)
-{
-    return b->slots[l] + (b->off[m] + (size_t)b->geom(m).base_off) * b->esz;
-}
-
-// entries [0, n) of `v` exist (zeros: frames, pads and guard zones of every member).  v: the store's slots, or their shadows
-// (wafer_batch_evolve_states), laid out alike
-int ensure_slots(wafer_batch *b, std::vector<DevArray<char>> &v, uint32_t n)
-{
-    while (v.size() < n) {
-        DevArray<char> p;
-        BUF_TRY(p.make(b->cells * b->esz));
-        v.push_back(std::move(p));
-        HIP_TRY(hipMemsetAsync(v.back(), 0, v.back().bytes(), b->s));
-    }
-    return WAFER_OK;
-}
-
 int check_capacity(const wafer_batch *b, uint32_t m)
 {
     if (b->nst[m] >= b->P[m].max_states) return fail(WAFER_ERR_STATE, "member %u: w_store is full (max_states = %u)", m, b->P[m].max_states);
     return WAFER_OK;
-}
-
-// member m's store changed: its Gram matrix (the one-pass form's, if it exists) is recomputed before the next one-pass call
-void mark_gram_stale(wafer_batch *b, uint32_t m)
-{
-    if (!b->gram_stale.empty()) b->gram_stale[m] = 1;
 }
 
 // phi of the active members to the end of their stores; nothing changes unless every one of them can take it
@@ -1080,351 +916,6 @@ int set_initial_conditions(wafer_batch *b, const uint8_t *active, const int *ics
     return WAFER_OK;
 }
 
-// ---- Rayleigh-Ritz on the stores ---------------------------------------------------------------------------------------------
-constexpr size_t RITZ_KK = (size_t)WAFER_RITZ_MAX * WAFER_RITZ_MAX;
-
-// every check of a call for every listed member, before anything is uploaded or launched; *nlisted: their number
-int ritz_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, bool need_pot, const char *call, int *nlisted)
-{
-    TRY(refuse_mixed(b, call));
-    *nlisted = 0;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (k[m] == 0 || k[m] > WAFER_RITZ_MAX)
-            return fail(WAFER_ERR_INVALID, "member %u: k = %u: Rayleigh-Ritz takes 1 .. %d states", m, k[m], WAFER_RITZ_MAX);
-        if (k[m] > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
-        if (need_pot && !b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
-        ++*nlisted;
-    }
-    return WAFER_OK;
-}
-
-int ensure_ritz(wafer_batch *b)
-{
-    if (b->ritz_coef.dev) return WAFER_OK;   // (made last: a call that failed before it starts over)
-    BUF_TRY(b->ritz_rec.make(b->n));
-    BUF_TRY(b->ritz_sums.make(2 * RITZ_KK * b->n));
-    BUF_TRY(b->ritz_coef.make(RITZ_KK * b->n));
-    memset(b->ritz_coef.host, 0, b->ritz_coef.host.bytes());
-    return WAFER_OK;
-}
-
-// What a per-call table gives its call: the listed members' number, the widest partition and the largest k among them, the grid of a
-// kernel that walks their spans in 16-byte vectors, the length of their partials end to end, the first listed member and the last + 1.
-struct CallTable {
-    int nact = 0, max_nb = 0, max_k = 0, blocks = 1;
-    size_t doubles = 0, m0 = 0, m1 = 0;
-};
-
-// The per-call table of the listed members into t's host side and to the device: member, k, the prefix sums of the member's rows of
-// obs_nb partials -- 2 k^2 and the member's span in a slot allocation (WaferBatchRitzRec), or 3 k and theta (WaferBatchResidualRec:
-// member m's at m * WAFER_RITZ_MAX; nullptr: zeros).  partials: ritz_partials holds them when this returns, grown on demand as a
-// context's ritz_buf.  The stream is idle (the callers synchronised: t's host side is not read by an earlier copy, and no launch
-// reads partials that go back).
-template <typename Rec>
-int upload_table(wafer_batch *b, Mirror<Rec> &t, const uint8_t *listed, const uint32_t *k, const double *theta, bool partials, CallTable *c)
-{
-    constexpr bool ritz = std::is_same<Rec, WaferBatchRitzRec>::value;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (listed && !listed[m]) continue;
-        Rec &r = t[c->nact++];
-        r.member = (int)m;
-        r.k = (int)k[m];
-        r.poff = (long long)c->doubles;
-        if constexpr (ritz) {
-            r.v0 = (long long)(b->off[m] * b->esz / 16);
-            r.n16 = (long long)((size_t)b->geom(m).total * b->esz / 16);
-            c->blocks = std::max(c->blocks, (int)std::min<long long>((r.n16 + 255) / 256, (long long)b->num_cus * 8));
-        } else {
-            for (uint32_t j = 0; j < WAFER_RITZ_MAX; ++j) r.theta[j] = (theta && j < k[m]) ? theta[(size_t)m * WAFER_RITZ_MAX + j] : 0.0;
-        }
-        c->doubles += (ritz ? 2 * (size_t)k[m] * k[m] : 3 * (size_t)k[m]) * (size_t)b->mem[m].obs_nb;
-        c->max_nb = std::max(c->max_nb, b->mem[m].obs_nb);
-        c->max_k = std::max(c->max_k, (int)k[m]);
-    }
-    if (!c->nact) return WAFER_OK;
-    c->m0 = (size_t)t[0].member;
-    c->m1 = (size_t)t[c->nact - 1].member + 1;
-    if (partials) BUF_TRY(b->ritz_partials.reserve(c->doubles));
-    BUF_TRY(t.upload(c->nact, b->s));
-    return WAFER_OK;
-}
-
-// the allocations of the store slots (or of their shadows) the kernels may touch
-WaferRitzPtrs ritz_slots(const std::vector<DevArray<char>> &v)
-{
-    WaferRitzPtrs st;
-    for (size_t l = 0; l < WAFER_RITZ_MAX && l < v.size(); ++l) st.p[l] = v[l];
-    return st;
-}
-
-// H and S of every listed member (checked: ritz_check) into ritz_sums' host side: the sums launch, the reduce, one read-back
-int ritz_matrices_impl(wafer_batch *b, const uint8_t *active, const uint32_t *k)
-{
-    HIP_TRY(hipSetDevice(b->device));
-    RoctxRange range_("wafer_batch_ritz_matrices");
-    TRY(ensure_ritz(b));
-    TRY(sync_members(b));
-    HIP_TRY(hipStreamSynchronize(b->s));
-    CallTable c;
-    TRY(upload_table(b, b->ritz_rec, active, k, nullptr, true, &c));
-    const WaferRitzPtrs st = ritz_slots(b->slots);
-    TRY(launch(b, "Rayleigh-Ritz sums", [&](const auto &gs) {
-        return wafer_entry_batch_ritz_sums(b->f32, b->g().R, gs, b->mem_dev, b->ritz_rec.dev, c.nact, c.max_nb, c.max_k, b->swz, st, b->ritz_partials,
-                                           b->ritz_sums.dev, b->s);
-    }));
-    b->n_ritz_launches += 2;
-    BUF_TRY(b->ritz_sums.download(2 * RITZ_KK * (c.m1 - c.m0), b->s, 2 * RITZ_KK * c.m0));
-    HIP_TRY(hipStreamSynchronize(b->s));
-    ++b->n_ritz_readbacks;
-    return WAFER_OK;
-}
-
-// member m's k x k matrices out of ritz_sums' host side
-void ritz_unpack(const wafer_batch *b, uint32_t m, uint32_t k, double *h, double *s)
-{
-    const double *r = &b->ritz_sums[(size_t)m * 2 * RITZ_KK];
-    for (size_t q = 0; q < (size_t)k * k; ++q) {
-        if (h) h[q] = r[q];
-        if (s) s[q] = r[RITZ_KK + q];
-    }
-}
-
-// the rotation of the listed members (checked; coef: member m's k[m] x k[m] at m * WAFER_RITZ_MAX^2, finite): one launch
-int ritz_rotate_impl(wafer_batch *b, const uint8_t *listed, const uint32_t *k, const double *coef)
-{
-    HIP_TRY(hipSetDevice(b->device));
-    RoctxRange range_("wafer_batch_rotate_states");
-    TRY(ensure_ritz(b));
-    HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table and coefficients are not read by an earlier call's copy
-    CallTable c;
-    TRY(upload_table(b, b->ritz_rec, listed, k, nullptr, false, &c));
-    if (!c.nact) return WAFER_OK;
-    for (int q = 0; q < c.nact; ++q) {
-        const uint32_t m = (uint32_t)b->ritz_rec[q].member;
-        memcpy(&b->ritz_coef[m * RITZ_KK], coef + m * RITZ_KK, sizeof(double) * k[m] * k[m]);
-    }
-    BUF_TRY(b->ritz_coef.upload(RITZ_KK * (c.m1 - c.m0), b->s, RITZ_KK * c.m0));
-    TRY(launched("rotation", wafer_entry_batch_rotate_states(b->f32, b->ritz_rec.dev, c.nact, c.blocks, ritz_slots(b->slots), b->ritz_coef.dev, b->s)));
-    ++b->n_ritz_launches;
-    for (int q = 0; q < c.nact; ++q) mark_gram_stale(b, (uint32_t)b->ritz_rec[q].member);   // the one-pass form sees the new store
-    return WAFER_OK;
-}
-
-// ---- residuals of the stores and of phi ------------------------------------------------------------------------------------------
-constexpr size_t RESID_ROWS = 3 * (size_t)WAFER_RITZ_MAX;
-
-// every check of wafer_batch_residuals for every listed member, before anything is uploaded or launched; *nlisted: their number
-int residual_check(const wafer_batch *b, int source, const uint8_t *active, const uint32_t *k, const double *theta_in, int *nlisted)
-{
-    if (source != WAFER_RESIDUAL_STATES && source != WAFER_RESIDUAL_PHI) return fail(WAFER_ERR_INVALID, "unknown residual source %d", source);
-    if (source == WAFER_RESIDUAL_STATES) TRY(refuse_mixed(b, "wafer_batch_residuals (stored states)"));
-    *nlisted = 0;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (k[m] == 0 || k[m] > WAFER_RITZ_MAX)
-            return fail(WAFER_ERR_INVALID, "member %u: k = %u: residuals take 1 .. %d states", m, k[m], WAFER_RITZ_MAX);
-        if (source == WAFER_RESIDUAL_PHI && k[m] != 1) return fail(WAFER_ERR_INVALID, "member %u: k = %u: the phi source is one array (k = 1)", m, k[m]);
-        if (theta_in)
-            for (uint32_t j = 0; j < k[m]; ++j)
-                if (!std::isfinite(theta_in[(size_t)m * WAFER_RITZ_MAX + j])) return fail(WAFER_ERR_INVALID, "member %u: theta_in[%u] is not finite", m, j);
-        if (source == WAFER_RESIDUAL_STATES && k[m] > b->nst[m])
-            return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
-        if (source == WAFER_RESIDUAL_PHI && !b->views[m]->have_phi) return fail(WAFER_ERR_STATE, "member %u: phi not set", m);
-        if (!b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
-        ++*nlisted;
-    }
-    return WAFER_OK;
-}
-
-int ensure_residual(wafer_batch *b)
-{
-    if (b->resid_sums.dev) return WAFER_OK;   // (made last: a call that failed before it starts over)
-    BUF_TRY(b->resid_rec.make(b->n));
-    BUF_TRY(b->resid_sums.make(RESID_ROWS * b->n));
-    return WAFER_OK;
-}
-
-// One pass over the listed members (checked: residual_check; at least one): the per-call table with theta (member m's at
-// m * WAFER_RITZ_MAX; nullptr: zeros), the sums launch, the reduce and one read-back into resid_sums' host side.
-int residual_pass(wafer_batch *b, int source, const uint8_t *listed, const uint32_t *k, const double *theta)
-{
-    HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table is not read by an earlier call's copy
-    CallTable c;
-    TRY(upload_table(b, b->resid_rec, listed, k, theta, true, &c));
-    const WaferRitzPtrs st = ritz_slots(b->slots);
-    TRY(launch(b, "residual sums", [&](const auto &gs) {
-        return wafer_entry_batch_residual_sums(b->f32, b->g().R, gs, b->mem_dev, b->resid_rec.dev, c.nact, c.max_nb, c.max_k, b->swz,
-                                               source == WAFER_RESIDUAL_PHI ? 1 : 0, st, b->ritz_partials, b->resid_sums.dev, b->s);
-    }));
-    b->n_resid_launches += 2;
-    BUF_TRY(b->resid_sums.download(RESID_ROWS * (c.m1 - c.m0), b->s, RESID_ROWS * c.m0));
-    HIP_TRY(hipStreamSynchronize(b->s));
-    ++b->n_resid_readbacks;
-    return WAFER_OK;
-}
-
-// ---- stepping the stores -----------------------------------------------------------------------------------------------------
-// every check of wafer_batch_evolve_states (and of wafer_batch_filter_states on its states: `call` names the one in the messages) for
-// every listed member, before anything is allocated, uploaded or launched.
-// A listed member with k[m] == 0 is allowed and costs nothing.  *max_k: the largest k among the listed members.
-int store_step_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, const char *call, uint32_t *max_k)
-{
-    TRY(refuse_mixed(b, call));
-    *max_k = 0;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (k[m] > WAFER_RITZ_MAX) return fail(WAFER_ERR_INVALID, "member %u: k = %u: %s steps at most %d states", m, k[m], call, WAFER_RITZ_MAX);
-        if (k[m] > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
-        if (k[m] && !b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
-        *max_k = std::max(*max_k, k[m]);
-    }
-    return WAFER_OK;
-}
-
-// n_steps plain steps of the first k[m] stored states of every listed member (wafer_batch_plan.h: wafer_batch_store_plan): one
-// launch per step between the slots and their shadows, and after an odd number of steps one batched copy back into the slots.
-int evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint64_t n_steps)
-{
-    uint32_t max_k = 0;
-    TRY(store_step_check(b, active, k, "wafer_batch_evolve_states", &max_k));
-    HIP_TRY(hipSetDevice(b->device));
-    RoctxRange range_("wafer_batch_evolve_states");
-    const WaferBatchStorePlan plan = wafer_batch_store_plan(n_steps, max_k);
-    std::vector<uint8_t> listed(b->n);
-    for (uint32_t m = 0; m < b->n; ++m) listed[m] = ((!active || active[m]) && k[m] > 0) ? 1 : 0;
-    if (max_k) {
-        TRY(ensure_slots(b, b->shadows, max_k));   // (zeroed: the kernel writes work cells only, frames and pads stay zeros)
-        TRY(ensure_ritz(b));   // (the copy's per-call table)
-        if (!b->store_k.dev) BUF_TRY(b->store_k.make(b->n));
-        TRY(sync_members(b));
-        TRY(build_blocks(b, b->blks, listed.data(), 1));
-        HIP_TRY(hipStreamSynchronize(b->s));   // the pinned tables are not read by an earlier call's copy
-        for (uint32_t m = 0; m < b->n; ++m) b->store_k[m] = listed[m] ? (int)k[m] : 0;
-        BUF_TRY(b->store_k.upload(b->n, b->s));
-    }
-    CallTable c;
-    if (plan.copy_back) TRY(upload_table(b, b->ritz_rec, listed.data(), k, nullptr, false, &c));
-    const WaferRitzPtrs slots = ritz_slots(b->slots), shadows = ritz_slots(b->shadows);   // (the kernels touch the first k[m] <= max_k of each)
-    HIP_TRY(hipEventRecord(b->ev_start, b->s));
-    if (max_k && !b->blks.host.empty()) {
-        for (uint64_t st = 0; st < plan.steps; ++st) {   // no host synchronisation in here
-            const bool from_shadow = wafer_batch_store_src_is_shadow(st);
-            TRY(launch(b, "store step", [&](const auto &gs) {
-                return wafer_entry_batch_store_step(b->dtype, b->g().R, gs, b->mem_dev, b->blks.dev, (int)b->blks.host.size(), plan.groups,
-                                                    b->store_k.dev, from_shadow ? shadows : slots, from_shadow ? slots : shadows, b->s);
-            }));
-            ++b->n_store_launches;
-        }
-        if (plan.copy_back && c.nact) {
-            TRY(launched("store copy", wafer_entry_batch_store_copy(b->ritz_rec.dev, c.nact, c.blocks, shadows, slots, b->s)));
-            ++b->n_store_launches;
-        }
-    }
-    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
-    b->last_steps = plan.steps;
-    b->timing_valid = true;
-    for (uint32_t m = 0; m < b->n; ++m)
-        if (listed[m]) mark_gram_stale(b, m);   // the one-pass form sees the new store
-    return WAFER_OK;
-}
-
-// ---- filtering the stores ----------------------------------------------------------------------------------------------------
-// wafer_batch_filter_states: the degree, store_step_check's checks and every listed member's interval, before anything is allocated,
-// uploaded or launched; then `degree` launches between the slots and their shadows (wafer_batch_filter_plan) and, after an odd
-// degree, the store step's batched copy back into the slots.
-int filter_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t degree, const double *a, const double *bb, const double *a0)
-{
-    if (degree == 0 || degree > WAFER_FILTER_MAX_DEGREE)
-        return fail(WAFER_ERR_INVALID, "degree = %u: wafer_batch_filter_states takes 1 .. %d", degree, WAFER_FILTER_MAX_DEGREE);
-    uint32_t max_k = 0;
-    TRY(store_step_check(b, active, k, "wafer_batch_filter_states", &max_k));
-    for (uint32_t m = 0; m < b->n; ++m)
-        if ((!active || active[m]) && k[m] && !wafer_filter_interval_ok(a[m], bb[m], a0[m]))
-            return fail(WAFER_ERR_INVALID, "member %u: the interval needs finite a0 < a < b (a0 = %g, a = %g, b = %g)", m, a0[m], a[m], bb[m]);
-    HIP_TRY(hipSetDevice(b->device));
-    RoctxRange range_("wafer_batch_filter_states");
-    const WaferBatchFilterPlan plan = wafer_batch_filter_plan(degree, max_k);
-    std::vector<uint8_t> listed(b->n);
-    for (uint32_t m = 0; m < b->n; ++m) listed[m] = ((!active || active[m]) && k[m] > 0) ? 1 : 0;
-    CallTable c;
-    if (max_k) {
-        TRY(ensure_slots(b, b->shadows, max_k));   // (zeroed: the kernel writes work cells only, frames and pads stay zeros)
-        TRY(ensure_ritz(b));   // (the copy's per-call table)
-        if (!b->store_k.dev) BUF_TRY(b->store_k.make(b->n));
-        if (!b->filt_coef.dev) BUF_TRY(b->filt_coef.make((size_t)WAFER_FILTER_MAX_DEGREE * b->n));
-        TRY(sync_members(b));
-        TRY(build_blocks(b, b->blks, listed.data(), 1));
-        HIP_TRY(hipStreamSynchronize(b->s));   // the pinned tables are not read by an earlier call's copy
-        std::vector<double> al(degree), be(degree);
-        for (uint32_t m = 0; m < b->n; ++m) {
-            b->store_k[m] = listed[m] ? (int)k[m] : 0;
-            double cc = 0.0;
-            if (listed[m]) (void)wafer_filter_coefficients_host(degree, a[m], bb[m], a0[m], al.data(), be.data(), &cc);   // (checked above)
-            for (uint32_t i = 0; i < degree; ++i) b->filt_coef[(size_t)i * b->n + m] = listed[m] ? WaferFilterCoef{al[i], be[i], cc} : WaferFilterCoef{0., 0., 0.};
-        }
-        BUF_TRY(b->store_k.upload(b->n, b->s));
-        BUF_TRY(b->filt_coef.upload((size_t)degree * b->n, b->s));
-        if (plan.copy_back) TRY(upload_table(b, b->ritz_rec, listed.data(), k, nullptr, false, &c));
-    }
-    const WaferRitzPtrs slots = ritz_slots(b->slots), shadows = ritz_slots(b->shadows);   // (the kernels touch the first k[m] <= max_k of each)
-    HIP_TRY(hipEventRecord(b->ev_start, b->s));
-    if (max_k && !b->blks.host.empty()) {
-        for (uint64_t i = 1; i <= plan.steps; ++i) {   // no host synchronisation in here
-            const bool from_shadow = wafer_batch_filter_src_is_shadow(i);
-            TRY(launch(b, "store filter", [&](const auto &gs) {
-                return wafer_entry_batch_store_filter(b->f32, b->g().R, gs, b->mem_dev, b->blks.dev, (int)b->blks.host.size(), plan.groups, b->store_k.dev,
-                                                      b->filt_coef.dev + (i - 1) * b->n, i == 1 ? 1 : 0, from_shadow ? shadows : slots,
-                                                      from_shadow ? slots : shadows, b->s);
-            }));
-            ++b->n_filter_launches;
-        }
-        if (plan.copy_back && c.nact) {
-            TRY(launched("store copy", wafer_entry_batch_store_copy(b->ritz_rec.dev, c.nact, c.blocks, shadows, slots, b->s)));
-            ++b->n_filter_launches;
-        }
-    }
-    HIP_TRY(hipEventRecord(b->ev_stop, b->s));
-    b->last_steps = plan.steps;
-    b->timing_valid = true;
-    for (uint32_t m = 0; m < b->n; ++m)
-        if (listed[m]) mark_gram_stale(b, m);   // the one-pass form sees the new store
-    return WAFER_OK;
-}
-
-// ub[m] = W_R / den + max V over member m's work cells, for every listed member: one launch, one read-back
-int spectral_bound(wafer_batch *b, const uint8_t *active, double *ub)
-{
-    int nlisted = 0;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        if (!b->views[m]->have_pot) return fail(WAFER_ERR_STATE, "member %u: potential not set", m);
-        ++nlisted;
-    }
-    if (!nlisted) return WAFER_OK;
-    HIP_TRY(hipSetDevice(b->device));
-    if (!b->vmax.dev) BUF_TRY(b->vmax.make(b->n));
-    TRY(sync_members(b));
-    int nact = 0;
-    TRY(upload_active(b, active, &nact));   // (synchronises the stream: vmax's host side is not read by an earlier call's copy either)
-    for (int q = 0; q < nact; ++q) b->vmax[q] = 0;   // below every key
-    BUF_TRY(b->vmax.upload((size_t)nact, b->s));
-    int max_tiles, max_planes;
-    max_tiles_planes(b, nact, false, &max_tiles, &max_planes);
-    TRY(launch(b, "spectral bound", [&](const auto &gs) {
-        return wafer_entry_batch_v_max(b->f32, gs, b->mem_dev, b->act.dev, nact, max_tiles, max_planes, b->vmax.dev, b->s);
-    }));
-    ++b->n_bound_launches;
-    BUF_TRY(b->vmax.download((size_t)nact, b->s));
-    HIP_TRY(hipStreamSynchronize(b->s));
-    for (int q = 0; q < nact; ++q) {
-        const uint32_t m = (uint32_t)b->act[q];
-        const wafer_params &P = b->P[m];
-        ub[m] = wafer_stencil_abs_weight(P.central_difference) / wafer_stencil_den(P.central_difference, P.dn, P.mass) + wafer_order_value(b->vmax[q]);
-    }
-    return WAFER_OK;
-}
-
 // ---- creation --------------------------------------------------------------------------------------------------------------
 // Every member's partition record and the places of its partials.  Observables: the partition wafer_launch_observables_lds gives a
 // single context of the member's shape and storage type -- 16 bytes per lane, so tiles 128 wide on doubles and 256 wide on floats
@@ -1995,189 +1486,4 @@ int wafer_batch_diag_gs_steps(wafer_batch *b, uint64_t *onepass, uint64_t *seque
     *sequential = b->n_sequential;
     return WAFER_OK;
 }
-
-int wafer_batch_ritz_matrices(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *h, double *s)
-{
-    if (!b || !k || !h || !s) return fail(WAFER_ERR_INVALID, "null argument");
-    int nlisted = 0;
-    TRY(ritz_check(b, active, k, true, "wafer_batch_ritz_matrices", &nlisted));
-    if (!nlisted) return WAFER_OK;
-    TRY(ritz_matrices_impl(b, active, k));
-    for (uint32_t m = 0; m < b->n; ++m)
-        if (!active || active[m]) ritz_unpack(b, m, k[m], h + m * RITZ_KK, s + m * RITZ_KK);
-    return WAFER_OK;
-}
-
-int wafer_batch_rotate_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, const double *coef)
-{
-    if (!b || !k || !coef) return fail(WAFER_ERR_INVALID, "null argument");
-    int nlisted = 0;
-    TRY(ritz_check(b, active, k, false, "wafer_batch_rotate_states", &nlisted));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        for (uint32_t q = 0; q < k[m] * k[m]; ++q)
-            if (!std::isfinite(coef[m * RITZ_KK + q])) return fail(WAFER_ERR_INVALID, "member %u: coef[%u] is not finite", m, q);
-    }
-    if (!nlisted) return WAFER_OK;
-    return ritz_rotate_impl(b, active, k, coef);
-}
-
-int wafer_batch_ritz(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *evals, double *coef, double *h, double *s, int *status)
-{
-    if (!b || !k || !evals || !coef || !status) return fail(WAFER_ERR_INVALID, "null argument");
-    int nlisted = 0;
-    TRY(ritz_check(b, active, k, true, "wafer_batch_ritz", &nlisted));
-    if (!nlisted) return WAFER_OK;
-    TRY(ritz_matrices_impl(b, active, k));
-    // the solves: a member whose solve fails keeps its store and its evals / coef entries; that is its status, not the call's
-    std::vector<uint8_t> solved(b->n, 0);
-    std::vector<double> ev((size_t)WAFER_RITZ_MAX * b->n), cf(RITZ_KK * b->n, 0.0);
-    std::string first_failure;
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        double hm[RITZ_KK], sm[RITZ_KK];
-        ritz_unpack(b, m, k[m], hm, sm);
-        const int rc = wafer_ritz_solve_host((int)k[m], hm, sm, ev.data() + (size_t)m * WAFER_RITZ_MAX, cf.data() + m * RITZ_KK);
-        solved[m] = rc == WAFER_RITZ_OK;
-        if (!solved[m] && first_failure.empty()) {
-            char msg[224];
-            if (rc == WAFER_RITZ_NO_CONVERGENCE)
-                snprintf(msg, sizeof msg, "member %u: Rayleigh-Ritz: the Jacobi iteration did not converge in %d sweeps", m, (int)WAFER_RITZ_SWEEPS);
-            else
-                snprintf(msg, sizeof msg, "member %u: Rayleigh-Ritz: the overlap matrix is not positive definite (linearly dependent states, "
-                                          "or a non-finite sum)", m);
-            first_failure = msg;
-        }
-    }
-    TRY(ritz_rotate_impl(b, solved.data(), k, cf.data()));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (active && !active[m]) continue;
-        ritz_unpack(b, m, k[m], h ? h + m * RITZ_KK : nullptr, s ? s + m * RITZ_KK : nullptr);
-        status[m] = solved[m] ? WAFER_OK : WAFER_ERR_STATE;
-        if (!solved[m]) continue;
-        for (size_t q = 0; q < (size_t)k[m] * k[m]; ++q) coef[m * RITZ_KK + q] = cf[m * RITZ_KK + q];
-        for (uint32_t q = 0; q < k[m]; ++q) evals[(size_t)m * WAFER_RITZ_MAX + q] = ev[(size_t)m * WAFER_RITZ_MAX + q];
-    }
-    if (!first_failure.empty()) (void)fail(WAFER_ERR_STATE, "%s", first_failure.c_str());   // wafer_last_error names the first failed member
-    return WAFER_OK;
-}
-
-int wafer_batch_diag_ritz_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks)
-{
-    if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
-    *launches = b->n_ritz_launches;
-    *readbacks = b->n_ritz_readbacks;
-    return WAFER_OK;
-}
-
-int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, const uint32_t *k, const double *theta_in, double *theta, double *r2,
-                          double *s, int *status)
-{
-    if (!b || !k || !theta || !r2 || !s || !status) return fail(WAFER_ERR_INVALID, "null argument");
-    int nlisted = 0;
-    TRY(residual_check(b, source, active, k, theta_in, &nlisted));
-    if (!nlisted) return WAFER_OK;
-    HIP_TRY(hipSetDevice(b->device));
-    RoctxRange range_("wafer_batch_residuals");
-    TRY(ensure_residual(b));
-    TRY(sync_members(b));
-    std::vector<uint8_t> ok(b->n, 0);
-    for (uint32_t m = 0; m < b->n; ++m) ok[m] = (!active || active[m]) ? 1 : 0;
-    std::vector<double> th((size_t)WAFER_RITZ_MAX * b->n, 0.0);
-    std::string first_failure;
-    if (theta_in) {
-        for (uint32_t m = 0; m < b->n; ++m)
-            for (uint32_t j = 0; ok[m] && j < k[m]; ++j) th[(size_t)m * WAFER_RITZ_MAX + j] = theta_in[(size_t)m * WAFER_RITZ_MAX + j];
-    } else {   // Rayleigh mode: theta_j = wh_j / s_j of a pass with theta = 0; a member without a quotient keeps its outputs: its status
-        TRY(residual_pass(b, source, ok.data(), k, nullptr));
-        bool any = false;
-        for (uint32_t m = 0; m < b->n; ++m) {
-            if (!ok[m]) continue;
-            const double *r = &b->resid_sums[m * RESID_ROWS];
-            for (uint32_t j = 0; j < k[m]; ++j) {
-                const double sj = r[j * 3 + 2];
-                if (!std::isfinite(sj) || !(sj > 0.0)) {
-                    if (first_failure.empty()) {
-                        char msg[192];
-                        snprintf(msg, sizeof msg, "member %u: state %u: <l|l> = %g: no Rayleigh quotient (a zero or non-finite state)", m, j, sj);
-                        first_failure = msg;
-                    }
-                    ok[m] = 0;
-                    status[m] = WAFER_ERR_STATE;
-                    break;
-                }
-                th[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 1] / sj;
-            }
-            any = any || ok[m];
-        }
-        if (!any) {   // nobody left for the second pass
-            (void)fail(WAFER_ERR_STATE, "%s", first_failure.c_str());
-            return WAFER_OK;
-        }
-    }
-    TRY(residual_pass(b, source, ok.data(), k, th.data()));
-    for (uint32_t m = 0; m < b->n; ++m) {
-        if (!ok[m]) continue;
-        const double *r = &b->resid_sums[m * RESID_ROWS];
-        for (uint32_t j = 0; j < k[m]; ++j) {
-            theta[(size_t)m * WAFER_RITZ_MAX + j] = th[(size_t)m * WAFER_RITZ_MAX + j];
-            r2[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 0];
-            s[(size_t)m * WAFER_RITZ_MAX + j] = r[j * 3 + 2];
-        }
-        status[m] = WAFER_OK;
-    }
-    if (!first_failure.empty()) (void)fail(WAFER_ERR_STATE, "%s", first_failure.c_str());   // wafer_last_error names the first such member
-    return WAFER_OK;
-}
-
-int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks)
-{
-    if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
-    *launches = b->n_resid_launches;
-    *readbacks = b->n_resid_readbacks;
-    return WAFER_OK;
-}
-
-int wafer_batch_evolve_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint64_t n_steps)
-{
-    if (!b || !k) return fail(WAFER_ERR_INVALID, "null argument");
-    return evolve_states(b, active, k, n_steps);
-}
-
-int wafer_batch_filter_states(wafer_batch *b, const uint8_t *active, const uint32_t *k, uint32_t degree, const double *a, const double *bb,
-                              const double *a0)
-{
-    if (!b || !k || !a || !bb || !a0) return fail(WAFER_ERR_INVALID, "null argument");
-    return filter_states(b, active, k, degree, a, bb, a0);
-}
-
-int wafer_batch_spectral_bound(wafer_batch *b, const uint8_t *active, double *ub)
-{
-    if (!b || !ub) return fail(WAFER_ERR_INVALID, "null argument");
-    return spectral_bound(b, active, ub);
-}
-
-int wafer_batch_diag_filter_counts(wafer_batch *b, uint64_t *launches, uint64_t *bound_launches)
-{
-    if (!b || !launches || !bound_launches) return fail(WAFER_ERR_INVALID, "null argument");
-    *launches = b->n_filter_launches;
-    *bound_launches = b->n_bound_launches;
-    return WAFER_OK;
-}
-
-int wafer_batch_diag_store_step(wafer_batch *b, char *buf, size_t n)
-{
-    if (!b || !buf || n == 0) return fail(WAFER_ERR_INVALID, "null argument");
-    snprintf(buf, n, "kernel=wafer_k_batch_store_step<%d,%s,%s> states_per_workgroup=%d shapes=%zu", b->g().R, KERNEL_TYPES[b->dtype],
-             b->mixed ? "WaferBatchGeomTable" : "WaferGeom", WAFER_STORE_SG, b->geoms.size());
-    return WAFER_OK;
-}
-
-int wafer_batch_diag_store_counts(wafer_batch *b, uint64_t *launches)
-{
-    if (!b || !launches) return fail(WAFER_ERR_INVALID, "null argument");
-    *launches = b->n_store_launches;
-    return WAFER_OK;
-}
-
 } // extern "C"

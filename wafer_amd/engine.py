@@ -422,6 +422,60 @@ def _enum_entries(names, table, n_members: int, mask, what: str) -> list:
 BLOCK_CONVERGED, BLOCK_MAX_BLOCKS, BLOCK_DEPENDENT = WAFER_OK, WAFER_ERR_MAX_STEP, WAFER_ERR_STATE
 
 
+def _solve_loop(ks, tolerance, per_block, max_blocks, advance, ritz, residuals, worst, dependent, exhausted, first=None) -> list:
+    """What block_solve_loop and filtered_solve_loop share (their statuses are the same three codes): the result dicts, the Ritz step
+    with its linearly-dependent branch, the residual call, the row record, the members that leave `going`, the max_blocks message.
+        advance(going, block, out)  moves the states of the members in `going` on by one block -> those it moved (the others got their
+                                    status and message from it and are done)
+        worst(o, m)                 the number that decides for member m: it is done when this is < tolerance
+        dependent, exhausted        the two messages: % (m, block, steps, k, per_block) and % (m, max_blocks, worst, tolerance)
+        first(going)                where given and anyone takes part: called once, and one Ritz step on the starts (block 0) follows"""
+    out = [None if n == 0 else dict(status=BLOCK_MAX_BLOCKS, message="", blocks=0, steps=0, evals=None, diff=None, rho=None, rows=[])
+           for n in ks]
+    going = [m for m, n in enumerate(ks) if n > 0]
+
+    def solve(members, block):
+        """Ritz on `members`: evals and diff into out, -> those it succeeded on"""
+        solved = ritz(list(members))
+        alive = []
+        for m in members:
+            status, evals = solved[m]
+            o = out[m]
+            if status != WAFER_OK:
+                o["status"] = BLOCK_DEPENDENT
+                o["message"] = dependent % (m, block, o["steps"], ks[m], per_block)
+                continue
+            evals = np.array(evals, dtype=np.float64)[:ks[m]]
+            o["diff"] = np.full(ks[m], np.inf) if o["evals"] is None else np.abs(evals - o["evals"])
+            o["evals"] = evals
+            alive.append(m)
+        return alive
+
+    if first is not None and going:
+        first(list(going))
+        going = solve(going, 0)
+    for block in range(1, max_blocks + 1):
+        going = advance(going, block, out) if going else []
+        if not going:
+            break
+        for m in going:
+            out[m]["blocks"], out[m]["steps"] = block, block * per_block
+        alive = solve(going, block)
+        rho = residuals(list(alive), {m: out[m]["evals"] for m in alive}) if alive else {}
+        going = []
+        for m in alive:
+            o = out[m]
+            o["rho"] = np.array(rho[m], dtype=np.float64)[:ks[m]]
+            o["rows"].append(dict(block=block, steps=o["steps"], evals=o["evals"].copy(), diff=o["diff"].copy(), rho=o["rho"].copy()))
+            if worst(o, m) < tolerance:
+                o["status"] = BLOCK_CONVERGED
+            else:
+                going.append(m)
+    for m in going:
+        out[m]["message"] = exhausted % (m, max_blocks, worst(out[m], m), tolerance)
+    return out
+
+
 def block_solve_loop(step, ritz, residuals, k, tolerance: float, steps_per_block: int, max_blocks: int) -> list:
     """Subspace iteration over a set of members, backend-free (Context.solve_block, Batch.solve_block and the numpy model of the
     tests all call this).  k: one state count per member (0 or None: the member takes no part).  Three callables over the members
@@ -443,45 +497,18 @@ def block_solve_loop(step, ritz, residuals, k, tolerance: float, steps_per_block
         raise ValueError("steps_per_block and max_blocks must be >= 1")
     if not tolerance > 0.0:
         raise ValueError("tolerance must be > 0")
-    out = [None if n == 0 else dict(status=BLOCK_MAX_BLOCKS, message="", blocks=0, steps=0, evals=None, diff=None, rho=None, rows=[])
-           for n in ks]
-    going = [m for m, n in enumerate(ks) if n > 0]
-    last = {m: None for m in going}
-    for block in range(1, max_blocks + 1):
-        if not going:
-            break
+
+    def advance(going, block, out):
         step(list(going), steps_per_block)
-        solved = ritz(list(going))
-        alive = []
-        for m in going:
-            status, evals = solved[m]
-            o = out[m]
-            o["blocks"], o["steps"] = block, block * steps_per_block
-            if status != WAFER_OK:
-                o["status"] = BLOCK_DEPENDENT
-                o["message"] = ("member %d: after block %d (%d steps) the Ritz step found the %d states linearly dependent: every state has "
-                                "collapsed onto the lowest ones; shorten steps_per_block (now %d)" % (m, block, o["steps"], ks[m], steps_per_block))
-                continue
-            evals = np.array(evals, dtype=np.float64)[:ks[m]]
-            o["diff"] = np.full(ks[m], np.inf) if last[m] is None else np.abs(evals - last[m])
-            o["evals"] = last[m] = evals
-            alive.append(m)
-        rho = residuals(list(alive), {m: out[m]["evals"] for m in alive}) if alive else {}
-        going = []
-        for m in alive:
-            o = out[m]
-            o["rho"] = np.array(rho[m], dtype=np.float64)[:ks[m]]
-            o["rows"].append(dict(block=block, steps=o["steps"], evals=o["evals"].copy(), diff=o["diff"].copy(), rho=o["rho"].copy()))
-            if float(np.max(o["diff"])) < tolerance:
-                o["status"] = BLOCK_CONVERGED
-            else:
-                going.append(m)
-    for m in going:
-        out[m]["message"] = "member %d: max_blocks = %d reached with max diff %g >= tolerance %g" % (m, max_blocks, float(np.max(out[m]["diff"])), tolerance)
-    return out
+        return going
+
+    return _solve_loop(ks, tolerance, steps_per_block, max_blocks, advance, ritz, residuals, lambda o, m: float(np.max(o["diff"])),
+                       "member %d: after block %d (%d steps) the Ritz step found the %d states linearly dependent: every state has "
+                       "collapsed onto the lowest ones; shorten steps_per_block (now %d)",
+                       "member %d: max_blocks = %d reached with max diff %g >= tolerance %g")
 
 
-# ---- Chebyshev-filtered subspace iteration on the state stores: the driver, written once ----------------------------------------
+# ---- Chebyshev-filtered subspace iteration on the state stores ---------------------------------------------------------------------
 FILTER_MAX_DEGREE = 256
 FILTER_CONVERGED, FILTER_MAX_BLOCKS, FILTER_DEPENDENT, FILTER_NO_INTERVAL = WAFER_OK, WAFER_ERR_MAX_STEP, WAFER_ERR_STATE, WAFER_ERR_INVALID
 
@@ -521,33 +548,10 @@ def filtered_solve_loop(bound, filt, ritz, residuals, k, tolerance: float, degre
         raise ValueError("tolerance must be > 0")
     if guard < 1 or any(n > 0 and n - guard < 1 for n in ks):
         raise ValueError("guard must be >= 1 and every k - guard >= 1")
-    out = [None if n == 0 else dict(status=FILTER_MAX_BLOCKS, message="", blocks=0, steps=0, evals=None, diff=None, rho=None, rows=[])
-           for n in ks]
-    going = [m for m, n in enumerate(ks) if n > 0]
-    if not going:
-        return out
-    ub = bound(list(going))
+    ub = {}
 
-    def solve(members, block):
-        """Ritz on `members`: evals and diff into out, -> those it succeeded on"""
-        solved = ritz(list(members))
-        alive = []
-        for m in members:
-            status, evals = solved[m]
-            o = out[m]
-            if status != WAFER_OK:
-                o["status"] = FILTER_DEPENDENT
-                o["message"] = ("member %d: after block %d (%d filter steps) the Ritz step found the %d states non-finite or linearly "
-                                "dependent: lower degree (now %d)" % (m, block, block * degree, ks[m], degree))
-                continue
-            evals = np.array(evals, dtype=np.float64)[:ks[m]]
-            o["diff"] = np.full(ks[m], np.inf) if o["evals"] is None else np.abs(evals - o["evals"])
-            o["evals"] = evals
-            alive.append(m)
-        return alive
-
-    going = solve(going, 0)
-    for block in range(1, max_blocks + 1):
+    def advance(going, block, out):
+        """the interval gate, then the filter on the members that have one"""
         iv, ready = {}, []
         for m in going:
             e = out[m]["evals"]
@@ -560,27 +564,25 @@ def filtered_solve_loop(bound, filt, ritz, residuals, k, tolerance: float, degre
             else:
                 iv[m] = (float(e[-1]), float(ub[m]), float(e[0]))
                 ready.append(m)
-        if not ready:
-            going = []
-            break
-        filt(list(ready), degree, iv)
-        for m in ready:
-            out[m]["blocks"], out[m]["steps"] = block, block * degree
-        alive = solve(ready, block)
-        rho = residuals(list(alive), {m: out[m]["evals"] for m in alive}) if alive else {}
-        going = []
-        for m in alive:
-            o = out[m]
-            o["rho"] = np.array(rho[m], dtype=np.float64)[:ks[m]]
-            o["rows"].append(dict(block=block, steps=o["steps"], evals=o["evals"].copy(), diff=o["diff"].copy(), rho=o["rho"].copy()))
-            if float(np.max(o["rho"][:ks[m] - guard])) < tolerance:
-                o["status"] = FILTER_CONVERGED
-            else:
-                going.append(m)
-    for m in going:
-        out[m]["message"] = "member %d: max_blocks = %d reached with max rho %g >= tolerance %g" % (
-            m, max_blocks, float(np.max(out[m]["rho"][:ks[m] - guard])), tolerance)
-    return out
+        if ready:
+            filt(list(ready), degree, iv)
+        return ready
+
+    return _solve_loop(ks, tolerance, degree, max_blocks, advance, ritz, residuals, lambda o, m: float(np.max(o["rho"][:ks[m] - guard])),
+                       "member %d: after block %d (%d filter steps) the Ritz step found the %d states non-finite or linearly "
+                       "dependent: lower degree (now %d)",
+                       "member %d: max_blocks = %d reached with max rho %g >= tolerance %g", first=lambda going: ub.update(bound(going)))
+
+
+def _ritz_status(fn):
+    """the loops' ritz callable on one member (index 0): fn() -> its Ritz values, where WAFER_ERR_STATE is the member's status and not
+    an exception"""
+    try:
+        return {0: (WAFER_OK, fn())}
+    except WaferError as e:
+        if e.code != WAFER_ERR_STATE:
+            raise
+        return {0: (WAFER_ERR_STATE, None)}
 
 
 class Context:
@@ -823,22 +825,8 @@ class Context:
         energies against the last block's, residuals(k, theta=evals) -- until every |e_j - e_last_j| < tolerance.
         -> {"status", "message", "blocks", "steps", "evals", "diff", "rho", "rows"}"""
         k = int(k)
-
-        def step(going, n):
-            self.evolve_states(k, n)
-
-        def ritz(going):
-            try:
-                return {0: (WAFER_OK, self.ritz(k)["evals"])}
-            except WaferError as e:
-                if e.code != WAFER_ERR_STATE:
-                    raise
-                return {0: (WAFER_ERR_STATE, None)}
-
-        def residuals(going, theta):
-            return {0: self.residuals(k, theta=theta[0])["rho"]}
-
-        return block_solve_loop(step, ritz, residuals, [k], tolerance, steps_per_block, max_blocks)[0]
+        return block_solve_loop(lambda going, n: self.evolve_states(k, n), lambda going: _ritz_status(lambda: self.ritz(k)["evals"]),
+                                lambda going, theta: {0: self.residuals(k, theta=theta[0])["rho"]}, [k], tolerance, steps_per_block, max_blocks)[0]
 
     # -- filtering w_store: Chebyshev-filtered subspace iteration (include/wafer_hip.h) ------------------
     def filter_states(self, k: int, degree: int, a: float, b: float, a0: float) -> None:
@@ -857,16 +845,8 @@ class Context:
         filter_states(k, degree, evals[k - 1], spectral_bound(), evals[0]), ritz(k), residuals(k, theta=evals) -- until rho < tolerance
         on the first k - guard states.  -> {"status", "message", "blocks", "steps", "evals", "diff", "rho", "rows"}"""
         k = int(k)
-
-        def ritz(going):
-            try:
-                return {0: (WAFER_OK, self.ritz(k)["evals"])}
-            except WaferError as e:
-                if e.code != WAFER_ERR_STATE:
-                    raise
-                return {0: (WAFER_ERR_STATE, None)}
-
-        return filtered_solve_loop(lambda going: {0: self.spectral_bound()}, lambda going, n, iv: self.filter_states(k, n, *iv[0]), ritz,
+        return filtered_solve_loop(lambda going: {0: self.spectral_bound()}, lambda going, n, iv: self.filter_states(k, n, *iv[0]),
+                                   lambda going: _ritz_status(lambda: self.ritz(k)["evals"]),
                                    lambda going, theta: {0: self.residuals(k, theta=theta[0])["rho"]}, [k], tolerance, degree, max_blocks, guard)[0]
 
     # -- residuals of w_store and of phi (include/wafer_hip.h) -------------------------------------------
@@ -1346,28 +1326,31 @@ class Batch:
         self._check(self._L.wafer_batch_clone_state_to_phi(self._h, self._u8(a), idx))
 
     # -- Rayleigh-Ritz on the stores (include/wafer_hip.h) ------------------------------------------------
-    def _ritz_ks(self, k, a) -> list:
-        """one k per member from an int (every listed member's), a sequence with one entry per member, or None (each member's own
-        state count); the listed entries checked against 1 .. RITZ_MAX and the member's max_states.  Entries of members not listed
-        are passed on as 0: the library does not read them."""
+    def _ks(self, k, a, lo, hi, outside, default=None, max_states=False) -> list:
+        """one k per member from an int (every listed member's), a sequence with one entry per member, or None (`default` for everyone;
+        None: each member's own state count).  The listed entries are checked against lo .. hi (hi None: no upper bound; `outside` ends
+        the message) and, with max_states, against the member's max_states.  Entries of members not listed become 0: the library does
+        not read them."""
         B = len(self.members)
         if k is None:
-            ks = self.num_states()
-        elif np.ndim(k) == 0:
-            ks = [int(k)] * B
+            ks = self.num_states() if default is None else [default] * B
         else:
-            ks = [0 if x is None else int(x) for x in k]
-            if len(ks) != B:
-                raise ValueError("k must hold one entry per member")
+            ks = [int(k)] * B if np.ndim(k) == 0 else [0 if x is None else int(x) for x in k]
+        if len(ks) != B:
+            raise ValueError("k must hold one entry per member")
         for m in range(B):
             if a is not None and not a[m]:
                 ks[m] = 0
                 continue
-            if not 1 <= ks[m] <= RITZ_MAX:
-                raise ValueError("member %d: k = %d is outside 1 .. RITZ_MAX = %d" % (m, ks[m], RITZ_MAX))
-            if ks[m] > self.members[m].max_states:
+            if ks[m] < lo or (hi is not None and ks[m] > hi):
+                raise ValueError("member %d: k = %d%s" % (m, ks[m], outside))
+            if max_states and ks[m] > self.members[m].max_states:
                 raise ValueError("member %d: k = %d is above its max_states = %d" % (m, ks[m], self.members[m].max_states))
         return ks
+
+    def _ritz_ks(self, k, a) -> list:
+        """k of the Rayleigh-Ritz calls: 1 .. RITZ_MAX and the member's max_states"""
+        return self._ks(k, a, 1, RITZ_MAX, " is outside 1 .. RITZ_MAX = %d" % RITZ_MAX, max_states=True)
 
     def ritz_matrices(self, k=None, active=None) -> list:
         """Context.ritz_matrices(k[m]) for every listed member (active[m] != 0; None: all) in one sums launch, one reduce and one
@@ -1433,17 +1416,8 @@ class Batch:
 
     # -- stepping the stores: subspace iteration (include/wafer_hip.h) ------------------------------------
     def _store_ks(self, k, a) -> list:
-        """one k per member as _ritz_ks takes it, but 0 is allowed (the member costs nothing) and members not listed get 0"""
-        B = len(self.members)
-        ks = self.num_states() if k is None else ([int(k)] * B if np.ndim(k) == 0 else [0 if x is None else int(x) for x in k])
-        if len(ks) != B:
-            raise ValueError("k must hold one entry per member")
-        for m in range(B):
-            if a is not None and not a[m]:
-                ks[m] = 0
-            elif ks[m] < 0:
-                raise ValueError("member %d: k = %d is negative" % (m, ks[m]))
-        return ks
+        """k of the calls that step the stores: as _ritz_ks takes it, but 0 is allowed (the member costs nothing)"""
+        return self._ks(k, a, 0, None, " is negative")
 
     def evolve_states(self, steps: int, k=None, active=None) -> None:
         """Context.evolve_states(k[m], steps) for every listed member (active[m] != 0; None: all) in ONE launch per step, whatever the
@@ -1500,19 +1474,34 @@ class Batch:
         self._check(self._L.wafer_batch_diag_filter_counts(self._h, C.byref(n), C.byref(r)))
         return n.value, r.value
 
-    def solve_filtered(self, k, tolerance: float, degree: int, max_blocks: int, guard: int = 1, active=None) -> list:
-        """Context.solve_filtered for every listed member at once (filtered_solve_loop): per block one filter_states, one ritz and one
-        residuals call over the members still going, each with its own interval; a member whose first k - guard states have
-        rho < tolerance leaves the active set and stays as it is.  -> per member the dict of Context.solve_filtered, None for members
-        not listed (or with k 0)."""
-        act = self._mask(active)
-        ks = self._store_ks(k, act)
+    def _solver_calls(self, ks):
+        """(mask, ritz, residuals) of solve_block and solve_filtered: the active array of a `going` list, and the loops' two callables
+        on the members' first ks[m] states"""
         B = len(self.members)
 
         def mask(going):
             m = np.zeros(B, dtype=np.uint8)
             m[going] = 1
             return m
+
+        def ritz(going):
+            r = self.ritz(ks, active=mask(going))
+            return {m: (r[m]["status"], r[m]["evals"]) for m in going}
+
+        def residuals(going, theta):
+            r = self.residuals(ks, theta=[theta.get(m) for m in range(B)], active=mask(going))
+            return {m: r[m]["rho"] for m in going}
+
+        return mask, ritz, residuals
+
+    def solve_filtered(self, k, tolerance: float, degree: int, max_blocks: int, guard: int = 1, active=None) -> list:
+        """Context.solve_filtered for every listed member at once (filtered_solve_loop): per block one filter_states, one ritz and one
+        residuals call over the members still going, each with its own interval; a member whose first k - guard states have
+        rho < tolerance leaves the active set and stays as it is.  -> per member the dict of Context.solve_filtered, None for members
+        not listed (or with k 0)."""
+        ks = self._store_ks(k, self._mask(active))
+        B = len(self.members)
+        mask, ritz, residuals = self._solver_calls(ks)
 
         def bound(going):
             ub = self.spectral_bound(active=mask(going))
@@ -1522,41 +1511,16 @@ class Batch:
             cols = [[iv[m][q] if m in iv else 0.0 for m in range(B)] for q in range(3)]
             self.filter_states(n, cols[0], cols[1], cols[2], ks, active=mask(going))
 
-        def ritz(going):
-            r = self.ritz(ks, active=mask(going))
-            return {m: (r[m]["status"], r[m]["evals"]) for m in going}
-
-        def residuals(going, theta):
-            r = self.residuals(ks, theta=[theta.get(m) for m in range(B)], active=mask(going))
-            return {m: r[m]["rho"] for m in going}
-
         return filtered_solve_loop(bound, filt, ritz, residuals, ks, tolerance, degree, max_blocks, guard)
 
     def solve_block(self, k, tolerance: float, steps_per_block: int, max_blocks: int, active=None) -> list:
         """Context.solve_block for every listed member at once (block_solve_loop): per block one evolve_states, one ritz and one
         residuals call over the members still going; a member whose Ritz energies all moved by less than `tolerance` leaves the
         active set, as in Batch.solve.  -> per member the dict of Context.solve_block, None for members not listed (or with k 0)."""
-        a = self._mask(active)
-        ks = self._store_ks(k, a)
-        B = len(self.members)
-
-        def mask(going):
-            m = np.zeros(B, dtype=np.uint8)
-            m[going] = 1
-            return m
-
-        def step(going, n):
-            self.evolve_states(n, ks, active=mask(going))
-
-        def ritz(going):
-            r = self.ritz(ks, active=mask(going))
-            return {m: (r[m]["status"], r[m]["evals"]) for m in going}
-
-        def residuals(going, theta):
-            r = self.residuals(ks, theta=[theta.get(m) for m in range(B)], active=mask(going))
-            return {m: r[m]["rho"] for m in going}
-
-        return block_solve_loop(step, ritz, residuals, ks, tolerance, steps_per_block, max_blocks)
+        ks = self._store_ks(k, self._mask(active))
+        mask, ritz, residuals = self._solver_calls(ks)
+        return block_solve_loop(lambda going, n: self.evolve_states(n, ks, active=mask(going)), ritz, residuals, ks, tolerance, steps_per_block,
+                                max_blocks)
 
     # -- residuals of the stores and of phi (include/wafer_hip.h) ----------------------------------------
     def residuals(self, k=None, theta=None, active=None, source: str = "states") -> list:
@@ -1569,17 +1533,7 @@ class Batch:
             raise ValueError("source must be 'states' or 'phi', not %r" % (source,))
         a = self._mask(active)
         B = len(self.members)
-        if source == "phi":
-            ks = [1] * B if k is None else ([int(k)] * B if np.ndim(k) == 0 else [0 if x is None else int(x) for x in k])
-            if len(ks) != B:
-                raise ValueError("k must hold one entry per member")
-            for m in range(B):
-                if a is not None and not a[m]:
-                    ks[m] = 0
-                elif ks[m] != 1:
-                    raise ValueError("member %d: k = %d: the phi source is one array (k = 1)" % (m, ks[m]))
-        else:
-            ks = self._ritz_ks(k, a)
+        ks = self._ks(k, a, 1, 1, ": the phi source is one array (k = 1)", default=1) if source == "phi" else self._ritz_ks(k, a)
         tin = None
         if theta is not None:
             if len(theta) != B:
