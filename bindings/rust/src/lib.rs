@@ -92,6 +92,13 @@ pub const WAFER_RESAMPLE_POTENTIAL: c_int = 1;
 pub const WAFER_RESAMPLE_POTSUB: c_int = 2;
 pub const WAFER_RESAMPLE_STATE: c_int = 3;
 /// `basis` of `wafer_batch_resample(_member)`: the member's padded size, or its work size
+pub const WAFER_MOMENT_S: usize = 0;
+pub const WAFER_MOMENT_X: usize = 1;
+pub const WAFER_MOMENT_Y: usize = 2;
+pub const WAFER_MOMENT_Z: usize = 3;
+pub const WAFER_MOMENT_R2: usize = 4;
+pub const WAFER_MOMENT_COUNT: usize = 5;
+
 pub const WAFER_BASIS_PADDED: c_int = 0;
 pub const WAFER_BASIS_WORK: c_int = 1;
 
@@ -203,6 +210,9 @@ extern "C" {
         ctx: *mut wafer_ctx, source: c_int, k: u32, theta_in: *const f64, theta: *mut f64, r2: *mut f64, s: *mut f64,
     ) -> c_int;
     pub fn wafer_residual_to_phi(ctx: *mut wafer_ctx, idx: u32, theta: f64) -> c_int;
+    /// The five moment matrices S, X, Y, Z, R2 of the first k stored states (include/wafer_hip.h; the origin lies one cell above the
+    /// geometric centre, as in wafer_observables): `m` holds WAFER_MOMENT_COUNT * k * k doubles, m[(q * k + j) * k + i]
+    pub fn wafer_moment_matrices(ctx: *mut wafer_ctx, k: u32, m: *mut f64) -> c_int;
     pub fn wafer_solve_state(
         ctx: *mut wafer_ctx, wnum: u32, tolerance: f64, screen_update: u64, has_max_steps: c_int, max_steps: u64,
         records: *mut wafer_block_record, max_records: usize, n_records: *mut usize, final_out: *mut wafer_observables_output,
@@ -311,6 +321,9 @@ extern "C" {
         s: *mut f64, status: *mut c_int,
     ) -> c_int;
     pub fn wafer_batch_diag_residual_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
+    /// wafer_moment_matrices for every listed member: member mb's matrix q, k[mb] x k[mb] row-major, at `(mb * 5 + q) * 64`
+    pub fn wafer_batch_moment_matrices(b: *mut wafer_batch, active: *const u8, k: *const u32, m: *mut f64) -> c_int;
+    pub fn wafer_batch_diag_moment_counts(b: *mut wafer_batch, launches: *mut u64, readbacks: *mut u64) -> c_int;
     /// wafer_evolve_states for every listed member with its own k[m] (0: nothing), one launch per step for all of them
     pub fn wafer_batch_evolve_states(b: *mut wafer_batch, active: *const u8, k: *const u32, n_steps: u64) -> c_int;
     pub fn wafer_batch_diag_store_step(b: *mut wafer_batch, buf: *mut c_char, n: usize) -> c_int;

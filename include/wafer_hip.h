@@ -308,6 +308,33 @@ int wafer_residuals(wafer_ctx *ctx, int source, uint32_t k, const double *theta_
  * leaves the store alone.  No state idx or no potential: WAFER_ERR_STATE; a non-finite theta or a z-slab: WAFER_ERR_INVALID. */
 int wafer_residual_to_phi(wafer_ctx *ctx, uint32_t idx, double theta);
 
+/* ---- moment matrices of w_store ------------------------------------------- */
+/* What else a converged set of levels is asked: for the first k stored states l_0 .. l_{k-1} the five k x k matrices
+ *   S_ij = <l_i|l_j>   X_ij = <l_i|x|l_j>   Y_ij = <l_i|y|l_j>   Z_ij = <l_i|z|l_j>   R2_ij = <l_i|r^2|l_j>
+ * -- sizes (R2_jj / S_jj) and dipole matrix elements -- from one sums launch, one reduce and one read-back.  For a work cell c with
+ * 0-based work indices (ix, iy, iz) of a grid nx x ny x nz
+ *   dx = (double)ix - ((double)nx + 1.) / 2.     dy, dz likewise     r2c = dx * dx + dy * dy + dz * dz
+ * which is the r^2 of wafer_observables letter for letter, in index units like wafer_observables_t's r2.  NOTE the origin: it lies
+ * ONE CELL ABOVE the geometric centre (n - 1) / 2 of the work indices.  That is the reference's convention (grid.rs:428-437),
+ * kept so that the diagonal ties to wafer_observables; S is returned so that a caller can move the origin without a second call:
+ * <i|x - c|j> = X_ij - c * S_ij.  For column j and every i <= j, every operand widened to double and every operation fp64 and
+ * unfused whatever the dtype:
+ *   w = l_j[c]   l = l_i[c]   p = l * w      S_ji += p   X_ji += p * dx   Y_ji += p * dy   Z_ji += p * dz   R2_ji += p * r2c
+ * over the work cells only (frame cells are never read), on the partition of wafer_observables and wafer_ritz_matrices, without
+ * floating-point atomics: R2[j][j] and S[j][j] have the bits of wafer_observables' r2 and norm2 on state j, every S entry the bits
+ * of wafer_ritz_matrices' s, and the entries of the columns below k do not depend on k.  The entries i > j are copies of their
+ * mirror images (l * w commutes: the copy is exact).  m: WAFER_MOMENT_COUNT * k * k doubles, matrix q row-major at q * k * k.
+ * Checked before any launch, and a refused call writes nothing: k == 0, k > WAFER_RITZ_MAX, m == NULL and a context that owns a
+ * z-slab are WAFER_ERR_INVALID; k above the number of stored states, WAFER_ERR_STATE.  Read-only like wafer_residuals: the store,
+ * phi, the Gram matrices and the two-step pass's images keep every bit.  V is not read: no potential is needed. */
+#define WAFER_MOMENT_S 0
+#define WAFER_MOMENT_X 1
+#define WAFER_MOMENT_Y 2
+#define WAFER_MOMENT_Z 3
+#define WAFER_MOMENT_R2 4
+#define WAFER_MOMENT_COUNT 5
+int wafer_moment_matrices(wafer_ctx *ctx, uint32_t k, double *m);   /* m[(q * k + j) * k + i] */
+
 /* ---- solve (grid.rs:50-246) for ONE state, snapshot branch excluded ------ */
 /* phi must hold the starting wavefunction.  Writes up to max_records rows,
  * *n_records = rows produced.  Returns WAFER_OK when converged (phi has then
@@ -816,6 +843,18 @@ int wafer_batch_residuals(wafer_batch *b, int source, const uint8_t *active, con
                           double *theta, double *r2, double *s, int *status);
 /* launches and read-backs of wafer_batch_residuals since creation */
 int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
+
+/* ---- moment matrices on a batch ---------------------------------------------
+ * wafer_moment_matrices (above) for every listed member (active[m] != 0; NULL: all), each with its own k[m] and the centres of its
+ * own nx, ny, nz: one sums launch, one reduce launch and one read-back for all listed members whatever their number and shapes.
+ * An empty list returns WAFER_OK and launches nothing.  Every member gets bit for bit what a wafer_ctx of its own wafer_params
+ * holding the same states gets.  k has n_members entries; m holds n_members * WAFER_MOMENT_COUNT * WAFER_RITZ_MAX^2 doubles: member
+ * mb's matrix q, k[mb] x k[mb] row-major, at (mb * WAFER_MOMENT_COUNT + q) * WAFER_RITZ_MAX^2.  Entries of members not listed are
+ * not written.  Every check of wafer_moment_matrices runs for every listed member before anything is uploaded or launched and names
+ * the member; a mixed-shape batch made without state stores is refused as every excited-state call there.  Read-only. */
+int wafer_batch_moment_matrices(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *m);
+/* launches and read-backs of wafer_batch_moment_matrices since creation: 2 and 1 per call */
+int wafer_batch_diag_moment_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks);
 
 /* ---- stepping the stores of a batch -----------------------------------------
  * wafer_evolve_states (above) for every listed member (active[m] != 0; NULL: all), each with its own k[m]: ONE launch per step

@@ -56,6 +56,10 @@ member's state 0, which waits for the rotation.  --reps repetitions after one wa
 both sides after the last repetition; "ritz_counts": the launches and read-backs one Batch.ritz adds.  Appended to
 profiles/batch_ritz_rows.jsonl unless --out names another file.
 
+--moments K: a mode of its own -- Batch.moments on K stored states per member (the stores of --ritz).  One line per B: "batch_moments_ms",
+"batch_ritz_matrices_ms" (the same stores, for scale: that call also reads V and the neighbours) and "ctx_moments_ms" (B Contexts calling
+moments one after another), `--reps` repetitions after one warm-up, all listed; "parity": every member's five matrices == on both sides.
+
 --residuals K: a mode of its own -- Batch.residuals on K stored states per member (the stores of --ritz).  One line per B:
 "batch_given_ms" / "ctx_given_ms": the wall clock around Batch.residuals(K, theta) (two launches and one read-back for all members) and
 around B Contexts calling residuals(K, theta) one after another; "batch_rayleigh_ms" / "ctx_rayleigh_ms": the same with theta=None (two
@@ -494,6 +498,55 @@ def residual_row(shapes, B, K, reps, ext=1, dtype="f64"):
     return out
 
 
+def moment_row(shapes, B, K, reps, ext=1, dtype="f64"):
+    """Batch.moments on K stored states per member beside Batch.ritz_matrices on the same stores and against B contexts calling
+    moments one after another; every member's five matrices compared == on both sides"""
+    pars = [wafer_amd.Params(*shapes[k % len(shapes)], dn=0.2, dt=0.002 + 0.008 * k / max(1, B), mass=1.0, central_difference=ext, dtype=dtype,
+                             max_states=K) for k in range(B)]
+    out = {"mode": "moments", "k": K, "shapes": [list(s) for s in shapes], "B": B, "reps": reps,
+           "stencil": ("ThreePoint", "FivePoint", "SevenPoint")[ext - 1], "dtype": dtype}
+    per_shape = {s: [store(pars[shapes.index(s)], K, seed=j) for j in range(2)] for s in dict.fromkeys(shapes)}   # (two stores per shape, shared out)
+    stores = [per_shape[shapes[k % len(shapes)]][(k // len(shapes)) % 2] for k in range(B)]
+    keys = ("batch_moments_ms", "batch_ritz_matrices_ms", "ctx_moments_ms")
+    for key in keys:
+        out[key] = []
+    mixed = len(set(shapes)) > 1
+    ctxs = [wafer_amd.Context(p) for p in pars]
+    try:
+        with wafer_amd.Batch(pars, mixed_shapes=mixed, state_stores=mixed) as b:
+            b.set_potentials(["Harmonic"] * B)
+            for k, c in enumerate(ctxs):
+                for i in range(K):
+                    c.load_state(i, stores[k][i])
+                    b.load_state(k, i, stores[k][i])
+
+            def timed_call(fn):
+                t0 = time.perf_counter()
+                res = fn()
+                return 1e3 * (time.perf_counter() - t0), res
+
+            calls = (lambda: b.moments(K), lambda: b.ritz_matrices(K), lambda: [c.moments(K) for c in ctxs])
+            for fn in calls:                                 # warm-up of each: the buffers are made here
+                fn()
+            for _ in range(reps):
+                for key, fn in zip(keys, calls):
+                    out[key].append(timed_call(fn)[0])
+            c0 = b.moment_counts()
+            got = b.moments(K)
+            out["moment_counts"] = [x - y for x, y in zip(b.moment_counts(), c0)]
+            same = lambda x, y: bool(np.array_equal(np.ascontiguousarray(x).view(np.int64), np.ascontiguousarray(y).view(np.int64)))
+            out["parity"] = all(same(br[name], cr[name]) for br, cr in zip(got, calls[2]()) for name in ("s", "x", "y", "z", "r2"))
+            out["shapes_in_batch"] = b.num_shapes()
+    finally:
+        for c in ctxs:
+            c.close()
+    for key in keys:
+        out[key.replace("_ms", "_spread")] = (max(out[key]) - min(out[key])) / float(np.median(out[key]))
+    out["ratio_contexts_over_batch"] = [c / h for c, h in zip(out["ctx_moments_ms"], out["batch_moments_ms"])]
+    out["ratio_ritz_matrices_over_moments"] = [r / h for r, h in zip(out["batch_ritz_matrices_ms"], out["batch_moments_ms"])]
+    return out
+
+
 def store_step_row(n, B, K, steps, warmup, reps, ext=1, dtype="f64"):
     """Batch.evolve_states(steps, K) on B members against Batch.evolve on B x K members and against excited steps with wnum = K - 1"""
     steps += steps % 2   # (an even number of steps: no trailing copy in the timed calls)
@@ -673,6 +726,8 @@ def main():
     ap.add_argument("--residuals", type=int, metavar="K", help="time Batch.residuals on K stored states per member, theta given and in Rayleigh "
                     "mode, against B contexts calling residuals one after another (a mode of its own; --batch, --reps, --sizes or --mixed, --ext, "
                     "--dtype apply)")
+    ap.add_argument("--moments", type=int, metavar="K", help="time Batch.moments on K stored states per member beside Batch.ritz_matrices and against "
+                    "B contexts calling moments one after another (a mode of its own; --batch, --reps, --sizes or --mixed, --ext, --dtype apply)")
     ap.add_argument("--store-step", type=int, metavar="K", help="time Batch.evolve_states on K stored states per member against Batch.evolve on "
                     "B x K members and against excited steps with wnum = K - 1 (a mode of its own; --batch, --steps, --warmup, --reps, --sizes, --ext, "
                     "--dtype apply)")
@@ -701,6 +756,16 @@ def main():
                 print(line, flush=True)
                 with open(a.out, "a") as f:
                     f.write(line + "\n")
+        return
+    if a.moments:
+        if not a.out:
+            a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "batch_moments_rows.jsonl")
+        shapes = parse_shapes(a.mixed) if a.mixed else [(a.sizes[0],) * 3]
+        for B in a.batch:
+            line = json.dumps(rounded(moment_row(shapes, B, a.moments, a.reps, a.ext, a.dtype)))
+            print(line, flush=True)
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
         return
     if a.residuals:
         if not a.out:

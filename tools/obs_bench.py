@@ -10,6 +10,11 @@
                                               states (each on phi after an untimed clone): one warm-up, then three repetitions, all
                                               listed; both read one state and V once per state, 2 K array passes of distinct reads
 
+    obs_bench.py [n] --moments K [--dtype D] [--out F]
+                                              moments(K) on K stored states beside ritz_matrices(K) and K calls of observables on the
+                                              same states (each on phi after an untimed clone): one warm-up, then three repetitions,
+                                              all listed; moments reads K (K + 3) / 2 arrays (per column j the states 0 .. j and l_j)
+
 The --ritz rows count bytes as array passes of n^3 elements: k (k + 2) reads for ritz_matrices (per column the state's own
 stencil, V and the k states), 2 k passes for rotate_states (k read, k written) -- whose time includes the k (k - 1) / 2 overlap
 passes of the Gram matrix the engine recomputes after every change of the store (at most 6: the matrix covers four states)."""
@@ -22,10 +27,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("n", nargs="?", type=int, default=512)
 ap.add_argument("--ritz", type=int, default=0, metavar="K")
 ap.add_argument("--residuals", type=int, default=0, metavar="K")
-ap.add_argument("--out", help="--residuals: also append the line to this file")
+ap.add_argument("--moments", type=int, default=0, metavar="K")
+ap.add_argument("--out", help="--residuals, --moments: also append the line to this file")
 ap.add_argument("--dtype", default="f64", choices=["f64", "f32", "f32fast"])
 args = ap.parse_args()
-n, k = args.n, args.ritz or args.residuals
+n, k = args.n, args.ritz or args.residuals or args.moments
 env = {a: b for a, b in os.environ.items() if a.startswith("WAFER_")}
 
 
@@ -49,6 +55,32 @@ with wafer_amd.Context(wafer_amd.Params(n, n, n, dn=0.05, dt=5e-4, max_states=ma
         ctx.evolve(0, 3)
         ctx.normalise(ctx.norm2())
         ctx.push_state()
+    if args.moments:
+        esz = 8 if args.dtype == "f64" else 4
+        passes = k * (k + 3) // 2                          # column j loads l_j and the states 0 .. j
+
+        def call_ms(fn):
+            ctx.synchronize(); t0 = time.perf_counter(); fn(); return (time.perf_counter() - t0) * 1e3
+
+        def observables_ms():
+            total = 0.0
+            for j in range(k):
+                ctx.clone_state_to_phi(j); ctx.synchronize(); t0 = time.perf_counter(); ctx.observables(); total += (time.perf_counter() - t0) * 1e3
+            return total
+
+        call_ms(lambda: ctx.moments(k)), call_ms(lambda: ctx.ritz_matrices(k)), observables_ms()   # one warm-up of each
+        mom, ritz, obs = [], [], []
+        for _ in range(3):
+            mom.append(call_ms(lambda: ctx.moments(k))); ritz.append(call_ms(lambda: ctx.ritz_matrices(k))); obs.append(observables_ms())
+        line = json.dumps({"op": "moments", "n": n, "dtype": args.dtype, "k": k, "moments_ms": [round(t, 4) for t in mom],
+                           "ritz_matrices_ms": [round(t, 4) for t in ritz], "observables_x_k_ms": [round(t, 4) for t in obs],
+                           "array_passes": passes, "moments_tbps_loads": [round(passes * float(n) ** 3 * esz / (t * 1e-3) / 1e12, 3) for t in mom],
+                           "env": env})
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+        sys.exit(0)
     if args.residuals:
         esz = 8 if args.dtype == "f64" else 4
         distinct = 2.0 * k * float(n) ** 3 * esz          # per state: the state and V, once each

@@ -18,12 +18,12 @@ LIB = os.path.join(HERE, "libwafer_hip.so")
 SOURCES = ["wafer_engine.hip", "wafer_engine_schedules.hip", "wafer_engine_comm.hip", "wafer_engine_solve.hip", "wafer_tu_lds.hip", "wafer_tu_excited_r1.hip", "wafer_tu_excited_r2.hip", "wafer_tu_excited_r3.hip",
            "wafer_tu_fused2.hip", "wafer_tu_fused2w.hip", "wafer_tu_fused3.hip", "wafer_tu_fused3_wide.hip", "wafer_tu_x2.hip", "wafer_mailbox.hip",
            "wafer_engine_batch.hip", "wafer_engine_batch_stores.hip", "wafer_tu_batch.hip", "wafer_tu_gs_batch.hip", "wafer_tu_batch_mixed.hip", "wafer_tu_gs_batch_mixed.hip", "wafer_tu_ritz.hip", "wafer_tu_ritz_batch.hip",
-           "wafer_tu_residual.hip", "wafer_tu_residual_batch.hip", "wafer_tu_store_step_batch.hip", "wafer_tu_store_step_batch_mixed.hip",
+           "wafer_tu_residual.hip", "wafer_tu_residual_batch.hip", "wafer_tu_moments.hip", "wafer_tu_moments_batch.hip", "wafer_tu_store_step_batch.hip", "wafer_tu_store_step_batch_mixed.hip",
            "wafer_tu_store_filter_batch.hip", "wafer_tu_store_filter_batch_mixed.hip"]
 HEADERS = ["wafer_engine.h", "wafer_engine_batch.h", "wafer_buffers.h", "wafer_passes.h", "wafer_storage.h", "wafer_geom.h", "wafer_tuning.h", "wafer_launch.h", "wafer_stencil_fused2w.hip.h", "wafer_stencil.hip.h", "wafer_stencil_lds.hip.h",
            "wafer_stencil_fused2.hip.h", "wafer_stencil_fused3.hip.h", "wafer_stencil_fused3_iter.inc.h", "wafer_stencil_x2.hip.h", "wafer_stencil_x2_iter.inc.h", "wafer_elementwise.hip.h", "wafer_rowwalk.h", "wafer_setup.hip.h",
            "wafer_tu_excited.inc", "wafer_tu_batch.inc", "wafer_tu_gs_batch.inc", "wafer_stencil_batch.hip.h", "wafer_batch_plan.h", "wafer_gs_batch.hip.h", "wafer_tile_roles.hip.h", "wafer_symmetry.hip.h", "wafer_resample_batch.hip.h", "wafer_setup_batch.hip.h", "wafer_ritz.hip.h", "wafer_ritz.h", "wafer_ritz_batch.hip.h",
-           "wafer_residual.hip.h", "wafer_residual_batch.hip.h", "wafer_store_step_batch.hip.h", "wafer_tu_store_step_batch.inc",
+           "wafer_residual.hip.h", "wafer_residual_batch.hip.h", "wafer_moments.hip.h", "wafer_moments_batch.hip.h", "wafer_store_step_batch.hip.h", "wafer_tu_store_step_batch.inc",
            "wafer_filter.h", "wafer_store_filter_batch.hip.h", "wafer_tu_store_filter_batch.inc"]
 # -ffp-contract=off: the stencil update must round exactly like the reference's
 # (rustc never fuses mul+add); see DESIGN.md "Parity contract".

@@ -125,6 +125,7 @@ struct Config {
     int device = 0;            // engine extension: optional `gpu.device`
     bool ritz = false;         // engine extension: optional `gpu.ritz` -- one Rayleigh-Ritz step on the stored states after the last solve
     bool residual = false;     // engine extension: optional `gpu.residual` -- theta and rho = |H l - theta l| / |l| of every stored state after the last solve
+    bool moments = false;      // engine extension: optional `gpu.moments` -- <i|1|j>, <i|x|j>, <i|y|j>, <i|z|j>, <i|r^2|j> of the stored states after the last solve
 };
 
 static int index_of(const char *const *names, int n, const std::string &v)
@@ -199,6 +200,7 @@ static bool load_config(const std::string &path, Config &c, std::string &err)
     if (kv.count("gpu.device")) c.device = atoi(kv["gpu.device"].c_str());
     if (kv.count("gpu.ritz") && !boolean("gpu.ritz", c.ritz)) return false;
     if (kv.count("gpu.residual") && !boolean("gpu.residual", c.residual)) return false;
+    if (kv.count("gpu.moments") && !boolean("gpu.moments", c.moments)) return false;
     // Config::parse, config.rs:362-370
     if (c.dt > c.dn * c.dn / 3.) { err = "ConfigParse: LargeDt: dt must be <= dn^2/3"; return false; }
     if (c.wavenum > c.wavemax) { err = "ConfigParse: LargeWavenum: wavenum must be <= wavemax"; return false; }
@@ -518,7 +520,7 @@ int main(int argc, char **argv)
                "\"central_difference\": %d, \"max_steps\": %s, \"wavenum\": %u, \"wavemax\": %u, \"potential\": \"%s\", "
                "\"mass\": %s, \"init_condition\": \"%s\", \"sig\": %s, \"init_symmetry\": \"%s\", \"screen_update\": %llu, "
                "\"snap_update\": %s, \"file_type\": \"%s\", \"save_wavefns\": %s, \"save_potential\": %s, \"dtype\": \"%s\", \"ritz\": %s, "
-               "\"residual\": %s}\n",
+               "\"residual\": %s, \"moments\": %s}\n",
                cfg.project_name.c_str(), cfg.nx, cfg.ny, cfg.nz, num_text(cfg.dn).c_str(), num_text(cfg.dt).c_str(),
                num_text(cfg.tolerance).c_str(), cfg.central_difference,
                cfg.has_max_steps ? std::to_string(cfg.max_steps).c_str() : "null", cfg.wavenum, cfg.wavemax,
@@ -526,7 +528,7 @@ int main(int argc, char **argv)
                num_text(cfg.sig).c_str(), cfg.init_symmetry.c_str(), (unsigned long long)cfg.screen_update,
                cfg.has_snap_update ? std::to_string(cfg.snap_update).c_str() : "null", kFileTypes[cfg.file_type],
                cfg.save_wavefns ? "true" : "false", cfg.save_potential ? "true" : "false", cfg.dtype.c_str(), cfg.ritz ? "true" : "false",
-               cfg.residual ? "true" : "false");
+               cfg.residual ? "true" : "false", cfg.moments ? "true" : "false");
         return 0;
     }
     const int symmetry = index_of(kSymmetry, 5, cfg.init_symmetry);
@@ -806,6 +808,25 @@ int main(int argc, char **argv)
             for (uint32_t a = 0; a < ns; ++a)
                 printf("%3u %s %s\n", a, pad_left(rust_lower_exp(theta[a], 10), 19).c_str(),
                        pad_left(rust_lower_exp(std::sqrt(r2[a] / s2[a]), 10), 19).c_str());
+            printf("\n");
+        }
+    }
+    if (cfg.moments) { // sizes and dipole matrix elements of the stored states, in index units from observables' origin (include/wafer_hip.h)
+        uint32_t ns = 0;
+        CHECK(wafer_num_states(ctx, &ns));
+        if (ns < 1 || ns > WAFER_RITZ_MAX) {
+            fprintf(stderr, "Moments: skipped, %u stored states (the call takes 1 .. %d)\n", ns, WAFER_RITZ_MAX);
+        } else {
+            std::vector<double> mm((size_t)WAFER_MOMENT_COUNT * ns * ns);
+            CHECK(wafer_moment_matrices(ctx, ns, mm.data()));
+            printf("Moments\n");   // i, j (i <= j), then <i|1|j>, <i|x|j>, <i|y|j>, <i|z|j>, <i|r^2|j>
+            for (uint32_t j = 0; j < ns; ++j)
+                for (uint32_t i = 0; i <= j; ++i) {
+                    printf("%3u %3u", i, j);
+                    for (uint32_t q = 0; q < WAFER_MOMENT_COUNT; ++q)
+                        printf(" %s", pad_left(rust_lower_exp(mm[((size_t)q * ns + j) * ns + i], 10), 19).c_str());
+                    printf("\n");
+                }
             printf("\n");
         }
     }

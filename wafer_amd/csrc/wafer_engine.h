@@ -274,6 +274,9 @@ int recompute_gram(wafer_ctx *c);
 // the argument block of the context's observables launch, and ritz_buf grown to hold `doubles`
 WaferStepArgs ritz_args(const wafer_ctx *c);
 int ensure_ritz_buf(wafer_ctx *c, size_t doubles);
+// ---- wafer_tu_moments.hip
+// the five moment matrices of the first k stored states (k checked by the caller) into m[(q * k + j) * k + i]
+int moment_matrices(wafer_ctx *c, uint32_t k, double *m);
 // ---- wafer_engine_comm.hip
 int exchange_halo_array(wafer_ctx *c, void *array, hipStream_t s, int planes);
 int exchange_halo(wafer_ctx *c, int buf, hipStream_t s, int planes);

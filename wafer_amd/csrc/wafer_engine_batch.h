@@ -8,6 +8,7 @@
 #include "wafer_setup_batch.hip.h"
 #include "wafer_ritz_batch.hip.h"
 #include "wafer_residual_batch.hip.h"
+#include "wafer_moments_batch.hip.h"
 #include "wafer_filter.h"
 #include "wafer_buffers.h"
 
@@ -126,6 +127,10 @@ struct wafer_batch {
     Mirror<WaferBatchResidualRec> resid_rec;  // the per-call table, n entries
     Mirror<double> resid_sums;                // [member][3 WAFER_RITZ_MAX]: r2, wh, s of column j at j * 3
     uint64_t n_resid_launches = 0, n_resid_readbacks = 0;     // of wafer_batch_residuals since creation (wafer_batch_diag_residual_counts)
+    // moment matrices (wafer_moments_batch.hip.h); made by the first call (ensure_moments).  The partials live in ritz_partials.
+    Mirror<WaferBatchMomentRec> moment_rec;   // the per-call table, n entries
+    Mirror<double> moment_sums;               // [member][WAFER_MOMENT_COUNT * WAFER_RITZ_MAX^2]: the member's 5 k (k + 1) / 2 computed rows first
+    uint64_t n_moment_launches = 0, n_moment_readbacks = 0;   // of wafer_batch_moment_matrices since creation (wafer_batch_diag_moment_counts)
     // stepping the stores (wafer_store_step_batch.hip.h): shadow l is laid out as slot l is, zeroed, made by the first call that needs it
     std::vector<DevArray<char>> shadows;
     Mirror<int> store_k;                      // [member]: the call's k (0: not listed)

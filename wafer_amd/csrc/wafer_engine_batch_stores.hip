@@ -5,6 +5,8 @@
 // read-back, the solves on the host (wafer_ritz.h), one rotation launch -- from a per-call table of (member, k, partials offset, span).
 // Residuals (wafer_batch_residuals; kernels: wafer_residual_batch.hip.h, wafer_tu_residual_batch.hip): a context's wafer_residuals for
 // every listed member with its own k and theta, on the stores or on phi -- one sums launch, one reduce and one read-back per pass.
+// Moment matrices (wafer_batch_moment_matrices; kernels: wafer_moments_batch.hip.h, wafer_tu_moments_batch.hip): a context's
+// wafer_moment_matrices for every listed member with its own k -- one sums launch, one reduce and one read-back.
 // Stepping the stores (wafer_batch_evolve_states; kernels: wafer_store_step_batch.hip.h, wafer_tu_store_step_batch*.hip): the first k[m]
 // stored states of every listed member advance by n plain steps, one launch per step over the listed members' workgroup table,
 // between the slots and shadow slots laid out as they are; an odd n ends with one batched copy back into the slots.
@@ -55,14 +57,14 @@ struct CallTable {
 };
 
 // The per-call table of the listed members into t's host side and to the device: member, k, the prefix sums of the member's rows of
-// obs_nb partials -- 2 k^2 and the member's span in a slot allocation (WaferBatchRitzRec), or 3 k and theta (WaferBatchResidualRec:
-// member m's at m * WAFER_RITZ_MAX; nullptr: zeros).  partials: ritz_partials holds them when this returns, grown on demand as a
+// obs_nb partials -- 2 k^2 and the member's span in a slot allocation (WaferBatchRitzRec), 3 k and theta (WaferBatchResidualRec:
+// member m's at m * WAFER_RITZ_MAX; nullptr: zeros), or 5 k (k + 1) / 2 (WaferBatchMomentRec).  partials: ritz_partials holds them when this returns, grown on demand as a
 // context's ritz_buf.  The stream is idle (the callers synchronised: t's host side is not read by an earlier copy, and no launch
 // reads partials that go back).
 template <typename Rec>
 int upload_table(wafer_batch *b, Mirror<Rec> &t, const uint8_t *listed, const uint32_t *k, const double *theta, bool partials, CallTable *c)
 {
-    constexpr bool ritz = std::is_same<Rec, WaferBatchRitzRec>::value;
+    constexpr bool ritz = std::is_same<Rec, WaferBatchRitzRec>::value, resid = std::is_same<Rec, WaferBatchResidualRec>::value;
     for (uint32_t m = 0; m < b->n; ++m) {
         if (listed && !listed[m]) continue;
         Rec &r = t[c->nact++];
@@ -73,10 +75,11 @@ int upload_table(wafer_batch *b, Mirror<Rec> &t, const uint8_t *listed, const ui
             r.v0 = (long long)(b->off[m] * b->esz / 16);
             r.n16 = (long long)((size_t)b->geom(m).total * b->esz / 16);
             c->blocks = std::max(c->blocks, (int)std::min<long long>((r.n16 + 255) / 256, (long long)b->num_cus * 8));
-        } else {
+        } else if constexpr (resid) {
             for (uint32_t j = 0; j < WAFER_RITZ_MAX; ++j) r.theta[j] = (theta && j < k[m]) ? theta[(size_t)m * WAFER_RITZ_MAX + j] : 0.0;
         }
-        c->doubles += (ritz ? 2 * (size_t)k[m] * k[m] : 3 * (size_t)k[m]) * (size_t)b->mem[m].obs_nb;
+        const size_t rows = ritz ? 2 * (size_t)k[m] * k[m] : resid ? 3 * (size_t)k[m] : (size_t)wafer_moment_rows((int)k[m]);
+        c->doubles += rows * (size_t)b->mem[m].obs_nb;
         c->max_nb = std::max(c->max_nb, b->mem[m].obs_nb);
         c->max_k = std::max(c->max_k, (int)k[m]);
     }
@@ -199,6 +202,55 @@ int residual_pass(wafer_batch *b, int source, const uint8_t *listed, const uint3
     BUF_TRY(b->resid_sums.download(RESID_ROWS * (c.m1 - c.m0), b->s, RESID_ROWS * c.m0));
     HIP_TRY(hipStreamSynchronize(b->s));
     ++b->n_resid_readbacks;
+    return WAFER_OK;
+}
+
+// ---- moment matrices of the stores -------------------------------------------------------------------------------------------
+constexpr size_t MOMENT_ROWS = (size_t)WAFER_MOMENT_COUNT * RITZ_KK;
+
+// every check of wafer_batch_moment_matrices for every listed member, before anything is uploaded or launched; *nlisted: their number
+int moment_check(const wafer_batch *b, const uint8_t *active, const uint32_t *k, int *nlisted)
+{
+    TRY(refuse_mixed(b, "wafer_batch_moment_matrices"));
+    *nlisted = 0;
+    for (uint32_t m = 0; m < b->n; ++m) {
+        if (active && !active[m]) continue;
+        if (k[m] == 0 || k[m] > WAFER_RITZ_MAX)
+            return fail(WAFER_ERR_INVALID, "member %u: k = %u: moment matrices take 1 .. %d states", m, k[m], WAFER_RITZ_MAX);
+        if (k[m] > b->nst[m]) return fail(WAFER_ERR_STATE, "member %u: k = %u but w_store holds %u states", m, k[m], b->nst[m]);
+        ++*nlisted;
+    }
+    return WAFER_OK;
+}
+
+int ensure_moments(wafer_batch *b)
+{
+    if (b->moment_sums.dev) return WAFER_OK;   // (made last: a call that failed before it starts over)
+    BUF_TRY(b->moment_rec.make(b->n));
+    BUF_TRY(b->moment_sums.make(MOMENT_ROWS * b->n));
+    return WAFER_OK;
+}
+
+// the computed rows of every listed member (checked: moment_check; at least one) into moment_sums' host side: the per-call table,
+// the sums launch, the reduce and one read-back
+int moment_pass(wafer_batch *b, const uint8_t *active, const uint32_t *k)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    RoctxRange range_("wafer_batch_moment_matrices");
+    TRY(ensure_moments(b));
+    TRY(sync_members(b));
+    HIP_TRY(hipStreamSynchronize(b->s));   // the pinned table is not read by an earlier call's copy
+    CallTable c;
+    TRY(upload_table(b, b->moment_rec, active, k, nullptr, true, &c));
+    const WaferRitzPtrs st = ritz_slots(b->slots);
+    TRY(launch(b, "moment sums", [&](const auto &gs) {
+        return wafer_entry_batch_moment_sums(b->f32, b->g().R, gs, b->mem_dev, b->moment_rec.dev, c.nact, c.max_nb, c.max_k, b->swz, st,
+                                             b->ritz_partials, b->moment_sums.dev, b->s);
+    }));
+    b->n_moment_launches += 2;
+    BUF_TRY(b->moment_sums.download(MOMENT_ROWS * (c.m1 - c.m0), b->s, MOMENT_ROWS * c.m0));
+    HIP_TRY(hipStreamSynchronize(b->s));
+    ++b->n_moment_readbacks;
     return WAFER_OK;
 }
 
@@ -492,6 +544,35 @@ int wafer_batch_diag_residual_counts(wafer_batch *b, uint64_t *launches, uint64_
     if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
     *launches = b->n_resid_launches;
     *readbacks = b->n_resid_readbacks;
+    return WAFER_OK;
+}
+
+int wafer_batch_moment_matrices(wafer_batch *b, const uint8_t *active, const uint32_t *k, double *m)
+{
+    if (!b || !k || !m) return fail(WAFER_ERR_INVALID, "null argument");
+    int nlisted = 0;
+    TRY(moment_check(b, active, k, &nlisted));
+    if (!nlisted) return WAFER_OK;
+    TRY(moment_pass(b, active, k));
+    // the entries i > j are copies of their mirror images: l * w commutes, so the copy is exact
+    for (uint32_t mb = 0; mb < b->n; ++mb) {
+        if (active && !active[mb]) continue;
+        const size_t kk = k[mb], tri = (size_t)wafer_moment_tri((int)kk);
+        const double *r = &b->moment_sums[mb * MOMENT_ROWS];
+        for (size_t q = 0; q < WAFER_MOMENT_COUNT; ++q) {
+            double *out = m + (mb * WAFER_MOMENT_COUNT + q) * RITZ_KK;
+            for (size_t j = 0; j < kk; ++j)
+                for (size_t i = 0; i <= j; ++i) out[j * kk + i] = out[i * kk + j] = r[q * tri + (size_t)wafer_moment_tri((int)j) + i];
+        }
+    }
+    return WAFER_OK;
+}
+
+int wafer_batch_diag_moment_counts(wafer_batch *b, uint64_t *launches, uint64_t *readbacks)
+{
+    if (!b || !launches || !readbacks) return fail(WAFER_ERR_INVALID, "null argument");
+    *launches = b->n_moment_launches;
+    *readbacks = b->n_moment_readbacks;
     return WAFER_OK;
 }
 

@@ -56,4 +56,17 @@ int wafer_solve_state(wafer_ctx *c, uint32_t wnum, double tolerance, uint64_t sc
     return wafer_push_state(c); // :239-242
 }
 
+// ---- moment matrices of the converged levels (kernel and launch: wafer_moments.hip.h, wafer_tu_moments.hip) ----
+// Every check runs before any launch; a refused call writes nothing.  Read-only, and V is not read: no potential is needed.
+int wafer_moment_matrices(wafer_ctx *c, uint32_t k, double *m)
+{
+    if (!c) return fail(WAFER_ERR_INVALID, "null context");
+    if (!m) return fail(WAFER_ERR_INVALID, "null argument");
+    if (k == 0 || k > WAFER_RITZ_MAX) return fail(WAFER_ERR_INVALID, "k = %u: moment matrices take 1 .. %d states", k, WAFER_RITZ_MAX);
+    if (c->P.z_count != 0)
+        return fail(WAFER_ERR_INVALID, "moment matrices are not available on a context that owns a z-slab (the sums would need an all-reduce)");
+    if (k > c->states.size()) return fail(WAFER_ERR_STATE, "k = %u but w_store holds %zu states", k, c->states.size());
+    return moment_matrices(c, k, m);
+}
+
 } // extern "C"

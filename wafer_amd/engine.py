@@ -69,8 +69,17 @@ EXPORTS = [
     "wafer_evolve_states", "wafer_batch_evolve_states", "wafer_batch_diag_store_step", "wafer_batch_diag_store_counts",
     "wafer_filter_coefficients", "wafer_filter_states", "wafer_spectral_bound", "wafer_batch_filter_states", "wafer_batch_spectral_bound",
     "wafer_batch_diag_filter_counts",
+    "wafer_moment_matrices", "wafer_batch_moment_matrices", "wafer_batch_diag_moment_counts",
 ]
 RITZ_MAX = 8   # WAFER_RITZ_MAX
+MOMENT_NAMES = ("s", "x", "y", "z", "r2")   # WAFER_MOMENT_S .. WAFER_MOMENT_R2
+MOMENT_COUNT = len(MOMENT_NAMES)            # WAFER_MOMENT_COUNT
+
+
+def moment_origin(nx: int, ny: int, nz: int) -> tuple:
+    """the centres the moment matrices (and observables' r2) measure from, in 0-based work indices: (n + 1) / 2 per axis -- one cell
+    above the geometric centre (n - 1) / 2, the reference's convention"""
+    return ((nx + 1.) / 2., (ny + 1.) / 2., (nz + 1.) / 2.)
 RESIDUAL_SOURCES = {"states": 0, "phi": 1}   # WAFER_RESIDUAL_STATES, WAFER_RESIDUAL_PHI
 
 
@@ -224,6 +233,7 @@ def load_library():
     L.wafer_ritz.argtypes = [vp, C.c_uint32, dp, dp, dp, dp]
     L.wafer_residuals.argtypes = [vp, C.c_int, C.c_uint32, dp, dp, dp, dp]
     L.wafer_residual_to_phi.argtypes = [vp, C.c_uint32, C.c_double]
+    L.wafer_moment_matrices.argtypes = [vp, C.c_uint32, dp]
     L.wafer_solve_state.argtypes = [vp, C.c_uint32, C.c_double, C.c_uint64, C.c_int, C.c_uint64,
                                     C.POINTER(_Record), C.c_size_t, C.POINTER(C.c_size_t),
                                     C.POINTER(_ObsOut)]
@@ -296,6 +306,8 @@ def load_library():
     L.wafer_batch_diag_ritz_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.wafer_batch_residuals.argtypes = [vp, C.c_int, u8p, u32p, dp, dp, dp, dp, C.POINTER(C.c_int)]
     L.wafer_batch_diag_residual_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.wafer_batch_moment_matrices.argtypes = [vp, u8p, u32p, dp]
+    L.wafer_batch_diag_moment_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.wafer_evolve_states.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.wafer_batch_evolve_states.argtypes = [vp, u8p, u32p, C.c_uint64]
     L.wafer_batch_diag_store_step.argtypes = [vp, C.c_char_p, C.c_size_t]
@@ -791,6 +803,19 @@ class Context:
         h, s = np.zeros((max(k, 1), max(k, 1))), np.zeros((max(k, 1), max(k, 1)))
         self._check(self._L.wafer_ritz_matrices(self._h, k, _dp(h), _dp(s)))
         return h, s
+
+    def moments(self, k: int | None = None) -> dict:
+        """-> {"s", "x", "y", "z", "r2": (k, k) each, "origin": (cx, cy, cz)}: <l_i|q|l_j> over the first k stored states (all of them
+        when k is None) for q = 1, x - cx, y - cy, z - cz and their squares' sum, in index units, from one sums launch.  The origin is
+        observables' own, (n + 1) / 2 per axis in 0-based work indices -- one cell above the geometric centre; <i|x - c|j> =
+        x[i, j] - (c - cx) * s[i, j] moves it.  r2[j, j] and s[j, j] have the bits of observables()'s r2 and norm2 on state j.
+        Read-only; needs no potential."""
+        k = self._ritz_k(k)
+        m = np.zeros((MOMENT_COUNT, max(k, 1), max(k, 1)))
+        self._check(self._L.wafer_moment_matrices(self._h, k, _dp(m)))
+        out = {name: m[q].copy() for q, name in enumerate(MOMENT_NAMES)}
+        out["origin"] = moment_origin(self.params.nx, self.params.ny, self.params.nz)
+        return out
 
     def rotate_states(self, coef: np.ndarray) -> None:
         """l'_a = sum_j coef[j, a] l_j for the first k = len(coef) stored states, in place"""
@@ -1407,6 +1432,32 @@ class Batch:
             out.append(dict(evals=evals[m, :n].copy() if ok else None, coef=coef[m, :n * n].reshape(n, n).copy() if ok else None,
                             h=h[m, :n * n].reshape(n, n).copy(), s=s[m, :n * n].reshape(n, n).copy(), status=int(st[m])))
         return out
+
+    def moments(self, k=None, active=None) -> list:
+        """Context.moments(k[m]) for every listed member (active[m] != 0; None: all) in one sums launch, one reduce and one read-back:
+        per member {"s", "x", "y", "z", "r2", "origin"}, bit for bit what a Context with its Params and states gives, each member from
+        its own centres; None for the members not listed.  k: as Batch.ritz_matrices."""
+        a = self._mask(active)
+        ks = self._ritz_ks(k, a)
+        B, KK = len(self.members), RITZ_MAX * RITZ_MAX
+        m = np.zeros((B, MOMENT_COUNT, KK))
+        self._check(self._L.wafer_batch_moment_matrices(self._h, self._u8(a), (C.c_uint32 * B)(*ks), _dp(m)))
+        out = []
+        for mb in range(B):
+            n = ks[mb]
+            if n == 0:
+                out.append(None)
+                continue
+            d = {name: m[mb, q, :n * n].reshape(n, n).copy() for q, name in enumerate(MOMENT_NAMES)}
+            d["origin"] = moment_origin(self.members[mb].nx, self.members[mb].ny, self.members[mb].nz)
+            out.append(d)
+        return out
+
+    def moment_counts(self) -> tuple:
+        """(launches, read-backs) of moments since creation: 2 and 1 per call"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.wafer_batch_diag_moment_counts(self._h, C.byref(n), C.byref(r)))
+        return n.value, r.value
 
     def ritz_counts(self) -> tuple:
         """(launches, read-backs) of ritz_matrices, rotate_states and ritz since creation: 2 and 1, 1 and 0, 3 and 1 per call"""

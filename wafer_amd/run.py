@@ -188,6 +188,9 @@ def main(argv=None) -> int:
     if cfg.get("residual"):
         raise SystemExit("wafer_amd.run: gpu.residual: true (the residuals of the stored states) is a wafer-hip feature; "
                          "z-slab contexts have no such call")
+    if cfg.get("moments"):
+        raise SystemExit("wafer_amd.run: gpu.moments: true (the moment matrices of the stored states) is a wafer-hip feature; "
+                         "z-slab contexts have no such call")
 
     import torch
     import wafer_amd

@@ -3,7 +3,7 @@ every time step ONE launch for all runs of a batch that are still going (wafer_a
 context per run.
 
     python -m wafer_amd.sweep -c a.yaml -c b.yaml ... [--output-dir DIR] [--input-dir DIR] [--max-batch N] [--seed S]
-                              [--progress] [--plan] [--mix-states] [--batched-setup] [--ritz] [--residuals]
+                              [--progress] [--plan] [--mix-states] [--batched-setup] [--ritz] [--residuals] [--moments]
 
 Configuration reading and validation are the native driver's (`wafer-hip --check-config`, through wafer_amd.run.load_config), the
 input files, the directory names and the table are wafer_amd.run's, and every run computes what `wafer-hip` computes for its file:
@@ -54,6 +54,12 @@ without it nothing changes.
 where the batch has state stores (after the --ritz step), on phi in a ground-state batch -- and a run's JSON line gains
 "residuals": {"theta": [...], "rho": [...]}: some eigenvalue of the run's discrete H lies within rho[j] of theta[j] (null for a run that
 did not take part).  The `gpu.residual` key of a wafer.yaml stays refused like `gpu.ritz`.  Off by default; without it nothing changes.
+
+--moments: every batch that has state stores then ends with moment_phase -- ONE Batch.moments call for all of its runs that hold
+1 .. 8 stored states, each with its own state count (after the --ritz and --residuals steps) -- and a run's JSON line gains
+"moments": {"s": [[...]], "x": ..., "y": ..., "z": ..., "r2": ...}, the matrices wafer-hip prints under `gpu.moments`, in index units
+from observables' origin (null for a run that did not take part, and in ground-state batches).  The `gpu.moments` key of a wafer.yaml
+stays refused like `gpu.ritz`.  Off by default; without it nothing changes.
 """
 from __future__ import annotations
 
@@ -125,6 +131,7 @@ class Run:
         self.states: list = []       # per state: dict(state, status, steps, energy)
         self.failed = False
         self.ritz = None             # --ritz: dict(evals=[...]) once the run's states have been rotated
+        self.moments = None          # --moments: dict(s=[[...]], x=..., y=..., z=..., r2=...) once the run has taken part in moment_phase
         self.residuals = None        # --residuals: dict(theta=[...], rho=[...]) once the run has taken part in residual_phase
         self.boundaries: list = []   # the steps of this phase's block boundaries
         # the phase's loop variables (grid.rs:122-125)
@@ -364,6 +371,27 @@ def residual_phase(batch, runs: list, states: bool) -> None:
             r.residuals = dict(theta=[float(x) for x in out["theta"]], rho=[float(x) for x in out["rho"]])
 
 
+# ---- moment matrices of the results (--moments) -----------------------------------------------------------------------------------
+def moment_phase(batch, runs: list) -> None:
+    """wafer-hip's `gpu.moments` read-out for every run of a batch with state stores, after ritz_phase and residual_phase: ONE
+    Batch.moments call for all runs that hold 1 .. RITZ_MAX stored states, each with its own state count.  A run that took part gets
+    r.moments = dict(s=..., x=..., y=..., z=..., r2=...), (k, k) nested lists; the others None."""
+    from wafer_amd.engine import MOMENT_NAMES, RITZ_MAX
+
+    for r in runs:
+        r.moments = None
+    held = batch.num_states()
+    part = [r for r in runs if 1 <= held[r.slot] <= RITZ_MAX]
+    if not part:
+        return
+    ks = [0] * len(runs)
+    for r in part:
+        ks[r.slot] = held[r.slot]
+    res = batch.moments(k=ks, active=_mask(runs, part))
+    for r in part:
+        r.moments = {name: [[float(v) for v in row] for row in res[r.slot][name]] for name in MOMENT_NAMES}
+
+
 # ---- set-up ---------------------------------------------------------------------------------------------------------------------
 def input_file(input_dir: str, stem: str, file_type: str):
     """the file a run reads for `stem` (a ready-made <stem>.npy first, as staged_array takes it) -> (real path, mtime) or None"""
@@ -580,10 +608,11 @@ def start_phase(batch, runs: list, pars: list, w: int, seed: int, load=_load, ba
         batch.symmetrise(cons, active=_mask(runs, part))
 
 
-def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False, ritz: bool = False, residuals: bool = False) -> tuple:
+def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool = False, ritz: bool = False, residuals: bool = False,
+              moments: bool = False) -> tuple:
     """one batch of the plan from creation to its last phase -> (fused passes, one-step launches).  batched: set_up_batch's and
     start_phase's (--batched-setup).  ritz: a batch that has state stores ends with ritz_phase (--ritz).  residuals: every batch ends
-    with residual_phase, after ritz_phase (--residuals)"""
+    with residual_phase, after ritz_phase (--residuals).  moments: a batch that has state stores then ends with moment_phase (--moments)"""
     import wafer_amd
 
     pars = []
@@ -606,6 +635,8 @@ def run_batch(plan: dict, runs: list, seed: int, progress: bool, batched: bool =
             ritz_phase(batch, runs)
         if residuals:
             residual_phase(batch, runs, states=plan["needs_states"])
+        if moments and plan["needs_states"]:
+            moment_phase(batch, runs)
         return batch.passes()
 
 
@@ -630,6 +661,10 @@ def main(argv=None) -> int:
     ap.add_argument("--residuals", action="store_true",
                     help="after the last phase of every batch (after the --ritz step), theta and rho = |H l - theta l| / |l| of every run's "
                          "stored states -- of its phi in a ground-state batch -- in one Batch.residuals call; a JSON line gains \"residuals\"")
+    ap.add_argument("--moments", action="store_true",
+                    help="after the last phase of every batch with state stores (after the --ritz and --residuals steps), the matrices "
+                         "<i|1|j>, <i|x|j>, <i|y|j>, <i|z|j>, <i|r^2|j> of every run's stored states (what gpu.moments: true prints in wafer-hip) "
+                         "in one Batch.moments call; a JSON line gains \"moments\"")
     args = ap.parse_args(argv)
     if args.max_batch < 1:
         raise SystemExit("--max-batch must be >= 1")
@@ -650,6 +685,9 @@ def main(argv=None) -> int:
         if c.get("residual"):
             raise SystemExit(f"{p}: wafer_amd.sweep: gpu.residual: true (the residuals of the stored states) is a wafer-hip key; "
                              "a sweep computes them for all of its runs with the command-line flag --residuals")
+        if c.get("moments"):
+            raise SystemExit(f"{p}: wafer_amd.sweep: gpu.moments: true (the moment matrices of the stored states) is a wafer-hip key; "
+                             "a sweep computes them for all of its runs with the command-line flag --moments")
     plan = plan_batches(cfgs, args.max_batch, mix_states=args.mix_states)
     if args.plan:
         inputs = []
@@ -683,6 +721,8 @@ def main(argv=None) -> int:
         more = dict(ritz=True) if args.ritz else {}   # (without the flags the call is what it has always been)
         if args.residuals:
             more["residuals"] = True
+        if args.moments:
+            more["moments"] = True
         launches.append(run_batch(b, members, seed, args.progress, batched=args.batched_setup, **more))
     ok = True
     for r in runs:
@@ -697,6 +737,8 @@ def main(argv=None) -> int:
             line["ritz"] = r.ritz
         if args.residuals:
             line["residuals"] = r.residuals
+        if args.moments:
+            line["moments"] = r.moments
         print(json.dumps(line), flush=True)
     print(f"Sweep complete. Elapsed time: {time.perf_counter() - t0:.3f} seconds.\nOutput directory: {args.output_dir}", flush=True)
     return 0 if ok else 1
